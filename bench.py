@@ -13,8 +13,12 @@ Started by a launcher (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environm
 rank; started plainly with --gpus N > 1 it starts the N ranks itself, before it touches a GPU.
 
 Prints ONE JSON line (rank 0).  `roofline` is the HBM roofline of the raycast kernel with the
-algorithmic bytes of SURVEY.md 8(d); `cpu_baseline` times the CPU oracle (oracle/, "port") on a
-bounded sample of the same workload on the host cores (rank 0, N = 1 only).
+algorithmic bytes of SURVEY.md 8(d), from the timed frames' own kernel events.  A plain run does only what
+that line's headline figure needs: set up, warm up, time --steps frames, write --dump-outputs, print.
+--full adds everything else: `cpu_baseline` times the CPU oracle (oracle/, "port") on a bounded sample of
+the same workload on the host cores (rank 0, N = 1 only); the extension measurements under `config`
+(trilinear, moving camera, frames in flight, read-back, per-ray LOD, noise volume; N = 1 only); at N > 1
+the single-frame latency per rank and the check of the assembled frame against one application's.
 """
 import argparse
 import ctypes
@@ -53,7 +57,7 @@ def parse():
                     help="N>1: frames per RCCL gather (sortfirst.BatchedTileGather); 0 = auto: 3 when every rank "
                          "has the same number of rows, else 1 (one gather per frame, sortfirst.TileGather)")
     ap.add_argument("--check-frames", action="store_true",
-                    help="(always on for N>1) after the timing, compare the last assembled frame on rank 0 with the "
+                    help="(on with --full) N>1: after the timing, compare the last assembled frame on rank 0 with the "
                          "full frame rendered by one application (must be bit-identical)")
     ap.add_argument("--gather", choices=["abi", "torch"], default="abi",
                     help="N>1: who moves the tiles: abi = vrc_gather_tiles (RCCL behind the C ABI, the product path); "
@@ -61,8 +65,15 @@ def parse():
     ap.add_argument("--require-abi-gather", action="store_true",
                     help="N>1: exit non-zero instead of falling back to torch.distributed when the C-ABI tile "
                          "exchange (vrc_gather_tiles over RCCL) is unavailable or fails its pattern check")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the trilinear-extension measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the "
+                         "extension measurements (N=1), the single-frame latency and the frame check (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last one rendered (rank 0: the assembled frame at "
+                         "N>1) as DIR/frame.npy, RGBA float32; a frame over 64 MiB is written as every k-th row, "
+                         "DIR/frame_row_sample.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extension measurements")
     ap.add_argument("--cpu-row-stride", type=int, default=1)
     ap.add_argument("--cpu-threads", type=int, default=16, help="oracle threads (GPU box CPU share)")
     return ap.parse_args()
@@ -72,6 +83,23 @@ def linear_ramp(alpha):
     import numpy as np
     i = np.arange(256, dtype=np.float32) / np.float32(255.0)
     return np.ascontiguousarray(np.stack([i, i, i, np.float32(alpha) * i], axis=1))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, frame):
+    """--dump-outputs: the RGBA32F frame of the last timed step (H x W x 4 float32, what render_frame hands its
+    caller), whole, or every k-th row when it is larger than DUMP_LIMIT_BYTES (k fixed by the frame's size)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    f = np.ascontiguousarray(frame, dtype=np.float32)
+    if f.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(d, "frame.npy"), f)
+        return
+    max_rows = max(1, DUMP_LIMIT_BYTES // f[0].nbytes)
+    k = -(-f.shape[0] // max_rows)
+    np.save(os.path.join(d, "frame_row_sample.npy"), np.ascontiguousarray(f[::k]))
 
 
 def cpu_baseline(a, samples_gpu_frame):
@@ -477,6 +505,13 @@ def main():
     dt = all_max(time.perf_counter() - t0)
     timing[0] = False
 
+    # what the last timed step computed, before anything below renders into the same buffers
+    if a.dump_outputs:
+        if world == 1:
+            dump_outputs(a.dump_outputs, fbs[(counter[0] - 1) % K].cpu().numpy())
+        elif rank == 0:
+            dump_outputs(a.dump_outputs, last_frame[0].cpu().numpy())
+
     # HIP-event kernel time of the timed region (events recorded by the library around every raycast launch on
     # the render stream): mean over the launches, which must be the timed frames, one launch each
     ksum, klaunch = 0.0, 0
@@ -497,7 +532,7 @@ def main():
     if gather_events:
         my_gather_ms = sum(g0.elapsed_time(g1) for g0, g1, _ in gather_events) / max(1, sum(n for _, _, n in gather_events))
     lat = []
-    if world > 1:
+    if world > 1 and a.full:
         for _ in range(8):
             dist.barrier()
             torch.cuda.synchronize()
@@ -516,7 +551,7 @@ def main():
 
     # the frame assembled from the ranks' bands is the frame one application renders (outside the timing)
     frame_check = None
-    if world > 1 and rank == 0 and last_frame[0] is not None:
+    if world > 1 and (a.full or a.check_frames) and rank == 0 and last_frame[0] is not None:
         with driver.App(uri, W, H, device=local_rank, synchronous=True, gpu_cache_mb=3072,
                         **(dict(sse=a.ray_lod_sse) if ray_lod_on else dict(min_lod=depth - 1, max_lod=depth - 1))) as whole:
             whole.set_ray_lod(ray_lod_on)
@@ -751,7 +786,7 @@ def main():
 
     # the extras can never cost the judged line: a failure is reported in their place
     def guarded(fn, default):
-        if world != 1 or a.no_extras or ray_lod_on:
+        if world != 1 or not a.full or a.no_extras or ray_lod_on:
             return default
         try:
             return fn()
@@ -814,8 +849,8 @@ def main():
             # measured on the torch.distributed fallback and is NOT a measurement of the C-ABI exchange
             "abi_gather_ok": (None if world == 1 else gather_kind == "abi"),
             "frames_in_flight": K, "frames_per_exchange": B,
-            "single_frame_latency_ms": (max(r["single_frame_latency_ms"] for r in per_rank) if world > 1 else
-                                        dt / a.steps * 1e3),
+            "single_frame_latency_ms": ((max(r["single_frame_latency_ms"] for r in per_rank) if lat else None)
+                                        if world > 1 else dt / a.steps * 1e3),
             "per_rank": per_rank,
             "config": {"workload": ("C2: %s uint8, %dx%d viewport, leaves only (%d bricks of %d^3), "
                                     "%d samples/ray, linear-ramp TF alpha=%.3g, default camera"
@@ -867,7 +902,7 @@ def main():
             # noise data), the linear ramp is a grey transfer function (VRC_OPT_GREY_TABLE: a coloured one costs ~3 %)
             "best_case_riders": ["axis-aligned default camera", "constant mem:// bricks", "grey transfer function"],
         }
-        if world == 1 and not a.no_cpu_baseline and not ray_lod_on:
+        if world == 1 and a.full and not a.no_cpu_baseline and not ray_lod_on:
             try:
                 out["cpu_baseline"] = cpu_baseline(a, samples_frame)
             except Exception as e:  # noqa: BLE001  (the GPU line must survive a broken checker build)
