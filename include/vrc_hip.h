@@ -97,9 +97,9 @@ typedef struct
                                    * VRC_VARIANT_CUDARAYCASTER (default) | VRC_VARIANT_GLRAYCASTER */
 
 #define VRC_OPT_KERNEL_USED 8      /* read-only (vrc_get_option): VRC_KERNEL_* of the last vrc_render, without the
-                                   * synchronisation vrc_get_stats implies.  Every kernel but REFERENCE_ORDER
-                                   * finds the bricks of a ray through the brick grid: the order of the node
-                                   * list does not matter to it */
+                                   * synchronisation vrc_get_stats implies.  It does not say how the bricks of
+                                   * a ray were found: PACKED marches a node list that is not a brick grid in
+                                   * list order, as REFERENCE_ORDER does -- VRC_OPT_GRID_WALK_USED says which */
 
 #define VRC_OPT_KERNEL_TIMING 9    /* 1 (default): a HIP event pair around every raycast launch feeds vrc_get_stats'
                                    * kernel times; 0: no events (two host calls less per vrc_render; vrc_get_stats
@@ -137,6 +137,12 @@ typedef struct
                                    * vrc_pool_create) the first time a frame with the trilinear filter could use it?
                                    * 0: AUTO stays with the LDS-staged / gather forms; asking for VRC_KERNEL_PACKED
                                    * explicitly still builds it */
+
+#define VRC_OPT_GRID_WALK_USED 14  /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render found the
+                                   * bricks of every ray through the brick grid (the grid walk of GRID_DDA, LDS or
+                                   * PACKED on a grid-aligned node set, or per-ray LOD) -- then the order of the node
+                                   * list did not matter to it; 0 if it marched the list in its order (the
+                                   * reference-order loop of any kernel form), or before the first vrc_render */
 
 #define VRC_VARIANT_CUDARAYCASTER 0 /* renderers/cudaRaycaster/cuda/Renderer.cu:95-230 */
 #define VRC_VARIANT_GLRAYCASTER 1   /* renderers/glRaycaster/shaders/fragRaycast.glsl:113-215: pixel centre

@@ -188,6 +188,7 @@ struct vrc_ctx
     uint32_t* dRayList = nullptr; /* counts | two ray lists (vrc_internal.h) */
     size_t dRayListCap = 0;       /* pixels */
     int lastErtParts = 0;         /* of the last vrc_render */
+    int64_t gridWalkUsed = 0;     /* VRC_OPT_GRID_WALK_USED: did the last vrc_render find its bricks through the grid? */
 
     vrc_stats stats = {};
 };
@@ -394,6 +395,7 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_PACKED_ATLAS: *value = c->optPackedAtlas; return VRC_OK;
     case VRC_OPT_VARIANT: *value = c->optVariant; return VRC_OK;
     case VRC_OPT_KERNEL_USED: *value = c->stats.kernel_variant; return VRC_OK;
+    case VRC_OPT_GRID_WALK_USED: *value = c->gridWalkUsed; return VRC_OK;
     default: return fail( VRC_EINVAL, "vrc_get_option: unknown option" );
     }
 }
@@ -1464,6 +1466,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                   : ( useDda ? VRC_KERNEL_GRID_DDA : VRC_KERNEL_REFERENCE_ORDER );
     for( int i = 0; i < 3; ++i )
         c->stats.grid_dims[i] = ( useDda || c->rayLod ) ? (uint32_t)f.gridDim[i] : 0u;
+    c->gridWalkUsed = ( useDda || c->rayLod ) ? 1 : 0;
     return VRC_OK;
 }
 

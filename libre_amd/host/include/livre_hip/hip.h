@@ -8,6 +8,8 @@
 #ifndef LIVRE_HIP_HIP_H
 #define LIVRE_HIP_HIP_H
 
+#include <array>
+
 #include "render.h"
 
 #include "vrc_hip.h" /* vrc_node_data */
@@ -114,7 +116,9 @@ private:
     std::vector< vrc_node_data > _sortedNodes;
     Matrix4f _sortedMV;
     vrc_pool* _sortedPool = nullptr;
-    bool _orderFree = false; /* the last kernel enumerated bricks through the grid: list order irrelevant */
+    bool _orderFree = false; /* the last vrc_render found its bricks through the grid (VRC_OPT_GRID_WALK_USED) ... */
+    std::array< int64_t, 5 > _orderFreeFor{}; /* ... with these settings (kernel, filter, variant, samples per pixel,
+                                               * per-ray LOD): a frame with others may march the list in its order */
     bool _orderExact = true; /* the kept node table is in front-to-back order for _sortedMV */
 };
 

@@ -482,17 +482,24 @@ void HipRaycastRenderer::render( const RenderInputs& renderInputs, const ConstCa
                      _sortedForTex[i] == obj.getTexPosition();
     }
     bool sameList = sameBricks && _sortedMV == frustum.getMVMatrix();
-    int64_t kernelWanted = VRC_KERNEL_AUTO;
+    /* how vrc_render enumerates the bricks depends on the bricks (a grid or not: not on the camera) and on
+     * these settings; the last frame's answer holds for this one only if they are the same */
+    int64_t kernelWanted = VRC_KERNEL_AUTO, filterWanted = VRC_FILTER_NEAREST, variantWanted = VRC_VARIANT_CUDARAYCASTER;
     (void)vrc_get_option( _ctx, VRC_OPT_KERNEL, &kernelWanted );
-    const bool orderFree = _orderFree && kernelWanted != VRC_KERNEL_REFERENCE_ORDER;
+    (void)vrc_get_option( _ctx, VRC_OPT_FILTER, &filterWanted );
+    (void)vrc_get_option( _ctx, VRC_OPT_VARIANT, &variantWanted );
+    const std::array< int64_t, 5 > enumeration = { kernelWanted, filterWanted, variantWanted,
+                                                   int64_t( renderInputs.vrParameters.getSamplesPerPixel() ),
+                                                   renderInputs.vrParameters.getRayLOD() ? 1 : 0 };
+    const bool orderFree = _orderFree && enumeration == _orderFreeFor;
     if( sameList && !_orderExact && !orderFree )
-        sameList = false; /* the kept list is in an older view's order and this kernel marches in list order */
+        sameList = false; /* the kept list is in an older view's order and this frame marches in list order */
     if( sameBricks && !sameList && orderFree )
     {
-        /* the same bricks from another view point, and the last frame's kernel found its bricks
-         * through the brick grid (whether the bricks form a grid does not depend on the camera):
-         * the order of the node list means nothing to it, so the list stays -- no 512 transforms,
-         * no sort, and vrc_render finds the device copy of the table current */
+        /* the same bricks from another view point, and the last frame found them through the brick
+         * grid (whether the bricks form a grid does not depend on the camera): the order of the node
+         * list means nothing to the kernel, so the list stays -- no 512 transforms, no sort, and
+         * vrc_render finds the device copy of the table current */
         sameList = true;
         _sortedMV = frustum.getMVMatrix();
         _orderExact = false;
@@ -619,9 +626,11 @@ void HipRaycastRenderer::render( const RenderInputs& renderInputs, const ConstCa
         rc = vrc_render( _ctx, &viewData, cut.data(), uint32_t( cut.size() ), &rData, pool );
     }
     throwOnVrcError( rc, "vrc_render" );
-    int64_t used = VRC_KERNEL_REFERENCE_ORDER;
-    (void)vrc_get_option( _ctx, VRC_OPT_KERNEL_USED, &used );
-    _orderFree = used != VRC_KERNEL_REFERENCE_ORDER && used != VRC_KERNEL_AUTO;
+    /* not the kernel's name: the packed kernel marches a list that is not a grid in list order.  An older library
+     * without the option (VRC_EINVAL) counts as marching in list order */
+    int64_t gridWalk = 0;
+    _orderFree = vrc_get_option( _ctx, VRC_OPT_GRID_WALK_USED, &gridWalk ) == VRC_OK && gridWalk != 0;
+    _orderFreeFor = enumeration;
 }
 
 void HipRaycastRenderer::postRender( const RenderInputs&, const ConstCacheObjects& )

@@ -34,7 +34,7 @@ int vrc_set_option( vrc_ctx* c, int o, int64_t v ) { if( o < 0 || o > 15 ) retur
 int vrc_get_option( vrc_ctx* c, int o, int64_t* v )
 {
     if( o < 0 || o > 15 ) return VRC_EINVAL;
-    *v = o == VRC_OPT_KERNEL_USED ? VRC_KERNEL_GRID_DDA : c->opt[o];
+    *v = o == VRC_OPT_KERNEL_USED ? VRC_KERNEL_GRID_DDA : o == VRC_OPT_GRID_WALK_USED ? 1 : c->opt[o];
     return VRC_OK;
 }
 int vrc_pool_create( vrc_ctx*, size_t bpv, int, int, size_t, const uint32_t mb[3], size_t maxBytes, vrc_pool** out )

@@ -92,3 +92,20 @@ def test_developer_switches_need_the_dev_build_guard(tmp_path):
         r = subprocess.run(base + [sw], capture_output=True, text=True)
         assert r.returncode != 0 and "VRC_DEV_BUILD" in r.stderr, sw
         assert subprocess.run(base + [sw, "-DVRC_DEV_BUILD"], capture_output=True).returncode == 0, sw
+
+
+def test_option_numbers_match_the_header(built):
+    # every VRC_OPT_* of include/vrc_hip.h has its number in the binding; VRC_OPT_GRID_WALK_USED (14) is read-only: the
+    # host plugin asks it, not the kernel's name, whether the last frame's list order mattered (tests/host_san's stub
+    # answers it too)
+    from libre_amd import vrc
+    txt = open(os.path.join(ROOT, "include", "vrc_hip.h")).read()
+    opts = dict(re.findall(r"#define VRC_(OPT_[A-Z_]+)\s+(\d+)", txt))
+    assert opts["OPT_GRID_WALK_USED"] == "14" and opts["OPT_KERNEL_USED"] == "8"
+    for name, value in opts.items():
+        assert getattr(vrc, name) == int(value), name
+    assert len(set(opts.values())) == len(opts)
+    plugin = open(os.path.join(ROOT, "libre_amd", "host", "src", "hip_plugin.cpp")).read()
+    assert "VRC_OPT_GRID_WALK_USED" in plugin
+    stub = open(os.path.join(ROOT, "tests", "host_san", "vrc_stub.cpp")).read()
+    assert "VRC_OPT_GRID_WALK_USED" in stub

@@ -4,6 +4,7 @@ same headers are what hipcc compiles into the gfx950 kernel."""
 import numpy as np
 import pytest
 
+import nongrid
 import orc
 import scenes
 
@@ -477,3 +478,87 @@ def test_the_parity_contract_is_frozen():
     n = scenes.nucleon_scene()  # alpha 0.3 at 512: strong
     a = float(np.asarray(n.tf).reshape(-1, 4)[:, 3].max())
     assert 1.0 - (1.0 - a) ** (32.0 / n.render.samplesPerRay) > scenes.STRONG_SAMPLE
+
+
+# ---- node lists that are not a brick grid (tests/nongrid.py) ---------------------------------------------------
+# Overlapping lists (coarse bricks among the finer ones inside them: an asynchronous frame's cached ancestors) and the
+# ragged UVF tree.  Every kernel form marches them with the reference-order loop; the grid walk refuses them.
+
+NONGRID = sorted(nongrid.OVERLAPPING) + sorted(nongrid.RAGGED)
+
+
+def nongrid_scene(name):
+    if name in nongrid.RAGGED:
+        from libre_amd import driver
+        driver.load_library()
+        return nongrid.uvf_scene(driver, name)
+    return nongrid.overlapping_scene(name)
+
+
+def colour_tf(alpha=0.3):
+    """A transfer function whose red, green and blue differ (the four-float colour forms)."""
+    i = np.arange(256, dtype=np.float32) / np.float32(255.0)
+    return np.ascontiguousarray(np.stack([i, 1 - i, i * i, np.float32(alpha) * i], axis=1).astype(np.float32))
+
+
+def _list_order_forms(s):
+    """(harness kernel, filter) of every list-order form that applies to the scene's voxel type: 1 / 3 classified
+    table with float / fixed-point stepping (8-bit), 7 per-sample classification, 5 trilinear gathers, 9 / 11 the
+    tap-packed atlas with four-float / (grey, alpha) colours."""
+    u16 = s.atlas.dtype.itemsize == 2
+    return ([] if u16 else [(1, 0), (3, 0)]) + [(7, 0), (5, 1), (9, 1), (11, 1)]
+
+
+@pytest.mark.parametrize("name", NONGRID)
+def test_non_grid_lists_every_list_order_form_matches_the_oracle(name):
+    s = nongrid_scene(name)
+    want = {f: orc.oracle_render(s, threads=4, filter_mode=f) for f in (0, 1)}
+    frames = {}
+    for kernel, f in _list_order_forms(s):
+        got, n_got, grid_ok = orc.harness_render(s, kernel=kernel)
+        assert not grid_ok, "%s: the list is not a grid" % name
+        scenes.assert_parity(got, want[f][0], "%s k%d" % (name, kernel))
+        assert abs(n_got - want[f][1]) <= 2e-4 * want[f][1] + 8, (name, kernel, n_got, want[f][1])
+        frames[kernel] = got
+    assert (frames[11] == frames[9]).all(), "%s: grey form of the packed march differs" % name
+    with pytest.raises(RuntimeError):  # the grid walk refuses the list
+        orc.harness_render(s, kernel=2)
+    # glRaycaster rules, one and three samples per pixel (the brick-by-brick average), both filters
+    for spp in (1, 3):
+        s.render.samplesPerPixel = spp
+        for kernel, f in ((1 if s.atlas.dtype.itemsize == 1 else 7, 0), (5, 1)):
+            want_gl, n_gl = orc.oracle_render(s, threads=4, variant=1, filter_mode=f)
+            got, n_got, _ = orc.harness_render(s, kernel=kernel, variant=1)
+            scenes.assert_parity(got, want_gl, "%s glRaycaster spp %d k%d" % (name, spp, kernel))
+            assert abs(n_got - n_gl) <= 3e-4 * n_gl + 8
+    s.render.samplesPerPixel = 1
+    # a coloured transfer function: the four-float forms
+    s.tf = colour_tf()
+    for kernel, f in _list_order_forms(s):
+        if kernel == 11:
+            continue  # the grey form is for grey tables only
+        w, _ = orc.oracle_render(s, threads=4, filter_mode=f)
+        got, _, _ = orc.harness_render(s, kernel=kernel)
+        scenes.assert_parity(got, w, "%s colour k%d" % (name, kernel))
+
+
+@pytest.mark.parametrize("seed", range(16 * scenes.FUZZ_SCALE))
+def test_random_views_of_overlapping_lists_match_the_oracle(seed):
+    # _fuzz_scene's volumes and views over random overlapping lists (tests/nongrid.py: fuzz_scene), u8 and u16,
+    # split into random passes for the packed march
+    rng = np.random.default_rng(21000 + seed)
+    s, kw = nongrid.fuzz_scene(rng, dtype="u16" if seed % 4 == 3 else "u8",
+                               **({"volume": "hash"} if seed % 4 == 3 else {}))
+    want = {f: orc.oracle_render(s, threads=4, filter_mode=f) for f in (0, 1)}
+    packed = min(s.vi.overlap[a] for a in range(3)) >= 1 and max(s.slot_dim) <= 248
+    for kernel, f in _list_order_forms(s):
+        if kernel in (9, 11) and not packed:
+            continue
+        got, n_got, grid_ok = orc.harness_render(s, kernel=kernel)
+        assert not grid_ok
+        _fuzz_parity(got, want[f][0], "seed %d k%d %r" % (seed, kernel, kw))
+        assert n_got == want[f][1] or (kw.get("alpha", 0.05) >= 0.3 and
+                                       abs(n_got - want[f][1]) <= 2e-4 * want[f][1] + 8), (seed, kernel, kw)
+    want_gl, _ = orc.oracle_render(s, threads=4, variant=1)
+    got, _, _ = orc.harness_render(s, kernel=1 if s.atlas.dtype.itemsize == 1 else 7, variant=1)
+    _fuzz_parity(got, want_gl, "seed %d glRaycaster %r" % (seed, kw))

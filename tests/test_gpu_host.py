@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import nongrid
 import orc
 import scenes
 
@@ -696,15 +697,57 @@ def test_moving_camera_keeps_the_brick_list_and_stays_correct(drv):
                 assert (got == a.render_frame()[0]).all(), spin
 
 
+def test_moving_camera_on_a_list_that_is_not_a_grid_with_the_trilinear_filter(drv):
+    # the renderer keeps its sorted node list across a camera move only while the last frame found its bricks through
+    # the brick grid.  On a list that is not a grid (the ragged UVF tree) the tap-packed kernel, which AUTO takes for the
+    # trilinear filter, marches the list in its order like the reference-order kernel: a camera that reorders the same
+    # bricks must get a freshly sorted list -- with the packed atlas, without it (gathers) and with the reference-order
+    # kernel asked for
+    from libre_amd import vrc
+    W, H = 56, 48
+    kw = dict(synchronous=True, min_lod=1, max_lod=1, gpu_cache_mb=8)
+    spins = [(0.0, 0.0), (0.05, 0.02), (3.14, 0.0), (1.57, 0.3)]
+
+    def setup(a, options, spin):
+        a.set_colormap(orc.linear_ramp_tf(0.3))
+        for o, v in options:
+            a.set_option(o, v)
+        a.set_camera(spin=spin)
+
+    L = vrc.load_library()
+    leaves = None
+    # (options besides the filter, the list-order instance the frames must come from: vrc_k_raycast<false,...>)
+    for extra, instance in (([], ",6,unsigned int,12,"), ([(vrc.OPT_PACKED_ATLAS, 0)], ",1,unsigned char,"),
+                            ([(vrc.OPT_KERNEL, vrc.KERNEL_REFERENCE_ORDER)], ",1,unsigned char,")):
+        options = [(vrc.OPT_FILTER, vrc.FILTER_TRILINEAR)] + extra
+        with drv.App(nongrid.UVF, W, H, **kw) as app:
+            for spin in spins:
+                setup(app, options, spin)
+                got, st = app.render_frame()
+                ran = L.vrc_last_kernel().decode()
+                assert ran.startswith("vrc_k_raycast<false,") and instance in ran, (extra, ran)
+                assert st.n_available == 45 and st.n_passes == 1
+                visible = sorted(app.visible_set())
+                leaves = leaves or visible
+                assert visible == leaves and len(leaves) == 45  # the same bricks in every view
+                with drv.App(nongrid.UVF, W, H, **kw) as ref:
+                    setup(ref, options, spin)
+                    want, _ = ref.render_frame()
+                    order = ref.node_order()
+                assert (got == want).all(), (extra, spin, float(np.abs(got - want).max()))
+                assert app.node_order() == order, (extra, spin)
+
+
 @pytest.mark.parametrize("seed", range(6 * scenes.FUZZ_SCALE))
 def test_random_frame_sequences_equal_fresh_applications(drv, seed):
     # the pipeline and the renderer keep state between frames (brick list, node table, tile schedule,
     # classified tables): after any sequence of changes a frame must be the frame a fresh application
-    # renders with the same settings -- bit for bit with the gather kernels
+    # renders with the same settings -- bit for bit with the gather kernels.  Every third seed on the ragged UVF tree
+    # (a list that is not a grid: every kernel marches it in list order)
     from libre_amd import vrc
     rng = np.random.default_rng(11000 + seed)
     volume = str(rng.choice(["hash", "mem"]))
-    uri = "%s://#64,64,64,16" % volume
+    uri = nongrid.UVF if seed % 3 == 2 else "%s://#64,64,64,16" % volume
     W, H = int(rng.integers(24, 72)), int(rng.integers(24, 72))
     sync = bool(rng.random() < 0.8)
     state = dict(spin=(0.0, 0.0), eye=(0.0, 0.0, 1.5), alpha=0.3, planes=[], ray_lod=False, kernel=vrc.KERNEL_AUTO,
@@ -734,7 +777,7 @@ def test_random_frame_sequences_equal_fresh_applications(drv, seed):
 
     with drv.App(uri, W, H, synchronous=sync, sse=sse, gpu_cache_mb=16) as app:
         for step in range(8):
-            what = int(rng.integers(0, 8))
+            what = int(rng.integers(0, 9))
             if what == 0:    # small camera move
                 state["spin"] = (state["spin"][0] + float(rng.uniform(-0.03, 0.03)), state["spin"][1] + float(rng.uniform(-0.03, 0.03)))
             elif what == 1:  # big camera move
@@ -750,6 +793,8 @@ def test_random_frame_sequences_equal_fresh_applications(drv, seed):
                 state["kernel"] = int(rng.choice([vrc.KERNEL_AUTO, vrc.KERNEL_REFERENCE_ORDER]))
             elif what == 6:
                 state["bands"] = [] if state["bands"] else [(8, 8), (H - 12, 8)]
+            elif what == 8:
+                state["flt"] = vrc.FILTER_TRILINEAR if state["flt"] == vrc.FILTER_NEAREST else vrc.FILTER_NEAREST
             # what == 7: the same frame again
             if state["ray_lod"]:
                 state["kernel"] = vrc.KERNEL_AUTO  # per-ray LOD has its own kernel

@@ -6,8 +6,10 @@ import os
 import numpy as np
 import pytest
 
+import nongrid
 import orc
 import scenes
+from test_cpu_harness import NONGRID, _fuzz_parity, nongrid_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -1302,6 +1304,12 @@ def test_tap_packed_atlas_of_more_than_4_gib(vrc):
         assert st.kernel_variant == vrc.KERNEL_RAY_LOD and _ran(g).endswith(",unsigned int,false>"), _ran(g)
         want, n_want, st = g.render(kernel=vrc.KERNEL_PACKED, filter_mode=vrc.FILTER_TRILINEAR)
         assert st.kernel_variant == vrc.KERNEL_PACKED and _ran(g).endswith(",false>"), _ran(g)
+        assert list(st.grid_dims) == [0, 0, 0] and _ran(g).startswith("vrc_k_raycast<false,"), _ran(g)
+    # the small pool's frame of this overlapping list (all three levels) against the oracle: the large pool's frames
+    # are tied to it bit for bit below
+    want_o, n_o = orc.oracle_render(s, threads=8, filter_mode=1)
+    scenes.assert_parity(want, want_o, "all levels, tap-packed atlas, small pool")
+    assert abs(n_want - n_o) <= 2e-4 * n_o + 8
     line = (2 ** 32) * 4 // 9  # voxels whose packed texels (2.25 bytes each) fill 4 GiB
     opts = {vrc.OPT_FILTER: vrc.FILTER_TRILINEAR, vrc.OPT_KERNEL: vrc.KERNEL_PACKED}
     got = _frames_in_a_large_pool(vrc, s, 3 * 1000 ** 3, line, [(opts, lod), (opts, None)])
@@ -1314,6 +1322,10 @@ def test_tap_packed_atlas_of_more_than_4_gib(vrc):
     with _gpu(s16) as g:
         want16, n16, st = g.render(kernel=vrc.KERNEL_PACKED, filter_mode=vrc.FILTER_TRILINEAR)
         assert st.kernel_variant == vrc.KERNEL_PACKED and _ran(g).endswith(",unsigned long,12,false>"), _ran(g)
+        assert list(st.grid_dims) == [0, 0, 0]
+    want16_o, n16_o = orc.oracle_render(s16, threads=8, filter_mode=1)
+    scenes.assert_parity(want16, want16_o, "all levels, 16-bit voxels, tap-packed atlas, small pool")
+    assert abs(n16 - n16_o) <= 2e-4 * n16_o + 8
     (fb, n, variant, name), = _frames_in_a_large_pool(vrc, s16, 6 * 1000 ** 3, (2 ** 32) * 2 // 9, [(opts, None)])
     assert variant == vrc.KERNEL_PACKED and name.endswith(",unsigned long,12,true>"), name
     assert n == n16 and (fb == want16).all(), name
@@ -1809,3 +1821,209 @@ def test_per_ray_lod_grey_form_is_bit_identical(vrc):
             grey, n_grey, st = g.render(ray_lod=lod)
             assert st.kernel_variant == vrc.KERNEL_RAY_LOD
             assert (grey == four).all() and n_grey == n_four
+
+
+# ---- node lists that are not a brick grid (tests/nongrid.py) ---------------------------------------------------
+# Overlapping lists (an asynchronous frame's cached ancestors among the finer bricks) and the ragged UVF tree: every
+# kernel form leaves the grid walk for the reference-order loop and its ballot tile culling (vrc_kernels.hip), in
+# the 8-bit and 16-bit, grey and colour, gather and tap-packed forms.  Each case checks that it ran the list-order
+# instance it is meant for (grid_dims 0, vrc_k_raycast<false,...>), so it cannot quietly fall back onto the grid.
+
+def _list_order(g, st, variant, mode=None, atlas=None):
+    """The last render marched the list in its order with the instance asked for; returns the template arguments."""
+    k = _ran(g)
+    args = k[k.index("<") + 1:-1].split(",")
+    assert st.kernel_variant == variant, (st.kernel_variant, variant, k)
+    assert list(st.grid_dims) == [0, 0, 0], list(st.grid_dims)
+    assert k.startswith("vrc_k_raycast<false,"), k
+    used = C.c_int64(-1)
+    from libre_amd import vrc
+    vrc.check(g.L, g.L.vrc_get_option(g.ctx, vrc.OPT_GRID_WALK_USED, C.byref(used)))
+    assert used.value == 0, k
+    if mode is not None:
+        assert int(args[4]) in mode, k
+    if atlas is not None:
+        assert args[5] == atlas, k
+    return args
+
+
+def _samples_agree(n_got, n_want, s):
+    # the same samples, one for one; with an opaque transfer function a ray may cross the early-exit threshold a
+    # sample sooner or later where a tie (tests/scenes.py) falls the other way
+    alpha = float(np.asarray(s.tf).reshape(-1, 4)[:, 3].max())
+    return n_got == n_want or (alpha >= 0.3 and abs(n_got - n_want) <= 1e-4 * n_want + 8)
+
+
+def _every_list_order_form(vrc, s, what, flipped=None):
+    """Every kernel form on the non-grid list of scene s against the oracle; flipped = (nearest, trilinear) frames of
+    the oracle with every brick-entry tie the other way, for the bias check."""
+    u16 = s.atlas.dtype.itemsize == 2
+    cell = "unsigned short" if u16 else "unsigned char"
+    packed_cell = "unsigned long" if u16 else "unsigned int"
+    want, n_want = orc.oracle_render(s, threads=16)
+    want_lin, n_lin = orc.oracle_render(s, threads=16, filter_mode=1)
+    with _gpu(s) as g:
+        L = g.L
+        # point sampling, REFERENCE_ORDER: classified table (u8) / per-sample classification (u16), grey and
+        # four-float tables, fixed-point and float stepping
+        first = None
+        for stepping in (1, 0):
+            for grey in (1, 0):
+                vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_GREY_TABLE, grey))
+                got, n_got, st = g.render(kernel=vrc.KERNEL_REFERENCE_ORDER, stepping=stepping)
+                # the grey forms come with the fixed-point march only
+                modes = ((4,) if u16 else (3,)) if (grey and stepping) else ((2,) if u16 else (0,))
+                _list_order(g, st, vrc.KERNEL_REFERENCE_ORDER, modes, cell)
+                scenes.assert_parity(got, want, "%s nearest, stepping %d, grey %d" % (what, stepping, grey))
+                assert _samples_agree(n_got, n_want, s), (what, stepping, grey, n_got, n_want)
+                if flipped is not None and stepping and grey:
+                    scenes.assert_no_tie_bias(got, want, flipped[0], what + " nearest, list order")
+                if first is None:
+                    first = got
+                elif stepping:
+                    assert (got == first).all(), "%s: the grey table form differs" % what
+        vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_GREY_TABLE, 1))
+        auto, _, st = g.render()
+        _list_order(g, st, vrc.KERNEL_REFERENCE_ORDER)
+        assert (auto == first).all()
+        with pytest.raises(vrc.VrcError):  # no grid to walk
+            g.render(kernel=vrc.KERNEL_GRID_DDA)
+        # trilinear: the gather form, the tap-packed atlas (grey and four-float colours), and what AUTO takes
+        gather, n_gather, st = g.render(kernel=vrc.KERNEL_REFERENCE_ORDER, filter_mode=vrc.FILTER_TRILINEAR)
+        _list_order(g, st, vrc.KERNEL_REFERENCE_ORDER, (1,), cell)
+        scenes.assert_parity(gather, want_lin, what + " trilinear, gather form")
+        assert abs(n_gather - n_lin) <= 2e-4 * n_lin + 8
+        if flipped is not None:
+            scenes.assert_no_tie_bias(gather, want_lin, flipped[1], what + " trilinear gather, list order")
+        pk, n_pk, st = g.render(kernel=vrc.KERNEL_PACKED, filter_mode=vrc.FILTER_TRILINEAR)
+        args = _list_order(g, st, vrc.KERNEL_PACKED, (6,), packed_cell)
+        assert args[6] == "12", args
+        scenes.assert_parity(pk, want_lin, what + " trilinear, tap-packed atlas")
+        assert abs(n_pk - n_lin) <= 2e-4 * n_lin + 8
+        if flipped is not None:
+            scenes.assert_no_tie_bias(pk, want_lin, flipped[1], what + " tap-packed, list order")
+        vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_GREY_TABLE, 0))
+        four, n_four, st = g.render(kernel=vrc.KERNEL_PACKED, filter_mode=vrc.FILTER_TRILINEAR)
+        _list_order(g, st, vrc.KERNEL_PACKED, (5,), packed_cell)
+        assert n_four == n_pk and (four == pk).all(), what + ": four-float colours of the packed march differ"
+        vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_GREY_TABLE, 1))
+        auto, _, st = g.render(filter_mode=vrc.FILTER_TRILINEAR)
+        _list_order(g, st, vrc.KERNEL_PACKED, (6,), packed_cell)
+        assert (auto == pk).all()
+        vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_PACKED_ATLAS, 0))  # AUTO without the packed atlas: gathers
+        auto, _, st = g.render(filter_mode=vrc.FILTER_TRILINEAR)
+        _list_order(g, st, vrc.KERNEL_REFERENCE_ORDER, (1,), cell)
+        assert (auto == gather).all()
+        vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_PACKED_ATLAS, 1))
+        # glRaycaster rules: one sample per pixel, and the brick-by-brick average of two and three (where the list-order
+        # loop is the only form), point-sampled and trilinear
+        for spp in (1, 2, 3):
+            s.render.samplesPerPixel = spp
+            for f in (vrc.FILTER_NEAREST, vrc.FILTER_TRILINEAR):
+                want_gl, n_gl = orc.oracle_render(s, threads=16, variant=1, filter_mode=f)
+                got, n_got, st = g.render(variant=vrc.VARIANT_GLRAYCASTER, filter_mode=f)
+                _list_order(g, st, vrc.KERNEL_PACKED if (f and spp == 1) else vrc.KERNEL_REFERENCE_ORDER)
+                scenes.assert_parity(got, want_gl, "%s glRaycaster spp %d filter %d" % (what, spp, f))
+                assert abs(n_got - n_gl) <= 3e-4 * n_gl + 8
+        s.render.samplesPerPixel = 1
+        # a coloured transfer function: the four-float forms
+        tf = s.tf
+        from test_cpu_harness import colour_tf
+        s.tf = colour_tf()
+        try:
+            for f, k, modes in ((vrc.FILTER_NEAREST, vrc.KERNEL_REFERENCE_ORDER, (2,) if u16 else (0,)),
+                                (vrc.FILTER_TRILINEAR, vrc.KERNEL_PACKED, (5,))):
+                w, _ = orc.oracle_render(s, threads=16, filter_mode=f)
+                got, _, st = g.render(kernel=k, filter_mode=f)
+                _list_order(g, st, k, modes)
+                scenes.assert_parity(got, w, "%s colour, kernel %d" % (what, k))
+        finally:
+            s.tf = tf
+
+
+@pytest.mark.parametrize("name", NONGRID)
+def test_non_grid_lists_every_kernel_form_matches_the_oracle(vrc, name):
+    _every_list_order_form(vrc, nongrid_scene(name), name)
+
+
+def test_non_grid_list_in_136_cubed_slots(vrc):
+    # BASELINE's slot shape (256^3 noise, bricks of 128: slots of 136^3) with the root over its eight leaves, 256^2: the
+    # list-order loop over slots whose address tables reach 135, with the bias check on the gather and packed forms
+    s = nongrid.baseline_root_and_leaves(spin=(0.5236, 0.349))
+    flipped = (orc.oracle_render(s, threads=16, entry_bias=orc.ENTRY_BIAS)[0],
+               orc.oracle_render(s, threads=16, filter_mode=1, entry_bias=orc.ENTRY_BIAS)[0])
+    _every_list_order_form(vrc, s, "root + 8 leaves in 136^3 slots", flipped=flipped)
+
+
+def test_grid_aligned_lod_cut_control(vrc):
+    # the control of the cases above: a grid-aligned cut of mixed brick sizes IS a grid (grid_dims set), AUTO keeps the
+    # reference order there for point sampling, and the grid walk composites the same samples along the rays
+    vi = orc.mem_volume_info(64, 64, 64, 16)
+    coarse = [orc.pack(1, 1, 0, 0), orc.pack(1, 0, 1, 1)]
+    ids = coarse + [i for i in orc.leaf_ids(vi) if orc.lib().orc_nodeid_parent(i) not in coarse]
+    s = orc.build_scene(voxels=(64, 64, 64), block=16, viewport=(64, 56), spin=(1.1, -0.4), ids=ids, volume="hash")
+    assert not nongrid.is_overlapping(s)
+    want, n_want = orc.oracle_render(s, threads=16)
+    with _gpu(s) as g:
+        ref, n_ref, st = g.render(kernel=vrc.KERNEL_REFERENCE_ORDER)
+        assert st.kernel_variant == vrc.KERNEL_REFERENCE_ORDER
+        scenes.assert_parity(ref, want, "grid-aligned LOD cut, reference order")
+        assert _samples_agree(n_ref, n_want, s)
+        auto, _, st = g.render()
+        assert st.kernel_variant == vrc.KERNEL_REFERENCE_ORDER and (auto == ref).all()
+        dda, n_dda, st = g.render(kernel=vrc.KERNEL_GRID_DDA)
+        assert st.kernel_variant == vrc.KERNEL_GRID_DDA and list(st.grid_dims) != [0, 0, 0]
+        used = C.c_int64(-1)
+        vrc.check(g.L, g.L.vrc_get_option(g.ctx, vrc.OPT_GRID_WALK_USED, C.byref(used)))
+        assert used.value == 1
+        assert _samples_agree(n_dda, n_ref, s)
+        scenes.assert_close_frames(dda, ref, "grid walk vs reference order")
+        _, _, st = g.render(filter_mode=vrc.FILTER_TRILINEAR)
+        assert st.kernel_variant == vrc.KERNEL_PACKED and list(st.grid_dims) != [0, 0, 0]
+        assert _ran(g).startswith("vrc_k_raycast<true,")
+
+
+@pytest.mark.parametrize("seed", range(8 * scenes.FUZZ_SCALE))
+def test_random_views_of_overlapping_lists_every_kernel_form(vrc, seed):
+    # _fuzz_scene's volumes and views (eye inside, clip planes, samples per ray) over random overlapping lists, u8 and
+    # u16; the list also split into random passes (what the plugin does when the atlas is smaller than the frame),
+    # accumulating in the pixel buffer, for the gather and tap-packed forms.  The passes are compared with the oracle's
+    # frame of the same passes: with clip planes it is not always the single pass's (tests/nongrid.py: oracle_passes).
+    # No pass is a grid by itself (non_grid_passes): the trilinear filter walks a grid-aligned list of mixed brick sizes
+    # along the rays (vrc_api.hip: it "stays on the grid"), not in the list order the oracle composites in
+    rng = np.random.default_rng(21000 + seed)
+    u16 = seed % 4 == 3
+    s, kw = nongrid.fuzz_scene(rng, dtype="u16" if u16 else "u8", **({"volume": "hash"} if u16 else {}))
+    what = "seed %d %r" % (seed, kw)
+    packed = min(s.vi.overlap[a] for a in range(3)) >= 1 and max(s.slot_dim) <= 248
+    want, n_want = orc.oracle_render(s, threads=16)
+    want_lin, n_lin = orc.oracle_render(s, threads=16, filter_mode=1)
+    want_gl, _ = orc.oracle_render(s, threads=16, variant=1)
+    cuts = sorted(set(int(c) for c in rng.integers(1, max(2, s.n_nodes), size=3)) | {0, s.n_nodes})
+    passes = nongrid.non_grid_passes(s, [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a])
+    want_mp, _ = nongrid.oracle_passes(s, passes, threads=16)
+    want_mp_lin, n_mp_lin = nongrid.oracle_passes(s, passes, threads=16, filter_mode=1)
+    with _gpu(s) as g:
+        for stepping in (1, 0):
+            got, n_got, st = g.render(kernel=vrc.KERNEL_REFERENCE_ORDER, stepping=stepping)
+            _list_order(g, st, vrc.KERNEL_REFERENCE_ORDER)
+            _fuzz_parity(got, want, "%s nearest stepping %d" % (what, stepping))
+            assert _samples_agree(n_got, n_want, s), (what, n_got, n_want)
+        gather, _, st = g.render(kernel=vrc.KERNEL_REFERENCE_ORDER, filter_mode=vrc.FILTER_TRILINEAR)
+        _list_order(g, st, vrc.KERNEL_REFERENCE_ORDER, (1,))
+        _fuzz_parity(gather, want_lin, what + " trilinear gather")
+        got, _, st = g.render(variant=vrc.VARIANT_GLRAYCASTER)
+        _list_order(g, st, vrc.KERNEL_REFERENCE_ORDER)
+        _fuzz_parity(got, want_gl, what + " glRaycaster")
+        got, _, st = g.render(kernel=vrc.KERNEL_REFERENCE_ORDER, passes=passes)
+        _fuzz_parity(got, want_mp, "%s nearest, passes %r" % (what, passes))
+        got, _, st = g.render(kernel=vrc.KERNEL_REFERENCE_ORDER, filter_mode=vrc.FILTER_TRILINEAR, passes=passes)
+        _fuzz_parity(got, want_mp_lin, "%s trilinear gather, passes %r" % (what, passes))
+        if packed:
+            one, n_one, st = g.render(filter_mode=vrc.FILTER_TRILINEAR)
+            _list_order(g, st, vrc.KERNEL_PACKED, (6,))
+            _fuzz_parity(one, want_lin, what + " tap-packed (AUTO)")
+            assert abs(n_one - n_lin) <= 2e-4 * n_lin + 8
+            got, n_got, _ = g.render(kernel=vrc.KERNEL_PACKED, filter_mode=vrc.FILTER_TRILINEAR, passes=passes)
+            _fuzz_parity(got, want_mp_lin, "%s tap-packed, passes %r" % (what, passes))
+            assert abs(n_got - n_mp_lin) <= 2e-4 * n_mp_lin + 8, (what, passes, n_got, n_mp_lin)
