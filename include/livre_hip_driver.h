@@ -88,6 +88,18 @@ int lvh_app_render_frame( lvh_app* app, float* host_rgba, lvh_frame_stats* stats
 int lvh_app_get_stats( lvh_app* app, lvh_frame_stats* stats ); /* kernel_ms/samples after sync */
 int lvh_app_wait_uploads( lvh_app* app );
 int lvh_app_synchronize( lvh_app* app );
+/* Frame histogram (the reference's HistogramFilter + SendHistogramFilter, livre/eq/Channel.cpp:92-125): off by
+ * default.  While on, every frame sums the per-brick histograms (binned on the GPU when a brick lands) of the nodes it
+ * rendered that this process counts: those whose box centre lies in its tile or bands of the full frame (half-open
+ * edges, frame borders extended to infinity), the SSE cut under per-ray LOD; each node once per frame, scaled by
+ * 8^(depth-1-level).  The caller sums the processes' histograms until their areas add up to 1 (Config::gatherHistogram,
+ * livre/eq/Config.cpp:109-175). */
+int lvh_app_set_histogram( lvh_app* app, int enable );
+/* the last frame of the selected renderer slot: bin_count bins (256 for uint8, 1024 for uint16 volumes; capacity
+ * must hold them, bins may be NULL to ask for the count), the value range of the bins, this process's share of the
+ * frame's area and the frame's id.  An error while the histogram is off or before such a frame. */
+int lvh_app_frame_histogram( lvh_app* app, uint64_t* bins, uint32_t capacity, uint32_t* bin_count, float range[2],
+                             float* area, uint64_t* frame_id );
 /* introspection used by the parity tests */
 int lvh_app_volume_info( lvh_app* app, uint32_t voxels[3], uint32_t max_block[3],
                          uint32_t overlap[3], float world_size[3], uint32_t* depth,

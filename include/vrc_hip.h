@@ -247,6 +247,24 @@ int vrc_pool_read_region( vrc_pool* pool, const uint32_t origin[3], const uint32
 int vrc_pool_histogram( vrc_pool* pool, const float slot[3], const uint32_t origin[3],
                         const uint32_t size[3], uint32_t bin_count, uint64_t scale_factor,
                         uint64_t* host_bins );
+/* Per-slot histograms kept by the pool (the reference's HistogramCache, livre/lib/cache/HistogramObject.cpp:134-205,
+ * here binned on the GPU when a brick lands).  bin_count > 0 turns them on: a device table of bin_count uint32 counts
+ * per slot; the slots resident now are binned by one launch, every later vrc_pool_copy_to_slot[_device] bins its
+ * brick's interior [overlap, size - overlap) on the upload stream behind its repack, and vrc_pool_release_slot
+ * invalidates the slot's row.  bin_count must divide the voxel type's range (256 for uint8, 1024 for uint16 in the
+ * reference, :164-176; at most 4096).  bin_count = 0 turns them off and frees the table (waits for the device).  Off by
+ * default: without this call nothing is allocated or launched. */
+int vrc_pool_enable_histograms( vrc_pool* pool, uint32_t bin_count, const uint32_t overlap[3] );
+/* Frame histogram on ctx's stream: sum over the n nodes of row(slots[i]) * scales[i] (scale 8^(depth-1-level),
+ * HistogramObject.cpp:158-161) into a uint64 histogram the context owns; accumulate = 1 adds to the one there (the
+ * passes of one frame).  Every slot must hold a binned brick (VRC_EINVAL otherwise).  Deterministic (one owner per
+ * bin, integer sums).  Enqueued behind the pool's uploads and before the context's render fence of the pool, so an
+ * upload that recycles one of these slots waits for it. */
+int vrc_frame_histogram( vrc_ctx* ctx, vrc_pool* pool, const float* slots /* n x 3 */, const uint64_t* scales,
+                         uint32_t n, int accumulate );
+/* copy the context's frame histogram to the host (waits for ctx's stream only).  bin_count must be that of the last
+ * vrc_frame_histogram; VRC_EINVAL before the first */
+int vrc_get_frame_histogram( vrc_ctx* ctx, uint64_t* host_bins, uint32_t bin_count );
 
 /* ---- renderer ----------------------------------------------------------------------------- */
 /* cuda::Renderer::update (cuda/Renderer.cu:245-250): 256 RGBA float texels as

@@ -93,6 +93,15 @@ struct vrc_pool
     };
     Staging staging[kStagingSlots];
     uint32_t nextStaging = 0;
+
+    /* per-slot histograms (vrc_pool_enable_histograms), guarded by `mutex`: binCount uint32 per slot, a row is
+     * valid while its slot holds a binned brick.  slotSize: the brick size of every slot's last upload */
+    uint32_t histBins = 0;
+    uint32_t histOverlap[3] = { 0, 0, 0 };
+    uint32_t* dHist = nullptr;
+    std::vector< uint8_t > histValid;
+    std::vector< uint8_t > resident;
+    std::vector< std::array< uint32_t, 3 > > slotSize;
 };
 
 struct vrc_ctx
@@ -191,6 +200,18 @@ struct vrc_ctx
     int64_t gridWalkUsed = 0;     /* VRC_OPT_GRID_WALK_USED: did the last vrc_render find its bricks through the grid? */
 
     vrc_stats stats = {};
+
+    /* frame histogram (vrc_frame_histogram): uint64 bins on the device, the refs of the last calls staged through a
+     * pinned ring (an area is rewritten only after the copy that read it has run) */
+    unsigned long long* dFrameHist = nullptr;
+    unsigned long long* hFrameHist = nullptr; /* pinned */
+    uint32_t frameHistCap = 0, frameHistBins = 0;
+    vrc_hist_ref* dHistRefs = nullptr;
+    vrc_hist_ref* hHistRefs = nullptr; /* pinned, kNodeStages areas of histRefsCap */
+    size_t histRefsCap = 0;
+    hipEvent_t histRefsEvent[kNodeStages] = { nullptr, nullptr, nullptr, nullptr };
+    bool histRefsUsed[kNodeStages] = { false, false, false, false };
+    uint32_t histRefsNext = 0;
 };
 
 int vrc_internal_fail( int code, const std::string& msg ) { return fail( code, msg ); }
@@ -314,6 +335,12 @@ void vrc_ctx_destroy( vrc_ctx* c )
     if( c->dRowMap ) (void)hipFree( c->dRowMap );
     if( c->dCounter ) (void)hipFree( c->dCounter );
     if( c->hCounter ) (void)hipHostFree( c->hCounter );
+    if( c->dFrameHist ) (void)hipFree( c->dFrameHist );
+    if( c->hFrameHist ) (void)hipHostFree( c->hFrameHist );
+    if( c->dHistRefs ) (void)hipFree( c->dHistRefs );
+    if( c->hHistRefs ) (void)hipHostFree( c->hHistRefs );
+    for( hipEvent_t e : c->histRefsEvent )
+        if( e ) (void)hipEventDestroy( e );
     for( auto& pr : c->evPairs )
     {
         (void)hipEventDestroy( pr.first );
@@ -488,6 +515,10 @@ int vrc_pool_create( vrc_ctx* c, size_t bytesPerVoxel, int isSigned, int isFloat
      * per-ray LOD kernels, whose slot bases are 32-bit, are not offered for such a pool) */
     p->bigAtlas = p->atlasBytes / p->elemBytes >= 0xFFFFFFFFull;
 
+    const size_t nSlots = (size_t)p->slots[0] * p->slots[1] * p->slots[2];
+    p->resident.assign( nSlots, 0 );
+    p->slotSize.assign( nSlots, { 0u, 0u, 0u } );
+
     /* cuda/TexturePool.cu:137-144: i,j,k descending, k innermost; slots are popped from the back */
     for( int i = (int)p->slots[0] - 1; i >= 0; --i )
         for( int j = (int)p->slots[1] - 1; j >= 0; --j )
@@ -550,6 +581,7 @@ void vrc_pool_destroy( vrc_pool* p )
         (void)hipEventDestroy( f.event );
     if( p->uploadStream ) (void)hipStreamDestroy( p->uploadStream );
     if( p->dPacked ) (void)hipFree( p->dPacked );
+    if( p->dHist ) (void)hipFree( p->dHist );
     if( p->dAtlas ) (void)hipFree( p->dAtlas );
     delete p;
 }
@@ -579,6 +611,53 @@ static void pool_slot_voxel( const vrc_pool* p, const float slot[3], uint32_t o[
     /* cuda/TexturePool.cu:193-197 */
     for( int a = 0; a < 3; ++a )
         o[a] = (uint32_t)std::lround( slot[a] * (float)p->atlasDim[a] );
+}
+
+/* linear index of the slot at atlas voxel o (the row of its histogram) */
+static uint32_t pool_slot_index( const vrc_pool* p, const uint32_t o[3] )
+{
+    return ( ( o[2] / p->slotDim[2] ) * p->slots[1] + o[1] / p->slotDim[1] ) * p->slots[0] + o[0] / p->slotDim[0];
+}
+static vrc_layout pool_layout( const vrc_pool* p )
+{
+    vrc_layout lay;
+    for( int a = 0; a < 3; ++a )
+    {
+        lay.slots[a] = p->slots[a];
+        lay.slotDim[a] = p->slotDim[a];
+    }
+    return lay;
+}
+/* the histogram entry of slot `index` holding a brick of `size` voxels: its interior [overlap, size - overlap)
+ * (HistogramObject.cpp:94-97); false if the interior is empty (the row stays zero) */
+static bool pool_hist_entry( const vrc_pool* p, uint32_t index, const uint32_t size[3], vrc_hist_entry& en )
+{
+    const uint32_t i = index % p->slots[0], j = ( index / p->slots[0] ) % p->slots[1],
+                   k = index / ( p->slots[0] * p->slots[1] );
+    en = vrc_hist_entry{};
+    en.base = vrc_slot_base( pool_layout( p ), i, j, k );
+    en.row = index;
+    for( int a = 0; a < 3; ++a )
+    {
+        if( size[a] <= 2u * p->histOverlap[a] )
+            return false;
+        en.origin[a] = p->histOverlap[a];
+        en.size[a] = size[a] - 2u * p->histOverlap[a];
+    }
+    return true;
+}
+/* zero the row of slot `index` and bin the brick of `size` voxels into it, on the upload stream (caller holds mutex) */
+static hipError_t pool_bin_slot( vrc_pool* p, uint32_t index, const uint32_t size[3] )
+{
+    hipError_t e = hipMemsetAsync( p->dHist + (size_t)index * p->histBins, 0, p->histBins * sizeof( uint32_t ),
+                                   p->uploadStream );
+    vrc_hist_entry en;
+    if( e == hipSuccess && pool_hist_entry( p, index, size, en ) )
+        e = vrc_launch_bin_bricks( p->dAtlas, p->elemBytes, p->slotDim, nullptr, 0, &en, 0, p->histBins, p->dHist,
+                                   p->uploadStream );
+    if( e == hipSuccess )
+        p->histValid[index] = 1;
+    return e;
 }
 
 static int pool_check_size( const vrc_pool* p, const uint32_t size[3] )
@@ -653,6 +732,12 @@ static int pool_upload( vrc_pool* p, const void* src, bool srcIsDevice, const ui
                 e = vrc_launch_pack_slots( p->dAtlas, p->dPacked, base,
                                            (uint64_t)p->slotDim[0] * p->slotDim[1] * p->slotDim[2], p->slotDim,
                                            p->elemBytes, p->uploadStream );
+            const uint32_t index = pool_slot_index( p, o );
+            p->resident[index] = 1;
+            p->slotSize[index] = { size[0], size[1], size[2] };
+            /* the slot's histogram row, behind the repack and before lastUpload (vrc_pool_enable_histograms) */
+            if( e == hipSuccess && p->histBins )
+                e = pool_bin_slot( p, index, size );
             if( e == hipSuccess )
                 e = hipEventRecord( st.done, p->uploadStream );
             if( e == hipSuccess )
@@ -751,7 +836,16 @@ int vrc_pool_release_slot( vrc_pool* p, const float slot[3] )
         return fail( VRC_EINVAL, "vrc_pool_release_slot: NULL argument" );
     if( slot[0] < 0.f || slot[1] < 0.f || slot[2] < 0.f )
         return fail( VRC_EINVAL, "vrc_pool_release_slot: invalid slot" );
+    uint32_t o[3];
+    pool_slot_voxel( p, slot, o );
     std::lock_guard< std::mutex > lock( p->mutex );
+    const uint32_t index = pool_slot_index( p, o );
+    if( index < p->resident.size() )
+    {
+        p->resident[index] = 0;
+        if( index < p->histValid.size() )
+            p->histValid[index] = 0;
+    }
     p->freeList.push_back( { slot[0], slot[1], slot[2], 1.0f } );
     return VRC_OK;
 }
@@ -833,32 +927,131 @@ int vrc_pool_histogram( vrc_pool* p, const float slot[3], const uint32_t origin[
     for( int a = 0; a < 3; ++a )
         if( (uint64_t)origin[a] + size[a] > p->slotDim[a] )
             return fail( VRC_EINVAL, "vrc_pool_histogram: region outside the slot" );
+    for( int a = 0; a < 3; ++a )
+        if( size[a] == 0 )
+        {
+            std::fill( hostBins, hostBins + binCount, (uint64_t)0 );
+            return VRC_OK;
+        }
     VRC_HIP_CHECK( hipSetDevice( p->device ) );
     uint32_t o[3];
     pool_slot_voxel( p, slot, o );
-    vrc_layout lay;
+    vrc_hist_entry en = {};
+    en.base = vrc_slot_base( pool_layout( p ), o[0] / p->slotDim[0], o[1] / p->slotDim[1], o[2] / p->slotDim[2] );
     for( int a = 0; a < 3; ++a )
     {
-        lay.slots[a] = p->slots[a];
-        lay.slotDim[a] = p->slotDim[a];
+        en.origin[a] = origin[a];
+        en.size[a] = size[a];
     }
-    const uint64_t base = vrc_slot_base( lay, o[0] / p->slotDim[0], o[1] / p->slotDim[1], o[2] / p->slotDim[2] );
-    unsigned long long* dBins = nullptr;
-    VRC_HIP_CHECK( hipMalloc( &dBins, binCount * sizeof( unsigned long long ) ) );
+    /* the brick binning kernel into one row of uint32 counts (a slot holds < 2^24 voxels), scaled on the host */
+    uint32_t* dRow = nullptr;
+    VRC_HIP_CHECK( hipMalloc( &dRow, binCount * sizeof( uint32_t ) ) );
+    std::vector< uint32_t > row( binCount );
     /* on the upload stream: ordered after the brick's own upload */
-    hipError_t e = hipMemsetAsync( dBins, 0, binCount * sizeof( unsigned long long ), p->uploadStream );
+    hipError_t e = hipMemsetAsync( dRow, 0, binCount * sizeof( uint32_t ), p->uploadStream );
     if( e == hipSuccess )
-        e = vrc_launch_brick_histogram( (const uint8_t*)p->dAtlas + (size_t)base * p->elemBytes, p->elemBytes,
-                                        p->slotDim[0] / VRC_MB, p->slotDim[1] / VRC_MB, origin, size,
-                                        binCount, (unsigned long long)scaleFactor, dBins, p->uploadStream );
+        e = vrc_launch_bin_bricks( p->dAtlas, p->elemBytes, p->slotDim, nullptr, 0, &en, 0, binCount, dRow,
+                                   p->uploadStream );
     if( e == hipSuccess )
-        e = hipMemcpyAsync( hostBins, dBins, binCount * sizeof( unsigned long long ), hipMemcpyDeviceToHost,
-                            p->uploadStream );
+        e = hipMemcpyAsync( row.data(), dRow, binCount * sizeof( uint32_t ), hipMemcpyDeviceToHost, p->uploadStream );
     if( e == hipSuccess )
         e = hipStreamSynchronize( p->uploadStream );
-    (void)hipFree( dBins );
+    (void)hipFree( dRow );
     if( e != hipSuccess )
         return fail( VRC_EHIP, std::string( "vrc_pool_histogram: " ) + hipGetErrorString( e ) );
+    for( uint32_t b = 0; b < binCount; ++b )
+        hostBins[b] = (uint64_t)row[b] * scaleFactor;
+    return VRC_OK;
+}
+
+int vrc_pool_enable_histograms( vrc_pool* p, uint32_t binCount, const uint32_t overlap[3] )
+{
+    if( !p )
+        return fail( VRC_EINVAL, "vrc_pool_enable_histograms: pool is NULL" );
+    const uint32_t typeRange = p->elemBytes == 1 ? 256u : 65536u;
+    if( binCount != 0 && ( !overlap || binCount > VRC_HIST_MAX_BINS || typeRange % binCount != 0 ) )
+        return fail( VRC_EINVAL, "vrc_pool_enable_histograms: bin count must divide the voxel type's range (max 4096), "
+                                 "overlap must be given" );
+    if( binCount != 0 && VRC_LAYOUT != 0 )
+        return fail( VRC_EUNSUPPORTED, "vrc_pool_enable_histograms: needs the product's atlas layout" );
+    if( binCount != 0 )
+        for( int a = 0; a < 3; ++a )
+            if( overlap[a] >= p->slotDim[a] )
+                return fail( VRC_EINVAL, "vrc_pool_enable_histograms: overlap larger than the slot" );
+    VRC_HIP_CHECK( hipSetDevice( p->device ) );
+    std::lock_guard< std::mutex > lock( p->mutex );
+    if( binCount == p->histBins && ( binCount == 0 || std::equal( overlap, overlap + 3, p->histOverlap ) ) )
+        return VRC_OK;
+    if( p->dHist )
+    {
+        /* a frame reduction may still read the table: wait for the device before freeing it */
+        VRC_HIP_CHECK( hipDeviceSynchronize() );
+        VRC_HIP_CHECK( hipFree( p->dHist ) );
+        p->dHist = nullptr;
+    }
+    p->histBins = 0;
+    p->histValid.clear();
+    if( binCount == 0 )
+        return VRC_OK;
+    const size_t nSlots = p->resident.size();
+    hipError_t e = hipMalloc( &p->dHist, nSlots * binCount * sizeof( uint32_t ) );
+    if( e != hipSuccess )
+    {
+        p->dHist = nullptr;
+        (void)hipGetLastError();
+        return fail( e == hipErrorOutOfMemory ? VRC_ENOMEM : VRC_EHIP,
+                     std::string( "vrc_pool_enable_histograms: " ) + hipGetErrorString( e ) );
+    }
+    p->histBins = binCount;
+    std::copy( overlap, overlap + 3, p->histOverlap );
+    p->histValid.assign( nSlots, 0 );
+    /* the bricks resident now: one launch over all of them, behind every upload queued so far */
+    std::vector< vrc_hist_entry > entries;
+    uint64_t maxVoxels = 0;
+    for( uint32_t index = 0; index < nSlots; ++index )
+        if( p->resident[index] )
+        {
+            vrc_hist_entry en;
+            if( pool_hist_entry( p, index, p->slotSize[index].data(), en ) )
+            {
+                entries.push_back( en );
+                maxVoxels = std::max< uint64_t >( maxVoxels, (uint64_t)en.size[0] * en.size[1] * en.size[2] );
+            }
+            p->histValid[index] = 1;
+        }
+    vrc_hist_entry* dEntries = nullptr;
+    e = hipMemsetAsync( p->dHist, 0, nSlots * binCount * sizeof( uint32_t ), p->uploadStream );
+    if( e == hipSuccess && !entries.empty() )
+        e = hipMalloc( &dEntries, entries.size() * sizeof( vrc_hist_entry ) );
+    for( size_t first = 0; e == hipSuccess && first < entries.size(); first += 65535u )
+    {
+        const uint32_t n = (uint32_t)std::min< size_t >( 65535u, entries.size() - first );
+        e = hipMemcpyAsync( dEntries + first, entries.data() + first, n * sizeof( vrc_hist_entry ),
+                            hipMemcpyHostToDevice, p->uploadStream );
+        if( e == hipSuccess )
+            e = vrc_launch_bin_bricks( p->dAtlas, p->elemBytes, p->slotDim, dEntries + first, n, nullptr, maxVoxels,
+                                       binCount, p->dHist, p->uploadStream );
+    }
+    if( e == hipSuccess )
+        e = hipEventRecord( p->lastUpload, p->uploadStream );
+    if( e == hipSuccess )
+        p->hasUpload = true;
+    if( dEntries )
+    {
+        const hipError_t e2 = hipStreamSynchronize( p->uploadStream ); /* the entries are read by the launch */
+        (void)hipFree( dEntries );
+        if( e == hipSuccess )
+            e = e2;
+    }
+    if( e != hipSuccess )
+    {
+        (void)hipStreamSynchronize( p->uploadStream );
+        (void)hipFree( p->dHist );
+        p->dHist = nullptr;
+        p->histBins = 0;
+        p->histValid.clear();
+        return fail( VRC_EHIP, std::string( "vrc_pool_enable_histograms: " ) + hipGetErrorString( e ) );
+    }
     return VRC_OK;
 }
 
@@ -1561,6 +1754,124 @@ int vrc_get_stats( vrc_ctx* c, vrc_stats* out )
             c->stats.samples = 0;
     }
     *out = c->stats;
+    return VRC_OK;
+}
+
+int vrc_frame_histogram( vrc_ctx* c, vrc_pool* pool, const float* slots, const uint64_t* scales, uint32_t n,
+                         int accumulate )
+{
+    if( !c || !pool || ( n && ( !slots || !scales ) ) )
+        return fail( VRC_EINVAL, "vrc_frame_histogram: NULL argument" );
+    if( accumulate && c->frameHistBins == 0 )
+        return fail( VRC_EINVAL, "vrc_frame_histogram: nothing to accumulate into" );
+    VRC_HIP_CHECK( hipSetDevice( c->device ) );
+    uint32_t bins = 0;
+    const uint32_t* dRows = nullptr;
+    std::vector< vrc_hist_ref > refs( n );
+    {
+        std::lock_guard< std::mutex > lock( pool->mutex );
+        bins = pool->histBins;
+        dRows = pool->dHist;
+        if( bins == 0 )
+            return fail( VRC_EINVAL, "vrc_frame_histogram: the pool keeps no histograms (vrc_pool_enable_histograms)" );
+        for( uint32_t i = 0; i < n; ++i )
+        {
+            const float* s = slots + 3 * (size_t)i;
+            if( !( s[0] >= 0.f && s[1] >= 0.f && s[2] >= 0.f && s[0] < 1.f && s[1] < 1.f && s[2] < 1.f ) )
+                return fail( VRC_EINVAL, "vrc_frame_histogram: invalid slot" );
+            uint32_t o[3];
+            pool_slot_voxel( pool, s, o );
+            const uint32_t index = pool_slot_index( pool, o );
+            if( index >= pool->histValid.size() || !pool->histValid[index] )
+                return fail( VRC_EINVAL, "vrc_frame_histogram: a slot holds no binned brick" );
+            refs[i].row = index;
+            refs[i].pad = 0;
+            refs[i].scale = scales[i];
+        }
+    }
+    if( accumulate && c->frameHistBins != bins )
+        return fail( VRC_EINVAL, "vrc_frame_histogram: the bin count changed inside a frame" );
+    if( c->frameHistCap < bins )
+    {
+        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+        if( c->dFrameHist ) VRC_HIP_CHECK( hipFree( c->dFrameHist ) );
+        if( c->hFrameHist ) VRC_HIP_CHECK( hipHostFree( c->hFrameHist ) );
+        c->dFrameHist = nullptr;
+        c->hFrameHist = nullptr;
+        c->frameHistCap = 0;
+        VRC_HIP_CHECK( hipMalloc( &c->dFrameHist, bins * sizeof( unsigned long long ) ) );
+        VRC_HIP_CHECK( hipHostMalloc( &c->hFrameHist, bins * sizeof( unsigned long long ) ) );
+        c->frameHistCap = bins;
+    }
+    if( n > c->histRefsCap )
+    {
+        /* grow the pinned ring and the device list: wait for every copy that reads the old ones */
+        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+        if( c->hHistRefs ) VRC_HIP_CHECK( hipHostFree( c->hHistRefs ) );
+        if( c->dHistRefs ) VRC_HIP_CHECK( hipFree( c->dHistRefs ) );
+        c->hHistRefs = nullptr;
+        c->dHistRefs = nullptr;
+        c->histRefsCap = 0;
+        const size_t cap = std::max< size_t >( 1024, n );
+        VRC_HIP_CHECK( hipHostMalloc( &c->hHistRefs, kNodeStages * cap * sizeof( vrc_hist_ref ) ) );
+        VRC_HIP_CHECK( hipMalloc( &c->dHistRefs, cap * sizeof( vrc_hist_ref ) ) );
+        c->histRefsCap = cap;
+        for( int s = 0; s < kNodeStages; ++s )
+            c->histRefsUsed[s] = false;
+    }
+    /* the rows are written on the pool's upload stream */
+    {
+        std::lock_guard< std::mutex > lock( pool->mutex );
+        if( pool->hasUpload )
+            VRC_HIP_CHECK( hipStreamWaitEvent( c->stream, pool->lastUpload, 0 ) );
+    }
+    if( n )
+    {
+        const uint32_t s = c->histRefsNext++ % kNodeStages;
+        if( !c->histRefsEvent[s] )
+            VRC_HIP_CHECK( hipEventCreateWithFlags( &c->histRefsEvent[s], hipEventDisableTiming ) );
+        if( c->histRefsUsed[s] )
+            VRC_HIP_CHECK( hipEventSynchronize( c->histRefsEvent[s] ) );
+        vrc_hist_ref* const h = c->hHistRefs + s * c->histRefsCap;
+        std::memcpy( h, refs.data(), n * sizeof( vrc_hist_ref ) );
+        VRC_HIP_CHECK( hipMemcpyAsync( c->dHistRefs, h, n * sizeof( vrc_hist_ref ), hipMemcpyHostToDevice, c->stream ) );
+        VRC_HIP_CHECK( hipEventRecord( c->histRefsEvent[s], c->stream ) );
+        c->histRefsUsed[s] = true;
+    }
+    VRC_HIP_CHECK( vrc_launch_frame_histogram( dRows, bins, c->dHistRefs, n, c->dFrameHist, accumulate != 0, c->stream ) );
+    c->frameHistBins = bins;
+    {
+        /* the context's render fence on the pool (pool_upload) now stands behind this reduction too: an upload that
+         * recycles one of these slots does not overwrite its row while the reduction reads it */
+        std::lock_guard< std::mutex > lock( pool->mutex );
+        hipEvent_t fence = nullptr;
+        for( const auto& f : pool->renderFences )
+            if( f.ctx == c )
+                fence = f.event;
+        if( !fence )
+        {
+            VRC_HIP_CHECK( hipEventCreateWithFlags( &fence, hipEventDisableTiming ) );
+            pool->renderFences.push_back( { c, fence } );
+        }
+        VRC_HIP_CHECK( hipEventRecord( fence, c->stream ) );
+    }
+    return VRC_OK;
+}
+
+int vrc_get_frame_histogram( vrc_ctx* c, uint64_t* hostBins, uint32_t binCount )
+{
+    if( !c || !hostBins )
+        return fail( VRC_EINVAL, "vrc_get_frame_histogram: NULL argument" );
+    if( c->frameHistBins == 0 )
+        return fail( VRC_EINVAL, "vrc_get_frame_histogram: no frame histogram yet (vrc_frame_histogram)" );
+    if( binCount != c->frameHistBins )
+        return fail( VRC_EINVAL, "vrc_get_frame_histogram: the frame histogram has " +
+                                     std::to_string( c->frameHistBins ) + " bins" );
+    VRC_HIP_CHECK( hipSetDevice( c->device ) );
+    VRC_HIP_CHECK( hipMemcpyAsync( c->hFrameHist, c->dFrameHist, binCount * sizeof( unsigned long long ),
+                                   hipMemcpyDeviceToHost, c->stream ) );
+    VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+    std::memcpy( hostBins, c->hFrameHist, binCount * sizeof( uint64_t ) );
     return VRC_OK;
 }
 

@@ -84,12 +84,31 @@ hipError_t vrc_launch_read_region( const void* atlas, void* dstRowMajor, uint32_
                                    const uint32_t origin[3], const uint32_t size[3],
                                    const vrc_layout& lay, hipStream_t stream );
 
-/* histogram of the voxels [origin, origin+size) of one slot (slot-local coordinates): bins[v /
- * (typeRange / binCount)] += scale per voxel; bins is device memory, zeroed by the caller */
-hipError_t vrc_launch_brick_histogram( const void* slot, uint32_t elemBytes, uint32_t sbx, uint32_t sby,
-                                       const uint32_t origin[3], const uint32_t size[3],
-                                       uint32_t binCount, unsigned long long scale,
-                                       unsigned long long* bins, hipStream_t stream );
+/* brick histograms (vrc_kernels.hip): an entry is a region of one slot and the row of `rows` its counts are added to
+ * (uint32, binCount per row; the caller zeroes the rows).  Bin = v / (typeRange / binCount); 8- or 16-bit voxels,
+ * binCount a divisor of the type's range, at most VRC_HIST_MAX_BINS.  maxRegionVoxels: the largest region of the list
+ * (sizes the launch).  one != NULL: a single entry passed by value (no device list) */
+#define VRC_HIST_MAX_BINS 4096u
+struct vrc_hist_entry
+{
+    uint64_t base;      /* element offset of the slot in the atlas */
+    uint32_t origin[3]; /* region, slot-local voxels */
+    uint32_t size[3];
+    uint32_t row;
+    uint32_t pad;
+};
+hipError_t vrc_launch_bin_bricks( const void* atlas, uint32_t elemBytes, const uint32_t slotDim[3],
+                                  const vrc_hist_entry* dEntries, uint32_t nEntries, const vrc_hist_entry* one,
+                                  uint64_t maxRegionVoxels, uint32_t binCount, uint32_t* rows, hipStream_t stream );
+/* frame histogram: out[b] = (out[b] if accumulate) + sum_i rows[refs[i].row][b] * refs[i].scale (uint64) */
+struct vrc_hist_ref
+{
+    uint32_t row;
+    uint32_t pad;
+    uint64_t scale;
+};
+hipError_t vrc_launch_frame_histogram( const uint32_t* rows, uint32_t binCount, const vrc_hist_ref* dRefs, uint32_t n,
+                                       unsigned long long* out, bool accumulate, hipStream_t stream );
 
 #define VRC_MAX_ERT_PARTS 8
 

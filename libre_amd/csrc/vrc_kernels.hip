@@ -144,55 +144,199 @@ __global__ void vrc_k_read_region( const T* __restrict__ atlas, T* __restrict__ 
 }
 
 /* ------------------------------------------------------------------------------------------
- * brick histogram, a side kernel on a resident brick (livre/lib/cache/HistogramObject.cpp:36-119
- * computes it on the CPU from the data cache): interior voxels only (the overlap is skipped,
- * :94-97), integral types are binned over the type's range (:48-52, :104-110), every voxel
- * counts scaleFactor times (:111).  One LDS histogram per workgroup, then 64-bit global adds.
+ * Brick histograms (livre/lib/cache/HistogramObject.cpp:36-119 bins the CPU copy of a brick):
+ * voxels of a region of a slot, integral types binned over the type's range (:48-52, :104-110).
+ * ONE kernel bins a list of (slot, region, row) entries in one launch: the pool's per-slot rows
+ * when a brick lands (or for every resident brick when the feature is turned on), and the one
+ * region of vrc_pool_histogram.
+ *
+ * The slot is read in its physical order (VRC_LAYOUT 0, vrc_core.h): 8x8x8 micro-blocks, inside
+ * a block 64 rows of 8 voxels.  A lane loads 16 bytes = two rows (y, y + 1) of 8-bit voxels or
+ * one row of 16-bit voxels and masks out the voxels outside the region; only the micro-blocks
+ * that meet the region are read.  Equal neighbours inside a lane's 16 bytes are counted as one
+ * run (a constant brick: one LDS add per lane instead of 16 on the same bin), and every wave has
+ * its own sub-histogram in LDS (up to VRC_HIST_SUBS).  Counts are integers throughout: the
+ * result is exact and the same on every run.
  * ---------------------------------------------------------------------------------------- */
+#define VRC_HIST_THREADS 256u
+#define VRC_HIST_SUBS 4u /* = waves per workgroup */
+#define VRC_HIST_UNROLL 4u
+
 template < typename T >
-__global__ __launch_bounds__( 256 ) void vrc_k_brick_histogram(
-    const T* __restrict__ slot, uint32_t sbx, uint32_t sby, uint32_t ox, uint32_t oy, uint32_t oz,
-    uint32_t nx, uint32_t ny, uint32_t nz, uint32_t binCount, uint32_t perBin,
-    unsigned long long scale, unsigned long long* __restrict__ bins )
+__global__ __launch_bounds__( VRC_HIST_THREADS ) void vrc_k_bin_bricks(
+    const T* __restrict__ atlas, const vrc_hist_entry* __restrict__ entries, const vrc_hist_entry one, uint32_t sbx,
+    uint32_t sby, uint32_t binCount, uint32_t binShift, uint32_t nSubs, uint32_t* __restrict__ rows )
 {
-    __shared__ uint32_t h[4096];
-    for( uint32_t i = threadIdx.x; i < binCount; i += blockDim.x )
-        h[i] = 0;
+    extern __shared__ uint32_t vrc_hist_lds[];
+    constexpr uint32_t kVox = 16u / sizeof( T );         /* voxels per 16-byte load */
+    constexpr uint32_t kPerBlock = VRC_MB_VOXELS / kVox; /* loads per micro-block */
+    const vrc_hist_entry en = entries ? entries[blockIdx.y] : one;
+    for( uint32_t i = threadIdx.x; i < binCount * nSubs; i += blockDim.x )
+        vrc_hist_lds[i] = 0u;
     __syncthreads();
-    const size_t total = (size_t)nx * ny * nz;
-    for( size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * blockDim.x )
+    uint32_t* const h = vrc_hist_lds + ( ( threadIdx.x >> 6 ) % nSubs ) * binCount;
+
+    /* micro-blocks that meet the region */
+    const uint32_t b0x = en.origin[0] >> 3, b0y = en.origin[1] >> 3, b0z = en.origin[2] >> 3;
+    const uint32_t nbx = ( ( en.origin[0] + en.size[0] - 1u ) >> 3 ) - b0x + 1u;
+    const uint32_t nby = ( ( en.origin[1] + en.size[1] - 1u ) >> 3 ) - b0y + 1u;
+    const uint32_t nbz = ( ( en.origin[2] + en.size[2] - 1u ) >> 3 ) - b0z + 1u;
+    const uint32_t nLoads = nbx * nby * nbz * kPerBlock;
+    const uint32_t perGroup = ( ( nLoads + gridDim.x - 1u ) / gridDim.x + VRC_HIST_THREADS - 1u ) /
+                              VRC_HIST_THREADS * VRC_HIST_THREADS;
+    const uint32_t first = blockIdx.x * perGroup;
+    const uint32_t last = min( first + perGroup, nLoads );
+    const uint4* const slot = (const uint4*)( atlas + en.base );
+
+    for( uint32_t i0 = first + threadIdx.x; i0 < last; i0 += VRC_HIST_THREADS * VRC_HIST_UNROLL )
     {
-        const uint32_t x = (uint32_t)( i % nx ), y = (uint32_t)( ( i / nx ) % ny ),
-                       z = (uint32_t)( i / ( (size_t)nx * ny ) );
-        const uint32_t v = (uint32_t)slot[vrc_slot_local_index( ox + x, oy + y, oz + z, sbx, sby )];
-        atomicAdd( &h[v / perBin], 1u );
+        uint4 q[VRC_HIST_UNROLL];
+#pragma unroll
+        for( uint32_t u = 0; u < VRC_HIST_UNROLL; ++u )
+        {
+            const uint32_t i = i0 + u * VRC_HIST_THREADS;
+            q[u] = make_uint4( 0u, 0u, 0u, 0u );
+            if( i < last )
+            {
+                const uint32_t blk = i / kPerBlock, inner = ( i % kPerBlock ) * kVox;
+                const uint32_t bx = b0x + blk % nbx, by = b0y + ( blk / nbx ) % nby, bz = b0z + blk / ( nbx * nby );
+                q[u] = slot[( ( ( bz * sby + by ) * sbx + bx ) * VRC_MB_VOXELS + inner ) / kVox];
+            }
+        }
+#pragma unroll
+        for( uint32_t u = 0; u < VRC_HIST_UNROLL; ++u )
+        {
+            const uint32_t i = i0 + u * VRC_HIST_THREADS;
+            if( i >= last )
+                continue;
+            const uint32_t blk = i / kPerBlock, inner = ( i % kPerBlock ) * kVox;
+            const uint32_t bx = b0x + blk % nbx, by = b0y + ( blk / nbx ) % nby, bz = b0z + blk / ( nbx * nby );
+            /* inverse of vrc_mb_y / vrc_mb_z: inner bits 3-4 = y & 3, 5-6 = z & 3, 7 = y & 4, 8 = z & 4 */
+            const uint32_t y = by * 8u + ( ( ( inner >> 3 ) & 3u ) | ( ( inner >> 5 ) & 4u ) );
+            const uint32_t z = bz * 8u + ( ( ( inner >> 5 ) & 3u ) | ( ( inner >> 6 ) & 4u ) );
+            const bool zIn = z - en.origin[2] < en.size[2];
+            /* x mask of the row: voxel j of the row (x = 8 bx + j) lies in [origin, origin + size) */
+            uint32_t xm = 0u;
+#pragma unroll
+            for( uint32_t j = 0; j < 8u; ++j )
+                xm |= ( bx * 8u + j - en.origin[0] < en.size[0] ? 1u : 0u ) << j;
+            uint32_t m = ( zIn && y - en.origin[1] < en.size[1] ) ? xm : 0u;
+            if( kVox == 16u && zIn && y + 1u - en.origin[1] < en.size[1] )
+                m |= xm << 8;
+            const uint32_t w[4] = { q[u].x, q[u].y, q[u].z, q[u].w };
+            uint32_t run = 0u, count = 0u;
+#pragma unroll
+            for( uint32_t k = 0; k < kVox; ++k )
+            {
+                if( !( ( m >> k ) & 1u ) )
+                    continue;
+                const uint32_t v = kVox == 16u ? ( w[k >> 2] >> ( ( k & 3u ) * 8u ) ) & 0xFFu
+                                               : ( w[k >> 1] >> ( ( k & 1u ) * 16u ) ) & 0xFFFFu;
+                const uint32_t b = v >> binShift;
+                if( count && b == run )
+                    ++count;
+                else
+                {
+                    if( count )
+                        atomicAdd( &h[run], count );
+                    run = b;
+                    count = 1u;
+                }
+            }
+            if( count )
+                atomicAdd( &h[run], count );
+        }
     }
     __syncthreads();
-    for( uint32_t i = threadIdx.x; i < binCount; i += blockDim.x )
-        if( h[i] )
-            atomicAdd( &bins[i], (unsigned long long)h[i] * scale );
+    uint32_t* const row = rows + (size_t)en.row * binCount;
+    for( uint32_t b = threadIdx.x; b < binCount; b += blockDim.x )
+    {
+        uint32_t s = 0u;
+        for( uint32_t k = 0; k < nSubs; ++k )
+            s += vrc_hist_lds[k * binCount + b];
+        if( s )
+            atomicAdd( &row[b], s );
+    }
 }
 
-hipError_t vrc_launch_brick_histogram( const void* slot, uint32_t elemBytes, uint32_t sbx, uint32_t sby,
-                                       const uint32_t origin[3], const uint32_t size[3],
-                                       uint32_t binCount, unsigned long long scale,
-                                       unsigned long long* bins, hipStream_t stream )
+hipError_t vrc_launch_bin_bricks( const void* atlas, uint32_t elemBytes, const uint32_t slotDim[3],
+                                  const vrc_hist_entry* dEntries, uint32_t nEntries, const vrc_hist_entry* one,
+                                  uint64_t maxRegionVoxels, uint32_t binCount, uint32_t* rows, hipStream_t stream )
 {
-    const size_t total = (size_t)size[0] * size[1] * size[2];
-    if( total == 0 || binCount == 0 || binCount > 4096 )
+    const vrc_hist_entry single = one ? *one : vrc_hist_entry{};
+    if( one )
+    {
+        dEntries = nullptr;
+        nEntries = 1;
+        maxRegionVoxels = (uint64_t)one->size[0] * one->size[1] * one->size[2];
+    }
+    if( nEntries == 0 )
+        return hipSuccess;
+    const uint32_t range = elemBytes == 1 ? 256u : 65536u;
+    if( ( elemBytes != 1 && elemBytes != 2 ) || binCount == 0 || binCount > VRC_HIST_MAX_BINS ||
+        range % binCount != 0 || VRC_LAYOUT != 0 || nEntries > 65535u )
         return hipErrorInvalidValue;
-    const uint32_t blocks = (uint32_t)std::min< size_t >( ( total + 255 ) / 256, 1024 );
-    if( elemBytes == 1 && 256u % binCount == 0 )
-        hipLaunchKernelGGL( vrc_k_brick_histogram< uint8_t >, dim3( blocks ), dim3( 256 ), 0, stream,
-                            (const uint8_t*)slot, sbx, sby, origin[0], origin[1], origin[2], size[0],
-                            size[1], size[2], binCount, 256u / binCount, scale, bins );
-    else if( elemBytes == 2 && 65536u % binCount == 0 )
-        hipLaunchKernelGGL( vrc_k_brick_histogram< uint16_t >, dim3( blocks ), dim3( 256 ), 0, stream,
-                            (const uint16_t*)slot, sbx, sby, origin[0], origin[1], origin[2], size[0],
-                            size[1], size[2], binCount, 65536u / binCount, scale, bins );
+    uint32_t shift = 0;
+    while( ( binCount << shift ) < range )
+        ++shift; /* every divisor of 2^8 / 2^16 is a power of two: range / binCount = 2^shift */
+    /* enough workgroups to fill the GPU when the list is short (one brick behind its upload), about 32 loads per
+     * lane when it is long (the resident set when the feature is turned on) */
+    const uint64_t loads = ( maxRegionVoxels + 511u ) / ( 16u / elemBytes );
+    const uint64_t per32 = VRC_HIST_THREADS * 32u, per2 = VRC_HIST_THREADS * 2u;
+    const uint32_t few = (uint32_t)std::max< uint64_t >( 1u, ( loads + per32 - 1u ) / per32 );
+    const uint32_t many = (uint32_t)std::max< uint64_t >( 1u, ( loads + per2 - 1u ) / per2 );
+    const uint32_t groups = std::max( few, std::min( many, ( 2048u + nEntries - 1u ) / nEntries ) );
+    const uint32_t subs = std::max( 1u, std::min( VRC_HIST_SUBS, 8192u / binCount ) ); /* <= 32 KiB of LDS */
+    const size_t lds = (size_t)subs * binCount * sizeof( uint32_t );
+    const uint32_t sbx = slotDim[0] / VRC_MB, sby = slotDim[1] / VRC_MB;
+    if( elemBytes == 1 )
+        hipLaunchKernelGGL( vrc_k_bin_bricks< uint8_t >, dim3( groups, nEntries ), dim3( VRC_HIST_THREADS ), lds,
+                            stream, (const uint8_t*)atlas, dEntries, single, sbx, sby, binCount, shift, subs, rows );
     else
+        hipLaunchKernelGGL( vrc_k_bin_bricks< uint16_t >, dim3( groups, nEntries ), dim3( VRC_HIST_THREADS ), lds,
+                            stream, (const uint16_t*)atlas, dEntries, single, sbx, sby, binCount, shift, subs, rows );
+    return hipGetLastError();
+}
+
+/* Frame histogram: out[b] (+)= sum over the refs of rows[ref.row][b] * ref.scale, 64-bit.  A workgroup owns 64
+ * bins; its 16 waves take every 16th ref and their partial sums are added in wave order: one owner per bin, no
+ * global atomics, the same bits on every run. */
+#define VRC_FRAME_HIST_WAVES 16u
+__global__ __launch_bounds__( 64 * VRC_FRAME_HIST_WAVES ) void vrc_k_frame_histogram(
+    const uint32_t* __restrict__ rows, uint32_t binCount, const vrc_hist_ref* __restrict__ refs, uint32_t n,
+    unsigned long long* __restrict__ out, int accumulate )
+{
+    __shared__ unsigned long long part[VRC_FRAME_HIST_WAVES][64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t bin = blockIdx.x * 64u + lane;
+    unsigned long long acc = 0ull;
+    if( bin < binCount )
+    {
+#pragma unroll 4
+        for( uint32_t i = wave; i < n; i += VRC_FRAME_HIST_WAVES )
+        {
+            const vrc_hist_ref r = refs[i];
+            acc += (unsigned long long)rows[(size_t)r.row * binCount + bin] * r.scale;
+        }
+    }
+    part[wave][lane] = acc;
+    __syncthreads();
+    if( wave == 0 && bin < binCount )
+    {
+        unsigned long long s = accumulate ? out[bin] : 0ull;
+        for( uint32_t w = 0; w < VRC_FRAME_HIST_WAVES; ++w )
+            s += part[w][lane];
+        out[bin] = s;
+    }
+}
+
+hipError_t vrc_launch_frame_histogram( const uint32_t* rows, uint32_t binCount, const vrc_hist_ref* dRefs, uint32_t n,
+                                       unsigned long long* out, bool accumulate, hipStream_t stream )
+{
+    if( binCount == 0 || binCount > VRC_HIST_MAX_BINS )
         return hipErrorInvalidValue;
+    hipLaunchKernelGGL( vrc_k_frame_histogram, dim3( ( binCount + 63u ) / 64u ), dim3( 64 * VRC_FRAME_HIST_WAVES ), 0,
+                        stream, rows, binCount, dRefs, n, out, accumulate ? 1 : 0 );
     return hipGetLastError();
 }
 

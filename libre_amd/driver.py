@@ -29,6 +29,7 @@ EXPORTS = [
     "lvh_app_set_modelview", "lvh_app_set_time_step", "lvh_datasource_frame_range", "lvh_app_set_colormap", "lvh_app_set_clip_planes",
     "lvh_app_set_bands", "lvh_app_set_frames_in_flight", "lvh_app_select_slot", "lvh_app_set_option", "lvh_app_set_data_range", "lvh_app_set_ray_lod", "lvh_app_set_stream", "lvh_app_set_framebuffer", "lvh_app_render_frame",
     "lvh_app_get_stats", "lvh_app_wait_uploads", "lvh_app_synchronize", "lvh_app_volume_info",
+    "lvh_app_set_histogram", "lvh_app_frame_histogram",
     "lvh_comm_unique_id", "lvh_app_comm_create", "lvh_app_set_layout", "lvh_app_gather_tiles",
     "lvh_app_visible_set", "lvh_app_node_order", "lvh_app_view_matrices", "lvh_app_cache_stats", "lvh_select_visibles",
     "lvh_selftest_cache", "lvh_selftest_plugin_factory", "lvh_selftest_camera",
@@ -67,6 +68,9 @@ def load_library():
     L.lvh_app_get_stats.argtypes = [vp, C.POINTER(FrameStats)]
     L.lvh_app_wait_uploads.argtypes = [vp]
     L.lvh_app_synchronize.argtypes = [vp]
+    L.lvh_app_set_histogram.argtypes = [vp, C.c_int]
+    L.lvh_app_frame_histogram.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                          C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
     L.lvh_app_volume_info.argtypes = [vp, C.c_uint32 * 3, C.c_uint32 * 3, C.c_uint32 * 3,
                                       C.c_float * 3, C.POINTER(C.c_uint32), C.c_uint32 * 3]
     L.lvh_app_visible_set.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
@@ -173,6 +177,19 @@ class App:
         st = FrameStats()
         check(self.L, self.L.lvh_app_get_stats(self.h, C.byref(st)))
         return st
+
+    def set_histogram(self, enable=True):
+        """Frame histogram of the rendered bricks (off by default; include/livre_hip_driver.h)."""
+        check(self.L, self.L.lvh_app_set_histogram(self.h, 1 if enable else 0))
+
+    def frame_histogram(self):
+        """(bins uint64 array, (lo, hi) value range, area share, frame id) of the selected slot's last frame."""
+        n, rng, area, fid = C.c_uint32(), (C.c_float * 2)(), C.c_float(), C.c_uint64()
+        check(self.L, self.L.lvh_app_frame_histogram(self.h, None, 0, C.byref(n), rng, C.byref(area), C.byref(fid)))
+        bins = np.zeros(n.value, dtype=np.uint64)
+        check(self.L, self.L.lvh_app_frame_histogram(self.h, bins.ctypes.data, n.value, C.byref(n), rng,
+                                                      C.byref(area), C.byref(fid)))
+        return bins, (float(rng[0]), float(rng[1])), float(area.value), int(fid.value)
 
     def wait_uploads(self):
         check(self.L, self.L.lvh_app_wait_uploads(self.h))

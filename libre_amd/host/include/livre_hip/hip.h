@@ -9,6 +9,9 @@
 #define LIVRE_HIP_HIP_H
 
 #include <array>
+#include <functional>
+#include <memory>
+#include <unordered_set>
 
 #include "render.h"
 
@@ -54,6 +57,8 @@ public:
     virtual ~HipTextureObject();
     size_t getSize() const final { return _size; }
     Vector3f getTexPosition() const { return _texturePos; }
+    /** normalized origin of the slot (vrc_pool_copy_to_slot): the key of its histogram row */
+    Vector3f getSlotPosition() const { return _slotPosition; }
     Vector3f getTexSize() const { return _textureSize; }
     HipTexturePool& getTexturePool() const { return _texturePool; }
     /** world box of the brick, kept from construction so the per-frame render path does not
@@ -101,7 +106,32 @@ public:
      *  reference (livre/eq/Channel.cpp:519-523) */
     vrc_ctx* deviceContext() const { return _ctx; }
 
+    /** Frame histogram (the reference's HistogramFilter, livre/lib/pipeline/HistogramFilter.cpp:77-132, run by
+     *  CudaRaycastPipeline.cpp:187-200): while on, every render() adds the per-brick histograms of the nodes it
+     *  rendered (kept by the pool, vrc_pool_enable_histograms) times 8^(depth-1-level) to the frame's, each node once
+     *  per frame; preRender (RENDER_BEGIN) starts a new one.  Off by default.  histogramSupported(): false when the
+     *  device layer lacks the entry points (they are bound weakly) -- setHistogram( true ) then throws. */
+    static bool histogramSupported();
+    void setHistogram( bool on );
+    bool histogramOn() const { return _histOn; }
+    /** which nodes this process counts (the centre rule of HistogramFilter.cpp:44-75, given the node's world box);
+     *  empty = every rendered node */
+    void setHistogramFilter( std::function< bool( const Boxf& ) > filter ) { _histFilter = std::move( filter ); }
+    /** per-ray LOD: count only these ids (the SSE cut, not the ancestors added for the walk); NULL = every node */
+    void setHistogramCut( std::shared_ptr< const std::unordered_set< Identifier > > cut ) { _histCut = std::move( cut ); }
+    /** the histogram of the last frame (waits for the render stream); false before the first frame with it on */
+    bool frameHistogram( std::vector< uint64_t >& bins, float range[2] );
+
 private:
+    bool _histOn = false;
+    bool _histFrame = false;     /* preRender has started a frame with the histogram on */
+    bool _histOnDevice = false;  /* ... and the context holds its counts so far */
+    uint32_t _histBins = 0;      /* of that frame: 256 (uint8) / 1024 (uint16), HistogramObject.cpp:164-176 */
+    float _histRange[2] = { 0.f, 0.f };
+    std::unordered_set< Identifier > _histCounted; /* nodes counted in this frame (passes, slabs) */
+    std::function< bool( const Boxf& ) > _histFilter;
+    std::shared_ptr< const std::unordered_set< Identifier > > _histCut;
+    void addToHistogram( const RenderInputs& renderInputs, const ConstCacheObjects& renderData );
     vrc_ctx* _ctx;
     uint32_t _computedSamplesPerRay;
     bool _lastRayLod = false;

@@ -2,6 +2,8 @@
  * Channel::frameDraw around the plugin surface). */
 #include "livre_hip_driver.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "livre_hip/hip.h"
@@ -38,6 +40,64 @@ struct lvh_app
     float dataRange[2] = { 0.0f, 0.0f }; /* lvh_app_set_data_range; empty = the voxel type's range */
     vrc_comm* comm = nullptr;              /* lvh_app_comm_create: sort-first tile exchange */
     std::vector< vrc_band > layout;        /* lvh_app_set_layout: every band of the frame, all ranks */
+    bool histogram = false;                /* lvh_app_set_histogram */
+    struct HistogramFrame                  /* per renderer slot: the area and id of its last frame */
+    {
+        bool valid = false;
+        float area = 0.f;
+        uint64_t frameId = 0;
+    };
+    HistogramFrame histFrames[8];
+
+    /* SendHistogramFilter (livre/eq/Channel.cpp:92-125) counts a node in the channel whose viewport holds the centre of
+     * its box, the frame's borders extended to infinity (HistogramFilter.cpp:44-75).  Here in window coordinates of the
+     * full frame (the same arithmetic on every process), edges half-open [min, max); a centre with clip w <= 0 counts
+     * where pixel (0,0) is.  Returns the filter and this process's share of the frame's area. */
+    std::function< bool( const Boxf& ) > histogramFilter( float* area ) const
+    {
+        uint32_t t[4];
+        tile( t );
+        const float W = float( params.width ), H = float( params.height );
+        const Matrix4f mv = camera.getModelViewMatrix();
+        const Matrix4f proj = perspectiveFrustum( -0.05f, 0.05f, -0.05f, 0.05f, nearPlane, farPlane );
+        auto window = [mv, proj, W, H]( const Boxf& box, float& px, float& py ) {
+            const Vector3f c = box.getCenter();
+            const Vector4f e = mv * Vector4f( c[0], c[1], c[2], 1.0f );
+            const Vector4f clip = proj * e;
+            if( !( clip[3] > 0.0f ) )
+            {
+                px = py = 0.0f;
+                return;
+            }
+            px = ( clip[0] / clip[3] * 0.5f + 0.5f ) * W;
+            py = ( clip[1] / clip[3] * 0.5f + 0.5f ) * H;
+            /* the frame's borders extend to infinity: clamp into [0, W) x [0, H) */
+            px = std::min( std::max( px, 0.0f ), std::nextafter( W, 0.0f ) );
+            py = std::min( std::max( py, 0.0f ), std::nextafter( H, 0.0f ) );
+        };
+        if( !rowMap.empty() )
+        {
+            std::vector< uint8_t > mine( params.height, 0 );
+            for( uint32_t r : rowMap )
+                mine[r] = 1;
+            *area = float( rowMap.size() ) / H;
+            return [window, mine]( const Boxf& box ) {
+                float px, py;
+                window( box, px, py );
+                const size_t row = std::min( size_t( py ), mine.size() - 1 );
+                return mine[row] != 0;
+            };
+        }
+        *area = float( t[2] ) * float( t[3] ) / ( W * H );
+        if( t[0] == 0 && t[1] == 0 && t[2] == params.width && t[3] == params.height )
+            return std::function< bool( const Boxf& ) >(); /* the whole frame: every node */
+        const float x0 = float( t[0] ), x1 = float( t[0] + t[2] ), y0 = float( t[1] ), y1 = float( t[1] + t[3] );
+        return [window, x0, x1, y0, y1]( const Boxf& box ) {
+            float px, py;
+            window( box, px, py );
+            return px >= x0 && px < x1 && py >= y0 && py < y1;
+        };
+    }
 
     Renderer& currentRenderer()
     {
@@ -212,9 +272,16 @@ int lvh_app_set_frames_in_flight( lvh_app* app, uint32_t n )
     try
     {
         while( app->extraRenderers.size() + 1 < n )
+        {
             app->extraRenderers.emplace_back( new Renderer( app->rendererName ) );
+            if( app->histogram )
+                static_cast< HipRaycastRenderer& >( app->extraRenderers.back()->getPlugin() ).setHistogram( true );
+        }
         while( app->extraRenderers.size() + 1 > n )
+        {
+            app->histFrames[app->extraRenderers.size()] = lvh_app::HistogramFrame();
             app->extraRenderers.pop_back();
+        }
         if( app->slot >= n )
             app->slot = 0;
         return 0;
@@ -299,12 +366,74 @@ int lvh_app_render_frame( lvh_app* app, float* host, lvh_frame_stats* stats )
     try
     {
         const RenderInputs in = app->inputs();
+        float area = 0.f;
+        if( app->histogram )
+            app->renderer().setHistogramFilter( app->histogramFilter( &area ) );
         app->lastStats = app->pipeline->getPlugin().render( app->currentRenderer(), in );
+        if( app->histogram )
+        {
+            lvh_app::HistogramFrame& hf = app->histFrames[app->slot];
+            hf.valid = true;
+            hf.area = area;
+            hf.frameId = app->frameId;
+        }
         ++app->frameId;
         if( host )
             app->renderer().readFrame( host );
         if( stats )
             fillStats( app, stats, false );
+        return 0;
+    }
+    catch( const std::exception& e )
+    {
+        return fail( e.what() );
+    }
+}
+
+int lvh_app_set_histogram( lvh_app* app, int enable )
+{
+    if( !app ) return fail( "NULL argument" );
+    try
+    {
+        const bool on = enable != 0;
+        if( on && !HipRaycastRenderer::histogramSupported() )
+            return fail( "lvh_app_set_histogram: the device layer does not support the frame histogram" );
+        static_cast< HipRaycastRenderer& >( app->pipeline->getRenderer().getPlugin() ).setHistogram( on );
+        for( auto& r : app->extraRenderers )
+            static_cast< HipRaycastRenderer& >( r->getPlugin() ).setHistogram( on );
+        app->histogram = on;
+        for( auto& hf : app->histFrames )
+            hf = lvh_app::HistogramFrame();
+        return 0;
+    }
+    catch( const std::exception& e )
+    {
+        return fail( e.what() );
+    }
+}
+
+int lvh_app_frame_histogram( lvh_app* app, uint64_t* bins, uint32_t capacity, uint32_t* binCount, float range[2],
+                             float* area, uint64_t* frameId )
+{
+    if( !app ) return fail( "NULL argument" );
+    if( !app->histogram )
+        return fail( "lvh_app_frame_histogram: the histogram is off (lvh_app_set_histogram)" );
+    const lvh_app::HistogramFrame& hf = app->histFrames[app->slot];
+    try
+    {
+        std::vector< uint64_t > h;
+        float r[2] = { 0.f, 0.f };
+        if( !hf.valid || !app->renderer().frameHistogram( h, r ) )
+            return fail( "lvh_app_frame_histogram: no frame rendered with the histogram on in this slot yet" );
+        if( bins && capacity < h.size() )
+            return fail( "lvh_app_frame_histogram: capacity " + std::to_string( capacity ) + " < " +
+                         std::to_string( h.size() ) + " bins" );
+        if( bins )
+            std::memcpy( bins, h.data(), h.size() * sizeof( uint64_t ) );
+        if( binCount ) *binCount = uint32_t( h.size() );
+        if( range ) { range[0] = r[0]; range[1] = r[1]; }
+        if( area ) *area = hf.area;
+        if( frameId ) *frameId = hf.frameId;
         return 0;
     }
     catch( const std::exception& e )

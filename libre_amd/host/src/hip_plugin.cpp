@@ -18,6 +18,12 @@
 
 #include "vrc_hip.h"
 
+/* the frame-histogram entry points are bound weakly: a device layer without them (the CPU stand-in of the host
+ * tests, tests/host_san/vrc_stub.cpp) leaves them NULL and the plugin reports the histogram as unsupported */
+#pragma weak vrc_pool_enable_histograms
+#pragma weak vrc_frame_histogram
+#pragma weak vrc_get_frame_histogram
+
 extern "C" int LunchboxPluginGetVersion() { return 1; } /* LIVRECORE_VERSION_ABI, CudaRaycastPipeline.cpp:50-51 */
 extern "C" bool LunchboxPluginRegister() { return true; } /* CudaRaycastPipeline.cpp:53-54 */
 
@@ -456,6 +462,82 @@ void HipRaycastRenderer::preRender( const RenderInputs& renderInputs, const Cons
                      "vrc_set_row_map" );
     const vrc_view_data viewData = makeViewData( renderInputs );
     throwOnVrcError( vrc_pre_render( _ctx, &viewData ), "vrc_pre_render" );
+    /* RENDER_BEGIN: a new frame histogram (HistogramFilter.cpp:77-132 builds one per frame) */
+    _histFrame = _histOn;
+    _histOnDevice = false;
+    _histCounted.clear();
+    if( _histOn )
+    {
+        _histBins = volInfo.getBytesPerVoxel() == 1 ? 256u : 1024u; /* HistogramObject.cpp:164-176 */
+        _histRange[0] = 0.f;                                         /* the type's range, :48-52 */
+        _histRange[1] = volInfo.getBytesPerVoxel() == 1 ? 255.f : 65535.f;
+    }
+}
+
+bool HipRaycastRenderer::histogramSupported()
+{
+    return vrc_pool_enable_histograms != nullptr && vrc_frame_histogram != nullptr &&
+           vrc_get_frame_histogram != nullptr;
+}
+
+void HipRaycastRenderer::setHistogram( bool on )
+{
+    if( on && !histogramSupported() )
+        throw std::runtime_error( "frame histogram: the device layer has no vrc_frame_histogram (unsupported)" );
+    _histOn = on;
+    if( !on )
+    {
+        _histFrame = false;
+        _histOnDevice = false;
+    }
+}
+
+/* HistogramFilter.cpp:77-132: the per-brick histograms of the nodes this pass rendered, each node once per frame, those
+ * this process counts (the centre rule, the SSE cut) */
+void HipRaycastRenderer::addToHistogram( const RenderInputs& renderInputs, const ConstCacheObjects& renderData )
+{
+    const VolumeInformation& volInfo = renderInputs.dataSource.getVolumeInfo();
+    const uint32_t depth = volInfo.rootNode.getDepth();
+    std::vector< float > slots;
+    std::vector< uint64_t > scales;
+    vrc_pool* pool = nullptr;
+    for( const auto& obj : renderData )
+    {
+        const HipTextureObject& tex = static_cast< const HipTextureObject& >( *obj );
+        const Identifier id = tex.getId();
+        if( _histCut && !_histCut->count( id ) )
+            continue;
+        if( _histCounted.count( id ) )
+            continue;
+        if( _histFilter && !_histFilter( tex.getWorldBox() ) )
+            continue;
+        _histCounted.insert( id );
+        const Vector3f s = tex.getSlotPosition();
+        slots.insert( slots.end(), { s[0], s[1], s[2] } );
+        const uint32_t level = NodeId( id ).getLevel();
+        scales.push_back( uint64_t( 1 ) << ( 3u * ( depth - 1u - level ) ) ); /* HistogramObject.cpp:158-161 */
+        pool = tex.getTexturePool()._getHipTexturePool();
+    }
+    if( !pool )
+        return;
+    const uint32_t overlap[3] = { volInfo.overlap[0], volInfo.overlap[1], volInfo.overlap[2] };
+    throwOnVrcError( vrc_pool_enable_histograms( pool, _histBins, overlap ), "vrc_pool_enable_histograms" );
+    throwOnVrcError( vrc_frame_histogram( _ctx, pool, slots.data(), scales.data(), uint32_t( scales.size() ),
+                                          _histOnDevice ? 1 : 0 ),
+                     "vrc_frame_histogram" );
+    _histOnDevice = true;
+}
+
+bool HipRaycastRenderer::frameHistogram( std::vector< uint64_t >& bins, float range[2] )
+{
+    if( !_histFrame )
+        return false;
+    bins.assign( _histBins, 0u );
+    range[0] = _histRange[0];
+    range[1] = _histRange[1];
+    if( _histOnDevice ) /* else nothing was counted in the frame */
+        throwOnVrcError( vrc_get_frame_histogram( _ctx, bins.data(), _histBins ), "vrc_get_frame_histogram" );
+    return true;
 }
 
 void HipRaycastRenderer::render( const RenderInputs& renderInputs, const ConstCacheObjects& renderData )
@@ -608,6 +690,8 @@ void HipRaycastRenderer::render( const RenderInputs& renderInputs, const ConstCa
                                       ( frustum.top() - frustum.bottom() ) /
                                           float( renderInputs.pixelViewPort[3] ) ),
                      "vrc_set_ray_lod" );
+    if( _histFrame ) /* on the render stream ahead of the march: the render fence of the pool covers it */
+        addToHistogram( renderInputs, renderData );
     int rc = vrc_render( _ctx, &viewData, nodeDatas.data(), uint32_t( nodeDatas.size() ), &rData, pool );
     _lastRayLod = rayLod && rc == VRC_OK;
     if( rayLod && rc == VRC_EHIERARCHY )
@@ -935,10 +1019,29 @@ struct HipRaycastPipeline::Impl
         return k;
     }
 
+    /* frame histogram with per-ray LOD: the nodes it counts are the SSE cut (`ids`), not the ancestors the walk needs;
+     * NULL (every rendered node) otherwise.  Only when the histogram is on. */
+    static void histogramCut( Renderer& renderer, bool rayLod, const NodeIds& ids )
+    {
+        HipRaycastRenderer& plugin = static_cast< HipRaycastRenderer& >( renderer.getPlugin() );
+        if( !plugin.histogramOn() )
+            return;
+        std::shared_ptr< std::unordered_set< Identifier > > cut;
+        if( rayLod )
+        {
+            cut = std::make_shared< std::unordered_set< Identifier > >();
+            for( const NodeId& id : ids )
+                cut->insert( id.getId() );
+        }
+        plugin.setHistogramCut( cut );
+    }
+
     /* CudaRaycastPipeline.cpp:129-206 */
     void renderSync( RenderStatistics& statistics, Renderer& renderer, const RenderInputs& in )
     {
         const FrameKey key = frameKey( in );
+        if( _keptValid )
+            histogramCut( renderer, _lastRayLod, _keptVisible );
         if( _keptValid && key == _keptKey )
         {
             RenderInputs plainKept( in );
@@ -967,6 +1070,7 @@ struct HipRaycastPipeline::Impl
             statistics.nRenderAvailable = statistics.nAvailable;
             return;
         }
+        histogramCut( renderer, in.vrParameters.getRayLOD(), nodeIds );
         /* the kept bricks are referenced, hence not evictable: let go before anything is loaded */
         _keptValid = false;
         _keptObjects.clear();
@@ -1341,8 +1445,10 @@ struct HipRaycastPipeline::Impl
         const uint32_t maxNodes = uint32_t( _texturePool->getTextureMem() / _texturePool->getSlotMemSize() );
         NodeIds hierarchy = visibles;
         bool rayLod = in.vrParameters.getRayLOD() && withAncestors( in, hierarchy );
+        histogramCut( renderer, false, visibles );
         if( rayLod && hierarchy.size() > maxNodes )
         {
+            histogramCut( renderer, true, visibles );
             /* the hierarchy does not fit the atlas: slabs of space, the prefix whose data has arrived */
             if( renderRayLodInSlabsAsync( statistics, renderer, in, hierarchy, maxNodes ) )
                 return;
@@ -1362,6 +1468,20 @@ struct HipRaycastPipeline::Impl
                 obj ? ++statistics.nAvailable : ++statistics.nNotAvailable;
             }
             statistics.nRenderAvailable = objects.size();
+            if( static_cast< HipRaycastRenderer& >( renderer.getPlugin() ).histogramOn() )
+            {
+                /* the rendering set's nodes without a descendant in it: the SSE cut where it is resident, the
+                 * coarser node standing in for it elsewhere (as generateRenderingSet's fallback ancestors count) */
+                std::unordered_set< Identifier > parents;
+                for( const auto& obj : objects )
+                    for( const NodeId& parent : NodeId( obj->getId() ).getParents() )
+                        parents.insert( parent.getId() );
+                NodeIds counted;
+                for( const auto& obj : objects )
+                    if( !parents.count( obj->getId() ) )
+                        counted.push_back( NodeId( obj->getId() ) );
+                histogramCut( renderer, true, counted );
+            }
         }
         else
             objects = generateRenderingSet( *_hipCache, visibles, statistics );

@@ -56,7 +56,7 @@ EXPORTS = [
     "vrc_ctx_create", "vrc_ctx_destroy", "vrc_ctx_set_stream", "vrc_set_option", "vrc_get_option", "vrc_set_ray_lod",
     "vrc_pool_create", "vrc_pool_destroy", "vrc_pool_copy_to_slot", "vrc_pool_copy_to_slot_device",
     "vrc_pool_release_slot", "vrc_pool_info", "vrc_pool_synchronize", "vrc_pool_read_region",
-    "vrc_pool_histogram",
+    "vrc_pool_histogram", "vrc_pool_enable_histograms", "vrc_frame_histogram", "vrc_get_frame_histogram",
     "vrc_update", "vrc_pre_render", "vrc_set_row_map", "vrc_set_framebuffer", "vrc_get_framebuffer", "vrc_render",
     "vrc_post_render", "vrc_synchronize", "vrc_get_stats", "vrc_get_ray_counts", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
     "vrc_comm_unique_id", "vrc_comm_create", "vrc_comm_destroy", "vrc_comm_info", "vrc_gather_tiles",
@@ -111,6 +111,9 @@ def load_library(path=None):
     L.vrc_pool_synchronize.argtypes = [vp]
     L.vrc_pool_read_region.argtypes = [vp, u32x3, u32x3, vp]
     L.vrc_pool_histogram.argtypes = [vp, f32x3, u32x3, u32x3, C.c_uint32, C.c_uint64, vp]
+    L.vrc_pool_enable_histograms.argtypes = [vp, C.c_uint32, vp]
+    L.vrc_frame_histogram.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_int]
+    L.vrc_get_frame_histogram.argtypes = [vp, vp, C.c_uint32]
     L.vrc_update.argtypes = [vp, vp, vp, C.c_uint32]
     L.vrc_pre_render.argtypes = [vp, C.POINTER(ViewData)]
     L.vrc_set_row_map.argtypes = [vp, vp, C.c_uint32]
