@@ -144,6 +144,14 @@ typedef struct
                                    * list did not matter to it; 0 if it marched the list in its order (the
                                    * reference-order loop of any kernel form), or before the first vrc_render */
 
+#define VRC_OPT_UNIFORM_BRICKS 15   /* 1 (default) | 0.  Every brick upload notes whether all the voxels it wrote (overlap
+                                   * included) hold one value.  A wave whose rays are all inside such bricks takes its
+                                   * samples from that value's classified-table entry instead of fetching them: same
+                                   * samples, same order, same arithmetic -- the same frame and sample count, bit for
+                                   * bit -- without the addressing and the gathers (empty space, background, padding).
+                                   * Point-sampled 8-bit volumes through the classified table only; the trilinear,
+                                   * 16-bit and LDS-staged forms always read the atlas.  0: every brick is fetched */
+
 #define VRC_VARIANT_CUDARAYCASTER 0 /* renderers/cudaRaycaster/cuda/Renderer.cu:95-230 */
 #define VRC_VARIANT_GLRAYCASTER 1   /* renderers/glRaycaster/shaders/fragRaycast.glsl:113-215: pixel centre
                                      * +0.5, hit test t0 <= t1, first sample of a brick snapped to the

@@ -56,6 +56,10 @@ struct vrc_pool
     size_t slotBytes = 0, atlasBytes = 0;
     void* dAtlas = nullptr;
     bool bigAtlas = false; /* more than 2^32 voxels */
+    /* one uniformity word per slot (vrc_core.h: VRC_SLOT_*), indexed by pool_slot_index.  Device memory only, written
+     * on uploadStream alone: cleared with the atlas, zeroed and refilled by every upload next to the voxels it describes,
+     * so a march ordered behind lastUpload sees the word of exactly the voxels it would fetch.  No host copy. */
+    uint32_t* dSlotInfo = nullptr;
     /* tap-packed atlas of the trilinear filter (vrc_core.h): same slots, a texel of twice the voxel's bytes per voxel in
      * blocks of 64 rows of 9.
      * Allocated and filled from the byte atlas the first time a render asks for it (pool_enable_packed); from then
@@ -194,6 +198,7 @@ struct vrc_ctx
     int64_t optDepthSplit = 0;
     int64_t optErtParts = 0;     /* VRC_OPT_ERT_COMPACTION */
     int64_t optPackedAtlas = 1;  /* VRC_OPT_PACKED_ATLAS */
+    int64_t optUniformBricks = 1; /* VRC_OPT_UNIFORM_BRICKS */
     uint32_t* dRayList = nullptr; /* counts | two ray lists (vrc_internal.h) */
     size_t dRayListCap = 0;       /* pixels */
     int lastErtParts = 0;         /* of the last vrc_render */
@@ -388,6 +393,7 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
     case VRC_OPT_DEPTH_SPLIT: c->optDepthSplit = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_GREY_TABLE: c->optGreyTable = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_PACKED_ATLAS: c->optPackedAtlas = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_UNIFORM_BRICKS: c->optUniformBricks = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_ERT_COMPACTION:
         if( value < 0 || value > VRC_MAX_ERT_PARTS )
             return fail( VRC_EINVAL, "VRC_OPT_ERT_COMPACTION: 0 (off) or 2.." + std::to_string( VRC_MAX_ERT_PARTS ) +
@@ -420,6 +426,7 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_ERT_COMPACTION: *value = c->optErtParts; return VRC_OK;
     case VRC_OPT_GREY_TABLE: *value = c->optGreyTable; return VRC_OK;
     case VRC_OPT_PACKED_ATLAS: *value = c->optPackedAtlas; return VRC_OK;
+    case VRC_OPT_UNIFORM_BRICKS: *value = c->optUniformBricks; return VRC_OK;
     case VRC_OPT_VARIANT: *value = c->optVariant; return VRC_OK;
     case VRC_OPT_KERNEL_USED: *value = c->stats.kernel_variant; return VRC_OK;
     case VRC_OPT_GRID_WALK_USED: *value = c->gridWalkUsed; return VRC_OK;
@@ -533,6 +540,8 @@ int vrc_pool_create( vrc_ctx* c, size_t bytesPerVoxel, int isSigned, int isFloat
      * not ordered with a non-blocking stream, and the first uploads of a large pool could be overtaken by it (seen once:
      * a 6 GB pool of 16-bit voxels, round 4) */
     if( e == hipSuccess ) e = hipMemsetAsync( p->dAtlas, 0, p->atlasBytes, p->uploadStream );
+    if( e == hipSuccess ) e = hipMalloc( &p->dSlotInfo, nSlots * sizeof( uint32_t ) );
+    if( e == hipSuccess ) e = hipMemsetAsync( p->dSlotInfo, 0, nSlots * sizeof( uint32_t ), p->uploadStream );
     if( e == hipSuccess ) e = hipEventCreateWithFlags( &p->lastUpload, hipEventDisableTiming );
     if( e == hipSuccess )
     {
@@ -582,6 +591,7 @@ void vrc_pool_destroy( vrc_pool* p )
     if( p->uploadStream ) (void)hipStreamDestroy( p->uploadStream );
     if( p->dPacked ) (void)hipFree( p->dPacked );
     if( p->dHist ) (void)hipFree( p->dHist );
+    if( p->dSlotInfo ) (void)hipFree( p->dSlotInfo );
     if( p->dAtlas ) (void)hipFree( p->dAtlas );
     delete p;
 }
@@ -727,12 +737,17 @@ static int pool_upload( vrc_pool* p, const void* src, bool srcIsDevice, const ui
             /* the writes of one upload are queued as a unit (pool_enable_packed packs every slot written before it
              * was called; every upload after it packs its own) */
             std::lock_guard< std::mutex > lock( p->mutex );
-            e = vrc_launch_repack_brick( devSrc, slotPtr, p->elemBytes, size, p->slotDim, p->uploadStream );
+            const uint32_t index = pool_slot_index( p, o );
+            /* the slot's uniformity word: back to "nothing known" before the new voxels land, then whatever the
+             * repack finds in them -- same stream, same fences, same lastUpload as the voxels */
+            uint32_t* const info = p->dSlotInfo + index;
+            e = hipMemsetAsync( info, 0, sizeof( uint32_t ), p->uploadStream );
+            if( e == hipSuccess )
+                e = vrc_launch_repack_brick( devSrc, slotPtr, p->elemBytes, size, p->slotDim, p->uploadStream, info );
             if( e == hipSuccess && p->packedOn )
                 e = vrc_launch_pack_slots( p->dAtlas, p->dPacked, base,
                                            (uint64_t)p->slotDim[0] * p->slotDim[1] * p->slotDim[2], p->slotDim,
                                            p->elemBytes, p->uploadStream );
-            const uint32_t index = pool_slot_index( p, o );
             p->resident[index] = 1;
             p->slotSize[index] = { size[0], size[1], size[2] };
             /* the slot's histogram row, behind the repack and before lastUpload (vrc_pool_enable_histograms) */
@@ -1531,6 +1546,8 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     /* fold the frame's clear into this march (after the tile-schedule cache compared frames) */
     f.clearFirst = c->clearPending ? 1u : 0u;
     c->clearPending = false;
+    /* the pool's uniformity words (VRC_OPT_UNIFORM_BRICKS): NULL = every brick takes the general march */
+    f.slotInfo = c->optUniformBricks ? pool->dSlotInfo : nullptr;
 
     a.nodes = c->dNodes;
     a.gridTable = ( useDda || c->rayLod ) ? c->dGrid : nullptr;

@@ -127,8 +127,17 @@ struct vrc_dev_node
     uint32_t slotBase;    /* element offset of the brick's slot in the atlas buffer, low 32 bits */
     uint32_t level;       /* per-ray LOD: 0 = the finest voxel size in the node list, +1 per doubling */
     uint32_t slotBaseHi;  /* high 32 bits: non-zero only in atlases of more than 2^32 voxels (BIG kernels) */
-    uint32_t pad;
+    uint32_t slotInfoIndex; /* linear ordinal of the slot + 1 into vrc_frame::slotInfo; 0 = none (general march) */
 };
+
+/* Per-slot uniformity word (vrc_frame::slotInfo), written by the brick upload together with the voxels it describes:
+ * low 16 bits = the brick's first voxel, KNOWN = some upload wrote the word, MIXED = a voxel of that upload differs
+ * from the first.  0 = nothing known.  A brick is marched from one table entry only when its word is KNOWN and not
+ * MIXED: every voxel the upload wrote -- overlap included, i.e. every voxel a sample of that brick can reach -- is
+ * the value. */
+#define VRC_SLOT_VALUE_MASK 0xFFFFu
+#define VRC_SLOT_KNOWN 0x10000u
+#define VRC_SLOT_MIXED 0x20000u
 
 /* Frame constants, derived on the host exactly as Renderer.cu:159-170 does per thread. */
 struct vrc_frame
@@ -156,6 +165,9 @@ struct vrc_frame
     /* sort-first row bands: frame row of every row of the pixel buffer (NULL = identity).  The
      * buffer then holds height rows picked from a frame of vpH rows (vrc_set_row_map). */
     const uint32_t* rowMap;
+    /* one uniformity word per atlas slot (VRC_SLOT_*), indexed by vrc_dev_node::slotInfoIndex - 1; NULL = every brick
+     * takes the general march (VRC_OPT_UNIFORM_BRICKS = 0, the CPU harness) */
+    const uint32_t* slotInfo;
     /* 0: cudaRaycaster semantics (cuda/Renderer.cu); 1: the GLSL twin's
      * (glRaycaster/shaders/fragRaycast.glsl), see vrc_brick_segment */
     uint32_t variant;
@@ -865,22 +877,29 @@ VRC_HD E vrc_entry( const E* lut, uint32_t d, const vrc_classifier* cls )
         return lut[d];
 }
 
-template < bool CLAMP, bool COUNT, bool FIXED, typename ATLAS_T, int GROUP, typename E, bool PERSAMPLE = false >
+/* UNIFORM: every voxel a sample of this brick can reach holds one value (the slot's uniformity word,
+ * vrc_march_brick) and `ue` is its table entry.  The control structure is the general form's, statement for
+ * statement -- groups under the same guard, the sequential travel chain, the early-exit test with its replay, the
+ * tail with its per-sample test, the counter -- so the composited sequence and the count are the general form's by
+ * construction; only the position stepping, the addresses, the gathers and the table reads are compiled out. */
+template < bool CLAMP, bool COUNT, bool FIXED, typename ATLAS_T, int GROUP, typename E, bool PERSAMPLE = false,
+           bool UNIFORM = false >
 VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc_segment s,
                                   const ATLAS_T* __restrict__ atlas, const E* lut,
                                   E& color, uint32_t& nSamples, float levelStep,
-                                  const vrc_classifier* cls = nullptr )
+                                  const vrc_classifier* cls = nullptr, const E ue = E{} )
 {
+    static_assert( !( UNIFORM && PERSAMPLE ), "the uniform march takes its entry from the classified table" );
     /* levelStep: step of a coarser brick under per-ray LOD (vrc_pixel_ray_lod); 0 = the frame's */
     const float stepSize = levelStep > 0.0f ? levelStep : f.stepSize;
-    const vrc_sampler sm = vrc_make_sampler( n, f );
+    const vrc_sampler sm = vrc_make_sampler( n, f ); /* (unused, and compiled out, when UNIFORM) */
     float travel = s.dist;
     vrc_f3 pos = s.pos;
     bool done = false;
     if( !( travel > 0.0f ) )
         return false;
     vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
-    if( FIXED )
+    if( FIXED && !UNIFORM )
         fp = vrc_fixpos_init( sm, pos, s.step );
 
     /* all GROUP samples of a group are reached by the reference loop if more than
@@ -893,7 +912,7 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
      * line touched once per frame, some lane of every group goes all the way to HBM); with the next group's
      * gathers already on their way that wait overlaps the current group's work instead of following it.  Same
      * samples in the same order: only when the loads are issued changes. */
-    if( travel > guard )
+    if( !UNIFORM && travel > guard )
     {
         uint32_t idx[GROUP], d[GROUP];
         if( FIXED )
@@ -971,7 +990,9 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
 #endif
     {
         uint32_t idx[GROUP];
-        if( FIXED )
+        if constexpr( UNIFORM )
+            (void)idx;
+        else if( FIXED )
             vrc_group_indices_fixed< GROUP >( sm, fp, idx );
         else
             vrc_group_indices< CLAMP, GROUP >( sm, pos, s.step, idx );
@@ -991,7 +1012,7 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
         /* developer experiment (tools/dev_layouts.sh): a lane keeps the dword of its voxel
          * column (four voxels along z) and loads a new one only when its dword address changes; the other lanes'
          * loads are out of range of the buffer descriptor and touch nothing */
-        if( sizeof( ATLAS_T ) == 1 )
+        if( sizeof( ATLAS_T ) == 1 && !UNIFORM )
         {
             const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast< ATLAS_T* >( atlas ), (short)0, (int)0xFFFFFFFEu, 0x00020000 );
@@ -1019,14 +1040,17 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
 #pragma unroll
         for( int k = 0; k < GROUP; ++k )
         {
+            if constexpr( UNIFORM )
+                e[k] = ue;
+            else
 #if defined( VRC_ABLATE_NO_FETCH ) /* timing experiment only */
-            e[k] = lut[64u + ( idx[k] >> 31 )];
+                e[k] = lut[64u + ( idx[k] >> 31 )];
 #elif defined( VRC_ABLATE_HALF_FETCH ) /* timing experiment only: every other gather dropped */
-            e[k] = lut[(uint32_t)atlas[idx[k & ~1]] + ( idx[k] >> 31 )];
+                e[k] = lut[(uint32_t)atlas[idx[k & ~1]] + ( idx[k] >> 31 )];
 #elif defined( VRC_ABLATE_QUARTER_FETCH ) /* timing experiment only */
-            e[k] = lut[(uint32_t)atlas[idx[k & ~3]] + ( idx[k] >> 31 )];
+                e[k] = lut[(uint32_t)atlas[idx[k & ~3]] + ( idx[k] >> 31 )];
 #else
-            e[k] = vrc_entry< PERSAMPLE, E >( lut, (uint32_t)atlas[idx[k]], cls );
+                e[k] = vrc_entry< PERSAMPLE, E >( lut, (uint32_t)atlas[idx[k]], cls );
 #endif
         }
 #if defined( VRC_SETPRIO ) && defined( __HIP_DEVICE_COMPILE__ )
@@ -1075,7 +1099,13 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
     while( travel > 0.0f && !done )
     {
         uint32_t idx[TAILG], d[TAILG], cnt = 0;
-        if( FIXED )
+        if constexpr( UNIFORM )
+        {
+#pragma unroll
+            for( int k = 0; k < TAILG; ++k )
+                idx[k] = 0u;
+        }
+        else if( FIXED )
             vrc_group_indices_fixed< TAILG >( sm, fp, idx );
         else
             vrc_group_indices< CLAMP, TAILG >( sm, pos, s.step, idx );
@@ -1089,12 +1119,18 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
         }
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
-            d[k] = (uint32_t)atlas[idx[k]];
+            d[k] = UNIFORM ? 0u : (uint32_t)atlas[idx[k]];
         E e[TAILG];
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
         {
-            if constexpr( PERSAMPLE )
+            if constexpr( UNIFORM )
+            {
+                /* a step the reference does not take blends table entry 256: all zeros */
+                const E z = {};
+                e[k] = (uint32_t)k < cnt ? ue : z;
+            }
+            else if constexpr( PERSAMPLE )
             {
                 /* a step the reference does not take blends nothing */
                 const E z = {};
@@ -1833,6 +1869,38 @@ VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vr
         const ATLAS_T* slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
         return vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, false >( f, local, s, slot, lut, cls,
                                                                                 color, nSamples, levelStep );
+    }
+    if constexpr( ( MODE == VRC_MODE_TABLE || MODE == VRC_MODE_GREY ) && sizeof( ATLAS_T ) == 1 )
+    {
+        /* A brick whose upload found one value in every voxel (the slot's uniformity word, written by the repack kernel
+         * on the stream and under the fences of the voxels themselves) is marched from that value's table entry: no
+         * addresses, no gathers, no table reads.  Taken by the whole wave or not at all -- a lane in a uniform brick
+         * of a wave that also holds other bricks gathers its constant voxels like the rest, the same samples either
+         * way.  Trilinear, 16-bit and per-sample classified forms do not look at the word. */
+        uint32_t word = 0u;
+        if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
+            word = f.slotInfo[n.slotInfoIndex - 1u];
+        bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
+#if defined( __HIP_DEVICE_COMPILE__ )
+        general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
+#endif
+        if( !general )
+        {
+            const uint32_t v = word & 0xFFu;
+            if constexpr( MODE == VRC_MODE_GREY )
+            {
+                const vrc_f2* const lut2 = reinterpret_cast< const vrc_f2* >( lut );
+                vrc_f2 c = { color.x, color.w };
+                const bool done = vrc_march_segment_as< CLAMP, COUNT, FIXED, ATLAS_T, GROUP, vrc_f2, false, true >(
+                    f, n, s, atlas, lut2, c, nSamples, levelStep, nullptr, lut2[v] );
+                color.x = color.y = color.z = c.x;
+                color.w = c.w;
+                return done;
+            }
+            else
+                return vrc_march_segment_as< CLAMP, COUNT, FIXED, ATLAS_T, GROUP, vrc_f4, false, true >(
+                    f, n, s, atlas, lut, color, nSamples, levelStep, nullptr, lut[v] );
+        }
     }
     if constexpr( MODE == VRC_MODE_GREY )
         return vrc_march_segment< CLAMP, COUNT, FIXED, ATLAS_T, GROUP, true >( f, n, s, atlas, lut, color, nSamples,

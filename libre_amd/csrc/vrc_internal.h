@@ -68,10 +68,12 @@ hipError_t vrc_launch_build_lut( const float* tf, vrc_f4* lut, vrc_lut_params p,
 
 /* row-major brick (size voxels, elemBytes per voxel) -> micro-blocked slot (slot = device
  * pointer to the slot's first element; slotDim = padded slot size in voxels).  A brick smaller
- * than the slot gets its border voxels replicated into the padding. */
+ * than the slot gets its border voxels replicated into the padding.
+ * slotInfo (may be NULL): the slot's uniformity word (vrc_core.h: VRC_SLOT_*), which the caller zeroed on `stream`
+ * before this call; the kernel ORs into it what it finds. */
 hipError_t vrc_launch_repack_brick( const void* srcRowMajor, void* slot, uint32_t elemBytes,
                                     const uint32_t size[3], const uint32_t slotDim[3],
-                                    hipStream_t stream );
+                                    hipStream_t stream, uint32_t* slotInfo = nullptr );
 
 /* atlas -> tap-packed atlas (vrc_core.h): the packed texels of elements [firstElem, firstElem + nElems) of the atlas of
  * 8- or 16-bit voxels (whole slots; the packed atlas holds vrc_packed_elems( atlas elements ) texels of

@@ -10,8 +10,11 @@
  *     dispatcher deals workgroups round-robin over the 8 XCDs; vrc_internal.h, "Tile schedule": spatial
  *     super-tiles per XCD were measured in round 4 -- 7 % fewer HBM requests, no time -- and one contiguous
  *     band per XCD in round 1, slower);
- *   - the atlas is read as 8x8x8-voxel micro-blocks (one z-slice of a block = one 64-byte
- *     segment), so the 64 fetches of a wave step land in a handful of cache lines;
+ *   - the atlas is read as 8x8x8-voxel micro-blocks whose 64 x-rows lie in the order y & 3, z & 3, y >> 2, z >> 2
+ *     (vrc_core.h: vrc_mb_y, vrc_mb_z; arithmetic address paths add VRC_MB_FIX_Y / _Z to 8 y + 64 z), so a 128-byte
+ *     line is a block of 8 x 4 x 4 voxels and the 64 fetches of a wave step land in a handful of lines;
+ *   - a brick whose upload found one value in all its voxels is marched without fetching any (vrc_march_brick,
+ *     the slot words of vrc_k_repack_u8x8);
  *   - TF lookup + opacity correction are folded into a 256-entry classified table staged
  *     in LDS once per workgroup (4 KiB): no per-sample pow, one ds_read_b128 per sample;
  *   - bricks are enumerated by a DDA over the brick grid instead of the O(nodes) loop;
@@ -71,12 +74,18 @@ hipError_t vrc_launch_build_lut( const float* tf, vrc_f4* lut, vrc_lut_params p,
  * a cudaArray of cuda/TexturePool.cu:187-201; the "array layout" is ours to define)
  * ---------------------------------------------------------------------------------------- */
 /* fast path: 1-byte voxels, x extent a multiple of 8: one thread moves one 8-voxel run
- * (= one row of a micro-block z-slice, 8-byte aligned on both sides) */
+ * (= one row of a micro-block z-slice, 8-byte aligned on both sides).
+ * info (may be NULL): the slot's uniformity word (vrc_core.h: VRC_SLOT_*), zeroed on this stream before the launch.
+ * Every thread compares the voxels it moves with the brick's first voxel; a wave that met another value ORs MIXED
+ * into the word, the thread that moves voxel 0 ORs value | KNOWN.  ORs commute: no order between workgroups needed,
+ * and the word is complete when the kernel is -- with the voxels it describes. */
 __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __restrict__ slot,
                                    uint32_t sx8, uint32_t sy, uint32_t sz, uint32_t sbx,
-                                   uint32_t sby )
+                                   uint32_t sby, uint32_t* __restrict__ info )
 {
     const uint32_t total = sx8 * sy * sz;
+    const uint32_t first = src[0].x & 0xFFu, all = first * 0x01010101u;
+    bool mixed = false;
     for( uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += gridDim.x * blockDim.x )
     {
@@ -86,6 +95,14 @@ __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __res
         const uint2 v = src[i];
         const uint32_t e = vrc_slot_local_index( x8 * 8u, y, z, sbx, sby );
         *reinterpret_cast< uint2* >( slot + e ) = v;
+        mixed = mixed || v.x != all || v.y != all;
+    }
+    if( info != nullptr )
+    {
+        if( __builtin_amdgcn_ballot_w64( mixed ) != 0ull && ( threadIdx.x & 63u ) == 0u )
+            atomicOr( info, VRC_SLOT_MIXED );
+        if( blockIdx.x == 0u && threadIdx.x == 0u )
+            atomicOr( info, first | VRC_SLOT_KNOWN );
     }
 }
 
@@ -352,8 +369,10 @@ static uint32_t grid_for( size_t total, uint32_t block )
 
 hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBytes,
                                     const uint32_t size[3], const uint32_t slotDim[3],
-                                    hipStream_t stream )
+                                    hipStream_t stream, uint32_t* slotInfo )
 {
+    /* slotInfo: only the kernel that fills a whole slot of 1-byte voxels tests for a uniform brick; after the others
+     * the (zeroed) word says "nothing known" and the brick takes the general march */
     const size_t total = (size_t)size[0] * size[1] * size[2];
     if( total == 0 )
         return hipSuccess;
@@ -382,7 +401,7 @@ hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBy
         const uint32_t sx8 = size[0] / 8u;
         hipLaunchKernelGGL( vrc_k_repack_u8x8, dim3( grid_for( total / 8, 256 ) ), dim3( 256 ), 0,
                             stream, (const uint2*)src, (uint8_t*)slot, sx8, size[1], size[2], sbx,
-                            sby );
+                            sby, slotInfo );
     }
     else if( elemBytes == 1 )
         hipLaunchKernelGGL( vrc_k_repack_generic< uint8_t >, dim3( grid_for( total, 256 ) ),

@@ -91,7 +91,8 @@ inline void vrc_build_tables( const vrc_atlas_geom& p, const vrc_node_data* in, 
         d.slotBase = (uint32_t)base;
         d.slotBaseHi = (uint32_t)( base >> 32 );
         d.level = 0;
-        d.pad = 0;
+        /* the slot's uniformity word (vrc_frame::slotInfo): the pool's linear slot ordinal, x fastest */
+        d.slotInfoIndex = ( slotIdx[2] * p.slots[1] + slotIdx[1] ) * p.slots[0] + slotIdx[0] + 1u;
     }
 
     /* brick grid: cells of the finest brick size covering the union of the node boxes */
@@ -335,6 +336,7 @@ inline void vrc_fill_frame( vrc_frame& f, const vrc_view_data& view, const vrc_r
     f.sbx = geom.slotDim[0] / VRC_MB;
     f.sby = geom.slotDim[1] / VRC_MB;
     f.rowMap = nullptr;
+    f.slotInfo = nullptr;
     f.samplesPerPixel = 1u; /* the caller sets it for the glRaycaster variant */
     f.lodLevels = 0;
     f.lodBase = 0.f;

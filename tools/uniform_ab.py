@@ -1,0 +1,63 @@
+"""A/B of VRC_OPT_UNIFORM_BRICKS on one scene through the C ABI: the same frame with the option off and on (compared bit
+for bit), then the raycast kernel timed from the library's HIP events (vrc_get_stats) in alternating rounds.
+usage: python tools/uniform_ab.py [--volume mem|hash] [--steps 20] [--rounds 3] [--lib libvrc_hip.so]
+A library that does not know the option (an older build) is timed once, as "off"."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import orc  # noqa: E402
+from gpu_run import GpuScene  # noqa: E402
+from libre_amd import vrc  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--voxels", type=int, default=1024)
+    ap.add_argument("--block", type=int, default=128)
+    ap.add_argument("--viewport", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--volume", default="mem")
+    ap.add_argument("--spin", type=float, nargs=2, default=(0.0, 0.0))
+    a = ap.parse_args()
+    s = orc.build_scene(voxels=(a.voxels,) * 3, block=a.block, viewport=(a.viewport,) * 2, volume=a.volume,
+                        spin=tuple(a.spin))
+    L = vrc.load_library(a.lib) if a.lib else vrc.load_library()
+    g = GpuScene(s, lib=L)
+    known = L.vrc_set_option(g.ctx, vrc.OPT_UNIFORM_BRICKS, 0) == 0
+    values = (0, 1) if known else (0,)
+    frames = {}
+    for v in values:
+        if known:
+            vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_UNIFORM_BRICKS, v))
+        frames[v] = g.render(count=True)[:2]
+    if known:
+        assert (frames[0][0] == frames[1][0]).all() and frames[0][1] == frames[1][1], "frames differ"
+    ms = {v: [] for v in values}
+    stats = vrc.Stats()
+    for _ in range(a.rounds):
+        for v in values:
+            if known:
+                vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_UNIFORM_BRICKS, v))
+            g.render(count=False)  # warm-up: the tile schedule
+            best = None
+            for _ in range(a.steps):
+                _, _, st = g.render(count=False)
+                best = st.kernel_ms if best is None else min(best, st.kernel_ms)
+            ms[v].append(round(best, 4))
+    kernel = L.vrc_last_kernel().decode() if hasattr(L, "vrc_last_kernel") else ""
+    print(json.dumps({"volume": a.volume, "spin": list(a.spin), "samples": frames[0][1], "kernel": kernel,
+                      "kernel_ms_min_per_round": {("on" if v else "off"): ms[v] for v in values},
+                      "frames_bit_identical": bool(known)}))
+    g.close()
+
+
+if __name__ == "__main__":
+    main()
