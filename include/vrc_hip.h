@@ -161,7 +161,11 @@ typedef struct
 
 #define VRC_FILTER_NEAREST 0   /* cuda/TexturePool.cu:167 (cudaFilterModePoint): the reference */
 #define VRC_FILTER_TRILINEAR 1 /* extension: texel centres at i+0.5, float weights, transfer function
-                                * and opacity correction evaluated per sample on the interpolated density */
+                                * and opacity correction evaluated per sample on the interpolated density.
+                                * Voxel i of a brick (overlap border included) has its centre at i + 0.5 in the
+                                * brick's voxel coordinate, overlap + (pos - boxMin) / boxSize * blockSize; a tap
+                                * outside the brick and its border (only with overlap 0) is clamped to the nearest
+                                * voxel, as the point sampler's address is (tests/ref64.py restates this) */
 
 #define VRC_KERNEL_AUTO 0            /* bricks of one size: GRID_DDA (meets them in the reference's order, sample for
                                       * sample); bricks of mixed sizes (an LOD cut): REFERENCE_ORDER up to

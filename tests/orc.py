@@ -642,10 +642,13 @@ def scene_from_datasource(drv, uri, ids, viewport, spin=(0.0, 0.0), alpha=0.05, 
     mv = np.array(list(s.mv), dtype=np.float32).reshape(4, 4).T  # column-major -> rows
     recs = []
     bricks = {}
+    s.lod = {}  # block size and world box per brick, as build_scene keeps them (tests/ref64.py samples brick-locally)
     for k, nid in enumerate(ids):
         node = drv.datasource_node(uri, nid)
         assert node["valid"]
         bs = node["block_size"]
+        s.lod[nid] = LODNode(nid, u32x3(*bs), u32x3(), u32x3(), f32x3(*node["world_box"][:3]),
+                             f32x3(*node["world_box"][3:6]))
         full = [bs[a] + 2 * ov[a] for a in range(3)]
         brick = drv.datasource_brick(uri, nid).reshape(full[2], full[1], full[0])
         bricks[nid] = np.ascontiguousarray(brick)
