@@ -26,6 +26,7 @@
     defined( VRC_ZRUN ) || \
     defined( VRC_SETPRIO ) || \
     defined( VRC_INT_STEPS ) || defined( VRC_WG_TIMELINE ) || \
+    defined( VRC_NO_UNIFORM_INT_STEPS ) || defined( VRC_UNIFORM_GROUP ) || defined( VRC_UNIFORM_SMALL_GROUP ) || \
     defined( VRC_PIPELINE ) || \
     defined( VRC_LAYOUT ) || \
     defined( VRC_LAYOUT_PADX ) || \
@@ -877,6 +878,125 @@ VRC_HD E vrc_entry( const E* lut, uint32_t d, const vrc_classifier* cls )
         return lut[d];
 }
 
+/* ------------------------------------------------------------------------------------------
+ * The uniform march counted in integers (the form vrc_march_segment_as< ..., UNIFORM > takes when it is exact).
+ *
+ * The reference steps a segment with `travel -= stepSize` while `travel > 0` (Renderer.cu:206-223).  When stepSize
+ * is a power of two 2^j and travel < 2^24 * stepSize, every one of those subtractions is exact as long as
+ * travel >= stepSize: travel is a multiple of its own ulp 2^k, and travel < 2^(j+24) gives k <= j, so stepSize is a
+ * multiple of 2^k as well and the smaller difference is representable.  The last subtraction (0 < travel <
+ * stepSize) only has to come out negative, which rounding cannot change.  The loop therefore takes exactly
+ * n = ceil( travel / stepSize ) trips, and q = travel * (1 / stepSize) is exact too (a change of exponent; should it
+ * underflow, q is below one and n = 1 either way).  With n in hand, "travel > 0" is "nLeft > 0", and a group of G
+ * samples is all the reference's when nLeft >= G -- no float chain, no guard of one spare step.
+ * stepSize is 1 / samplesPerRay (vrc_fill_frame), times 2^level under per-ray LOD: sample counts of 256, 512, 1024,
+ * 2048 qualify, 300 or 1000 do not and keep the float chain.
+ * ---------------------------------------------------------------------------------------- */
+VRC_HD uint32_t vrc_float_bits( float v )
+{
+#if defined( __HIP_DEVICE_COMPILE__ )
+    return __float_as_uint( v );
+#else
+    uint32_t u;
+    memcpy( &u, &v, 4 );
+    return u;
+#endif
+}
+VRC_HD float vrc_bits_float( uint32_t u )
+{
+#if defined( __HIP_DEVICE_COMPILE__ )
+    return __uint_as_float( u );
+#else
+    float v;
+    memcpy( &v, &u, 4 );
+    return v;
+#endif
+}
+
+/* travel > 0.  Whether the count is exact, and the count: the trips of `for( ; travel > 0; travel -= stepSize )` */
+VRC_HD bool vrc_exact_step_count( float travel, float stepSize, uint32_t* n )
+{
+    const uint32_t sb = vrc_float_bits( stepSize );
+    const uint32_t e = sb >> 23; /* (a negative step has bit 8 set here and fails the range test) */
+    /* exponent 254 is left out: its reciprocal is not a normal number */
+    const bool pow2 = ( sb & 0x7FFFFFu ) == 0u && e >= 1u && e <= 253u;
+    const float inv = vrc_bits_float( ( 254u - ( pow2 ? e : 127u ) ) << 23 );
+    const float q = travel * inv;
+    const bool ok = pow2 && q < 16777216.0f;
+    const float qs = ok ? q : 0.0f;
+    uint32_t c = (uint32_t)qs; /* truncation; qs is an integer already from 2^23 on */
+    c += (float)c < qs ? 1u : 0u;
+    *n = c == 0u ? 1u : c;
+    return ok;
+}
+
+#if defined( VRC_UNIFORM_FORM_HOOK ) && !defined( __HIPCC__ )
+/* host test builds only (tests/cpu_harness/intsteps_harness.cpp): 1 = never take the counted form; and how many
+ * segments took the [0] float chain, [1] counted form */
+extern int vrc_uniform_form_hook;
+extern uint64_t vrc_uniform_form_taken[2];
+#endif
+
+/* Groups of the counted form.  Nothing is fetched, so the group is not sized by gather latency or by the registers
+ * of GROUP indices (the gather path's 14 and its tails of 4, vrc_march_segment_as): a group costs its samples plus
+ * the copy of `saved`, one exit test and the count's subtract and compare.  What is left below a whole group is marched
+ * sample by sample with the reference's exit test after each -- a lane runs exactly its own samples, no predicated
+ * slots -- and that same loop is the replay of a group the threshold was crossed in.  Two loops and no per-size
+ * bodies on purpose: this code is inlined into every table-form kernel, next to a gather march that fills the
+ * register budget of its occupancy (a first version with unrolled bodies of 8, 4, 2 and 1 samples after the groups
+ * of 16 made the four-float gather kernels spill).
+ * Measured on C2 (profiles/r7_int_steps.txt; the float chain: 0.1119 ms): groups of 8 / 16 / 32: 0.0988 / 0.0942 /
+ * 0.0996 ms; groups of 16, then of 4, then single samples: 0.0964 ms. */
+#ifndef VRC_UNIFORM_GROUP
+#define VRC_UNIFORM_GROUP 16
+#endif
+#ifndef VRC_UNIFORM_SMALL_GROUP
+#define VRC_UNIFORM_SMALL_GROUP 0 /* a second round of smaller groups before the single samples: 0 = none */
+#endif
+
+/* Whole groups of G while nLeft >= G: all G samples are the reference's, the early-exit test comes once at the end
+ * (alpha never decreases).  Crossed inside a group: the colour goes back to the group's start and nLeft becomes G --
+ * the caller's sample-by-sample loop replays it and stops after the crossing sample, as the reference does. */
+template < bool COUNT, int G, typename E >
+VRC_HD bool vrc_uniform_groups( E& color, const E ue, uint32_t& nLeft, uint32_t& nSamples )
+{
+    while( nLeft >= (uint32_t)G )
+    {
+        const E saved = color;
+#pragma unroll
+        for( int k = 0; k < G; ++k )
+            vrc_composite( color, ue );
+        if( color.w > VRC_EARLY_EXIT )
+        {
+            color = saved;
+            nLeft = (uint32_t)G;
+            return true;
+        }
+        nLeft -= (uint32_t)G;
+        if( COUNT )
+            nSamples += (uint32_t)G;
+    }
+    return false;
+}
+
+template < bool COUNT, typename E >
+VRC_HD bool vrc_march_uniform_counted( E& color, const E ue, uint32_t nLeft, uint32_t& nSamples )
+{
+    bool crossed = vrc_uniform_groups< COUNT, VRC_UNIFORM_GROUP, E >( color, ue, nLeft, nSamples );
+    if constexpr( VRC_UNIFORM_SMALL_GROUP > 0 )
+        crossed = crossed || vrc_uniform_groups< COUNT, VRC_UNIFORM_SMALL_GROUP, E >( color, ue, nLeft, nSamples );
+    (void)crossed;
+    for( ; nLeft > 0u; --nLeft )
+    {
+        vrc_composite( color, ue );
+        if( COUNT )
+            nSamples += 1u;
+        if( color.w > VRC_EARLY_EXIT )
+            return true;
+    }
+    return false;
+}
+
 /* UNIFORM: every voxel a sample of this brick can reach holds one value (the slot's uniformity word,
  * vrc_march_brick) and `ue` is its table entry.  The control structure is the general form's, statement for
  * statement -- groups under the same guard, the sequential travel chain, the early-exit test with its replay, the
@@ -898,6 +1018,23 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
     bool done = false;
     if( !( travel > 0.0f ) )
         return false;
+#if !defined( VRC_NO_UNIFORM_INT_STEPS )
+    if constexpr( UNIFORM )
+    {
+        /* counted in integers where that is the float chain's count exactly (vrc_exact_step_count); taken, like the
+         * uniform form itself, by the whole wave or not at all, so that a wave runs one loop and not two */
+        uint32_t nLeft;
+        bool counted = vrc_exact_step_count( travel, stepSize, &nLeft );
+#if defined( __HIP_DEVICE_COMPILE__ )
+        counted = __builtin_amdgcn_ballot_w64( !counted ) == 0ull;
+#elif defined( VRC_UNIFORM_FORM_HOOK )
+        counted = counted && vrc_uniform_form_hook != 1;
+        ++vrc_uniform_form_taken[counted ? 1 : 0];
+#endif
+        if( counted )
+            return vrc_march_uniform_counted< COUNT, E >( color, ue, nLeft, nSamples );
+    }
+#endif
     vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
     if( FIXED && !UNIFORM )
         fp = vrc_fixpos_init( sm, pos, s.step );

@@ -1,7 +1,12 @@
 """A/B of VRC_OPT_UNIFORM_BRICKS on one scene through the C ABI: the same frame with the option off and on (compared bit
 for bit), then the raycast kernel timed from the library's HIP events (vrc_get_stats) in alternating rounds.
 usage: python tools/uniform_ab.py [--volume mem|hash] [--steps 20] [--rounds 3] [--lib libvrc_hip.so]
-A library that does not know the option (an older build) is timed once, as "off"."""
+A library that does not know the option (an older build) is timed once, as "off".
+Forms of the uniform march against each other (the product carries no switch for them: they are builds,
+tools/build_variants.sh NAME "-DVRC_NO_UNIFORM_INT_STEPS" / "-DVRC_UNIFORM_GROUP=8", or an older commit's library):
+       python tools/uniform_ab.py --libs parent=variants/libvrc_hip_parent.so new=libre_amd/lib/libvrc_hip.so ...
+renders the frame with every library, option on (compared bit for bit with the first one's, counts included), and
+times them in alternating rounds in this one process."""
 import argparse
 import ctypes as C
 import json
@@ -16,6 +21,40 @@ from gpu_run import GpuScene  # noqa: E402
 from libre_amd import vrc  # noqa: E402
 
 
+def several(a):
+    """--libs: the same frame, option on, through several builds of the library."""
+    s = orc.build_scene(voxels=(a.voxels,) * 3, block=a.block, viewport=(a.viewport,) * 2, volume=a.volume,
+                        spin=tuple(a.spin), spr=a.spr)
+    names, scenes = [], {}
+    for spec in a.libs:
+        name, path = spec.split("=", 1)
+        L = vrc.load_library(os.path.abspath(path))
+        names.append(name)
+        scenes[name] = GpuScene(s, lib=L)
+    first = None
+    for name in names:
+        fb, n = scenes[name].render(count=True)[:2]
+        if first is None:
+            first = (fb, n)
+        assert (fb == first[0]).all() and n == first[1], "%s: frame or count differs from %s" % (name, names[0])
+    ms = {name: [] for name in names}
+    kernels = {}
+    for _ in range(a.rounds):
+        for name in names:
+            g = scenes[name]
+            g.render(count=False)  # warm-up: the tile schedule
+            best = None
+            for _ in range(a.steps):
+                _, _, st = g.render(count=False)
+                best = st.kernel_ms if best is None else min(best, st.kernel_ms)
+            ms[name].append(round(best, 4))
+            kernels[name] = g.L.vrc_last_kernel().decode()
+    print(json.dumps({"volume": a.volume, "spin": list(a.spin), "spr": s.render.samplesPerRay, "samples": first[1],
+                      "kernel": kernels, "kernel_ms_min_per_round": ms, "frames_bit_identical": True}))
+    for g in scenes.values():
+        g.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=None)
@@ -26,7 +65,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--volume", default="mem")
     ap.add_argument("--spin", type=float, nargs=2, default=(0.0, 0.0))
+    ap.add_argument("--spr", type=int, default=0, help="samples per ray (0 = the automatic value)")
+    ap.add_argument("--libs", nargs="+", default=None, metavar="NAME=PATH")
     a = ap.parse_args()
+    if a.libs:
+        return several(a)
     s = orc.build_scene(voxels=(a.voxels,) * 3, block=a.block, viewport=(a.viewport,) * 2, volume=a.volume,
                         spin=tuple(a.spin))
     L = vrc.load_library(a.lib) if a.lib else vrc.load_library()
