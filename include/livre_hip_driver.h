@@ -64,9 +64,12 @@ int lvh_app_set_clip_planes( lvh_app* app, const float* planes, uint32_t n );
  * frame, stacked in that order in its pixel buffer (replaces params.tile; n = 0 -> back to it) */
 int lvh_app_set_bands( lvh_app* app, const uint32_t* y0, const uint32_t* h, uint32_t n );
 int lvh_app_set_option( lvh_app* app, int vrc_option, int64_t value );
-/* RenderInputs::dataSourceRange for volumes that are not uint8 (the reference forces (0,255),
- * livre/eq/Channel.cpp:284, and its CUDA renderer ignores the field; 16-bit volumes are an
- * extension here and default to (0,65535)) */
+/* RenderInputs::dataSourceRange, in the volume's own values, for volumes that are not uint8 (the reference forces
+ * (0,255), livre/eq/Channel.cpp:284, and its CUDA renderer ignores the field; the other voxel types are an extension
+ * here).  Without this call uint16 volumes take (0,65535), int8 (-128,127), int16 (-32768,32767): the type's range.
+ * uint32, int32 and float volumes have NO default -- the type's range says nothing about the data and a float has
+ * none: lvh_app_render_frame fails, and says to call this, until a range is set.  lvh_app_set_histogram reports
+ * signed, 32-bit and float volumes as unsupported. */
 int lvh_app_set_data_range( lvh_app* app, float lo, float hi );
 /* EXTENSION (BASELINE C5): per-ray adaptive LOD.  The pipeline makes the ancestors of the visible
  * set (SelectVisibles cut at --sse) resident as well and every ray applies the screen-space-error

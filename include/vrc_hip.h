@@ -224,10 +224,42 @@ int vrc_set_ray_lod( vrc_ctx* ctx, int enable, float screen_space_error, float w
 /* cuda::TexturePool::TexturePool (cuda/TexturePool.cu:101-173).  max_block is the slot size
  * in voxels (block + 2*overlap), max_bytes the atlas budget.  Slot grid and free-list order
  * follow TexturePool.cu:128-144 with VRC_MAX_TEXTURE_3D standing in for maxTexture3D. */
+/* vrc_pool_create makes pools of unsigned 8- and 16-bit single-component voxels and returns VRC_EUNSUPPORTED for every
+ * other combination; signed, 32-bit and float voxels have vrc_pool_create_typed below. */
 #define VRC_MAX_TEXTURE_3D 4096
 int vrc_pool_create( vrc_ctx* ctx, size_t bytes_per_voxel, int is_signed, int is_float,
                      size_t n_components, const uint32_t max_block[3], size_t max_bytes,
                      vrc_pool** out );
+/* EXTENSION: a pool by voxel type, single component (the reference's GL raycaster samples usampler3D / isampler3D /
+ * sampler3D and applies the real dataSourceRange, renderers/glRaycaster/shaders/fragRaycast.glsl:197-203; its CUDA
+ * kernel fetches unsigned char only).  vrc_pool_copy_to_slot[_device] takes bricks of that type, everything else is as
+ * for vrc_pool_create; VRC_VOXEL_UINT8 / _UINT16 give exactly the pool vrc_pool_create gives.  An unknown type:
+ * VRC_EINVAL.  vrc_render_data::dataSourceRange is in the volume's own values for every type.
+ *   INT8 / INT16    stored offset-binary (the upload flips the sign bit, v + 128 / + 32768 as an unsigned number, and
+ *                   vrc_render moves dataSourceRange by the same amount): every kernel form of the unsigned 8- and
+ *                   16-bit pools serves them -- the same frame, bit for bit, as the unsigned pool of v + 128 / + 32768
+ *                   with the moved range.  vrc_pool_read_region returns the signed values.
+ *   FLOAT32         a float atlas, bricks copied as they are.
+ *   UINT32 / INT32  the same float atlas: the upload converts every voxel to float32, round to nearest even, once
+ *                   (the conversion GLSL applies per sample).  vrc_pool_read_region returns what the atlas holds:
+ *                   float32.
+ * The float atlas is point-sampled (classified per sample, as 16-bit voxels are) or filtered trilinearly by the gather
+ * kernels: VRC_KERNEL_AUTO, _REFERENCE_ORDER, _GRID_DDA, per-ray LOD by gathers; an explicit VRC_KERNEL_LDS or _PACKED
+ * is VRC_EINVAL, also under vrc_set_ray_lod, and VRC_OPT_UNIFORM_BRICKS does not apply.  Voxels that are not finite are
+ * not inspected by the upload; a NaN density classifies as the first texel of the transfer function (the clamp of the
+ * texel coordinate drops it), +-infinity as the last / first.
+ * vrc_pool_histogram, vrc_pool_enable_histograms and vrc_frame_histogram return VRC_EUNSUPPORTED for the five types
+ * vrc_pool_create does not make. */
+#define VRC_VOXEL_UINT8 0
+#define VRC_VOXEL_UINT16 1
+#define VRC_VOXEL_UINT32 2
+#define VRC_VOXEL_INT8 3
+#define VRC_VOXEL_INT16 4
+#define VRC_VOXEL_INT32 5
+#define VRC_VOXEL_FLOAT32 6
+int vrc_pool_create_typed( vrc_ctx* ctx, int voxel_type, const uint32_t max_block[3], size_t max_bytes,
+                           vrc_pool** out );
+int vrc_pool_voxel_type( const vrc_pool* pool, int* voxel_type );
 void vrc_pool_destroy( vrc_pool* pool );
 /* cuda::TexturePool::copyToSlot (cuda/TexturePool.cu:175-203): host brick of size[] voxels,
  * tightly packed, x fastest.  Writes the normalized slot origin; on a full pool returns
@@ -245,7 +277,8 @@ int vrc_pool_info( const vrc_pool* pool, size_t* slot_bytes, uint32_t atlas_dim[
 /* block until every pending upload of the pool has landed in HBM */
 int vrc_pool_synchronize( vrc_pool* pool );
 /* debug/test: read back the voxel at logical atlas coordinate (x,y,z) region into host memory,
- * row-major; used by the parity tests to check the atlas layout transform */
+ * row-major; used by the parity tests to check the atlas layout transform.  Voxels come back in the pool's type,
+ * except from a pool of 32-bit integers: float32, what its atlas holds (vrc_pool_create_typed) */
 int vrc_pool_read_region( vrc_pool* pool, const uint32_t origin[3], const uint32_t size[3],
                           void* host_out );
 
@@ -361,7 +394,9 @@ const char* vrc_last_kernel( void );
  * checkable without a profiler.  The vrc_k_raycast instances only (VRC_EINVAL after another kernel). */
 int vrc_last_kernel_occupancy( int* workgroups_per_cu, int* threads_per_workgroup );
 /* ABI version of this header */
-#define VRC_ABI_VERSION 4 /* 3: vrc_gather_tiles takes the frame height; 4: VRC_KERNEL_PACKED, VRC_OPT_PACKED_ATLAS, vrc_last_kernel_occupancy */
+#define VRC_ABI_VERSION 4 /* 3: vrc_gather_tiles takes the frame height; 4: VRC_KERNEL_PACKED, VRC_OPT_PACKED_ATLAS, vrc_last_kernel_occupancy
+                           * (added since without a new number, as symbols a caller may bind weakly: the frame histogram,
+                           * vrc_pool_create_typed / vrc_pool_voxel_type) */
 /* = VRC_ABI_VERSION for the product build; -VRC_ABI_VERSION for a developer build of the library (compiled with
  * -DVRC_DEV_BUILD: experiment switches, statistics, ablations that render wrong pixels on purpose) */
 int vrc_abi_version( void );

@@ -48,7 +48,10 @@ struct vrc_pool
     vrc_ctx* ctx = nullptr; /* creating context (device identification only) */
     int device = 0;
     uint64_t uid = 0;       /* unique per process, keys the node-table caches of contexts */
-    uint32_t elemBytes = 1;
+    uint32_t elemBytes = 1; /* of an atlas element = of a voxel as uploaded: 1, 2 or 4 (the float atlas) */
+    int voxelType = VRC_VOXEL_UINT8;
+    uint32_t xform = VRC_XF_NONE; /* what the upload does to a voxel (vrc_core.h: VRC_XF_*) */
+    float rangeShift = 0.0f;      /* signed 8/16-bit voxels are stored offset-binary: + 128 / + 32768 on dataSourceRange */
     uint32_t maxBlock[3] = { 0, 0, 0 };
     uint32_t slotDim[3] = { 0, 0, 0 }; /* maxBlock rounded up to the micro-block size */
     uint32_t slots[3] = { 1, 1, 1 };
@@ -451,6 +454,8 @@ int vrc_set_ray_lod( vrc_ctx* c, int enable, float screenSpaceError, float world
 }
 
 /* ---------------------------------------------------------------------------------------- */
+static int pool_create( vrc_ctx* c, int voxelType, const uint32_t maxBlock[3], size_t maxBytes, vrc_pool** out );
+
 int vrc_pool_create( vrc_ctx* c, size_t bytesPerVoxel, int isSigned, int isFloat,
                      size_t nComponents, const uint32_t maxBlock[3], size_t maxBytes,
                      vrc_pool** out )
@@ -461,12 +466,51 @@ int vrc_pool_create( vrc_ctx* c, size_t bytesPerVoxel, int isSigned, int isFloat
     /* cuda/TexturePool.cu:66-67 */
     if( nComponents == 0 || nComponents > 4 )
         return fail( VRC_EUNSUPPORTED, "Channel number cannot be 0 or larger than 4" );
-    /* the reference kernel only ever fetches unsigned char (Renderer.cu:211, quirk Q2); this
-     * layer renders unsigned 8-bit (the reference path) and, as an extension, unsigned 16-bit
-     * single-channel volumes, and says so for the rest instead of mis-rendering them */
+    /* the reference kernel only ever fetches unsigned char (Renderer.cu:211, quirk Q2); this entry point
+     * makes pools of unsigned 8-bit (the reference path) and, as an extension, unsigned 16-bit
+     * single-channel volumes, and says so for the rest: signed, 32-bit and float volumes have
+     * vrc_pool_create_typed */
     if( ( bytesPerVoxel != 1 && bytesPerVoxel != 2 ) || nComponents != 1 || isFloat || isSigned )
         return fail( VRC_EUNSUPPORTED,
-                     "vrc_pool_create: only unsigned 8/16-bit single-channel volumes are implemented" );
+                     "vrc_pool_create: only unsigned 8/16-bit single-channel volumes are implemented "
+                     "(signed, 32-bit and float: vrc_pool_create_typed)" );
+    return pool_create( c, bytesPerVoxel == 1 ? VRC_VOXEL_UINT8 : VRC_VOXEL_UINT16, maxBlock, maxBytes, out );
+}
+
+int vrc_pool_create_typed( vrc_ctx* c, int voxelType, const uint32_t maxBlock[3], size_t maxBytes, vrc_pool** out )
+{
+    if( !c || !out || !maxBlock )
+        return fail( VRC_EINVAL, "vrc_pool_create_typed: NULL argument" );
+    *out = nullptr;
+    if( voxelType < VRC_VOXEL_UINT8 || voxelType > VRC_VOXEL_FLOAT32 )
+        return fail( VRC_EINVAL, "vrc_pool_create_typed: unknown voxel type " + std::to_string( voxelType ) );
+    return pool_create( c, voxelType, maxBlock, maxBytes, out );
+}
+
+int vrc_pool_voxel_type( const vrc_pool* p, int* voxelType )
+{
+    if( !p || !voxelType )
+        return fail( VRC_EINVAL, "vrc_pool_voxel_type: NULL argument" );
+    *voxelType = p->voxelType;
+    return VRC_OK;
+}
+
+static int pool_create( vrc_ctx* c, int voxelType, const uint32_t maxBlock[3], size_t maxBytes, vrc_pool** out )
+{
+    size_t bytesPerVoxel = 1;
+    const size_t nComponents = 1;
+    uint32_t xform = VRC_XF_NONE;
+    float rangeShift = 0.0f;
+    switch( voxelType )
+    {
+    case VRC_VOXEL_UINT8: break;
+    case VRC_VOXEL_UINT16: bytesPerVoxel = 2; break;
+    case VRC_VOXEL_INT8: xform = VRC_XF_FLIP; rangeShift = 128.0f; break;
+    case VRC_VOXEL_INT16: bytesPerVoxel = 2; xform = VRC_XF_FLIP; rangeShift = 32768.0f; break;
+    case VRC_VOXEL_UINT32: bytesPerVoxel = 4; xform = VRC_XF_U32F; break;
+    case VRC_VOXEL_INT32: bytesPerVoxel = 4; xform = VRC_XF_I32F; break;
+    default: bytesPerVoxel = 4; break; /* VRC_VOXEL_FLOAT32: copied as it is */
+    }
     if( maxBlock[0] == 0 || maxBlock[1] == 0 || maxBlock[2] == 0 )
         return fail( VRC_EINVAL, "vrc_pool_create: zero block size" );
     VRC_HIP_CHECK( hipSetDevice( c->device ) );
@@ -481,6 +525,9 @@ int vrc_pool_create( vrc_ctx* c, size_t bytesPerVoxel, int isSigned, int isFloat
         p->uid = nextUid++;
     }
     p->elemBytes = (uint32_t)( bytesPerVoxel * nComponents );
+    p->voxelType = voxelType;
+    p->xform = xform;
+    p->rangeShift = rangeShift;
     for( int a = 0; a < 3; ++a )
     {
         p->maxBlock[a] = maxBlock[a];
@@ -743,7 +790,8 @@ static int pool_upload( vrc_pool* p, const void* src, bool srcIsDevice, const ui
             uint32_t* const info = p->dSlotInfo + index;
             e = hipMemsetAsync( info, 0, sizeof( uint32_t ), p->uploadStream );
             if( e == hipSuccess )
-                e = vrc_launch_repack_brick( devSrc, slotPtr, p->elemBytes, size, p->slotDim, p->uploadStream, info );
+                e = vrc_launch_repack_brick( devSrc, slotPtr, p->elemBytes, size, p->slotDim, p->uploadStream, info,
+                                             p->xform );
             if( e == hipSuccess && p->packedOn )
                 e = vrc_launch_pack_slots( p->dAtlas, p->dPacked, base,
                                            (uint64_t)p->slotDim[0] * p->slotDim[1] * p->slotDim[2], p->slotDim,
@@ -917,8 +965,9 @@ int vrc_pool_read_region( vrc_pool* p, const uint32_t origin[3], const uint32_t 
             lay.slots[a] = p->slots[a];
             lay.slotDim[a] = p->slotDim[a];
         }
+        /* offset-binary voxels come back signed; a 4-byte atlas comes back as what it holds, float32 */
         e = vrc_launch_read_region( p->dAtlas, tmp, p->elemBytes, origin, size, lay,
-                                    p->uploadStream );
+                                    p->uploadStream, p->xform == VRC_XF_FLIP ? VRC_XF_FLIP : VRC_XF_NONE );
     }
     if( e == hipSuccess ) e = hipStreamSynchronize( p->uploadStream );
     if( e == hipSuccess ) e = hipMemcpy( hostOut, tmp, bytes, hipMemcpyDeviceToHost );
@@ -926,6 +975,12 @@ int vrc_pool_read_region( vrc_pool* p, const uint32_t origin[3], const uint32_t 
     if( e != hipSuccess )
         return fail( VRC_EHIP, std::string( "vrc_pool_read_region: " ) + hipGetErrorString( e ) );
     return VRC_OK;
+}
+
+/* brick histograms bin unsigned 8/16-bit voxels over the type's range */
+static bool pool_has_histograms( const vrc_pool* p )
+{
+    return p->voxelType == VRC_VOXEL_UINT8 || p->voxelType == VRC_VOXEL_UINT16;
 }
 
 int vrc_pool_histogram( vrc_pool* p, const float slot[3], const uint32_t origin[3],
@@ -936,6 +991,8 @@ int vrc_pool_histogram( vrc_pool* p, const float slot[3], const uint32_t origin[
         return fail( VRC_EINVAL, "vrc_pool_histogram: NULL argument" );
     if( slot[0] < 0.f || slot[1] < 0.f || slot[2] < 0.f )
         return fail( VRC_EINVAL, "vrc_pool_histogram: invalid slot" );
+    if( !pool_has_histograms( p ) )
+        return fail( VRC_EUNSUPPORTED, "vrc_pool_histogram: histograms of signed, 32-bit and float voxels are not implemented" );
     const uint32_t typeRange = p->elemBytes == 1 ? 256u : 65536u;
     if( binCount == 0 || binCount > 4096 || typeRange % binCount != 0 )
         return fail( VRC_EINVAL, "vrc_pool_histogram: bin count must divide the voxel type's range (max 4096)" );
@@ -983,6 +1040,8 @@ int vrc_pool_enable_histograms( vrc_pool* p, uint32_t binCount, const uint32_t o
 {
     if( !p )
         return fail( VRC_EINVAL, "vrc_pool_enable_histograms: pool is NULL" );
+    if( binCount != 0 && !pool_has_histograms( p ) )
+        return fail( VRC_EUNSUPPORTED, "vrc_pool_enable_histograms: histograms of signed, 32-bit and float voxels are not implemented" );
     const uint32_t typeRange = p->elemBytes == 1 ? 256u : 65536u;
     if( binCount != 0 && ( !overlap || binCount > VRC_HIST_MAX_BINS || typeRange % binCount != 0 ) )
         return fail( VRC_EINVAL, "vrc_pool_enable_histograms: bin count must divide the voxel type's range (max 4096), "
@@ -1294,10 +1353,15 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
 
     /* classified table, rebuilt only when one of its inputs changed */
     vrc_lut_params lp;
-    lp.rangeMin = render->dataSourceRange[0];
-    lp.rangeMax = render->dataSourceRange[1];
+    /* signed 8/16-bit voxels are in the atlas offset-binary (v + 128 / + 32768): the range moves with them, and every
+     * kernel form serves the pool as the unsigned one it then is (the trilinear filter commutes with the offset) */
+    lp.rangeMin = render->dataSourceRange[0] + pool->rangeShift;
+    lp.rangeMax = render->dataSourceRange[1] + pool->rangeShift;
     lp.alphaCorrection = (float)render->maxSamplesPerRay / (float)render->samplesPerRay;
     lp.fracBits = (int)c->optTfFracBits;
+    if( pool->elemBytes == 4 && ( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED ) )
+        return fail( VRC_EINVAL, "vrc_render: 32-bit and float voxels are marched by gathers; the LDS-staged and tap-packed "
+                                 "forms take 8- and 16-bit voxels (VRC_OPT_KERNEL = AUTO, REFERENCE_ORDER or GRID_DDA)" );
     const bool linear = c->optFilter == VRC_FILTER_TRILINEAR;
     /* samples classified one by one (padded transfer function in the table buffer) whenever the
      * 257-entry classified table cannot be used: continuous or 16-bit densities */
@@ -1779,6 +1843,8 @@ int vrc_frame_histogram( vrc_ctx* c, vrc_pool* pool, const float* slots, const u
 {
     if( !c || !pool || ( n && ( !slots || !scales ) ) )
         return fail( VRC_EINVAL, "vrc_frame_histogram: NULL argument" );
+    if( pool->voxelType != VRC_VOXEL_UINT8 && pool->voxelType != VRC_VOXEL_UINT16 )
+        return fail( VRC_EUNSUPPORTED, "vrc_frame_histogram: histograms of signed, 32-bit and float voxels are not implemented" );
     if( accumulate && c->frameHistBins == 0 )
         return fail( VRC_EINVAL, "vrc_frame_histogram: nothing to accumulate into" );
     VRC_HIP_CHECK( hipSetDevice( c->device ) );

@@ -869,8 +869,20 @@ VRC_HD vrc_f2 vrc_classify( const vrc_f2* tfp, float d, const vrc_classifier& k 
 /* table entry of a fetched voxel: lut[d] -- or, PERSAMPLE (volumes the 257-entry table cannot index: 16-bit
  * voxels), the transfer function and the opacity correction evaluated on the value (vrc_classify; lut is then the
  * padded transfer function and the entries are four floats) */
-template < bool PERSAMPLE, typename E >
-VRC_HD E vrc_entry( const E* lut, uint32_t d, const vrc_classifier* cls )
+/* D: what a fetched voxel is held as between the gather and the table: uint32_t for the integer atlases, float for the
+ * float atlas (32-bit and float volumes, include/vrc_hip.h: vrc_pool_create_typed), which is always PERSAMPLE */
+template < typename ATLAS_T >
+struct vrc_density
+{
+    typedef uint32_t type;
+};
+template <>
+struct vrc_density< float >
+{
+    typedef float type;
+};
+template < bool PERSAMPLE, typename E, typename D >
+VRC_HD E vrc_entry( const E* lut, D d, const vrc_classifier* cls )
 {
     if constexpr( PERSAMPLE )
         return vrc_classify( lut, (float)d, *cls );
@@ -911,6 +923,29 @@ VRC_HD float vrc_bits_float( uint32_t u )
     memcpy( &v, &u, 4 );
     return v;
 #endif
+}
+
+/* What a brick upload does to a voxel on its way into the atlas (include/vrc_hip.h: vrc_pool_create_typed), and
+ * vrc_pool_read_region undoes where it can.  T is the unsigned integer of the voxel's size; the 32-bit forms return
+ * the bits of the float the atlas holds.
+ *   FLIP  signed 8/16-bit: offset binary, v ^ sign bit = v + 128 / + 32768 as an unsigned number (its own inverse);
+ *   U32F / I32F  32-bit integers: converted to float32, round to nearest even (the conversion the GLSL reference
+ *         applies to every usampler3D / isampler3D texel, fragRaycast.glsl:197-203, done once). */
+#define VRC_XF_NONE 0
+#define VRC_XF_FLIP 1
+#define VRC_XF_U32F 2
+#define VRC_XF_I32F 3
+template < int XF, typename T >
+VRC_HD T vrc_voxel_xform( T v )
+{
+    if constexpr( XF == VRC_XF_FLIP )
+        return (T)( v ^ (T)( (T)1 << ( 8u * sizeof( T ) - 1u ) ) );
+    else if constexpr( XF == VRC_XF_U32F )
+        return (T)vrc_float_bits( (float)(uint32_t)v );
+    else if constexpr( XF == VRC_XF_I32F )
+        return (T)vrc_float_bits( (float)(int32_t)v );
+    else
+        return v;
 }
 
 /* travel > 0.  Whether the count is exact, and the count: the trips of `for( ; travel > 0; travel -= stepSize )` */
@@ -1010,6 +1045,8 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
                                   const vrc_classifier* cls = nullptr, const E ue = E{} )
 {
     static_assert( !( UNIFORM && PERSAMPLE ), "the uniform march takes its entry from the classified table" );
+    typedef typename vrc_density< ATLAS_T >::type D;
+    static_assert( PERSAMPLE || sizeof( D ) == sizeof( uint32_t ), "a table is indexed by an integer voxel" );
     /* levelStep: step of a coarser brick under per-ray LOD (vrc_pixel_ray_lod); 0 = the frame's */
     const float stepSize = levelStep > 0.0f ? levelStep : f.stepSize;
     const vrc_sampler sm = vrc_make_sampler( n, f ); /* (unused, and compiled out, when UNIFORM) */
@@ -1187,7 +1224,7 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
 #elif defined( VRC_ABLATE_QUARTER_FETCH ) /* timing experiment only */
                 e[k] = lut[(uint32_t)atlas[idx[k & ~3]] + ( idx[k] >> 31 )];
 #else
-                e[k] = vrc_entry< PERSAMPLE, E >( lut, (uint32_t)atlas[idx[k]], cls );
+                e[k] = vrc_entry< PERSAMPLE, E >( lut, (D)atlas[idx[k]], cls );
 #endif
         }
 #if defined( VRC_SETPRIO ) && defined( __HIP_DEVICE_COMPILE__ )
@@ -1235,7 +1272,8 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
 #endif
     while( travel > 0.0f && !done )
     {
-        uint32_t idx[TAILG], d[TAILG], cnt = 0;
+        uint32_t idx[TAILG], cnt = 0;
+        D d[TAILG];
         if constexpr( UNIFORM )
         {
 #pragma unroll
@@ -1256,7 +1294,7 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
         }
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
-            d[k] = UNIFORM ? 0u : (uint32_t)atlas[idx[k]];
+            d[k] = UNIFORM ? (D)0 : (D)atlas[idx[k]];
         E e[TAILG];
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
@@ -2058,11 +2096,12 @@ VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vr
          * is replaced by vrc_classify */
         return vrc_march_segment_as< CLAMP, COUNT, true, ATLAS_T, GROUP, vrc_f4, true >( f, n, s, atlas, lut, color,
                                                                                        nSamples, levelStep, &cls );
-    else if( MODE != VRC_MODE_TABLE )
+    else if constexpr( MODE != VRC_MODE_TABLE )
         return vrc_march_segment_linear< CLAMP, COUNT, MODE == VRC_MODE_TRILINEAR, ATLAS_T >(
             f, n, s, atlas, lut, cls, color, nSamples, levelStep );
-    return vrc_march_segment< CLAMP, COUNT, FIXED, ATLAS_T, GROUP >( f, n, s, atlas, lut, color, nSamples,
-                                                                   levelStep );
+    else
+        return vrc_march_segment< CLAMP, COUNT, FIXED, ATLAS_T, GROUP >( f, n, s, atlas, lut, color, nSamples,
+                                                                       levelStep );
 }
 
 /* ---- tile culling for the reference-order loop -------------------------------------------------------------

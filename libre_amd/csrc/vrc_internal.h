@@ -69,11 +69,13 @@ hipError_t vrc_launch_build_lut( const float* tf, vrc_f4* lut, vrc_lut_params p,
 /* row-major brick (size voxels, elemBytes per voxel) -> micro-blocked slot (slot = device
  * pointer to the slot's first element; slotDim = padded slot size in voxels).  A brick smaller
  * than the slot gets its border voxels replicated into the padding.
+ * xform: what a voxel undergoes on the way (vrc_core.h: VRC_XF_*; elemBytes is the size of a voxel on both sides).
  * slotInfo (may be NULL): the slot's uniformity word (vrc_core.h: VRC_SLOT_*), which the caller zeroed on `stream`
  * before this call; the kernel ORs into it what it finds. */
 hipError_t vrc_launch_repack_brick( const void* srcRowMajor, void* slot, uint32_t elemBytes,
                                     const uint32_t size[3], const uint32_t slotDim[3],
-                                    hipStream_t stream, uint32_t* slotInfo = nullptr );
+                                    hipStream_t stream, uint32_t* slotInfo = nullptr,
+                                    uint32_t xform = VRC_XF_NONE );
 
 /* atlas -> tap-packed atlas (vrc_core.h): the packed texels of elements [firstElem, firstElem + nElems) of the atlas of
  * 8- or 16-bit voxels (whole slots; the packed atlas holds vrc_packed_elems( atlas elements ) texels of
@@ -81,10 +83,10 @@ hipError_t vrc_launch_repack_brick( const void* srcRowMajor, void* slot, uint32_
 hipError_t vrc_launch_pack_slots( const void* atlas, void* packed, uint64_t firstElem, uint64_t nElems,
                                   const uint32_t slotDim[3], uint32_t elemBytes, hipStream_t stream );
 
-/* inverse, for tests: logical atlas region -> row-major */
+/* inverse, for tests: logical atlas region -> row-major (xform: VRC_XF_NONE or VRC_XF_FLIP, its own inverse) */
 hipError_t vrc_launch_read_region( const void* atlas, void* dstRowMajor, uint32_t elemBytes,
                                    const uint32_t origin[3], const uint32_t size[3],
-                                   const vrc_layout& lay, hipStream_t stream );
+                                   const vrc_layout& lay, hipStream_t stream, uint32_t xform = VRC_XF_NONE );
 
 /* brick histograms (vrc_kernels.hip): an entry is a region of one slot and the row of `rows` its counts are added to
  * (uint32, binCount per row; the caller zeroes the rows).  Bin = v / (typeRange / binCount); 8- or 16-bit voxels,
@@ -128,8 +130,8 @@ struct vrc_raycast_args
     bool gridDda;
     bool fixedStepping; /* VRC_OPT_STEPPING */
     bool linear;        /* VRC_OPT_FILTER = 1 (trilinear) */
-    uint32_t elemBytes; /* voxel size: 1 (u8) or 2 (u16; classified per sample).  lut holds the padded
-                         * transfer function whenever samples are classified one by one */
+    uint32_t elemBytes; /* atlas element size: 1 (u8), 2 (u16; classified per sample) or 4 (float; classified per
+                         * sample).  lut holds the padded transfer function whenever samples are classified one by one */
     vrc_classifier classifier;
     bool bigAtlas; /* more than 2^32 voxels: node slot bases are 64-bit (BIG kernel instances) */
     bool greyTable;    /* the transfer function is grey and the frame starts from zero: the two-float table form

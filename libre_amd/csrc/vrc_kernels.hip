@@ -23,6 +23,7 @@
 #include "vrc_internal.h"
 
 #include <algorithm>
+#include <type_traits>
 
 /* pixel tile of one wave: VRC_TILE_W x VRC_TILE_H = 64 (vrc_internal.h) */
 #define VRC_WG 64u
@@ -79,12 +80,16 @@ hipError_t vrc_launch_build_lut( const float* tf, vrc_f4* lut, vrc_lut_params p,
  * Every thread compares the voxels it moves with the brick's first voxel; a wave that met another value ORs MIXED
  * into the word, the thread that moves voxel 0 ORs value | KNOWN.  ORs commute: no order between workgroups needed,
  * and the word is complete when the kernel is -- with the voxels it describes. */
+/* FLIP: signed voxels, stored offset-binary (vrc_core.h: VRC_XF_FLIP) -- the sign bit of all eight flipped on the way;
+ * the uniformity word then holds the value the atlas holds, which is what the march indexes its table with */
+template < bool FLIP >
 __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __restrict__ slot,
                                    uint32_t sx8, uint32_t sy, uint32_t sz, uint32_t sbx,
                                    uint32_t sby, uint32_t* __restrict__ info )
 {
     const uint32_t total = sx8 * sy * sz;
-    const uint32_t first = src[0].x & 0xFFu, all = first * 0x01010101u;
+    constexpr uint32_t flip = FLIP ? 0x80808080u : 0u;
+    const uint32_t first = ( src[0].x ^ flip ) & 0xFFu, all = first * 0x01010101u;
     bool mixed = false;
     for( uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += gridDim.x * blockDim.x )
@@ -92,7 +97,9 @@ __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __res
         const uint32_t x8 = i % sx8;
         const uint32_t y = ( i / sx8 ) % sy;
         const uint32_t z = i / ( sx8 * sy );
-        const uint2 v = src[i];
+        uint2 v = src[i];
+        v.x ^= flip;
+        v.y ^= flip;
         const uint32_t e = vrc_slot_local_index( x8 * 8u, y, z, sbx, sby );
         *reinterpret_cast< uint2* >( slot + e ) = v;
         mixed = mixed || v.x != all || v.y != all;
@@ -106,7 +113,8 @@ __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __res
     }
 }
 
-template < typename T >
+/* XF: what happens to a voxel on the way (vrc_core.h: vrc_voxel_xform) */
+template < typename T, int XF = VRC_XF_NONE >
 __global__ void vrc_k_repack_generic( const T* __restrict__ src, T* __restrict__ slot,
                                       uint32_t sx, uint32_t sy, uint32_t sz, uint32_t sbx,
                                       uint32_t sby )
@@ -118,7 +126,7 @@ __global__ void vrc_k_repack_generic( const T* __restrict__ src, T* __restrict__
         const uint32_t x = (uint32_t)( i % sx );
         const uint32_t y = (uint32_t)( ( i / sx ) % sy );
         const uint32_t z = (uint32_t)( i / ( (size_t)sx * sy ) );
-        slot[vrc_slot_local_index( x, y, z, sbx, sby )] = src[i];
+        slot[vrc_slot_local_index( x, y, z, sbx, sby )] = vrc_voxel_xform< XF, T >( src[i] );
     }
 }
 
@@ -126,7 +134,7 @@ __global__ void vrc_k_repack_generic( const T* __restrict__ src, T* __restrict__
  * voxels, i.e. clamp addressing at the brick border is baked into the data -- what the
  * clamped trilinear taps one voxel past the brick must read (cudaAddressModeClamp on a
  * texture that ends with the brick, cuda/TexturePool.cu:163-170) */
-template < typename T >
+template < typename T, int XF = VRC_XF_NONE >
 __global__ void vrc_k_repack_padded( const T* __restrict__ src, T* __restrict__ slot, uint32_t sx,
                                      uint32_t sy, uint32_t sz, uint32_t dx, uint32_t dy,
                                      uint32_t dz )
@@ -140,11 +148,11 @@ __global__ void vrc_k_repack_padded( const T* __restrict__ src, T* __restrict__ 
         const uint32_t y = (uint32_t)( ( i / dx ) % dy );
         const uint32_t z = (uint32_t)( i / ( (size_t)dx * dy ) );
         const uint32_t cx = x < sx ? x : sx - 1u, cy = y < sy ? y : sy - 1u, cz = z < sz ? z : sz - 1u;
-        slot[vrc_slot_local_index( x, y, z, sbx, sby )] = src[( (size_t)cz * sy + cy ) * sx + cx];
+        slot[vrc_slot_local_index( x, y, z, sbx, sby )] = vrc_voxel_xform< XF, T >( src[( (size_t)cz * sy + cy ) * sx + cx] );
     }
 }
 
-template < typename T >
+template < typename T, int XF = VRC_XF_NONE >
 __global__ void vrc_k_read_region( const T* __restrict__ atlas, T* __restrict__ dst,
                                    uint32_t sx, uint32_t sy, uint32_t sz, uint32_t ox,
                                    uint32_t oy, uint32_t oz, const vrc_layout lay )
@@ -156,7 +164,7 @@ __global__ void vrc_k_read_region( const T* __restrict__ atlas, T* __restrict__ 
         const uint32_t x = (uint32_t)( i % sx );
         const uint32_t y = (uint32_t)( ( i / sx ) % sy );
         const uint32_t z = (uint32_t)( i / ( (size_t)sx * sy ) );
-        dst[i] = atlas[vrc_atlas_index( lay, ox + x, oy + y, oz + z )];
+        dst[i] = vrc_voxel_xform< XF, T >( atlas[vrc_atlas_index( lay, ox + x, oy + y, oz + z )] );
     }
 }
 
@@ -369,78 +377,108 @@ static uint32_t grid_for( size_t total, uint32_t block )
 
 hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBytes,
                                     const uint32_t size[3], const uint32_t slotDim[3],
-                                    hipStream_t stream, uint32_t* slotInfo )
+                                    hipStream_t stream, uint32_t* slotInfo, uint32_t xform )
 {
     /* slotInfo: only the kernel that fills a whole slot of 1-byte voxels tests for a uniform brick; after the others
      * the (zeroed) word says "nothing known" and the brick takes the general march */
     const size_t total = (size_t)size[0] * size[1] * size[2];
     if( total == 0 )
         return hipSuccess;
+    /* the transforms a voxel size has: the sign flip for 1 and 2 bytes, the conversions to float for 4 */
+    if( xform != VRC_XF_NONE && ( elemBytes == 4 ? ( xform != VRC_XF_U32F && xform != VRC_XF_I32F )
+                                                 : ( xform != VRC_XF_FLIP || ( elemBytes != 1 && elemBytes != 2 ) ) ) )
+        return hipErrorInvalidValue;
     const uint32_t sbx = slotDim[0] >> VRC_MB_SHIFT, sby = slotDim[1] >> VRC_MB_SHIFT;
     if( size[0] != slotDim[0] || size[1] != slotDim[1] || size[2] != slotDim[2] )
     {
         const size_t all = (size_t)slotDim[0] * slotDim[1] * slotDim[2];
         const dim3 g( grid_for( all, 256 ) ), b( 256 );
-        if( elemBytes == 1 )
-            hipLaunchKernelGGL( vrc_k_repack_padded< uint8_t >, g, b, 0, stream, (const uint8_t*)src,
-                                (uint8_t*)slot, size[0], size[1], size[2], slotDim[0], slotDim[1], slotDim[2] );
+#define VRC_PADDED( T, XF )                                                                                       \
+    hipLaunchKernelGGL( ( vrc_k_repack_padded< T, XF > ), g, b, 0, stream, (const T*)src, (T*)slot, size[0], size[1], \
+                        size[2], slotDim[0], slotDim[1], slotDim[2] )
+        if( elemBytes == 1 && xform == VRC_XF_FLIP )
+            VRC_PADDED( uint8_t, VRC_XF_FLIP );
+        else if( elemBytes == 1 )
+            VRC_PADDED( uint8_t, VRC_XF_NONE );
+        else if( elemBytes == 2 && xform == VRC_XF_FLIP )
+            VRC_PADDED( uint16_t, VRC_XF_FLIP );
         else if( elemBytes == 2 )
-            hipLaunchKernelGGL( vrc_k_repack_padded< uint16_t >, g, b, 0, stream, (const uint16_t*)src,
-                                (uint16_t*)slot, size[0], size[1], size[2], slotDim[0], slotDim[1], slotDim[2] );
+            VRC_PADDED( uint16_t, VRC_XF_NONE );
+        else if( elemBytes == 4 && xform == VRC_XF_U32F )
+            VRC_PADDED( uint32_t, VRC_XF_U32F );
+        else if( elemBytes == 4 && xform == VRC_XF_I32F )
+            VRC_PADDED( uint32_t, VRC_XF_I32F );
         else if( elemBytes == 4 )
-            hipLaunchKernelGGL( vrc_k_repack_padded< uint32_t >, g, b, 0, stream, (const uint32_t*)src,
-                                (uint32_t*)slot, size[0], size[1], size[2], slotDim[0], slotDim[1], slotDim[2] );
+            VRC_PADDED( uint32_t, VRC_XF_NONE );
         else
             return hipErrorInvalidValue;
+#undef VRC_PADDED
         return hipGetLastError();
     }
+#define VRC_GENERIC( T, XF )                                                                                          \
+    hipLaunchKernelGGL( ( vrc_k_repack_generic< T, XF > ), dim3( grid_for( total, 256 ) ), dim3( 256 ), 0, stream,     \
+                        (const T*)src, (T*)slot, size[0], size[1], size[2], sbx, sby )
     /* (the experimental layout 5 has no 8-voxel runs along x: generic kernel) */
     if( VRC_LAYOUT != 5 && elemBytes == 1 && ( size[0] % 8u ) == 0 && ( ( (uintptr_t)src ) % 8u ) == 0 &&
         ( ( (uintptr_t)slot ) % 8u ) == 0 && total / 8 < 0xFFFFFFFFull )
     {
         const uint32_t sx8 = size[0] / 8u;
-        hipLaunchKernelGGL( vrc_k_repack_u8x8, dim3( grid_for( total / 8, 256 ) ), dim3( 256 ), 0,
-                            stream, (const uint2*)src, (uint8_t*)slot, sx8, size[1], size[2], sbx,
-                            sby, slotInfo );
+        if( xform == VRC_XF_FLIP )
+            hipLaunchKernelGGL( vrc_k_repack_u8x8< true >, dim3( grid_for( total / 8, 256 ) ), dim3( 256 ), 0,
+                                stream, (const uint2*)src, (uint8_t*)slot, sx8, size[1], size[2], sbx,
+                                sby, slotInfo );
+        else
+            hipLaunchKernelGGL( vrc_k_repack_u8x8< false >, dim3( grid_for( total / 8, 256 ) ), dim3( 256 ), 0,
+                                stream, (const uint2*)src, (uint8_t*)slot, sx8, size[1], size[2], sbx,
+                                sby, slotInfo );
     }
+    else if( elemBytes == 1 && xform == VRC_XF_FLIP )
+        VRC_GENERIC( uint8_t, VRC_XF_FLIP );
     else if( elemBytes == 1 )
-        hipLaunchKernelGGL( vrc_k_repack_generic< uint8_t >, dim3( grid_for( total, 256 ) ),
-                            dim3( 256 ), 0, stream, (const uint8_t*)src, (uint8_t*)slot, size[0],
-                            size[1], size[2], sbx, sby );
+        VRC_GENERIC( uint8_t, VRC_XF_NONE );
+    else if( elemBytes == 2 && xform == VRC_XF_FLIP )
+        VRC_GENERIC( uint16_t, VRC_XF_FLIP );
     else if( elemBytes == 2 )
-        hipLaunchKernelGGL( vrc_k_repack_generic< uint16_t >, dim3( grid_for( total, 256 ) ),
-                            dim3( 256 ), 0, stream, (const uint16_t*)src, (uint16_t*)slot, size[0],
-                            size[1], size[2], sbx, sby );
+        VRC_GENERIC( uint16_t, VRC_XF_NONE );
+    else if( elemBytes == 4 && xform == VRC_XF_U32F )
+        VRC_GENERIC( uint32_t, VRC_XF_U32F );
+    else if( elemBytes == 4 && xform == VRC_XF_I32F )
+        VRC_GENERIC( uint32_t, VRC_XF_I32F );
     else if( elemBytes == 4 )
-        hipLaunchKernelGGL( vrc_k_repack_generic< uint32_t >, dim3( grid_for( total, 256 ) ),
-                            dim3( 256 ), 0, stream, (const uint32_t*)src, (uint32_t*)slot, size[0],
-                            size[1], size[2], sbx, sby );
+        VRC_GENERIC( uint32_t, VRC_XF_NONE );
     else
         return hipErrorInvalidValue;
+#undef VRC_GENERIC
     return hipGetLastError();
 }
 
 hipError_t vrc_launch_read_region( const void* atlas, void* dst, uint32_t elemBytes,
                                    const uint32_t o[3], const uint32_t size[3],
-                                   const vrc_layout& lay, hipStream_t stream )
+                                   const vrc_layout& lay, hipStream_t stream, uint32_t xform )
 {
     const size_t total = (size_t)size[0] * size[1] * size[2];
     if( total == 0 )
         return hipSuccess;
     const dim3 g( grid_for( total, 256 ) ), b( 256 );
-    if( elemBytes == 1 )
-        hipLaunchKernelGGL( vrc_k_read_region< uint8_t >, g, b, 0, stream, (const uint8_t*)atlas,
-                            (uint8_t*)dst, size[0], size[1], size[2], o[0], o[1], o[2], lay );
+#define VRC_READ( T, XF )                                                                                          \
+    hipLaunchKernelGGL( ( vrc_k_read_region< T, XF > ), g, b, 0, stream, (const T*)atlas, (T*)dst, size[0], size[1], \
+                        size[2], o[0], o[1], o[2], lay )
+    /* the sign flip is its own inverse; a 4-byte atlas is read as it is (float32) */
+    if( xform != VRC_XF_NONE && ( xform != VRC_XF_FLIP || ( elemBytes != 1 && elemBytes != 2 ) ) )
+        return hipErrorInvalidValue;
+    if( elemBytes == 1 && xform == VRC_XF_FLIP )
+        VRC_READ( uint8_t, VRC_XF_FLIP );
+    else if( elemBytes == 1 )
+        VRC_READ( uint8_t, VRC_XF_NONE );
+    else if( elemBytes == 2 && xform == VRC_XF_FLIP )
+        VRC_READ( uint16_t, VRC_XF_FLIP );
     else if( elemBytes == 2 )
-        hipLaunchKernelGGL( vrc_k_read_region< uint16_t >, g, b, 0, stream,
-                            (const uint16_t*)atlas, (uint16_t*)dst, size[0], size[1], size[2],
-                            o[0], o[1], o[2], lay );
+        VRC_READ( uint16_t, VRC_XF_NONE );
     else if( elemBytes == 4 )
-        hipLaunchKernelGGL( vrc_k_read_region< uint32_t >, g, b, 0, stream,
-                            (const uint32_t*)atlas, (uint32_t*)dst, size[0], size[1], size[2],
-                            o[0], o[1], o[2], lay );
+        VRC_READ( uint32_t, VRC_XF_NONE );
     else
         return hipErrorInvalidValue;
+#undef VRC_READ
     return hipGetLastError();
 }
 
@@ -879,7 +917,7 @@ static hipError_t launch_variant( const vrc_raycast_args& a, hipStream_t stream 
         return hipSuccess;
     vrc_internal_note_kernel( "vrc_k_raycast<%s,%s,%s,%s,%d,%s,%d,%s>", DDA ? "true" : "false", CLAMP ? "true" : "false",
                               COUNT ? "true" : "false", FIXED ? "true" : "false", (int)MODE,
-                              sizeof( ATLAS_T ) == 1 ? "unsigned char" : ( sizeof( ATLAS_T ) == 2 ? "unsigned short" : ( sizeof( ATLAS_T ) == 4 ? "unsigned int" : "unsigned long" ) ),
+                              std::is_same< ATLAS_T, float >::value ? "float" : sizeof( ATLAS_T ) == 1 ? "unsigned char" : ( sizeof( ATLAS_T ) == 2 ? "unsigned short" : ( sizeof( ATLAS_T ) == 4 ? "unsigned int" : "unsigned long" ) ),
                               (int)GROUP, BIG ? "true" : "false" );
     vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast< DDA, CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >,
                                  (int)VRC_WG_THREADS, 0 );
@@ -1160,12 +1198,12 @@ static hipError_t launch_parts( const vrc_raycast_args& a, hipStream_t stream )
     return hipGetLastError();
 }
 
-/* per-sample classification modes: trilinear or point, u8 or u16 voxels.  Point sampling of 16-bit voxels with
- * overlap (no clamped sampler) takes the fixed-point grouped march (vrc_march_brick) */
+/* per-sample classification modes: trilinear or point; u8, u16 or float voxels.  Point sampling of 16-bit and float
+ * voxels with overlap (no clamped sampler) takes the fixed-point grouped march (vrc_march_brick) */
 template < int MODE, typename ATLAS_T >
 static hipError_t launch_classify( const vrc_raycast_args& a, bool count, hipStream_t stream )
 {
-    if constexpr( MODE == VRC_MODE_POINT && sizeof( ATLAS_T ) == 2 )
+    if constexpr( MODE == VRC_MODE_POINT && sizeof( ATLAS_T ) >= 2 )
         if( a.fixedStepping && !a.clamp )
         {
             if( a.greyTable )
@@ -1201,7 +1239,7 @@ static hipError_t launch_classify( const vrc_raycast_args& a, bool count, hipStr
 template < int MODE, typename ATLAS_T >
 static hipError_t launch_big( const vrc_raycast_args& a, bool count, hipStream_t stream )
 {
-    if constexpr( MODE == VRC_MODE_POINT && sizeof( ATLAS_T ) == 2 )
+    if constexpr( MODE == VRC_MODE_POINT && sizeof( ATLAS_T ) >= 2 )
         if( a.fixedStepping && !a.clamp )
         {
 #define VRC_BIG_FIXED( M )                                                                                         \
@@ -1259,8 +1297,12 @@ hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream )
             return a.packedWide ? launch_packed< true, uint64_t >( a, count, stream ) : launch_packed< false, uint64_t >( a, count, stream );
         return a.packedWide ? launch_packed< true, uint32_t >( a, count, stream ) : launch_packed< false, uint32_t >( a, count, stream );
     }
+    /* the float atlas (32-bit and float volumes): ATLAS_T = float -- uint32_t is the tap-packed tag */
     if( a.bigAtlas )
     {
+        if( a.elemBytes == 4 )
+            return a.linear ? launch_big< VRC_MODE_TRILINEAR, float >( a, count, stream )
+                            : launch_big< VRC_MODE_POINT, float >( a, count, stream );
         if( a.elemBytes == 2 )
             return a.linear ? launch_big< VRC_MODE_TRILINEAR, uint16_t >( a, count, stream )
                             : launch_big< VRC_MODE_POINT, uint16_t >( a, count, stream );
@@ -1269,6 +1311,9 @@ hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream )
         return a.linear ? launch_big< VRC_MODE_TRILINEAR, uint8_t >( a, count, stream )
                         : launch_big< VRC_MODE_TABLE, uint8_t >( a, count, stream );
     }
+    if( a.elemBytes == 4 )
+        return a.linear ? launch_classify< VRC_MODE_TRILINEAR, float >( a, count, stream )
+                        : launch_classify< VRC_MODE_POINT, float >( a, count, stream );
     if( a.elemBytes == 2 )
         return a.linear ? launch_classify< VRC_MODE_TRILINEAR, uint16_t >( a, count, stream )
                         : launch_classify< VRC_MODE_POINT, uint16_t >( a, count, stream );

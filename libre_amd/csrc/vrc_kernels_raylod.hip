@@ -14,6 +14,8 @@
  */
 #include "vrc_internal.h"
 
+#include <type_traits>
+
 #ifndef VRC_RL_WAVES
 #define VRC_RL_WAVES 4u
 #endif
@@ -124,7 +126,7 @@ static hipError_t launch_raylod( const vrc_raycast_args& a, hipStream_t stream )
                                     : ( ( MODE == VRC_MODE_PACKED || MODE == VRC_MODE_PACKED_GREY ) ? VRC_CLS8_ENTRIES : VRC_TFP_ENTRIES );
     vrc_internal_note_kernel( "vrc_k_raycast_raylod<%s,%s,%s,%d,%s,%s>", CLAMP ? "true" : "false", COUNT ? "true" : "false",
                               FIXED ? "true" : "false", (int)MODE,
-                              sizeof( ATLAS_T ) == 1 ? "unsigned char" : ( sizeof( ATLAS_T ) == 2 ? "unsigned short" : ( sizeof( ATLAS_T ) == 4 ? "unsigned int" : "unsigned long" ) ),
+                              std::is_same< ATLAS_T, float >::value ? "float" : sizeof( ATLAS_T ) == 1 ? "unsigned char" : ( sizeof( ATLAS_T ) == 2 ? "unsigned short" : ( sizeof( ATLAS_T ) == 4 ? "unsigned int" : "unsigned long" ) ),
                               BIG ? "true" : "false" );
     hipLaunchKernelGGL( ( vrc_k_raycast_raylod< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG > ),
                         dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_RL_WAVES - 1u ) / VRC_RL_WAVES ),
@@ -175,6 +177,9 @@ hipError_t vrc_launch_raycast_raylod( const vrc_raycast_args& a, hipStream_t str
     if( a.bigAtlas )
     {
         /* 64-bit slot bases: float positions (the classified tables of the levels for 8-bit point sampling) */
+        if( a.elemBytes == 4 )
+            return a.linear ? launch_raylod_classify< VRC_MODE_TRILINEAR, float, true >( a, count, stream )
+                            : launch_raylod_classify< VRC_MODE_POINT, float, true >( a, count, stream );
         if( a.elemBytes == 2 )
             return a.linear ? launch_raylod_classify< VRC_MODE_TRILINEAR, uint16_t, true >( a, count, stream )
                             : launch_raylod_classify< VRC_MODE_POINT, uint16_t, true >( a, count, stream );
@@ -183,6 +188,10 @@ hipError_t vrc_launch_raycast_raylod( const vrc_raycast_args& a, hipStream_t str
         return a.linear ? launch_raylod_classify< VRC_MODE_TRILINEAR, uint8_t, true >( a, count, stream )
                         : launch_raylod_classify< VRC_MODE_TABLE, uint8_t, true >( a, count, stream );
     }
+    /* the float atlas (32-bit and float volumes), as 16-bit voxels: classified per sample, by gathers */
+    if( a.elemBytes == 4 )
+        return a.linear ? launch_raylod_classify< VRC_MODE_TRILINEAR, float >( a, count, stream )
+                        : launch_raylod_classify< VRC_MODE_POINT, float >( a, count, stream );
     if( a.elemBytes == 2 )
         return a.linear ? launch_raylod_classify< VRC_MODE_TRILINEAR, uint16_t >( a, count, stream )
                         : launch_raylod_classify< VRC_MODE_POINT, uint16_t >( a, count, stream );

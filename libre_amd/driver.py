@@ -154,7 +154,9 @@ class App:
         check(self.L, self.L.lvh_app_set_option(self.h, option, value))
 
     def set_data_range(self, lo, hi):
-        """dataSourceRange of a volume that is not uint8 (extension)."""
+        """dataSourceRange of a volume that is not uint8 (extension), in the volume's own values.  uint16, int8 and
+        int16 volumes default to their type's range; uint32, int32 and float volumes have no default and
+        render_frame raises DriverError until this has been called."""
         check(self.L, self.L.lvh_app_set_data_range(self.h, lo, hi))
 
     def set_ray_lod(self, enable=True):

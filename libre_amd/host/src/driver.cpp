@@ -136,14 +136,23 @@ struct lvh_app
         return perspectiveFrustum( tl, tr, tb, tt, nearPlane, farPlane );
     }
 
-    /** (0,255) is hard-coded at Channel.cpp:284; 16-bit volumes (extension) get the type's
-     *  range unless lvh_app_set_data_range gave one */
+    /** (0,255) is hard-coded at Channel.cpp:284; the other integral types of up to 16 bits (extension) get the
+     *  type's range unless lvh_app_set_data_range gave one.  32-bit integers and floats have no default: the
+     *  type's range says nothing about the data and a float has none, so rendering them needs the call */
     Vector2f dataSourceRange() const
     {
         if( dataRange[1] > dataRange[0] )
             return Vector2f( dataRange[0], dataRange[1] );
-        const size_t bytes = dataSource->getVolumeInfo().getBytesPerVoxel();
-        return bytes == 2 ? Vector2f( 0.0f, 65535.0f ) : Vector2f( 0.0f, 255.0f );
+        switch( dataSource->getVolumeInfo().dataType )
+        {
+        case DT_UINT16: return Vector2f( 0.0f, 65535.0f );
+        case DT_INT8: return Vector2f( -128.0f, 127.0f );
+        case DT_INT16: return Vector2f( -32768.0f, 32767.0f );
+        case DT_UINT32: case DT_INT32: case DT_FLOAT:
+            throw std::runtime_error( "32-bit and float volumes have no default data range: call "
+                                      "lvh_app_set_data_range before rendering" );
+        default: return Vector2f( 0.0f, 255.0f );
+        }
     }
 
     RenderInputs inputs()
@@ -398,6 +407,9 @@ int lvh_app_set_histogram( lvh_app* app, int enable )
         const bool on = enable != 0;
         if( on && !HipRaycastRenderer::histogramSupported() )
             return fail( "lvh_app_set_histogram: the device layer does not support the frame histogram" );
+        const DataType dt = app->dataSource->getVolumeInfo().dataType;
+        if( on && dt != DT_UINT8 && dt != DT_UINT16 )
+            return fail( "lvh_app_set_histogram: histograms of signed, 32-bit and float volumes are not supported" );
         static_cast< HipRaycastRenderer& >( app->pipeline->getRenderer().getPlugin() ).setHistogram( on );
         for( auto& r : app->extraRenderers )
             static_cast< HipRaycastRenderer& >( r->getPlugin() ).setHistogram( on );

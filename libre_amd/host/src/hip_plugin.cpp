@@ -23,6 +23,9 @@
 #pragma weak vrc_pool_enable_histograms
 #pragma weak vrc_frame_histogram
 #pragma weak vrc_get_frame_histogram
+/* ... and so is the typed pool (signed, 32-bit and float voxels): without it the pool comes from vrc_pool_create,
+ * which makes unsigned 8- and 16-bit pools and refuses the rest */
+#pragma weak vrc_pool_create_typed
 
 extern "C" int LunchboxPluginGetVersion() { return 1; } /* LIVRECORE_VERSION_ABI, CudaRaycastPipeline.cpp:50-51 */
 extern "C" bool LunchboxPluginRegister() { return true; } /* CudaRaycastPipeline.cpp:53-54 */
@@ -280,9 +283,25 @@ HipTexturePool::HipTexturePool( const DataSource& dataSource, size_t textureMemo
     }
     const uint32_t maxBlock[3] = { volInfo.maximumBlockSize[0], volInfo.maximumBlockSize[1],
                                    volInfo.maximumBlockSize[2] };
-    throwOnVrcError( vrc_pool_create( _ctx, volInfo.getBytesPerVoxel(), isSigned, isFloat,
-                                      volInfo.compCount, maxBlock, textureMemory, &_pool ),
-                     "vrc_pool_create" );
+    int voxelType = -1;
+    switch( volInfo.dataType )
+    {
+    case DT_UINT8: voxelType = VRC_VOXEL_UINT8; break;
+    case DT_UINT16: voxelType = VRC_VOXEL_UINT16; break;
+    case DT_UINT32: voxelType = VRC_VOXEL_UINT32; break;
+    case DT_INT8: voxelType = VRC_VOXEL_INT8; break;
+    case DT_INT16: voxelType = VRC_VOXEL_INT16; break;
+    case DT_INT32: voxelType = VRC_VOXEL_INT32; break;
+    case DT_FLOAT: voxelType = VRC_VOXEL_FLOAT32; break;
+    default: break;
+    }
+    if( vrc_pool_create_typed != nullptr && volInfo.compCount == 1 && voxelType >= 0 )
+        throwOnVrcError( vrc_pool_create_typed( _ctx, voxelType, maxBlock, textureMemory, &_pool ),
+                         "vrc_pool_create_typed" );
+    else
+        throwOnVrcError( vrc_pool_create( _ctx, volInfo.getBytesPerVoxel(), isSigned, isFloat,
+                                          volInfo.compCount, maxBlock, textureMemory, &_pool ),
+                         "vrc_pool_create" );
     guard.armed = false;
 }
 
@@ -677,10 +696,10 @@ void HipRaycastRenderer::render( const RenderInputs& renderInputs, const ConstCa
     rData.datatype = getShaderDataType( volInfo );
     rData.dataSourceRange[0] = 0.0f; /* hard-coded (0,255), CudaRaycastRenderer.cpp:205 */
     rData.dataSourceRange[1] = 255.0f;
-    if( volInfo.getBytesPerVoxel() != 1 )
+    if( volInfo.dataType != DT_UINT8 )
     {
-        /* extension (16-bit voxels): the range the GL twin takes from the render inputs,
-         * GLRaycastRenderer.cpp:311-312 */
+        /* extension (every voxel type but the reference's unsigned char): the range the GL twin takes from the
+         * render inputs, GLRaycastRenderer.cpp:311-312, in the volume's own values */
         rData.dataSourceRange[0] = renderInputs.dataSourceRange[0];
         rData.dataSourceRange[1] = renderInputs.dataSourceRange[1];
     }

@@ -15,6 +15,8 @@ VARIANT_CUDARAYCASTER, VARIANT_GLRAYCASTER = 0, 1
 FILTER_NEAREST, FILTER_TRILINEAR = 0, 1
 KERNEL_AUTO, KERNEL_REFERENCE_ORDER, KERNEL_GRID_DDA, KERNEL_LDS, KERNEL_RAY_LOD, KERNEL_PACKED = 0, 1, 2, 3, 4, 5
 
+VOXEL_UINT8, VOXEL_UINT16, VOXEL_UINT32, VOXEL_INT8, VOXEL_INT16, VOXEL_INT32, VOXEL_FLOAT32 = range(7)  # VRC_VOXEL_*
+
 ABI_VERSION = 4  # VRC_ABI_VERSION of include/vrc_hip.h this binding was written against
 
 f32x3 = C.c_float * 3
@@ -54,7 +56,7 @@ class VrcError(RuntimeError):
 #: every symbol include/vrc_hip.h declares; tests check the library exports all of them
 EXPORTS = [
     "vrc_ctx_create", "vrc_ctx_destroy", "vrc_ctx_set_stream", "vrc_set_option", "vrc_get_option", "vrc_set_ray_lod",
-    "vrc_pool_create", "vrc_pool_destroy", "vrc_pool_copy_to_slot", "vrc_pool_copy_to_slot_device",
+    "vrc_pool_create", "vrc_pool_create_typed", "vrc_pool_voxel_type", "vrc_pool_destroy", "vrc_pool_copy_to_slot", "vrc_pool_copy_to_slot_device",
     "vrc_pool_release_slot", "vrc_pool_info", "vrc_pool_synchronize", "vrc_pool_read_region",
     "vrc_pool_histogram", "vrc_pool_enable_histograms", "vrc_frame_histogram", "vrc_get_frame_histogram",
     "vrc_update", "vrc_pre_render", "vrc_set_row_map", "vrc_set_framebuffer", "vrc_get_framebuffer", "vrc_render",
@@ -101,6 +103,8 @@ def load_library(path=None):
     L.vrc_get_option.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
     L.vrc_pool_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, u32x3, C.c_size_t,
                                   C.POINTER(vp)]
+    L.vrc_pool_create_typed.argtypes = [vp, C.c_int, u32x3, C.c_size_t, C.POINTER(vp)]
+    L.vrc_pool_voxel_type.argtypes = [vp, C.POINTER(C.c_int)]
     L.vrc_pool_destroy.argtypes = [vp]
     L.vrc_pool_destroy.restype = None
     L.vrc_pool_copy_to_slot.argtypes = [vp, vp, u32x3, f32x3]
