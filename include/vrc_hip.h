@@ -152,6 +152,45 @@ typedef struct
                                    * Point-sampled 8-bit volumes through the classified table only; the trilinear,
                                    * 16-bit and LDS-staged forms always read the atlas.  0: every brick is fetched */
 
+#define VRC_OPT_PROJECTION 16       /* how a pixel is formed from its ray's samples: VRC_PROJECTION_COMPOSITE (default: the
+                                    * reference's emission/absorption compositing with early ray termination) |
+                                    * VRC_PROJECTION_MIP (maximum-intensity projection, an extension: see below) */
+#define VRC_PROJECTION_COMPOSITE 0
+#define VRC_PROJECTION_MIP 1
+#define VRC_OPT_MIP_SKIP 17         /* 1 (default) | 0.  MIP only: a ray does not march a brick whose largest voxel cannot
+                                    * beat the maximum the ray already holds (every upload notes it per slot).  The
+                                    * maximum does not depend on the order or on samples that cannot raise it: the same
+                                    * frame, bit for bit; only vrc_stats.samples falls.  0: every brick is marched */
+
+/* A MIP frame (VRC_OPT_PROJECTION = VRC_PROJECTION_MIP).
+ *   Sample set.  A ray's sample set S is exactly what the composite march takes with a transfer function whose alpha
+ *     is 0 everywhere: the same ray set-up, global-box and clip-plane interval and near plane; the same node list
+ *     order, including the reference's quirk that a brick whose tNear lies beyond the ray's interval ends the ray
+ *     (cuda/Renderer.cu:183-186); the same restart per brick, sample positions and count per segment
+ *     (VRC_OPT_STEPPING 0 and 1); no early termination.
+ *   Value.  M = the maximum over S of the sampled density: VRC_FILTER_NEAREST the voxel's value, in the volume's own
+ *     units; VRC_FILTER_TRILINEAR the interpolated float.  A float atlas folds with fmaxf starting from -infinity, so
+ *     NaN samples drop out (a ray whose samples are all NaN has M = -infinity).
+ *   Pixel, S not empty.  t = TF((M - r0) / (r1 - r0)), r = dataSourceRange, fetched as every sample's is (256 texels,
+ *     linear filter, the weight in VRC_OPT_TF_FRAC_BITS bits); no opacity correction and no 255/256 clamp, as no step
+ *     length is involved; stored premultiplied, (t.rgb * t.a, t.a), the frame buffer's convention.  Classified once
+ *     per ray, after the march.
+ *   Pixel, S empty.  Keeps its cleared value.
+ *   Passes of one frame (vrc_render several times between vrc_pre_render and vrc_post_render).  The context owns one
+ *     running maximum per pixel of the pixel buffer -- internal, caller-owned or row-mapped.  vrc_pre_render
+ *     invalidates it, the frame's first pass does not read it, later passes take the maximum with it: after every pass
+ *     the frame buffer holds the MIP of the passes so far.  Changing VRC_OPT_PROJECTION between vrc_pre_render and
+ *     vrc_post_render: the next vrc_render returns VRC_EINVAL.
+ *   Sample count (VRC_OPT_COUNT_SAMPLES).  vrc_stats.samples counts the samples actually taken: with VRC_OPT_MIP_SKIP
+ *     = 0 that is |S| summed over the rays.
+ * Served: VRC_KERNEL_AUTO, _REFERENCE_ORDER and _GRID_DDA; point samples and trilinear samples (by gathers) of the
+ * 8-bit, 16-bit and float atlases, i.e. all seven voxel types (offset binary is monotone: the maximum commutes with
+ * it); atlases of more than 2^32 voxels; row maps.  AUTO with the trilinear filter takes the gather form and does not
+ * build the tap-packed atlas.  VRC_EINVAL from vrc_render, naming the option: an explicit VRC_KERNEL_LDS or _PACKED,
+ * vrc_set_ray_lod on, VRC_VARIANT_GLRAYCASTER.  VRC_OPT_DEPTH_SPLIT and VRC_OPT_ERT_COMPACTION are silently the plain
+ * kernel.  VRC_OPT_UNIFORM_BRICKS: a ray whose segment lies in a slot known to hold one value takes max(M, value) and
+ * the segment's step count without fetching (point samples of 8- and 16-bit voxels; same frame and count, bit for bit). */
+
 #define VRC_VARIANT_CUDARAYCASTER 0 /* renderers/cudaRaycaster/cuda/Renderer.cu:95-230 */
 #define VRC_VARIANT_GLRAYCASTER 1   /* renderers/glRaycaster/shaders/fragRaycast.glsl:113-215: pixel centre
                                      * +0.5, hit test t0 <= t1, first sample of a brick snapped to the
@@ -396,7 +435,8 @@ int vrc_last_kernel_occupancy( int* workgroups_per_cu, int* threads_per_workgrou
 /* ABI version of this header */
 #define VRC_ABI_VERSION 4 /* 3: vrc_gather_tiles takes the frame height; 4: VRC_KERNEL_PACKED, VRC_OPT_PACKED_ATLAS, vrc_last_kernel_occupancy
                            * (added since without a new number, as symbols a caller may bind weakly: the frame histogram,
-                           * vrc_pool_create_typed / vrc_pool_voxel_type) */
+                           * vrc_pool_create_typed / vrc_pool_voxel_type; as option values only: VRC_OPT_PROJECTION,
+                           * VRC_OPT_MIP_SKIP) */
 /* = VRC_ABI_VERSION for the product build; -VRC_ABI_VERSION for a developer build of the library (compiled with
  * -DVRC_DEV_BUILD: experiment switches, statistics, ablations that render wrong pixels on purpose) */
 int vrc_abi_version( void );

@@ -63,6 +63,10 @@ struct vrc_pool
      * on uploadStream alone: cleared with the atlas, zeroed and refilled by every upload next to the voxels it describes,
      * so a march ordered behind lastUpload sees the word of exactly the voxels it would fetch.  No host copy. */
     uint32_t* dSlotInfo = nullptr;
+    /* the largest value every slot's last upload stored (vrc_core.h: vrc_frame::slotMax; the MIP march skips bricks by
+     * it): the second half of dSlotInfo's allocation, so the same lifetime; zeroed and refilled by every upload with the
+     * uniformity word -- same stream, same fences, same lastUpload */
+    uint32_t* dSlotMax = nullptr;
     /* tap-packed atlas of the trilinear filter (vrc_core.h): same slots, a texel of twice the voxel's bytes per voxel in
      * blocks of 64 rows of 9.
      * Allocated and filled from the byte atlas the first time a render asks for it (pool_enable_packed); from then
@@ -202,6 +206,15 @@ struct vrc_ctx
     int64_t optErtParts = 0;     /* VRC_OPT_ERT_COMPACTION */
     int64_t optPackedAtlas = 1;  /* VRC_OPT_PACKED_ATLAS */
     int64_t optUniformBricks = 1; /* VRC_OPT_UNIFORM_BRICKS */
+    int64_t optProjection = VRC_PROJECTION_COMPOSITE; /* VRC_OPT_PROJECTION */
+    int64_t optMipSkip = 1;                           /* VRC_OPT_MIP_SKIP */
+    /* MIP: one running maximum per pixel of the pixel buffer (vrc_core.h: vrc_frame::mipMax), whichever buffer that
+     * is; vrc_pre_render invalidates it (mipFirst: the next MIP pass does not read it) and forgets the projection of
+     * the frame before (frameProjection: that of the frame's first vrc_render, -1 = none yet) */
+    uint32_t* dMipMax = nullptr;
+    size_t dMipMaxPixels = 0;
+    bool mipFirst = true;
+    int64_t frameProjection = -1;
     uint32_t* dRayList = nullptr; /* counts | two ray lists (vrc_internal.h) */
     size_t dRayListCap = 0;       /* pixels */
     int lastErtParts = 0;         /* of the last vrc_render */
@@ -340,6 +353,7 @@ void vrc_ctx_destroy( vrc_ctx* c )
         if( e ) (void)hipEventDestroy( e );
     if( c->dTileOrder ) (void)hipFree( c->dTileOrder );
     if( c->dRayList ) (void)hipFree( c->dRayList );
+    if( c->dMipMax ) (void)hipFree( c->dMipMax );
     if( c->dRowMap ) (void)hipFree( c->dRowMap );
     if( c->dCounter ) (void)hipFree( c->dCounter );
     if( c->hCounter ) (void)hipHostFree( c->hCounter );
@@ -397,6 +411,12 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
     case VRC_OPT_GREY_TABLE: c->optGreyTable = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_PACKED_ATLAS: c->optPackedAtlas = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_UNIFORM_BRICKS: c->optUniformBricks = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_PROJECTION:
+        if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite) or 1 (maximum intensity)" );
+        c->optProjection = value;
+        return VRC_OK;
+    case VRC_OPT_MIP_SKIP: c->optMipSkip = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_ERT_COMPACTION:
         if( value < 0 || value > VRC_MAX_ERT_PARTS )
             return fail( VRC_EINVAL, "VRC_OPT_ERT_COMPACTION: 0 (off) or 2.." + std::to_string( VRC_MAX_ERT_PARTS ) +
@@ -430,6 +450,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_GREY_TABLE: *value = c->optGreyTable; return VRC_OK;
     case VRC_OPT_PACKED_ATLAS: *value = c->optPackedAtlas; return VRC_OK;
     case VRC_OPT_UNIFORM_BRICKS: *value = c->optUniformBricks; return VRC_OK;
+    case VRC_OPT_PROJECTION: *value = c->optProjection; return VRC_OK;
+    case VRC_OPT_MIP_SKIP: *value = c->optMipSkip; return VRC_OK;
     case VRC_OPT_VARIANT: *value = c->optVariant; return VRC_OK;
     case VRC_OPT_KERNEL_USED: *value = c->stats.kernel_variant; return VRC_OK;
     case VRC_OPT_GRID_WALK_USED: *value = c->gridWalkUsed; return VRC_OK;
@@ -587,8 +609,9 @@ static int pool_create( vrc_ctx* c, int voxelType, const uint32_t maxBlock[3], s
      * not ordered with a non-blocking stream, and the first uploads of a large pool could be overtaken by it (seen once:
      * a 6 GB pool of 16-bit voxels, round 4) */
     if( e == hipSuccess ) e = hipMemsetAsync( p->dAtlas, 0, p->atlasBytes, p->uploadStream );
-    if( e == hipSuccess ) e = hipMalloc( &p->dSlotInfo, nSlots * sizeof( uint32_t ) );
-    if( e == hipSuccess ) e = hipMemsetAsync( p->dSlotInfo, 0, nSlots * sizeof( uint32_t ), p->uploadStream );
+    if( e == hipSuccess ) e = hipMalloc( &p->dSlotInfo, 2 * nSlots * sizeof( uint32_t ) );
+    if( e == hipSuccess ) e = hipMemsetAsync( p->dSlotInfo, 0, 2 * nSlots * sizeof( uint32_t ), p->uploadStream );
+    if( e == hipSuccess ) p->dSlotMax = p->dSlotInfo + nSlots;
     if( e == hipSuccess ) e = hipEventCreateWithFlags( &p->lastUpload, hipEventDisableTiming );
     if( e == hipSuccess )
     {
@@ -788,10 +811,13 @@ static int pool_upload( vrc_pool* p, const void* src, bool srcIsDevice, const ui
             /* the slot's uniformity word: back to "nothing known" before the new voxels land, then whatever the
              * repack finds in them -- same stream, same fences, same lastUpload as the voxels */
             uint32_t* const info = p->dSlotInfo + index;
+            uint32_t* const top = p->dSlotMax + index; /* ... and the slot's largest stored value */
             e = hipMemsetAsync( info, 0, sizeof( uint32_t ), p->uploadStream );
             if( e == hipSuccess )
+                e = hipMemsetAsync( top, 0, sizeof( uint32_t ), p->uploadStream );
+            if( e == hipSuccess )
                 e = vrc_launch_repack_brick( devSrc, slotPtr, p->elemBytes, size, p->slotDim, p->uploadStream, info,
-                                             p->xform );
+                                             p->xform, top );
             if( e == hipSuccess && p->packedOn )
                 e = vrc_launch_pack_slots( p->dAtlas, p->dPacked, base,
                                            (uint64_t)p->slotDim[0] * p->slotDim[1] * p->slotDim[2], p->slotDim,
@@ -1226,6 +1252,9 @@ int vrc_pre_render( vrc_ctx* c, const vrc_view_data* view )
      * clear is folded into the first march of the frame (vrc_frame::clearFirst); whoever looks at
      * the buffer before a march has run gets it done then (resolve_clear). */
     c->clearPending = true;
+    /* a new frame: its MIP passes start over, and it may take either projection */
+    c->mipFirst = true;
+    c->frameProjection = -1;
     return VRC_OK;
 }
 
@@ -1362,10 +1391,27 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     if( pool->elemBytes == 4 && ( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED ) )
         return fail( VRC_EINVAL, "vrc_render: 32-bit and float voxels are marched by gathers; the LDS-staged and tap-packed "
                                  "forms take 8- and 16-bit voxels (VRC_OPT_KERNEL = AUTO, REFERENCE_ORDER or GRID_DDA)" );
+    const bool mip = c->optProjection == VRC_PROJECTION_MIP;
+    if( c->frameProjection >= 0 && c->frameProjection != c->optProjection )
+        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_PROJECTION changed between vrc_pre_render and vrc_post_render; the "
+                                 "passes of one frame take one projection" );
+    if( mip )
+    {
+        /* what the maximum-intensity projection is not defined for (include/vrc_hip.h) */
+        if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no maximum-intensity form; "
+                                     "VRC_OPT_PROJECTION = MIP is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
+        if( c->rayLod )
+            return fail( VRC_EINVAL, "vrc_render: vrc_set_ray_lod is on; VRC_OPT_PROJECTION = MIP renders a per-brick cut" );
+        if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_PROJECTION = MIP is defined on the "
+                                     "cudaRaycaster variant's sample set" );
+    }
     const bool linear = c->optFilter == VRC_FILTER_TRILINEAR;
     /* samples classified one by one (padded transfer function in the table buffer) whenever the
      * 257-entry classified table cannot be used: continuous or 16-bit densities */
-    const bool classify = linear || pool->elemBytes != 1;
+    /* (MIP: the one classification per ray reads the padded transfer function too) */
+    const bool classify = linear || pool->elemBytes != 1 || mip;
     /* per-ray LOD: one classified table per level, opacity exponent doubled per level (a level-j
      * brick is sampled with step * 2^j); always all levels, so the table does not depend on the list */
     const uint32_t lutLevels = ( c->rayLod && !classify ) ? (uint32_t)VRC_MAX_LOD_LEVELS : 1u;
@@ -1507,7 +1553,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * positions and its classifier need -- 8- or 16-bit bricks with overlap >= 1 in slots of at most 248 voxels a side,
      * VRC_OPT_TF_FRAC_BITS = 8, fixed-point stepping -- and 2.25 times the atlas in device memory; either brick
      * enumeration (grid walk where the node set is grid-aligned, else the reference-order loop) */
-    const bool packedEligible = linear && !glSuper && !c->cachedClamp && slotsFit8Bits &&
+    const bool packedEligible = linear && !glSuper && !mip && !c->cachedClamp && slotsFit8Bits &&
                                 pool_packed_possible( pool ) && c->optTfFracBits == 8 && c->optStepping != 0;
     bool usePacked = false;
     if( c->optKernel == VRC_KERNEL_PACKED )
@@ -1524,7 +1570,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
          * it the frame takes the staged form below */
         usePacked = pool_enable_packed( pool );
     const bool useLds = c->rayLod ? ( ldsLodEligible && c->optKernel != VRC_KERNEL_GRID_DDA && !usePacked )
-                                  : !glSuper && !usePacked && ( c->optKernel == VRC_KERNEL_LDS ||
+                                  : !glSuper && !usePacked && !mip && ( c->optKernel == VRC_KERNEL_LDS ||
                                                   ( c->optKernel == VRC_KERNEL_AUTO && linear && ldsEligible ) );
 
     vrc_raycast_args a;
@@ -1612,6 +1658,27 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     c->clearPending = false;
     /* the pool's uniformity words (VRC_OPT_UNIFORM_BRICKS): NULL = every brick takes the general march */
     f.slotInfo = c->optUniformBricks ? pool->dSlotInfo : nullptr;
+    if( mip )
+    {
+        /* the running maxima: one word per pixel of the pixel buffer in use */
+        const size_t pixels = (size_t)c->fbW * c->fbH;
+        if( pixels > c->dMipMaxPixels )
+        {
+            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+            if( c->dMipMax ) VRC_HIP_CHECK( hipFree( c->dMipMax ) );
+            c->dMipMax = nullptr;
+            c->dMipMaxPixels = 0;
+            VRC_HIP_CHECK( hipMalloc( &c->dMipMax, pixels * sizeof( uint32_t ) ) );
+            c->dMipMaxPixels = pixels;
+            if( !c->mipFirst ) /* a later pass of a frame whose pixel buffer grew (vrc_set_framebuffer): nothing known */
+                VRC_HIP_CHECK( hipMemsetAsync( c->dMipMax, 0xFF, pixels * sizeof( uint32_t ), c->stream ) );
+        }
+        f.mipMax = c->dMipMax;
+        f.mipFirst = c->mipFirst ? 1u : 0u;
+        f.slotMax = c->optMipSkip ? pool->dSlotMax : nullptr;
+        c->mipFirst = false;
+    }
+    c->frameProjection = c->optProjection;
 
     a.nodes = c->dNodes;
     a.gridTable = ( useDda || c->rayLod ) ? c->dGrid : nullptr;
@@ -1635,7 +1702,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * restart sample per brick).  (ii) The frame starts from zero (first pass: the clear is folded in).
      * (iii) the table-driven point-sampling walk kernel. */
     a.depthSplit = false;
-    if( c->optDepthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 && !pool->bigAtlas &&
+    if( c->optDepthSplit && !mip && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 && !pool->bigAtlas &&
         !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && f.clearFirst )
     {
         const double nMax = 1.7320508 * (double)render->samplesPerRay +
@@ -1651,7 +1718,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     a.ertParts = 0;
     a.rayList = nullptr;
     /* (the same predicate as the launcher's, vrc_launch_raycast: what vrc_get_ray_counts reports is what ran) */
-    if( c->optErtParts > 1 && !a.depthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 &&
+    if( c->optErtParts > 1 && !mip && !a.depthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 &&
         !pool->bigAtlas && !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && c->fbW < 65536u && c->fbH < 65536u &&
         VRC_TILE_W == 8u )
     {
@@ -1710,7 +1777,8 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     vrc_internal_note_kernel_fn( nullptr, 0, 0 ); /* set again by the launchers that report their occupancy */
     if( c->optTiming )
         VRC_HIP_CHECK( hipEventRecord( evp.first, c->stream ) );
-    VRC_HIP_CHECK( useLds      ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
+    VRC_HIP_CHECK( mip         ? vrc_launch_raycast_mip( a, c->stream )
+                   : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
                    : c->rayLod ? vrc_launch_raycast_raylod( a, c->stream )
                                : vrc_launch_raycast( a, c->stream ) );
     if( c->optTiming )

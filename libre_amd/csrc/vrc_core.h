@@ -68,6 +68,7 @@
 
 
 #include <stdint.h>
+#include <type_traits>
 
 #if defined( __HIPCC__ )
 #define VRC_HD __host__ __device__ __forceinline__
@@ -169,6 +170,13 @@ struct vrc_frame
     /* one uniformity word per atlas slot (VRC_SLOT_*), indexed by vrc_dev_node::slotInfoIndex - 1; NULL = every brick
      * takes the general march (VRC_OPT_UNIFORM_BRICKS = 0, the CPU harness) */
     const uint32_t* slotInfo;
+    /* maximum-intensity projection (VRC_MODE_MIP*): one word per atlas slot holding the largest value the slot's last
+     * upload stored (vrc_slot_max_*; same index, stream and fences as slotInfo), NULL = no brick is skipped
+     * (VRC_OPT_MIP_SKIP = 0); the context's running maximum per pixel of the pixel buffer (VRC_MIP_EMPTY: no sample
+     * yet); and whether this is the frame's first MIP pass, which does not read mipMax */
+    const uint32_t* slotMax;
+    uint32_t* mipMax;
+    uint32_t mipFirst;
     /* 0: cudaRaycaster semantics (cuda/Renderer.cu); 1: the GLSL twin's
      * (glRaycaster/shaders/fragRaycast.glsl), see vrc_brick_segment */
     uint32_t variant;
@@ -1993,6 +2001,295 @@ VRC_HD bool vrc_march_segment_packed( const vrc_frame& f, const vrc_dev_node& n,
 }
 
 /* ------------------------------------------------------------------------------------------
+ * EXTENSION: maximum-intensity projection (VRC_OPT_PROJECTION = VRC_PROJECTION_MIP; include/vrc_hip.h has the
+ * definition of a MIP frame).  The sample set of a ray is the composite march's with an all-transparent transfer
+ * function -- same ray, same bricks in the same order, same segments, positions and counts, no early termination -- and
+ * the pixel is ONE classification of the largest sampled density, after the march.  The march bodies below keep the
+ * control structure of vrc_march_segment_as / vrc_march_segment_linear (whole groups under the same guard, the
+ * sequential travel chain, the same tails), so positions and counts are theirs by construction; the per-sample work
+ * is a maximum folded into one register, two samples per instruction (v_max3_u32 / v_max3_f32).
+ *
+ * M is held as uint32_t for point samples of the integer atlases (the stored, offset-binary value: the shift is
+ * monotone) and as float for the float atlas and every trilinear sample; a float M starts at -infinity and is folded
+ * with fmaxf, so NaN samples drop out.
+ * ---------------------------------------------------------------------------------------- */
+#define VRC_MODE_MIP 7           /* point samples */
+#define VRC_MODE_MIP_TRILINEAR 8 /* trilinear samples by gathers */
+#define VRC_MIP_EMPTY 0xFFFFFFFFu /* vrc_frame::mipMax: the pixel's rays have taken no sample (no integer voxel, and a NaN no float M can be) */
+
+VRC_HD uint32_t vrc_mip_max( uint32_t a, uint32_t b ) { return a > b ? a : b; }
+VRC_HD float vrc_mip_max( float a, float b ) { return fmaxf( a, b ); }
+template < typename D >
+VRC_HD D vrc_mip_max3( D m, D a, D b ) { return vrc_mip_max( vrc_mip_max( m, a ), b ); }
+VRC_HD uint32_t vrc_mip_bits( uint32_t m ) { return m; }
+VRC_HD uint32_t vrc_mip_bits( float m ) { return vrc_float_bits( m ); }
+VRC_HD void vrc_mip_from_bits( uint32_t b, uint32_t& m ) { m = b; }
+VRC_HD void vrc_mip_from_bits( uint32_t b, float& m ) { m = vrc_bits_float( b ); }
+/* the value that changes no maximum: what M starts from, and what a step the march does not take contributes */
+VRC_HD void vrc_mip_identity( uint32_t& m ) { m = 0u; }
+VRC_HD void vrc_mip_identity( float& m ) { m = vrc_bits_float( 0xFF800000u ); }
+
+/* vrc_frame::slotMax words.  0 = nothing known (the slot is never skipped).  Integer atlases: largest stored value + 1.
+ * Float atlas: the largest voxel that is not NaN (-infinity if all are) as a key that orders like the floats do when
+ * compared as unsigned integers -- what the upload's atomicMax needs; no float maps to 0. */
+VRC_HD uint32_t vrc_slot_max_key( float v )
+{
+    const uint32_t b = vrc_float_bits( v );
+    return ( b & 0x80000000u ) ? ~b : ( b | 0x80000000u );
+}
+VRC_HD float vrc_slot_max_float( uint32_t key )
+{
+    return vrc_bits_float( ( key & 0x80000000u ) ? ( key & 0x7FFFFFFFu ) : ~key );
+}
+/* can no sample of the slot raise M?  A point sample is a voxel of the slot: M >= the slot's maximum settles it.  A
+ * trilinear sample is a convex combination of voxels of the slot (clamped taps stay inside it) evaluated in float:
+ * three interpolations of a (1 - w) + b w, each at most (1 + 2.5 * 2^-24) times the larger operand's magnitude above
+ * it, so below max + |max| * 1e-6; M has to reach that bound.  With operands of mixed sign a term can be far larger in
+ * magnitude than |max|, and its rounding error with it -- but such a term is negative (no operand exceeds max, the
+ * weights lie in [0, 1]) and lowers the result by 2^23 times its error: a result near max has terms of max's magnitude
+ * or less, which is the case the bound is for.  (A bound that is not a number -- an all-NaN slot -- skips nothing.) */
+template < bool TRILINEAR, typename ATLAS_T >
+VRC_HD bool vrc_mip_cannot_raise( uint32_t word, uint32_t m )
+{
+    static_assert( !TRILINEAR, "a trilinear M is a float" );
+    return m >= word - 1u;
+}
+template < bool TRILINEAR, typename ATLAS_T >
+VRC_HD bool vrc_mip_cannot_raise( uint32_t word, float m )
+{
+    float top;
+    if constexpr( sizeof( ATLAS_T ) == 4 )
+        top = vrc_slot_max_float( word );
+    else
+        top = (float)( word - 1u );
+    if constexpr( TRILINEAR )
+    {
+        VRC_STRICT_FP
+        top = top + fabsf( top ) * 1e-6f;
+    }
+    return m >= top;
+}
+
+/* trips of the reference's `for( ; travel > 0; travel -= stepSize )` (travel > 0): in integers where that is exact
+ * (vrc_exact_step_count), else by the float chain itself */
+VRC_HD uint32_t vrc_step_count( float travel, float stepSize )
+{
+    uint32_t n;
+    if( vrc_exact_step_count( travel, stepSize, &n ) )
+        return n;
+    n = 0u;
+    for( ; travel > 0.0f; travel -= stepSize )
+        ++n;
+    return n;
+}
+
+/* point samples of one brick segment (travel > 0 or nothing is taken): vrc_march_segment_as without table, blend and exit */
+template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename D >
+VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
+                                   const ATLAS_T* __restrict__ atlas, D& m, uint32_t& nSamples )
+{
+    const float stepSize = f.stepSize;
+    const vrc_sampler sm = vrc_make_sampler( n, f );
+    vrc_f3 pos = s.pos;
+    if( !( travel > 0.0f ) )
+        return;
+    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
+    if( FIXED )
+        fp = vrc_fixpos_init( sm, pos, s.step );
+    const float guard = stepSize * (float)( GROUP + 1 );
+    while( travel > guard )
+    {
+        uint32_t idx[GROUP];
+        if( FIXED )
+            vrc_group_indices_fixed< GROUP >( sm, fp, idx );
+        else
+            vrc_group_indices< CLAMP, GROUP >( sm, pos, s.step, idx );
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            travel -= stepSize; /* same sequential subtraction as the reference */
+        D d[GROUP];
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            d[k] = (D)vrc_gather( atlas, idx[k] );
+#pragma unroll
+        for( int k = 0; k + 1 < GROUP; k += 2 )
+            m = vrc_mip_max3( m, d[k], d[k + 1] );
+        if( GROUP & 1 )
+            m = vrc_mip_max( m, d[GROUP - 1] );
+        nSamples += GROUP;
+    }
+    constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
+    D none;
+    vrc_mip_identity( none );
+    while( travel > 0.0f )
+    {
+        uint32_t idx[TAILG], cnt = 0;
+        D d[TAILG];
+        if( FIXED )
+            vrc_group_indices_fixed< TAILG >( sm, fp, idx );
+        else
+            vrc_group_indices< CLAMP, TAILG >( sm, pos, s.step, idx );
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+        {
+            const bool v = travel > 0.0f;
+            cnt += v ? 1u : 0u;
+            idx[k] = v ? idx[k] : 0u; /* a step the reference does not take reads element 0 and contributes nothing */
+            travel -= stepSize;
+        }
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+            d[k] = (D)vrc_gather( atlas, idx[k] );
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+            m = vrc_mip_max( m, (uint32_t)k < cnt ? d[k] : none );
+        nSamples += cnt;
+    }
+}
+
+/* trilinear samples of one brick segment: vrc_march_segment_linear without classification, blend and exit */
+template < bool CLAMP, typename ATLAS_T >
+VRC_HD void vrc_mip_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
+                                       const ATLAS_T* __restrict__ atlas, float& m, uint32_t& nSamples )
+{
+    const float stepSize = f.stepSize;
+    const vrc_sampler sm = vrc_make_sampler( n, f );
+    vrc_f3 pos = s.pos;
+    const float none = vrc_bits_float( 0xFF800000u );
+    while( travel > 0.0f )
+    {
+        bool valid[VRC_LGROUP];
+        vrc_taps t[VRC_LGROUP];
+#pragma unroll
+        for( int k = 0; k < VRC_LGROUP; ++k )
+        {
+            VRC_FAST_FP
+            valid[k] = travel > 0.0f;
+            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
+            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
+            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
+            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
+            pos.x += s.step.x;
+            pos.y += s.step.y;
+            pos.z += s.step.z;
+            travel -= stepSize;
+        }
+        float v[VRC_LGROUP][8];
+#pragma unroll
+        for( int k = 0; k < VRC_LGROUP; ++k )
+#pragma unroll
+            for( int c = 0; c < 8; ++c )
+            {
+                const uint32_t e = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
+                v[k][c] = (float)vrc_gather( atlas, valid[k] ? e : 0u );
+            }
+        float d[VRC_LGROUP];
+#pragma unroll
+        for( int k = 0; k < VRC_LGROUP; ++k )
+        {
+            d[k] = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
+            d[k] = valid[k] ? d[k] : none;
+            nSamples += valid[k] ? 1u : 0u;
+        }
+#pragma unroll
+        for( int k = 0; k + 1 < VRC_LGROUP; k += 2 )
+            m = vrc_mip_max3( m, d[k], d[k + 1] );
+        if( VRC_LGROUP & 1 )
+            m = vrc_mip_max( m, d[VRC_LGROUP - 1] );
+    }
+}
+
+/* One brick of one ray.  The ray's state travels in the colour the brick walks hand on: x = the bits of M, y != 0 once
+ * a sample was taken, w = 0 (no walk ever sees an opaque pixel).
+ *   skipping (vrc_frame::slotMax)  a lane whose M no sample of the slot can raise takes none of them;
+ *   uniform bricks (vrc_frame::slotInfo; point samples of the 8- and 16-bit atlases)  a lane in a slot known to hold
+ *     one value takes max(M, value) and the segment's step count, without addressing or gathers (a trilinear sample
+ *     of equal voxels is the value only up to rounding: those are fetched);
+ *   a wave none of whose lanes is left to march does not set the march up. */
+template < bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, int GROUP, bool BIG >
+VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s,
+                           const ATLAS_T* __restrict__ atlas, vrc_f4& state, uint32_t& nSamples )
+{
+    constexpr bool TRILINEAR = MODE == VRC_MODE_MIP_TRILINEAR;
+    typedef typename vrc_density< ATLAS_T >::type P;
+    typedef typename std::conditional< TRILINEAR, float, P >::type D;
+    D m;
+    vrc_mip_from_bits( vrc_float_bits( state.x ), m );
+    bool has = state.y != 0.0f;
+    bool march = s.dist > 0.0f;
+    if( march && n.slotInfoIndex != 0u )
+    {
+        if( f.slotMax != nullptr && has )
+        {
+            const uint32_t word = f.slotMax[n.slotInfoIndex - 1u];
+            if( word != 0u && vrc_mip_cannot_raise< TRILINEAR, ATLAS_T >( word, m ) )
+                march = false;
+        }
+        if constexpr( !TRILINEAR && sizeof( ATLAS_T ) <= 2 )
+        {
+            if( march && f.slotInfo != nullptr )
+            {
+                const uint32_t word = f.slotInfo[n.slotInfoIndex - 1u];
+                if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) == VRC_SLOT_KNOWN )
+                {
+                    m = vrc_mip_max( m, (D)( word & VRC_SLOT_VALUE_MASK ) );
+                    has = true;
+                    nSamples += vrc_step_count( s.dist, f.stepSize );
+                    march = false;
+                }
+            }
+        }
+    }
+    bool any = march;
+#if defined( __HIP_DEVICE_COMPILE__ )
+    any = __builtin_amdgcn_ballot_w64( march ) != 0ull;
+#endif
+    if( any )
+    {
+        const float travel = march ? s.dist : 0.0f;
+        vrc_dev_node local = n;
+        const ATLAS_T* slot = atlas;
+        if( BIG )
+        {
+            /* the slot's 64-bit base moves into the lane's atlas pointer (vrc_march_brick) */
+            local.slotBase = 0u;
+            slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
+        }
+        if constexpr( TRILINEAR )
+            vrc_mip_segment_trilinear< CLAMP, ATLAS_T >( f, local, s, travel, slot, m, nSamples );
+        else
+            vrc_mip_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, D >( f, local, s, travel, slot, m, nSamples );
+        has = has || march;
+    }
+    state.x = vrc_bits_float( vrc_mip_bits( m ) );
+    state.y = has ? 1.0f : 0.0f;
+}
+
+/* the pixel of a maximum M: TF((M - r0) / (r1 - r0)) as vrc_classify fetches it (256 texels, linear, the weight in
+ * VRC_OPT_TF_FRAC_BITS bits), no opacity correction and no 255/256 clamp -- no step length is involved --, stored
+ * premultiplied as the frame buffer's convention is */
+VRC_HD vrc_f4 vrc_classify_mip( const vrc_f4* tfp, float d, const vrc_classifier& k )
+{
+    VRC_FAST_FP
+    float xB = d * k.mult + k.add;
+    xB = fminf( fmaxf( xB, -1.0f ), 255.99998f );
+    const float fl = floorf( xB );
+    float a = xB - fl;
+    if( k.q > 0.0f )
+        a = floorf( a * k.q + 0.5f ) * k.invq;
+    const int j = (int)fl + 1;
+    const vrc_f4 t0 = tfp[j], t1 = tfp[j + 1];
+    const float b = 1.0f - a;
+    const float alpha = VRC_LERP2( b, t0.w, a, t1.w );
+    vrc_f4 e;
+    e.x = VRC_LERP2( b, t0.x, a, t1.x ) * alpha;
+    e.y = VRC_LERP2( b, t0.y, a, t1.y ) * alpha;
+    e.z = VRC_LERP2( b, t0.z, a, t1.z ) * alpha;
+    e.w = alpha;
+    return e;
+}
+
+/* ------------------------------------------------------------------------------------------
  * Reference-order pixel: the O(nodeCount) loop of Renderer.cu:172-227, nodes in host order.
  * ---------------------------------------------------------------------------------------- */
 /* MODE: how a sample is fetched and classified.
@@ -2420,8 +2717,10 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                     if( sp != part )
                         return; /* another part's brick */
                 }
-                if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, lut, cls, color,
-                                                                             nSamples ) )
+                if constexpr( MODE == VRC_MODE_MIP || MODE == VRC_MODE_MIP_TRILINEAR )
+                    vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, color, nSamples ); /* (color: the ray's MIP state) */
+                else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, lut, cls, color,
+                                                                                  nSamples ) )
                     finished = true;
             }
             else if( stop )
@@ -2730,6 +3029,75 @@ VRC_HD void vrc_pixel_ray_lod( const vrc_frame& f, const vrc_dev_node* __restric
         }
     }
     pixelBuffer[pixelPos] = color;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * MIP pixel: the bricks of the ray as the composite pixel finds them (DDA: the grid walk; else the list in its order,
+ * with the reference's `break` where a brick's tNear lies beyond the ray's interval, which is part of the sample set's
+ * definition), one classification at the end.  tfp: the padded transfer function in global memory, read twice per
+ * ray.  Passes of one frame meet in vrc_frame::mipMax: the first pass writes it, later ones start from it, and after
+ * every pass the pixel is that of the maximum so far.  A ray without samples leaves its pixel cleared.
+ * ---------------------------------------------------------------------------------------- */
+template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, int GROUP = VRC_GROUP, bool BIG = false >
+VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ nodes,
+                           const int32_t* __restrict__ gridTable, const ATLAS_T* __restrict__ atlas,
+                           const vrc_f4* __restrict__ tfp, const vrc_classifier& cls,
+                           vrc_f4* __restrict__ pixelBuffer, uint32_t px, uint32_t py, uint32_t& nSamples,
+                           const uint16_t* candidates = nullptr, uint32_t nCandidates = 0 )
+{
+    static_assert( MODE == VRC_MODE_MIP || MODE == VRC_MODE_MIP_TRILINEAR, "a MIP mode" );
+    const vrc_ray r = vrc_setup_ray( f, px, f.rowMap ? f.rowMap[py] : py );
+    const uint32_t pixelPos = py * f.width + px;
+    const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
+    uint32_t bits = VRC_MIP_EMPTY;
+    if( r.hit )
+    {
+        if( !f.mipFirst )
+            bits = f.mipMax[pixelPos];
+        vrc_f4 state = zero;
+        if( bits != VRC_MIP_EMPTY )
+        {
+            state.x = vrc_bits_float( bits );
+            state.y = 1.0f;
+        }
+        else if( MODE == VRC_MODE_MIP_TRILINEAR || sizeof( ATLAS_T ) == 4 )
+            state.x = vrc_bits_float( 0xFF800000u ); /* a float M starts at -infinity */
+        if constexpr( DDA )
+            vrc_ray_grid_dda< CLAMP, true, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, r, nodes, gridTable, atlas, tfp, cls, state,
+                                                                             nSamples );
+        else
+        {
+            /* the loop of vrc_pixel_reference_order */
+            const uint32_t nLoop = candidates ? nCandidates : f.nodeCount;
+            for( uint32_t c = 0; c < nLoop; ++c )
+            {
+                const uint32_t i = candidates ? (uint32_t)candidates[c] : c;
+                const vrc_dev_node n = nodes[i];
+                vrc_segment s;
+                bool stop;
+                if( !vrc_brick_segment( f, r, n, f.stepSize, &s, &stop ) )
+                {
+                    if( stop )
+                        break;
+                    continue;
+                }
+                vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, state, nSamples );
+            }
+        }
+        bits = state.y != 0.0f ? vrc_float_bits( state.x ) : VRC_MIP_EMPTY;
+    }
+    f.mipMax[pixelPos] = bits;
+    if( bits != VRC_MIP_EMPTY )
+    {
+        float d;
+        if constexpr( MODE == VRC_MODE_MIP && sizeof( ATLAS_T ) != 4 )
+            d = (float)bits;
+        else
+            d = vrc_bits_float( bits );
+        pixelBuffer[pixelPos] = vrc_classify_mip( tfp, d, cls );
+    }
+    else if( f.clearFirst )
+        pixelBuffer[pixelPos] = zero;
 }
 
 #endif /* VRC_CORE_H */

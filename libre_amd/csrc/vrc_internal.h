@@ -71,11 +71,13 @@ hipError_t vrc_launch_build_lut( const float* tf, vrc_f4* lut, vrc_lut_params p,
  * than the slot gets its border voxels replicated into the padding.
  * xform: what a voxel undergoes on the way (vrc_core.h: VRC_XF_*; elemBytes is the size of a voxel on both sides).
  * slotInfo (may be NULL): the slot's uniformity word (vrc_core.h: VRC_SLOT_*), which the caller zeroed on `stream`
- * before this call; the kernel ORs into it what it finds. */
+ * before this call; the kernel ORs into it what it finds.
+ * slotMax (may be NULL): the slot's largest stored value (vrc_core.h: vrc_frame::slotMax), zeroed by the caller in the
+ * same way; the kernel leaves the word of the voxels it wrote (padding copies repeat voxels of the brick). */
 hipError_t vrc_launch_repack_brick( const void* srcRowMajor, void* slot, uint32_t elemBytes,
                                     const uint32_t size[3], const uint32_t slotDim[3],
                                     hipStream_t stream, uint32_t* slotInfo = nullptr,
-                                    uint32_t xform = VRC_XF_NONE );
+                                    uint32_t xform = VRC_XF_NONE, uint32_t* slotMax = nullptr );
 
 /* atlas -> tap-packed atlas (vrc_core.h): the packed texels of elements [firstElem, firstElem + nElems) of the atlas of
  * 8- or 16-bit voxels (whole slots; the packed atlas holds vrc_packed_elems( atlas elements ) texels of
@@ -153,6 +155,10 @@ hipError_t vrc_launch_tile_order( const vrc_frame& f, uint32_t* order, uint32_t*
                                   uint8_t* bucket, hipStream_t stream );
 
 hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream );
+
+/* maximum-intensity projection (vrc_kernels_mip.hip): point or trilinear (a.linear) samples by gathers, reference-order
+ * loop or grid walk (a.gridDda); lut = the padded transfer function; frame.mipMax set */
+hipError_t vrc_launch_raycast_mip( const vrc_raycast_args& a, hipStream_t stream );
 
 /* LDS-staged form (vrc_kernels_lds.hip): needs gridTable, !clamp, 8x8 tiles */
 hipError_t vrc_launch_raycast_lds( const vrc_raycast_args& a, hipStream_t stream );

@@ -74,6 +74,50 @@ hipError_t vrc_launch_build_lut( const float* tf, vrc_f4* lut, vrc_lut_params p,
  * brick upload: row-major brick -> micro-blocked atlas (replaces the cudaMemcpy3DAsync into
  * a cudaArray of cuda/TexturePool.cu:187-201; the "array layout" is ours to define)
  * ---------------------------------------------------------------------------------------- */
+/* The slot's largest stored value (vrc_core.h: vrc_frame::slotMax, what the MIP march skips bricks by): every repack
+ * kernel folds the voxels it writes into a key -- integer voxels: the stored (shifted) value + 1; the float atlas:
+ * vrc_slot_max_key of a voxel that is not NaN -- and every wave leaves its largest with one atomicMax.  max (mayBeNull):
+ * zeroed on this stream before the launch, as the uniformity word is; maxima commute, and the word is complete when the
+ * kernel is.  A float brick's first thread also leaves -infinity: the word of a brick whose voxels are all NaN. */
+template < typename T >
+__device__ inline uint32_t vrc_voxel_max_key( T stored )
+{
+    if constexpr( sizeof( T ) == 4 )
+    {
+        const float v = vrc_bits_float( (uint32_t)stored );
+        return v != v ? 0u : vrc_slot_max_key( v );
+    }
+    else
+        return (uint32_t)stored + 1u;
+}
+template < typename T >
+__device__ inline void vrc_leave_slot_max( uint32_t* __restrict__ max, uint32_t key )
+{
+    if( max == nullptr )
+        return;
+    if( sizeof( T ) == 4 && blockIdx.x == 0u && threadIdx.x == 0u )
+        key = key > vrc_slot_max_key( vrc_bits_float( 0xFF800000u ) ) ? key : vrc_slot_max_key( vrc_bits_float( 0xFF800000u ) );
+#pragma unroll
+    for( int off = 32; off > 0; off >>= 1 )
+    {
+        const uint32_t o = (uint32_t)__shfl_xor( (int)key, off, 64 );
+        key = key > o ? key : o;
+    }
+    if( ( threadIdx.x & 63u ) == 0u && key != 0u )
+        atomicMax( max, key );
+}
+/* 16-bit voxels: the uniformity word as vrc_k_repack_u8x8 leaves it (first = the brick's first stored voxel) */
+template < typename T >
+__device__ inline void vrc_leave_slot_info( uint32_t* __restrict__ info, bool mixed, uint32_t first )
+{
+    if( sizeof( T ) != 2 || info == nullptr )
+        return;
+    if( __builtin_amdgcn_ballot_w64( mixed ) != 0ull && ( threadIdx.x & 63u ) == 0u )
+        atomicOr( info, VRC_SLOT_MIXED );
+    if( blockIdx.x == 0u && threadIdx.x == 0u )
+        atomicOr( info, first | VRC_SLOT_KNOWN );
+}
+
 /* fast path: 1-byte voxels, x extent a multiple of 8: one thread moves one 8-voxel run
  * (= one row of a micro-block z-slice, 8-byte aligned on both sides).
  * info (may be NULL): the slot's uniformity word (vrc_core.h: VRC_SLOT_*), zeroed on this stream before the launch.
@@ -85,12 +129,13 @@ hipError_t vrc_launch_build_lut( const float* tf, vrc_f4* lut, vrc_lut_params p,
 template < bool FLIP >
 __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __restrict__ slot,
                                    uint32_t sx8, uint32_t sy, uint32_t sz, uint32_t sbx,
-                                   uint32_t sby, uint32_t* __restrict__ info )
+                                   uint32_t sby, uint32_t* __restrict__ info, uint32_t* __restrict__ max )
 {
     const uint32_t total = sx8 * sy * sz;
     constexpr uint32_t flip = FLIP ? 0x80808080u : 0u;
     const uint32_t first = ( src[0].x ^ flip ) & 0xFFu, all = first * 0x01010101u;
     bool mixed = false;
+    uint32_t top = 0u; /* largest byte this thread moved, + 1 */
     for( uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += gridDim.x * blockDim.x )
     {
@@ -103,7 +148,15 @@ __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __res
         const uint32_t e = vrc_slot_local_index( x8 * 8u, y, z, sbx, sby );
         *reinterpret_cast< uint2* >( slot + e ) = v;
         mixed = mixed || v.x != all || v.y != all;
+#pragma unroll
+        for( uint32_t b = 0; b < 32u; b += 8u )
+        {
+            const uint32_t lo = ( ( v.x >> b ) & 0xFFu ) + 1u, hi = ( ( v.y >> b ) & 0xFFu ) + 1u;
+            top = top > lo ? top : lo;
+            top = top > hi ? top : hi;
+        }
     }
+    vrc_leave_slot_max< uint8_t >( max, top );
     if( info != nullptr )
     {
         if( __builtin_amdgcn_ballot_w64( mixed ) != 0ull && ( threadIdx.x & 63u ) == 0u )
@@ -117,17 +170,26 @@ __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __res
 template < typename T, int XF = VRC_XF_NONE >
 __global__ void vrc_k_repack_generic( const T* __restrict__ src, T* __restrict__ slot,
                                       uint32_t sx, uint32_t sy, uint32_t sz, uint32_t sbx,
-                                      uint32_t sby )
+                                      uint32_t sby, uint32_t* __restrict__ info, uint32_t* __restrict__ max )
 {
     const size_t total = (size_t)sx * sy * sz;
+    const T first = vrc_voxel_xform< XF, T >( src[0] );
+    bool mixed = false;
+    uint32_t top = 0u;
     for( size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (size_t)gridDim.x * blockDim.x )
     {
         const uint32_t x = (uint32_t)( i % sx );
         const uint32_t y = (uint32_t)( ( i / sx ) % sy );
         const uint32_t z = (uint32_t)( i / ( (size_t)sx * sy ) );
-        slot[vrc_slot_local_index( x, y, z, sbx, sby )] = vrc_voxel_xform< XF, T >( src[i] );
+        const T v = vrc_voxel_xform< XF, T >( src[i] );
+        slot[vrc_slot_local_index( x, y, z, sbx, sby )] = v;
+        mixed = mixed || v != first;
+        const uint32_t key = vrc_voxel_max_key< T >( v );
+        top = top > key ? top : key;
     }
+    vrc_leave_slot_max< T >( max, top );
+    vrc_leave_slot_info< T >( info, mixed, (uint32_t)first );
 }
 
 /* brick smaller than its (8-voxel padded) slot: the slot padding gets the brick's border
@@ -137,10 +199,13 @@ __global__ void vrc_k_repack_generic( const T* __restrict__ src, T* __restrict__
 template < typename T, int XF = VRC_XF_NONE >
 __global__ void vrc_k_repack_padded( const T* __restrict__ src, T* __restrict__ slot, uint32_t sx,
                                      uint32_t sy, uint32_t sz, uint32_t dx, uint32_t dy,
-                                     uint32_t dz )
+                                     uint32_t dz, uint32_t* __restrict__ info, uint32_t* __restrict__ max )
 {
     const size_t total = (size_t)dx * dy * dz;
     const uint32_t sbx = dx >> VRC_MB_SHIFT, sby = dy >> VRC_MB_SHIFT;
+    const T first = vrc_voxel_xform< XF, T >( src[0] );
+    bool mixed = false;
+    uint32_t top = 0u;
     for( size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (size_t)gridDim.x * blockDim.x )
     {
@@ -148,8 +213,14 @@ __global__ void vrc_k_repack_padded( const T* __restrict__ src, T* __restrict__ 
         const uint32_t y = (uint32_t)( ( i / dx ) % dy );
         const uint32_t z = (uint32_t)( i / ( (size_t)dx * dy ) );
         const uint32_t cx = x < sx ? x : sx - 1u, cy = y < sy ? y : sy - 1u, cz = z < sz ? z : sz - 1u;
-        slot[vrc_slot_local_index( x, y, z, sbx, sby )] = vrc_voxel_xform< XF, T >( src[( (size_t)cz * sy + cy ) * sx + cx] );
+        const T v = vrc_voxel_xform< XF, T >( src[( (size_t)cz * sy + cy ) * sx + cx] );
+        slot[vrc_slot_local_index( x, y, z, sbx, sby )] = v;
+        mixed = mixed || v != first;
+        const uint32_t key = vrc_voxel_max_key< T >( v );
+        top = top > key ? top : key;
     }
+    vrc_leave_slot_max< T >( max, top );
+    vrc_leave_slot_info< T >( info, mixed, (uint32_t)first );
 }
 
 template < typename T, int XF = VRC_XF_NONE >
@@ -377,10 +448,12 @@ static uint32_t grid_for( size_t total, uint32_t block )
 
 hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBytes,
                                     const uint32_t size[3], const uint32_t slotDim[3],
-                                    hipStream_t stream, uint32_t* slotInfo, uint32_t xform )
+                                    hipStream_t stream, uint32_t* slotInfo, uint32_t xform, uint32_t* slotMax )
 {
-    /* slotInfo: only the kernel that fills a whole slot of 1-byte voxels tests for a uniform brick; after the others
-     * the (zeroed) word says "nothing known" and the brick takes the general march */
+    /* slotInfo: of 1-byte voxels only the kernel that fills a whole slot tests for a uniform brick; after the others
+     * the (zeroed) word says "nothing known" and the brick takes the general march.  Bricks of 2-byte voxels are
+     * tested by the kernels that move them (the MIP march reads their word; the composite march does not).
+     * slotMax: left by every kernel */
     const size_t total = (size_t)size[0] * size[1] * size[2];
     if( total == 0 )
         return hipSuccess;
@@ -395,7 +468,7 @@ hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBy
         const dim3 g( grid_for( all, 256 ) ), b( 256 );
 #define VRC_PADDED( T, XF )                                                                                       \
     hipLaunchKernelGGL( ( vrc_k_repack_padded< T, XF > ), g, b, 0, stream, (const T*)src, (T*)slot, size[0], size[1], \
-                        size[2], slotDim[0], slotDim[1], slotDim[2] )
+                        size[2], slotDim[0], slotDim[1], slotDim[2], slotInfo, slotMax )
         if( elemBytes == 1 && xform == VRC_XF_FLIP )
             VRC_PADDED( uint8_t, VRC_XF_FLIP );
         else if( elemBytes == 1 )
@@ -417,7 +490,7 @@ hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBy
     }
 #define VRC_GENERIC( T, XF )                                                                                          \
     hipLaunchKernelGGL( ( vrc_k_repack_generic< T, XF > ), dim3( grid_for( total, 256 ) ), dim3( 256 ), 0, stream,     \
-                        (const T*)src, (T*)slot, size[0], size[1], size[2], sbx, sby )
+                        (const T*)src, (T*)slot, size[0], size[1], size[2], sbx, sby, slotInfo, slotMax )
     /* (the experimental layout 5 has no 8-voxel runs along x: generic kernel) */
     if( VRC_LAYOUT != 5 && elemBytes == 1 && ( size[0] % 8u ) == 0 && ( ( (uintptr_t)src ) % 8u ) == 0 &&
         ( ( (uintptr_t)slot ) % 8u ) == 0 && total / 8 < 0xFFFFFFFFull )
@@ -426,11 +499,11 @@ hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBy
         if( xform == VRC_XF_FLIP )
             hipLaunchKernelGGL( vrc_k_repack_u8x8< true >, dim3( grid_for( total / 8, 256 ) ), dim3( 256 ), 0,
                                 stream, (const uint2*)src, (uint8_t*)slot, sx8, size[1], size[2], sbx,
-                                sby, slotInfo );
+                                sby, slotInfo, slotMax );
         else
             hipLaunchKernelGGL( vrc_k_repack_u8x8< false >, dim3( grid_for( total / 8, 256 ) ), dim3( 256 ), 0,
                                 stream, (const uint2*)src, (uint8_t*)slot, sx8, size[1], size[2], sbx,
-                                sby, slotInfo );
+                                sby, slotInfo, slotMax );
     }
     else if( elemBytes == 1 && xform == VRC_XF_FLIP )
         VRC_GENERIC( uint8_t, VRC_XF_FLIP );

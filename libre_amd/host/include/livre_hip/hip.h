@@ -91,6 +91,9 @@ public:
     void setFrameBuffer( void* deviceRgba, uint32_t width, uint32_t height );
     void setStream( void* hipStream );
     void setOption( int option, int64_t value );
+    /** VRC_OPT_PROJECTION = VRC_PROJECTION_MIP was set: the maximum-intensity projection has no per-ray LOD form, a frame
+     *  that asks for per-ray LOD is then rendered with its per-brick cut (the path taken on VRC_EHIERARCHY) */
+    bool projectionIsMip() const { return _mip; }
     /** kernel time (HIP events) of the last launch, sum and count since the previous call,
      *  and the sample counter of the last launch; synchronizes the render stream */
     void kernelStats( float* lastMs, double* sumMs, uint32_t* launches, uint64_t* samples );
@@ -135,6 +138,7 @@ private:
     vrc_ctx* _ctx;
     uint32_t _computedSamplesPerRay;
     bool _lastRayLod = false;
+    bool _mip = false;
     std::vector< Vector4f > _uploadedPlanes; /* what the device layer has (vrc_update): render() uploads a change */
     void uploadSettings( const RenderInputs& renderInputs );
     /* render(): the sorted node list of the last call, kept while the bricks and the model-view matrix repeat */

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 
 #include "livre_hip/hip.h"
 
@@ -35,6 +36,7 @@ struct lvh_app
     RenderStatistics lastStats;
     std::vector< uint32_t > rowMap; /* lvh_app_set_bands */
     std::vector< std::unique_ptr< Renderer > > extraRenderers; /* frames in flight beyond the first */
+    std::map< int, int64_t > projectionOptions; /* VRC_OPT_PROJECTION / VRC_OPT_MIP_SKIP as set: for renderers made later */
     uint32_t slot = 0;
     std::string rendererName;
     float dataRange[2] = { 0.0f, 0.0f }; /* lvh_app_set_data_range; empty = the voxel type's range */
@@ -283,6 +285,8 @@ int lvh_app_set_frames_in_flight( lvh_app* app, uint32_t n )
         while( app->extraRenderers.size() + 1 < n )
         {
             app->extraRenderers.emplace_back( new Renderer( app->rendererName ) );
+            for( const auto& o : app->projectionOptions )
+                static_cast< HipRaycastRenderer& >( app->extraRenderers.back()->getPlugin() ).setOption( o.first, o.second );
             if( app->histogram )
                 static_cast< HipRaycastRenderer& >( app->extraRenderers.back()->getPlugin() ).setHistogram( true );
         }
@@ -311,6 +315,22 @@ int lvh_app_select_slot( lvh_app* app, uint32_t slot )
 int lvh_app_set_option( lvh_app* app, int option, int64_t value )
 {
     if( !app ) return fail( "NULL argument" );
+    if( option == VRC_OPT_PROJECTION || option == VRC_OPT_MIP_SKIP )
+    {
+        /* how the app forms its pixels: every renderer it has, and every one it makes later (lvh_app_set_frames_in_flight) */
+        try
+        {
+            static_cast< HipRaycastRenderer& >( app->pipeline->getRenderer().getPlugin() ).setOption( option, value );
+            for( auto& r : app->extraRenderers )
+                static_cast< HipRaycastRenderer& >( r->getPlugin() ).setOption( option, value );
+            app->projectionOptions[option] = value;
+            return 0;
+        }
+        catch( const std::exception& e )
+        {
+            return fail( e.what() );
+        }
+    }
     LVH_TRY( app->renderer().setOption( option, value ) )
 }
 int lvh_app_set_data_range( lvh_app* app, float lo, float hi )

@@ -704,7 +704,7 @@ void HipRaycastRenderer::render( const RenderInputs& renderInputs, const ConstCa
         rData.dataSourceRange[1] = renderInputs.dataSourceRange[1];
     }
     /* per-ray LOD (extension): SelectVisibles.cpp:55-57 worldSpacePerPixel of this frame */
-    const bool rayLod = renderInputs.vrParameters.getRayLOD();
+    const bool rayLod = renderInputs.vrParameters.getRayLOD() && !_mip; /* (MIP: the per-brick cut) */
     throwOnVrcError( vrc_set_ray_lod( _ctx, rayLod ? 1 : 0, renderInputs.vrParameters.getSSE(),
                                       ( frustum.top() - frustum.bottom() ) /
                                           float( renderInputs.pixelViewPort[3] ) ),
@@ -756,7 +756,12 @@ void HipRaycastRenderer::setFrameBuffer( void* d, uint32_t w, uint32_t h )
     throwOnVrcError( vrc_set_framebuffer( _ctx, d, w, h ), "vrc_set_framebuffer" );
 }
 void HipRaycastRenderer::setStream( void* s ) { throwOnVrcError( vrc_ctx_set_stream( _ctx, s ), "vrc_ctx_set_stream" ); }
-void HipRaycastRenderer::setOption( int o, int64_t v ) { throwOnVrcError( vrc_set_option( _ctx, o, v ), "vrc_set_option" ); }
+void HipRaycastRenderer::setOption( int o, int64_t v )
+{
+    throwOnVrcError( vrc_set_option( _ctx, o, v ), "vrc_set_option" );
+    if( o == VRC_OPT_PROJECTION )
+        _mip = v == VRC_PROJECTION_MIP;
+}
 void HipRaycastRenderer::synchronize() { throwOnVrcError( vrc_synchronize( _ctx ), "vrc_synchronize" ); }
 void HipRaycastRenderer::kernelStats( float* lastMs, double* sumMs, uint32_t* launches, uint64_t* samples )
 {
@@ -1098,7 +1103,9 @@ struct HipRaycastPipeline::Impl
             uint32_t( _texturePool->getTextureMem() / _texturePool->getSlotMemSize() );
         /* per-ray LOD: one pass over the visible set and its ancestors; when that does not fit the
          * atlas (or the tree is ragged) the frame is rendered with the reference's per-brick cut */
-        bool rayLod = in.vrParameters.getRayLOD();
+        /* (the maximum-intensity projection has no per-ray LOD form: its frames take the per-brick cut) */
+        bool rayLod = in.vrParameters.getRayLOD() &&
+                      !static_cast< HipRaycastRenderer& >( renderer.getPlugin() ).projectionIsMip();
         if( rayLod )
         {
             NodeIds hierarchy = nodeIds;
@@ -1463,7 +1470,9 @@ struct HipRaycastPipeline::Impl
         ConstCacheObjects objects;
         const uint32_t maxNodes = uint32_t( _texturePool->getTextureMem() / _texturePool->getSlotMemSize() );
         NodeIds hierarchy = visibles;
-        bool rayLod = in.vrParameters.getRayLOD() && withAncestors( in, hierarchy );
+        bool rayLod = in.vrParameters.getRayLOD() &&
+                      !static_cast< HipRaycastRenderer& >( renderer.getPlugin() ).projectionIsMip() &&
+                      withAncestors( in, hierarchy );
         histogramCut( renderer, false, visibles );
         if( rayLod && hierarchy.size() > maxNodes )
         {

@@ -1,0 +1,106 @@
+"""Developer timing of the maximum-intensity projection (VRC_OPT_PROJECTION) against the composite kernel, in one
+session and at the same cameras: the C2 volume (mem://, constant bricks) and the noise volume of the same size (hash://),
+at the default camera and with the model spun by 30 / 20 degrees.  Per volume and camera: composite, MIP with
+VRC_OPT_MIP_SKIP 0 and MIP with VRC_OPT_MIP_SKIP 1, point-sampled; the same three with the trilinear filter on the noise
+volume.  Kernel ms from the library's HIP events (mean per frame over --steps frames after --warmup), samples from one
+counted frame each.  The report goes to standard output and to --out (profiles/mip_projection.txt).
+
+Under rocprofv3 (a counter run is kept apart from any tracing) pass --only to keep the run to one row, e.g.
+--only noise:off_axis:nearest:mip_skip0 --steps 1 --warmup 0."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from libre_amd import driver, vrc  # noqa: E402
+
+CAMERAS = (("default", (0.0, 0.0)), ("off_axis", (0.5235988, 0.3490659)))
+# (row, VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP)
+ROWS = (("composite", vrc.PROJECTION_COMPOSITE, 1), ("mip_skip0", vrc.PROJECTION_MIP, 0), ("mip_skip1", vrc.PROJECTION_MIP, 1))
+
+
+def linear_ramp(alpha):
+    i = np.arange(256, dtype=np.float32) / np.float32(255.0)
+    return np.ascontiguousarray(np.stack([i, i, i, np.float32(alpha) * i], axis=1).astype(np.float32))
+
+
+def time_kernel(app, n_warm, n_timed):
+    import torch
+    for _ in range(n_warm):
+        app.render_frame(readback=False)
+    torch.cuda.synchronize()
+    app.stats()
+    for _ in range(n_timed):
+        app.render_frame(readback=False)
+    torch.cuda.synchronize()
+    st = app.stats()
+    return st.kernel_ms_sum / max(1, st.kernel_launches)
+
+
+def count_samples(app):
+    app.set_option(vrc.OPT_COUNT_SAMPLES, 1)
+    app.render_frame(readback=False)
+    n = int(app.stats().samples)
+    app.set_option(vrc.OPT_COUNT_SAMPLES, 0)
+    return n
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--voxels", type=int, default=1024)
+    ap.add_argument("--block", type=int, default=128)
+    ap.add_argument("--viewport", type=int, default=1024)
+    ap.add_argument("--alpha", type=float, default=0.05)
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--only", default=None, help="volume:camera:filter:row, e.g. noise:off_axis:nearest:mip_skip0")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mip_projection.txt"))
+    a = ap.parse_args()
+    driver.load_library()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    say("# tools/dev_mip.py: %d^3 voxels in %d^3 bricks, %dx%d viewport, alpha %.3g, %d frames after %d warm-up" % (
+        a.voxels, a.block, a.viewport, a.viewport, a.alpha, a.steps, a.warmup))
+    say("# volume camera filter row: kernel, kernel ms per frame, samples per frame, Gsamples/s, ms against composite")
+    for volume, scheme, filters in (("C2", "mem", (0,)), ("noise", "hash", (0, 1))):
+        uri = "%s://#%d,%d,%d,%d" % (scheme, a.voxels, a.voxels, a.voxels, a.block)
+        with driver.App(uri, a.viewport, a.viewport, synchronous=True, gpu_cache_mb=3072) as probe:
+            leaf = probe.volume_info()["depth"] - 1
+        with driver.App(uri, a.viewport, a.viewport, synchronous=True, min_lod=leaf, max_lod=leaf, gpu_cache_mb=3072) as app:
+            app.set_colormap(linear_ramp(a.alpha))
+            for camera, spin in CAMERAS:
+                app.set_camera(spin=spin)
+                for flt in filters:
+                    fname = "trilinear" if flt else "nearest"
+                    app.set_option(vrc.OPT_FILTER, vrc.FILTER_TRILINEAR if flt else vrc.FILTER_NEAREST)
+                    base = None
+                    for row, projection, skip in ROWS:
+                        if a.only and a.only != "%s:%s:%s:%s" % (volume, camera, fname, row):
+                            continue
+                        app.set_option(vrc.OPT_PROJECTION, projection)
+                        app.set_option(vrc.OPT_MIP_SKIP, skip)
+                        n = count_samples(app)
+                        ms = time_kernel(app, a.warmup, a.steps)
+                        kernel = (vrc.load_library().vrc_last_kernel() or b"").decode()
+                        base = ms if row == "composite" else base
+                        say("%-5s %-8s %-9s %-9s %-34s %8.3f ms %13d samples %7.2f Gsamples/s %s" % (
+                            volume, camera, fname, row, kernel, ms, n, n / ms / 1e6,
+                            "x%.3f" % (ms / base) if base else "-"))
+                    app.set_option(vrc.OPT_PROJECTION, vrc.PROJECTION_COMPOSITE)
+                    app.set_option(vrc.OPT_MIP_SKIP, 1)
+            app.set_option(vrc.OPT_FILTER, vrc.FILTER_NEAREST)
+    if not a.only:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
