@@ -169,8 +169,9 @@ typedef struct
  *     (cuda/Renderer.cu:183-186); the same restart per brick, sample positions and count per segment
  *     (VRC_OPT_STEPPING 0 and 1); no early termination.
  *   Value.  M = the maximum over S of the sampled density: VRC_FILTER_NEAREST the voxel's value, in the volume's own
- *     units; VRC_FILTER_TRILINEAR the interpolated float.  A float atlas folds with fmaxf starting from -infinity, so
- *     NaN samples drop out (a ray whose samples are all NaN has M = -infinity).
+ *     units; VRC_FILTER_TRILINEAR the interpolated float.  A float atlas folds starting from -infinity with a maximum
+ *     that keeps M over a sample that is not a number, so NaN samples, quiet or signalling, drop out (a ray whose
+ *     samples are all NaN has M = -infinity: a pixel with S not empty, the classification of -infinity).
  *   Pixel, S not empty.  t = TF((M - r0) / (r1 - r0)), r = dataSourceRange, fetched as every sample's is (256 texels,
  *     linear filter, the weight in VRC_OPT_TF_FRAC_BITS bits); no opacity correction and no 255/256 clamp, as no step
  *     length is involved; stored premultiplied, (t.rgb * t.a, t.a), the frame buffer's convention.  Classified once
@@ -286,7 +287,8 @@ int vrc_pool_create( vrc_ctx* ctx, size_t bytes_per_voxel, int is_signed, int is
  * kernels: VRC_KERNEL_AUTO, _REFERENCE_ORDER, _GRID_DDA, per-ray LOD by gathers; an explicit VRC_KERNEL_LDS or _PACKED
  * is VRC_EINVAL, also under vrc_set_ray_lod, and VRC_OPT_UNIFORM_BRICKS does not apply.  Voxels that are not finite are
  * not inspected by the upload; a NaN density classifies as the first texel of the transfer function (the clamp of the
- * texel coordinate drops it), +-infinity as the last / first.
+ * texel coordinate drops it), +-infinity as the last / first.  Under VRC_FILTER_TRILINEAR a sample with a tap that is
+ * NaN has a NaN density; what a sample with an infinite tap comes out as (inf * 0, inf - inf) is unspecified.
  * vrc_pool_histogram, vrc_pool_enable_histograms and vrc_frame_histogram return VRC_EUNSUPPORTED for the five types
  * vrc_pool_create does not make. */
 #define VRC_VOXEL_UINT8 0

@@ -2007,18 +2007,22 @@ VRC_HD bool vrc_march_segment_packed( const vrc_frame& f, const vrc_dev_node& n,
  * the pixel is ONE classification of the largest sampled density, after the march.  The march bodies below keep the
  * control structure of vrc_march_segment_as / vrc_march_segment_linear (whole groups under the same guard, the
  * sequential travel chain, the same tails), so positions and counts are theirs by construction; the per-sample work
- * is a maximum folded into one register, two samples per instruction (v_max3_u32 / v_max3_f32).
+ * is a maximum folded into one register (integer voxels: two samples per instruction, v_max3_u32).
  *
  * M is held as uint32_t for point samples of the integer atlases (the stored, offset-binary value: the shift is
  * monotone) and as float for the float atlas and every trilinear sample; a float M starts at -infinity and is folded
- * with fmaxf, so NaN samples drop out.
+ * with a comparison that keeps M over a sample that is not a number, so NaN samples drop out.
  * ---------------------------------------------------------------------------------------- */
 #define VRC_MODE_MIP 7           /* point samples */
 #define VRC_MODE_MIP_TRILINEAR 8 /* trilinear samples by gathers */
 #define VRC_MIP_EMPTY 0xFFFFFFFFu /* vrc_frame::mipMax: the pixel's rays have taken no sample (no integer voxel, and a NaN no float M can be) */
 
 VRC_HD uint32_t vrc_mip_max( uint32_t a, uint32_t b ) { return a > b ? a : b; }
-VRC_HD float vrc_mip_max( float a, float b ) { return fmaxf( a, b ); }
+/* a: the maximum so far, never NaN (it starts at -infinity); b: a sample.  NOT fmaxf: a point sample of the float atlas
+ * reaches this as the voxel's bits, and the maximum of a number and a SIGNALLING NaN is a NaN by IEEE 754-2008 maxNum --
+ * v_max_f32 / v_max3_f32 in IEEE mode and glibc's fmaxf alike -- which would throw away the maximum so far.  The
+ * comparison is false for every NaN and keeps a. */
+VRC_HD float vrc_mip_max( float a, float b ) { return b > a ? b : a; }
 template < typename D >
 VRC_HD D vrc_mip_max3( D m, D a, D b ) { return vrc_mip_max( vrc_mip_max( m, a ), b ); }
 VRC_HD uint32_t vrc_mip_bits( uint32_t m ) { return m; }
