@@ -63,9 +63,10 @@ int lvh_app_set_clip_planes( lvh_app* app, const float* planes, uint32_t n );
 /* sort-first row bands rendered by this process in one launch: bands (y0[i], h[i]) of the full
  * frame, stacked in that order in its pixel buffer (replaces params.tile; n = 0 -> back to it) */
 int lvh_app_set_bands( lvh_app* app, const uint32_t* y0, const uint32_t* h, uint32_t n );
-/* vrc_set_option on the renderer of the selected slot.  VRC_OPT_PROJECTION and VRC_OPT_MIP_SKIP say how the app forms its
- * pixels: they reach every renderer of the app, those of extra slots and those made later included.  With the
- * maximum-intensity projection a frame that asks for per-ray LOD (lvh_app_set_ray_lod) renders its per-brick cut. */
+/* vrc_set_option on the renderer of the selected slot.  VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP and VRC_OPT_MIP_FOLD say how
+ * the app forms its pixels: they reach every renderer of the app, those of extra slots and those made later included.
+ * With VRC_PROJECTION_MIP, whichever fold (maximum, minimum, mean), a frame that asks for per-ray LOD
+ * (lvh_app_set_ray_lod) renders its per-brick cut. */
 int lvh_app_set_option( lvh_app* app, int vrc_option, int64_t value );
 /* RenderInputs::dataSourceRange, in the volume's own values, for volumes that are not uint8 (the reference forces
  * (0,255), livre/eq/Channel.cpp:284, and its CUDA renderer ignores the field; the other voxel types are an extension

@@ -162,6 +162,15 @@ typedef struct
                                     * maximum does not depend on the order or on samples that cannot raise it: the same
                                     * frame, bit for bit; only vrc_stats.samples falls.  0: every brick is marched */
 
+#define VRC_OPT_MIP_FOLD 18         /* what a MIP frame folds a ray's samples into (read only when VRC_OPT_PROJECTION =
+                                    * VRC_PROJECTION_MIP): VRC_MIP_FOLD_MAX (default: the maximum, the MIP frame below
+                                    * bit for bit) | VRC_MIP_FOLD_MIN (minimum-intensity projection) | VRC_MIP_FOLD_MEAN
+                                    * (mean-intensity / X-ray projection): see "The folds of a MIP frame" below.  Any
+                                    * other value: VRC_EINVAL */
+#define VRC_MIP_FOLD_MAX 0
+#define VRC_MIP_FOLD_MIN 1
+#define VRC_MIP_FOLD_MEAN 2
+
 /* A MIP frame (VRC_OPT_PROJECTION = VRC_PROJECTION_MIP).
  *   Sample set.  A ray's sample set S is exactly what the composite march takes with a transfer function whose alpha
  *     is 0 everywhere: the same ray set-up, global-box and clip-plane interval and near plane; the same node list
@@ -191,6 +200,32 @@ typedef struct
  * vrc_set_ray_lod on, VRC_VARIANT_GLRAYCASTER.  VRC_OPT_DEPTH_SPLIT and VRC_OPT_ERT_COMPACTION are silently the plain
  * kernel.  VRC_OPT_UNIFORM_BRICKS: a ray whose segment lies in a slot known to hold one value takes max(M, value) and
  * the segment's step count without fetching (point samples of 8- and 16-bit voxels; same frame and count, bit for bit). */
+
+/* The folds of a MIP frame (VRC_OPT_MIP_FOLD).  The sample set S of a ray is the MIP frame's, exactly, whatever the fold:
+ * nothing about it is new.  Served, refused (VRC_KERNEL_LDS and _PACKED, vrc_set_ray_lod, VRC_VARIANT_GLRAYCASTER) and
+ * silently the plain kernel (VRC_OPT_DEPTH_SPLIT, VRC_OPT_ERT_COMPACTION) as above.  The pixel is one classification of
+ * M as above; a ray with S empty keeps its cleared value.  Changing VRC_OPT_MIP_FOLD between vrc_pre_render and
+ * vrc_post_render: the next vrc_render returns VRC_EINVAL and names the option, as for a changed projection.
+ *   VRC_MIP_FOLD_MAX.  M = the maximum over S: the frame above.
+ *   VRC_MIP_FOLD_MIN.  M = the minimum over S.  A float atlas folds starting from +infinity with a comparison that keeps
+ *     M over a sample that is not a number: NaN samples drop out, and a ray whose samples are all NaN has M =
+ *     +infinity.  Passes meet in the same running word per pixel.  VRC_OPT_MIP_SKIP: a ray does not march a brick whose
+ *     SMALLEST stored voxel cannot lower M (every upload notes that per slot too).  VRC_OPT_UNIFORM_BRICKS: min(M,
+ *     value) and the step count without fetching.  Both leave the frame bit-identical; only vrc_stats.samples falls
+ *     with skipping.
+ *   VRC_MIP_FOLD_MEAN.  M = (the sum of the sampled densities) / |S|, classified once.  Passes meet in a running (sum,
+ *     count) per pixel of the pixel buffer, which the context owns as it owns the running maximum.  Point samples of
+ *     the 8- and 16-bit atlases are summed exactly, in 64-bit integers (of the stored values: an offset-binary
+ *     atlas's shift is taken off once per ray); M is that quotient formed in float64 and rounded to float32 once.
+ *     Samples of the float atlas and all trilinear samples are accumulated in float64, in the order of the march; NaN
+ *     and infinities propagate by IEEE rules, and a NaN mean classifies as a NaN density does (the first texel).
+ *     VRC_OPT_MIP_SKIP does nothing.  VRC_OPT_UNIFORM_BRICKS: value x step count is added without fetching (point
+ *     samples of 8- and 16-bit voxels; exact).  vrc_stats.samples is always |S|.
+ * The running state of a pixel is read as what the current pass makes of it -- an integer for point samples of the 8- and
+ * 16-bit atlases, a float (the mean: a float64 sum) for everything else -- so VRC_OPT_FILTER must not change between
+ * the passes of one MIP frame, whatever the fold: the library does not check it, and the frame and the read-back values
+ * are unspecified if it does.
+ * vrc_get_projection_values returns M itself. */
 
 #define VRC_VARIANT_CUDARAYCASTER 0 /* renderers/cudaRaycaster/cuda/Renderer.cu:95-230 */
 #define VRC_VARIANT_GLRAYCASTER 1   /* renderers/glRaycaster/shaders/fragRaycast.glsl:113-215: pixel centre
@@ -389,6 +424,17 @@ int vrc_get_stats( vrc_ctx* ctx, vrc_stats* out );
  * that render did not use compaction.  Waits for the render. */
 int vrc_get_ray_counts( vrc_ctx* ctx, uint32_t counts[8], int* parts );
 
+/* The projected values of a MIP frame, any fold: M per pixel, for window / level and for measurements (the frame
+ * buffer holds only its classification).  Synchronous on the context's stream.  W x H entries, those of the pixel buffer
+ * the frame's last MIP vrc_render wrote -- internal, caller-owned or row-mapped (then H is the number of mapped rows).
+ *   host_values[i]  M in the volume's own units: signed voxel types are un-shifted, a float M is returned as it is;
+ *                   unspecified where the count is 0.
+ *   host_counts[i]  (may be NULL)  VRC_MIP_FOLD_MEAN: the samples of the pixel over the passes so far; _MAX and _MIN: 1
+ *                   where S is not empty, else 0.
+ * Valid from a frame's first MIP vrc_render until the next vrc_pre_render; VRC_EINVAL otherwise (before any MIP render,
+ * after a composite frame). */
+int vrc_get_projection_values( vrc_ctx* ctx, float* host_values, uint32_t* host_counts );
+
 /* ---- sort-first tile exchange (multi-GPU) ------------------------------------------------------- */
 /* One process per GPU renders row bands of the frame (vrc_set_row_map); the display rank receives
  * them over RCCL (xGMI inside a node) directly at their rows of the full frame.  This is the step
@@ -437,8 +483,8 @@ int vrc_last_kernel_occupancy( int* workgroups_per_cu, int* threads_per_workgrou
 /* ABI version of this header */
 #define VRC_ABI_VERSION 4 /* 3: vrc_gather_tiles takes the frame height; 4: VRC_KERNEL_PACKED, VRC_OPT_PACKED_ATLAS, vrc_last_kernel_occupancy
                            * (added since without a new number, as symbols a caller may bind weakly: the frame histogram,
-                           * vrc_pool_create_typed / vrc_pool_voxel_type; as option values only: VRC_OPT_PROJECTION,
-                           * VRC_OPT_MIP_SKIP) */
+                           * vrc_pool_create_typed / vrc_pool_voxel_type, vrc_get_projection_values; as option values only:
+                           * VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP, VRC_OPT_MIP_FOLD) */
 /* = VRC_ABI_VERSION for the product build; -VRC_ABI_VERSION for a developer build of the library (compiled with
  * -DVRC_DEV_BUILD: experiment switches, statistics, ablations that render wrong pixels on purpose) */
 int vrc_abi_version( void );

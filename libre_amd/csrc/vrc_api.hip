@@ -67,6 +67,8 @@ struct vrc_pool
      * it): the second half of dSlotInfo's allocation, so the same lifetime; zeroed and refilled by every upload with the
      * uniformity word -- same stream, same fences, same lastUpload */
     uint32_t* dSlotMax = nullptr;
+    /* ... and the smallest, as a complemented key (vrc_frame::slotMin; the minimum fold skips by it): the third part */
+    uint32_t* dSlotMin = nullptr;
     /* tap-packed atlas of the trilinear filter (vrc_core.h): same slots, a texel of twice the voxel's bytes per voxel in
      * blocks of 64 rows of 9.
      * Allocated and filled from the byte atlas the first time a render asks for it (pool_enable_packed); from then
@@ -208,6 +210,7 @@ struct vrc_ctx
     int64_t optUniformBricks = 1; /* VRC_OPT_UNIFORM_BRICKS */
     int64_t optProjection = VRC_PROJECTION_COMPOSITE; /* VRC_OPT_PROJECTION */
     int64_t optMipSkip = 1;                           /* VRC_OPT_MIP_SKIP */
+    int64_t optMipFold = VRC_MIP_FOLD_MAX;            /* VRC_OPT_MIP_FOLD */
     /* MIP: one running maximum per pixel of the pixel buffer (vrc_core.h: vrc_frame::mipMax), whichever buffer that
      * is; vrc_pre_render invalidates it (mipFirst: the next MIP pass does not read it) and forgets the projection of
      * the frame before (frameProjection: that of the frame's first vrc_render, -1 = none yet) */
@@ -215,6 +218,17 @@ struct vrc_ctx
     size_t dMipMaxPixels = 0;
     bool mipFirst = true;
     int64_t frameProjection = -1;
+    /* the mean fold's running (sum, count) per pixel (vrc_frame::meanSum, meanCount): allocated, invalidated and grown
+     * where dMipMax is; frameFold: the fold of the frame's first MIP vrc_render, as frameProjection is its projection */
+    unsigned long long* dMeanSum = nullptr;
+    uint32_t* dMeanCount = nullptr;
+    size_t dMeanPixels = 0;
+    int64_t frameFold = -1;
+    /* what vrc_get_projection_values reads: the state the frame's last MIP pass left (pixels = 0: none -- no MIP pass
+     * since vrc_pre_render), and the device buffer its kernel writes (values | counts) */
+    vrc_projection_state projState = { nullptr, nullptr, nullptr, 0u, 0u, 0u, 0.0f };
+    float* dProjOut = nullptr;
+    size_t dProjOutPixels = 0;
     uint32_t* dRayList = nullptr; /* counts | two ray lists (vrc_internal.h) */
     size_t dRayListCap = 0;       /* pixels */
     int lastErtParts = 0;         /* of the last vrc_render */
@@ -354,6 +368,9 @@ void vrc_ctx_destroy( vrc_ctx* c )
     if( c->dTileOrder ) (void)hipFree( c->dTileOrder );
     if( c->dRayList ) (void)hipFree( c->dRayList );
     if( c->dMipMax ) (void)hipFree( c->dMipMax );
+    if( c->dMeanSum ) (void)hipFree( c->dMeanSum );
+    if( c->dMeanCount ) (void)hipFree( c->dMeanCount );
+    if( c->dProjOut ) (void)hipFree( c->dProjOut );
     if( c->dRowMap ) (void)hipFree( c->dRowMap );
     if( c->dCounter ) (void)hipFree( c->dCounter );
     if( c->hCounter ) (void)hipHostFree( c->hCounter );
@@ -417,6 +434,11 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
         c->optProjection = value;
         return VRC_OK;
     case VRC_OPT_MIP_SKIP: c->optMipSkip = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_MIP_FOLD:
+        if( value != VRC_MIP_FOLD_MAX && value != VRC_MIP_FOLD_MIN && value != VRC_MIP_FOLD_MEAN )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_MIP_FOLD is 0 (maximum), 1 (minimum) or 2 (mean)" );
+        c->optMipFold = value;
+        return VRC_OK;
     case VRC_OPT_ERT_COMPACTION:
         if( value < 0 || value > VRC_MAX_ERT_PARTS )
             return fail( VRC_EINVAL, "VRC_OPT_ERT_COMPACTION: 0 (off) or 2.." + std::to_string( VRC_MAX_ERT_PARTS ) +
@@ -452,6 +474,7 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_UNIFORM_BRICKS: *value = c->optUniformBricks; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->optProjection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->optMipSkip; return VRC_OK;
+    case VRC_OPT_MIP_FOLD: *value = c->optMipFold; return VRC_OK;
     case VRC_OPT_VARIANT: *value = c->optVariant; return VRC_OK;
     case VRC_OPT_KERNEL_USED: *value = c->stats.kernel_variant; return VRC_OK;
     case VRC_OPT_GRID_WALK_USED: *value = c->gridWalkUsed; return VRC_OK;
@@ -609,9 +632,10 @@ static int pool_create( vrc_ctx* c, int voxelType, const uint32_t maxBlock[3], s
      * not ordered with a non-blocking stream, and the first uploads of a large pool could be overtaken by it (seen once:
      * a 6 GB pool of 16-bit voxels, round 4) */
     if( e == hipSuccess ) e = hipMemsetAsync( p->dAtlas, 0, p->atlasBytes, p->uploadStream );
-    if( e == hipSuccess ) e = hipMalloc( &p->dSlotInfo, 2 * nSlots * sizeof( uint32_t ) );
-    if( e == hipSuccess ) e = hipMemsetAsync( p->dSlotInfo, 0, 2 * nSlots * sizeof( uint32_t ), p->uploadStream );
+    if( e == hipSuccess ) e = hipMalloc( &p->dSlotInfo, 3 * nSlots * sizeof( uint32_t ) );
+    if( e == hipSuccess ) e = hipMemsetAsync( p->dSlotInfo, 0, 3 * nSlots * sizeof( uint32_t ), p->uploadStream );
     if( e == hipSuccess ) p->dSlotMax = p->dSlotInfo + nSlots;
+    if( e == hipSuccess ) p->dSlotMin = p->dSlotInfo + 2 * nSlots;
     if( e == hipSuccess ) e = hipEventCreateWithFlags( &p->lastUpload, hipEventDisableTiming );
     if( e == hipSuccess )
     {
@@ -812,12 +836,15 @@ static int pool_upload( vrc_pool* p, const void* src, bool srcIsDevice, const ui
              * repack finds in them -- same stream, same fences, same lastUpload as the voxels */
             uint32_t* const info = p->dSlotInfo + index;
             uint32_t* const top = p->dSlotMax + index; /* ... and the slot's largest stored value */
+            uint32_t* const low = p->dSlotMin + index; /* ... and its smallest */
             e = hipMemsetAsync( info, 0, sizeof( uint32_t ), p->uploadStream );
             if( e == hipSuccess )
                 e = hipMemsetAsync( top, 0, sizeof( uint32_t ), p->uploadStream );
             if( e == hipSuccess )
+                e = hipMemsetAsync( low, 0, sizeof( uint32_t ), p->uploadStream );
+            if( e == hipSuccess )
                 e = vrc_launch_repack_brick( devSrc, slotPtr, p->elemBytes, size, p->slotDim, p->uploadStream, info,
-                                             p->xform, top );
+                                             p->xform, top, low );
             if( e == hipSuccess && p->packedOn )
                 e = vrc_launch_pack_slots( p->dAtlas, p->dPacked, base,
                                            (uint64_t)p->slotDim[0] * p->slotDim[1] * p->slotDim[2], p->slotDim,
@@ -1255,6 +1282,8 @@ int vrc_pre_render( vrc_ctx* c, const vrc_view_data* view )
     /* a new frame: its MIP passes start over, and it may take either projection */
     c->mipFirst = true;
     c->frameProjection = -1;
+    c->frameFold = -1;
+    c->projState.pixels = 0u; /* vrc_get_projection_values: nothing to read until a MIP pass of this frame */
     return VRC_OK;
 }
 
@@ -1395,6 +1424,9 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     if( c->frameProjection >= 0 && c->frameProjection != c->optProjection )
         return fail( VRC_EINVAL, "vrc_render: VRC_OPT_PROJECTION changed between vrc_pre_render and vrc_post_render; the "
                                  "passes of one frame take one projection" );
+    if( mip && c->frameFold >= 0 && c->frameFold != c->optMipFold )
+        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_MIP_FOLD changed between vrc_pre_render and vrc_post_render; the "
+                                 "passes of one frame take one fold" );
     if( mip )
     {
         /* what the maximum-intensity projection is not defined for (include/vrc_hip.h) */
@@ -1673,10 +1705,40 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             if( !c->mipFirst ) /* a later pass of a frame whose pixel buffer grew (vrc_set_framebuffer): nothing known */
                 VRC_HIP_CHECK( hipMemsetAsync( c->dMipMax, 0xFF, pixels * sizeof( uint32_t ), c->stream ) );
         }
+        const bool mean = c->optMipFold == VRC_MIP_FOLD_MEAN;
+        if( mean && pixels > c->dMeanPixels )
+        {
+            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+            if( c->dMeanSum ) VRC_HIP_CHECK( hipFree( c->dMeanSum ) );
+            if( c->dMeanCount ) VRC_HIP_CHECK( hipFree( c->dMeanCount ) );
+            c->dMeanSum = nullptr;
+            c->dMeanCount = nullptr;
+            c->dMeanPixels = 0;
+            VRC_HIP_CHECK( hipMalloc( &c->dMeanSum, pixels * sizeof( unsigned long long ) ) );
+            VRC_HIP_CHECK( hipMalloc( &c->dMeanCount, pixels * sizeof( uint32_t ) ) );
+            c->dMeanPixels = pixels;
+            if( !c->mipFirst ) /* as above: no sample yet, which is a sum of 0 (integer and double alike) and a count of 0 */
+            {
+                VRC_HIP_CHECK( hipMemsetAsync( c->dMeanSum, 0, pixels * sizeof( unsigned long long ), c->stream ) );
+                VRC_HIP_CHECK( hipMemsetAsync( c->dMeanCount, 0, pixels * sizeof( uint32_t ), c->stream ) );
+            }
+        }
         f.mipMax = c->dMipMax;
         f.mipFirst = c->mipFirst ? 1u : 0u;
         f.slotMax = c->optMipSkip ? pool->dSlotMax : nullptr;
+        f.slotMin = c->optMipSkip ? pool->dSlotMin : nullptr;
+        f.meanSum = mean ? c->dMeanSum : nullptr;
+        f.meanCount = mean ? c->dMeanCount : nullptr;
         c->mipFirst = false;
+        c->frameFold = c->optMipFold;
+        /* what this pass leaves for vrc_get_projection_values */
+        c->projState.mipMax = c->dMipMax;
+        c->projState.meanSum = c->dMeanSum;
+        c->projState.meanCount = c->dMeanCount;
+        c->projState.pixels = (uint32_t)pixels;
+        c->projState.fold = (uint32_t)c->optMipFold;
+        c->projState.floatState = ( linear || pool->elemBytes == 4 ) ? 1u : 0u;
+        c->projState.shift = pool->rangeShift;
     }
     c->frameProjection = c->optProjection;
 
@@ -1777,7 +1839,9 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     vrc_internal_note_kernel_fn( nullptr, 0, 0 ); /* set again by the launchers that report their occupancy */
     if( c->optTiming )
         VRC_HIP_CHECK( hipEventRecord( evp.first, c->stream ) );
-    VRC_HIP_CHECK( mip         ? vrc_launch_raycast_mip( a, c->stream )
+    VRC_HIP_CHECK( mip         ? ( c->optMipFold == VRC_MIP_FOLD_MIN    ? vrc_launch_raycast_minip( a, c->stream )
+                                   : c->optMipFold == VRC_MIP_FOLD_MEAN ? vrc_launch_raycast_meanip( a, c->stream )
+                                                                        : vrc_launch_raycast_mip( a, c->stream ) )
                    : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
                    : c->rayLod ? vrc_launch_raycast_raylod( a, c->stream )
                                : vrc_launch_raycast( a, c->stream ) );
@@ -1831,6 +1895,36 @@ int vrc_post_render( vrc_ctx* c, float* hostRgba )
                                        hipMemcpyDeviceToHost, c->stream ) );
         VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
     }
+    return VRC_OK;
+}
+
+static_assert( VRC_MIP_FOLD_MAX == VRC_FOLD_MAX && VRC_MIP_FOLD_MIN == VRC_FOLD_MIN && VRC_MIP_FOLD_MEAN == VRC_FOLD_MEAN,
+               "the option's values are the march's folds" );
+
+int vrc_get_projection_values( vrc_ctx* c, float* hostValues, uint32_t* hostCounts )
+{
+    if( !c || !hostValues )
+        return fail( VRC_EINVAL, "vrc_get_projection_values: NULL argument" );
+    if( c->projState.pixels == 0u )
+        return fail( VRC_EINVAL, "vrc_get_projection_values: no VRC_OPT_PROJECTION = MIP vrc_render since the last "
+                                 "vrc_pre_render; the values exist from a frame's first MIP pass until the next frame" );
+    VRC_HIP_CHECK( hipSetDevice( c->device ) );
+    const size_t pixels = c->projState.pixels;
+    if( pixels > c->dProjOutPixels )
+    {
+        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+        if( c->dProjOut ) VRC_HIP_CHECK( hipFree( c->dProjOut ) );
+        c->dProjOut = nullptr;
+        c->dProjOutPixels = 0;
+        VRC_HIP_CHECK( hipMalloc( &c->dProjOut, pixels * ( sizeof( float ) + sizeof( uint32_t ) ) ) );
+        c->dProjOutPixels = pixels;
+    }
+    uint32_t* const dCounts = reinterpret_cast< uint32_t* >( c->dProjOut + pixels );
+    VRC_HIP_CHECK( vrc_launch_projection_values( c->projState, c->dProjOut, dCounts, c->stream ) );
+    VRC_HIP_CHECK( hipMemcpyAsync( hostValues, c->dProjOut, pixels * sizeof( float ), hipMemcpyDeviceToHost, c->stream ) );
+    if( hostCounts )
+        VRC_HIP_CHECK( hipMemcpyAsync( hostCounts, dCounts, pixels * sizeof( uint32_t ), hipMemcpyDeviceToHost, c->stream ) );
+    VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
     return VRC_OK;
 }
 

@@ -200,6 +200,15 @@ struct vrc_frame
     float lodInvCell[VRC_MAX_LOD_LEVELS][3];
     int32_t lodDim[VRC_MAX_LOD_LEVELS][3];
     uint32_t lodTable[VRC_MAX_LOD_LEVELS];
+    /* the other folds of a MIP frame (VRC_OPT_MIP_FOLD; at the end: no field above moves).  slotMin: one word per atlas
+     * slot holding the smallest value the slot's last upload stored, as a complemented key (vrc_slot_min_*; a part of
+     * slotInfo's allocation, same index, stream and fences), NULL = the minimum fold skips no brick.  meanSum /
+     * meanCount: the mean fold's running state per pixel of the pixel buffer, the context's as mipMax is -- the sum of
+     * the samples so far (point samples of the 8- and 16-bit atlases: an unsigned 64-bit integer of stored values;
+     * everything else: the bits of a double) and their number; a first pass (mipFirst) does not read them */
+    const uint32_t* slotMin;
+    unsigned long long* meanSum;
+    uint32_t* meanCount;
 };
 
 /* Atlas memory layout.  The logical atlas is the reference's 3-D array of slots
@@ -2017,6 +2026,23 @@ VRC_HD bool vrc_march_segment_packed( const vrc_frame& f, const vrc_dev_node& n,
 #define VRC_MODE_MIP_TRILINEAR 8 /* trilinear samples by gathers */
 #define VRC_MIP_EMPTY 0xFFFFFFFFu /* vrc_frame::mipMax: the pixel's rays have taken no sample (no integer voxel, and a NaN no float M can be) */
 
+/* The fold of a MIP frame (VRC_OPT_MIP_FOLD) rides in the march mode, above the four bits that say how samples are taken:
+ * the brick walks hand MODE through untouched.  Fold 0 -- the maximum -- leaves VRC_MODE_MIP and VRC_MODE_MIP_TRILINEAR
+ * the numbers, and their instances the code, they were before there was a choice.
+ *   minimum  the mirror of the maximum: identity (all ones / +infinity), comparison, skipping by the slot's smallest
+ *            stored value (vrc_frame::slotMin).
+ *   mean     the same march with an accumulate per sample: (sum, count) instead of M, see vrc_mean_state. */
+#define VRC_FOLD_MAX 0
+#define VRC_FOLD_MIN 1
+#define VRC_FOLD_MEAN 2
+#define VRC_MODE_WITH_FOLD( mode, fold ) ( ( mode ) + 16 * ( fold ) )
+VRC_HD constexpr int vrc_mode_base( int mode ) { return mode & 15; }
+VRC_HD constexpr int vrc_mode_fold( int mode ) { return mode >> 4; }
+VRC_HD constexpr bool vrc_mode_is_mip( int mode )
+{
+    return vrc_mode_base( mode ) == VRC_MODE_MIP || vrc_mode_base( mode ) == VRC_MODE_MIP_TRILINEAR;
+}
+
 VRC_HD uint32_t vrc_mip_max( uint32_t a, uint32_t b ) { return a > b ? a : b; }
 /* a: the maximum so far, never NaN (it starts at -infinity); b: a sample.  NOT fmaxf: a point sample of the float atlas
  * reaches this as the voxel's bits, and the maximum of a number and a SIGNALLING NaN is a NaN by IEEE 754-2008 maxNum --
@@ -2032,6 +2058,38 @@ VRC_HD void vrc_mip_from_bits( uint32_t b, float& m ) { m = vrc_bits_float( b );
 /* the value that changes no maximum: what M starts from, and what a step the march does not take contributes */
 VRC_HD void vrc_mip_identity( uint32_t& m ) { m = 0u; }
 VRC_HD void vrc_mip_identity( float& m ) { m = vrc_bits_float( 0xFF800000u ); }
+
+/* the same four for the minimum.  a: the minimum so far, never NaN (it starts at +infinity); the comparison form for the
+ * reason vrc_mip_max( float ) gives: v_min_f32 and fminf make a NaN of a number and a signalling NaN too */
+VRC_HD uint32_t vrc_mip_min( uint32_t a, uint32_t b ) { return a < b ? a : b; }
+VRC_HD float vrc_mip_min( float a, float b ) { return b < a ? b : a; }
+template < int FOLD, typename D >
+VRC_HD D vrc_mip_fold( D m, D a )
+{
+    if constexpr( FOLD == VRC_FOLD_MIN )
+        return vrc_mip_min( m, a );
+    else
+        return vrc_mip_max( m, a );
+}
+template < int FOLD, typename D >
+VRC_HD D vrc_mip_fold3( D m, D a, D b )
+{
+    if constexpr( FOLD == VRC_FOLD_MIN )
+        return vrc_mip_min( vrc_mip_min( m, a ), b ); /* integer voxels: v_min3_u32 */
+    else
+        return vrc_mip_max3( m, a, b );
+}
+/* (all ones is no voxel of an 8- or 16-bit atlas; a pixel's word holds it only as VRC_MIP_EMPTY, which means the same) */
+template < int FOLD >
+VRC_HD void vrc_mip_fold_identity( uint32_t& m )
+{
+    m = FOLD == VRC_FOLD_MIN ? 0xFFFFFFFFu : 0u;
+}
+template < int FOLD >
+VRC_HD void vrc_mip_fold_identity( float& m )
+{
+    m = vrc_bits_float( FOLD == VRC_FOLD_MIN ? 0x7F800000u : 0xFF800000u );
+}
 
 /* vrc_frame::slotMax words.  0 = nothing known (the slot is never skipped).  Integer atlases: largest stored value + 1.
  * Float atlas: the largest voxel that is not NaN (-infinity if all are) as a key that orders like the floats do when
@@ -2074,6 +2132,41 @@ VRC_HD bool vrc_mip_cannot_raise( uint32_t word, float m )
     return m >= top;
 }
 
+/* vrc_frame::slotMin words: the mirror, folded by the upload with the same atomicMax.  0 = nothing known.  Integer
+ * atlases: the complement of the smallest stored value (never 0: a voxel has 16 bits at most).  Float atlas:
+ * vrc_slot_max_key of the NEGATED voxel, NaN left out, the key of -infinity -- a minimum of +infinity -- for a brick
+ * whose voxels are all NaN. */
+VRC_HD uint32_t vrc_slot_min_key( uint32_t stored ) { return ~stored; }
+VRC_HD uint32_t vrc_slot_min_key( float v ) { return vrc_slot_max_key( -v ); }
+VRC_HD uint32_t vrc_slot_min_value( uint32_t word ) { return ~word; }
+VRC_HD float vrc_slot_min_float( uint32_t word ) { return -vrc_slot_max_float( word ); }
+/* can no sample of the slot lower M?  vrc_mip_cannot_raise read in a mirror.  Trilinear samples: the interpolation is
+ * made of a (1 - w) + b w, products and sums that round to nearest, and rounding to nearest is an odd function, so
+ * trilerp( -v ) = -trilerp( v ) bit for bit: the minimum of the samples of v is minus the maximum of the samples of -v,
+ * whose voxels lie below -min.  The bound proven for the maximum therefore reads: no sample lies below
+ * min - |min| * 1e-6, and M has to reach that. */
+template < bool TRILINEAR, typename ATLAS_T >
+VRC_HD bool vrc_mip_cannot_lower( uint32_t word, uint32_t m )
+{
+    static_assert( !TRILINEAR, "a trilinear M is a float" );
+    return m <= vrc_slot_min_value( word );
+}
+template < bool TRILINEAR, typename ATLAS_T >
+VRC_HD bool vrc_mip_cannot_lower( uint32_t word, float m )
+{
+    float bottom;
+    if constexpr( sizeof( ATLAS_T ) == 4 )
+        bottom = vrc_slot_min_float( word );
+    else
+        bottom = (float)vrc_slot_min_value( word );
+    if constexpr( TRILINEAR )
+    {
+        VRC_STRICT_FP
+        bottom = bottom - fabsf( bottom ) * 1e-6f;
+    }
+    return m <= bottom;
+}
+
 /* trips of the reference's `for( ; travel > 0; travel -= stepSize )` (travel > 0): in integers where that is exact
  * (vrc_exact_step_count), else by the float chain itself */
 VRC_HD uint32_t vrc_step_count( float travel, float stepSize )
@@ -2088,7 +2181,7 @@ VRC_HD uint32_t vrc_step_count( float travel, float stepSize )
 }
 
 /* point samples of one brick segment (travel > 0 or nothing is taken): vrc_march_segment_as without table, blend and exit */
-template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename D >
+template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename D, int FOLD = VRC_FOLD_MAX >
 VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
                                    const ATLAS_T* __restrict__ atlas, D& m, uint32_t& nSamples )
 {
@@ -2117,14 +2210,14 @@ VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, co
             d[k] = (D)vrc_gather( atlas, idx[k] );
 #pragma unroll
         for( int k = 0; k + 1 < GROUP; k += 2 )
-            m = vrc_mip_max3( m, d[k], d[k + 1] );
+            m = vrc_mip_fold3< FOLD >( m, d[k], d[k + 1] );
         if( GROUP & 1 )
-            m = vrc_mip_max( m, d[GROUP - 1] );
+            m = vrc_mip_fold< FOLD >( m, d[GROUP - 1] );
         nSamples += GROUP;
     }
     constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
     D none;
-    vrc_mip_identity( none );
+    vrc_mip_fold_identity< FOLD >( none );
     while( travel > 0.0f )
     {
         uint32_t idx[TAILG], cnt = 0;
@@ -2146,20 +2239,21 @@ VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, co
             d[k] = (D)vrc_gather( atlas, idx[k] );
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
-            m = vrc_mip_max( m, (uint32_t)k < cnt ? d[k] : none );
+            m = vrc_mip_fold< FOLD >( m, (uint32_t)k < cnt ? d[k] : none );
         nSamples += cnt;
     }
 }
 
 /* trilinear samples of one brick segment: vrc_march_segment_linear without classification, blend and exit */
-template < bool CLAMP, typename ATLAS_T >
+template < bool CLAMP, typename ATLAS_T, int FOLD = VRC_FOLD_MAX >
 VRC_HD void vrc_mip_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
                                        const ATLAS_T* __restrict__ atlas, float& m, uint32_t& nSamples )
 {
     const float stepSize = f.stepSize;
     const vrc_sampler sm = vrc_make_sampler( n, f );
     vrc_f3 pos = s.pos;
-    const float none = vrc_bits_float( 0xFF800000u );
+    float none;
+    vrc_mip_fold_identity< FOLD >( none );
     while( travel > 0.0f )
     {
         bool valid[VRC_LGROUP];
@@ -2197,10 +2291,261 @@ VRC_HD void vrc_mip_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n
         }
 #pragma unroll
         for( int k = 0; k + 1 < VRC_LGROUP; k += 2 )
-            m = vrc_mip_max3( m, d[k], d[k + 1] );
+            m = vrc_mip_fold3< FOLD >( m, d[k], d[k + 1] );
         if( VRC_LGROUP & 1 )
-            m = vrc_mip_max( m, d[VRC_LGROUP - 1] );
+            m = vrc_mip_fold< FOLD >( m, d[VRC_LGROUP - 1] );
     }
+}
+
+/* ---- the mean fold (VRC_FOLD_MEAN) ------------------------------------------------------------------------------------
+ * The two marches above once more, control structure and all -- groups, guard, travel chain, tails: positions and
+ * counts stay the composite's -- with an accumulate where the maximum was.  The sum of a ray is
+ *   an unsigned 64-bit integer  for point samples of the 8- and 16-bit atlases: the stored values add exactly.  A group
+ *     is summed in 32 bits, two samples per three-operand add (v_add3_u32; a group of 16-bit voxels stays far below
+ *     2^32), and carried into the 64 once;
+ *   a double  for the float atlas and every trilinear sample: one add per sample (full rate on this hardware), each
+ *     float sample exact in it.  NaN and infinities go through the adds by IEEE rules.
+ * A step the tail does not take contributes 0 and no count.  The ray's sample count is its nSamples. */
+template < typename ACC >
+VRC_HD uint32_t vrc_mean_bits_lo( ACC sum )
+{
+    unsigned long long b;
+    memcpy( &b, &sum, 8 );
+    return (uint32_t)b;
+}
+template < typename ACC >
+VRC_HD uint32_t vrc_mean_bits_hi( ACC sum )
+{
+    unsigned long long b;
+    memcpy( &b, &sum, 8 );
+    return (uint32_t)( b >> 32 );
+}
+template < typename ACC >
+VRC_HD ACC vrc_mean_from_bits( uint32_t lo, uint32_t hi )
+{
+    const unsigned long long b = ( (unsigned long long)hi << 32 ) | lo;
+    ACC sum;
+    memcpy( &sum, &b, 8 );
+    return sum;
+}
+
+template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename ACC >
+VRC_HD void vrc_mean_segment_point( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
+                                    const ATLAS_T* __restrict__ atlas, ACC& sum, uint32_t& nSamples )
+{
+    constexpr bool INTEGER = sizeof( ATLAS_T ) <= 2;
+    const float stepSize = f.stepSize;
+    const vrc_sampler sm = vrc_make_sampler( n, f );
+    vrc_f3 pos = s.pos;
+    if( !( travel > 0.0f ) )
+        return;
+    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
+    if( FIXED )
+        fp = vrc_fixpos_init( sm, pos, s.step );
+    const float guard = stepSize * (float)( GROUP + 1 );
+    while( travel > guard )
+    {
+        uint32_t idx[GROUP];
+        if( FIXED )
+            vrc_group_indices_fixed< GROUP >( sm, fp, idx );
+        else
+            vrc_group_indices< CLAMP, GROUP >( sm, pos, s.step, idx );
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            travel -= stepSize; /* same sequential subtraction as the reference */
+        if constexpr( INTEGER )
+        {
+            uint32_t d[GROUP], g = 0u;
+#pragma unroll
+            for( int k = 0; k < GROUP; ++k )
+                d[k] = (uint32_t)vrc_gather( atlas, idx[k] );
+#pragma unroll
+            for( int k = 0; k + 1 < GROUP; k += 2 )
+                g = g + d[k] + d[k + 1];
+            if( GROUP & 1 )
+                g += d[GROUP - 1];
+            sum += (ACC)g;
+        }
+        else
+        {
+            float d[GROUP];
+#pragma unroll
+            for( int k = 0; k < GROUP; ++k )
+                d[k] = (float)vrc_gather( atlas, idx[k] );
+#pragma unroll
+            for( int k = 0; k < GROUP; ++k )
+                sum += (ACC)d[k];
+        }
+        nSamples += GROUP;
+    }
+    constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
+    while( travel > 0.0f )
+    {
+        uint32_t idx[TAILG], cnt = 0;
+        if( FIXED )
+            vrc_group_indices_fixed< TAILG >( sm, fp, idx );
+        else
+            vrc_group_indices< CLAMP, TAILG >( sm, pos, s.step, idx );
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+        {
+            const bool v = travel > 0.0f;
+            cnt += v ? 1u : 0u;
+            idx[k] = v ? idx[k] : 0u; /* a step the reference does not take reads element 0 and contributes nothing */
+            travel -= stepSize;
+        }
+        if constexpr( INTEGER )
+        {
+            uint32_t d[TAILG], g = 0u;
+#pragma unroll
+            for( int k = 0; k < TAILG; ++k )
+                d[k] = (uint32_t)vrc_gather( atlas, idx[k] );
+#pragma unroll
+            for( int k = 0; k < TAILG; ++k )
+                g += (uint32_t)k < cnt ? d[k] : 0u;
+            sum += (ACC)g;
+        }
+        else
+        {
+            float d[TAILG];
+#pragma unroll
+            for( int k = 0; k < TAILG; ++k )
+                d[k] = (float)vrc_gather( atlas, idx[k] );
+#pragma unroll
+            for( int k = 0; k < TAILG; ++k )
+                if( (uint32_t)k < cnt )
+                    sum += (ACC)d[k];
+        }
+        nSamples += cnt;
+    }
+}
+
+template < bool CLAMP, typename ATLAS_T >
+VRC_HD void vrc_mean_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
+                                        const ATLAS_T* __restrict__ atlas, double& sum, uint32_t& nSamples )
+{
+    const float stepSize = f.stepSize;
+    const vrc_sampler sm = vrc_make_sampler( n, f );
+    vrc_f3 pos = s.pos;
+    while( travel > 0.0f )
+    {
+        bool valid[VRC_LGROUP];
+        vrc_taps t[VRC_LGROUP];
+#pragma unroll
+        for( int k = 0; k < VRC_LGROUP; ++k )
+        {
+            VRC_FAST_FP
+            valid[k] = travel > 0.0f;
+            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
+            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
+            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
+            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
+            pos.x += s.step.x;
+            pos.y += s.step.y;
+            pos.z += s.step.z;
+            travel -= stepSize;
+        }
+        float v[VRC_LGROUP][8];
+#pragma unroll
+        for( int k = 0; k < VRC_LGROUP; ++k )
+#pragma unroll
+            for( int c = 0; c < 8; ++c )
+            {
+                const uint32_t e = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
+                v[k][c] = (float)vrc_gather( atlas, valid[k] ? e : 0u );
+            }
+#pragma unroll
+        for( int k = 0; k < VRC_LGROUP; ++k )
+        {
+            const float d = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
+            if( valid[k] )
+                sum += (double)d;
+            nSamples += valid[k] ? 1u : 0u;
+        }
+    }
+}
+
+/* the mean of a pixel's state, less the shift of an offset-binary atlas: the quotient in double, rounded to float once */
+template < bool INTEGER >
+VRC_HD float vrc_mean_value( uint32_t lo, uint32_t hi, uint32_t count, double shift )
+{
+    double sum;
+    if constexpr( INTEGER )
+        sum = (double)vrc_mean_from_bits< unsigned long long >( lo, hi );
+    else
+        sum = vrc_mean_from_bits< double >( lo, hi );
+    return (float)( sum / (double)count - shift );
+}
+
+/* What vrc_get_projection_values returns for one pixel of the state a MIP frame's passes left: M in the volume's own
+ * units and the pixel's count (the mean's samples; 1 or 0 for a maximum or minimum that exists or not).  floatState: M
+ * is a float / the sum a double (the float atlas, trilinear samples), else integers; shift: what an offset-binary atlas
+ * added to every voxel (exact in float, as an integer M is; a float M of such an atlas is a trilinear sample). */
+VRC_HD void vrc_projection_value( uint32_t fold, bool floatState, float shift, uint32_t mipBits, unsigned long long meanSum,
+                                  uint32_t meanCount, float& value, uint32_t& count )
+{
+    value = 0.0f;
+    count = 0u;
+    if( fold == VRC_FOLD_MEAN )
+    {
+        count = meanCount;
+        if( count != 0u )
+            value = floatState ? vrc_mean_value< false >( (uint32_t)meanSum, (uint32_t)( meanSum >> 32 ), count, (double)shift )
+                               : vrc_mean_value< true >( (uint32_t)meanSum, (uint32_t)( meanSum >> 32 ), count, (double)shift );
+    }
+    else if( mipBits != VRC_MIP_EMPTY )
+    {
+        count = 1u;
+        value = floatState ? (float)( (double)vrc_bits_float( mipBits ) - (double)shift ) : (float)mipBits - shift;
+    }
+}
+
+/* One brick of one ray, mean fold.  The state: x, y = the low and high word of the sum, w = 0.  There is nothing to skip
+ * by; uniform bricks (point samples of the 8- and 16-bit atlases) add value x step count, which is what the march
+ * would have summed, exactly. */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, typename ATLAS_T, int GROUP, bool BIG >
+VRC_HD void vrc_mean_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s,
+                            const ATLAS_T* __restrict__ atlas, vrc_f4& state, uint32_t& nSamples )
+{
+    constexpr bool INTEGER = !TRILINEAR && sizeof( ATLAS_T ) <= 2;
+    typedef typename std::conditional< INTEGER, unsigned long long, double >::type ACC;
+    ACC sum = vrc_mean_from_bits< ACC >( vrc_float_bits( state.x ), vrc_float_bits( state.y ) );
+    bool march = s.dist > 0.0f;
+    if constexpr( INTEGER )
+    {
+        if( march && n.slotInfoIndex != 0u && f.slotInfo != nullptr )
+        {
+            const uint32_t word = f.slotInfo[n.slotInfoIndex - 1u];
+            if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) == VRC_SLOT_KNOWN )
+            {
+                const uint32_t steps = vrc_step_count( s.dist, f.stepSize );
+                sum += (ACC)( word & VRC_SLOT_VALUE_MASK ) * (ACC)steps;
+                nSamples += steps;
+                march = false;
+            }
+        }
+    }
+    bool any = march;
+#if defined( __HIP_DEVICE_COMPILE__ )
+    any = __builtin_amdgcn_ballot_w64( march ) != 0ull;
+#endif
+    if( any )
+    {
+        const float travel = march ? s.dist : 0.0f;
+        vrc_dev_node local = n;
+        const ATLAS_T* slot = atlas;
+        if( BIG )
+        {
+            local.slotBase = 0u;
+            slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
+        }
+        if constexpr( TRILINEAR )
+            vrc_mean_segment_trilinear< CLAMP, ATLAS_T >( f, local, s, travel, slot, sum, nSamples );
+        else
+            vrc_mean_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, ACC >( f, local, s, travel, slot, sum, nSamples );
+    }
+    state.x = vrc_bits_float( vrc_mean_bits_lo( sum ) );
+    state.y = vrc_bits_float( vrc_mean_bits_hi( sum ) );
 }
 
 /* One brick of one ray.  The ray's state travels in the colour the brick walks hand on: x = the bits of M, y != 0 once
@@ -2214,7 +2559,13 @@ template < bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, int GROUP, bool B
 VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s,
                            const ATLAS_T* __restrict__ atlas, vrc_f4& state, uint32_t& nSamples )
 {
-    constexpr bool TRILINEAR = MODE == VRC_MODE_MIP_TRILINEAR;
+    constexpr bool TRILINEAR = vrc_mode_base( MODE ) == VRC_MODE_MIP_TRILINEAR;
+    constexpr int FOLD = vrc_mode_fold( MODE );
+    if constexpr( FOLD == VRC_FOLD_MEAN )
+    {
+        vrc_mean_brick< CLAMP, FIXED, TRILINEAR, ATLAS_T, GROUP, BIG >( f, n, s, atlas, state, nSamples );
+        return;
+    }
     typedef typename vrc_density< ATLAS_T >::type P;
     typedef typename std::conditional< TRILINEAR, float, P >::type D;
     D m;
@@ -2223,7 +2574,16 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
     bool march = s.dist > 0.0f;
     if( march && n.slotInfoIndex != 0u )
     {
-        if( f.slotMax != nullptr && has )
+        if constexpr( FOLD == VRC_FOLD_MIN )
+        {
+            if( f.slotMin != nullptr && has )
+            {
+                const uint32_t word = f.slotMin[n.slotInfoIndex - 1u];
+                if( word != 0u && vrc_mip_cannot_lower< TRILINEAR, ATLAS_T >( word, m ) )
+                    march = false;
+            }
+        }
+        else if( f.slotMax != nullptr && has )
         {
             const uint32_t word = f.slotMax[n.slotInfoIndex - 1u];
             if( word != 0u && vrc_mip_cannot_raise< TRILINEAR, ATLAS_T >( word, m ) )
@@ -2236,7 +2596,7 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
                 const uint32_t word = f.slotInfo[n.slotInfoIndex - 1u];
                 if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) == VRC_SLOT_KNOWN )
                 {
-                    m = vrc_mip_max( m, (D)( word & VRC_SLOT_VALUE_MASK ) );
+                    m = vrc_mip_fold< FOLD >( m, (D)( word & VRC_SLOT_VALUE_MASK ) );
                     has = true;
                     nSamples += vrc_step_count( s.dist, f.stepSize );
                     march = false;
@@ -2260,9 +2620,9 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
             slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
         }
         if constexpr( TRILINEAR )
-            vrc_mip_segment_trilinear< CLAMP, ATLAS_T >( f, local, s, travel, slot, m, nSamples );
+            vrc_mip_segment_trilinear< CLAMP, ATLAS_T, FOLD >( f, local, s, travel, slot, m, nSamples );
         else
-            vrc_mip_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, D >( f, local, s, travel, slot, m, nSamples );
+            vrc_mip_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, D, FOLD >( f, local, s, travel, slot, m, nSamples );
         has = has || march;
     }
     state.x = vrc_bits_float( vrc_mip_bits( m ) );
@@ -2721,7 +3081,7 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                     if( sp != part )
                         return; /* another part's brick */
                 }
-                if constexpr( MODE == VRC_MODE_MIP || MODE == VRC_MODE_MIP_TRILINEAR )
+                if constexpr( vrc_mode_is_mip( MODE ) )
                     vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, color, nSamples ); /* (color: the ray's MIP state) */
                 else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, lut, cls, color,
                                                                                   nSamples ) )
@@ -3041,6 +3401,9 @@ VRC_HD void vrc_pixel_ray_lod( const vrc_frame& f, const vrc_dev_node* __restric
  * definition), one classification at the end.  tfp: the padded transfer function in global memory, read twice per
  * ray.  Passes of one frame meet in vrc_frame::mipMax: the first pass writes it, later ones start from it, and after
  * every pass the pixel is that of the maximum so far.  A ray without samples leaves its pixel cleared.
+ * The other folds (vrc_mode_fold( MODE )): the minimum meets in mipMax too, starting from the other end; the mean meets
+ * in vrc_frame::meanSum / meanCount, and its pixel is the classification of sum / count -- the quotient formed in
+ * double and rounded to float once, of the stored values: the classifier carries an offset-binary atlas's shift.
  * ---------------------------------------------------------------------------------------- */
 template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, int GROUP = VRC_GROUP, bool BIG = false >
 VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ nodes,
@@ -3049,23 +3412,44 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
                            vrc_f4* __restrict__ pixelBuffer, uint32_t px, uint32_t py, uint32_t& nSamples,
                            const uint16_t* candidates = nullptr, uint32_t nCandidates = 0 )
 {
-    static_assert( MODE == VRC_MODE_MIP || MODE == VRC_MODE_MIP_TRILINEAR, "a MIP mode" );
+    static_assert( vrc_mode_is_mip( MODE ), "a MIP mode" );
+    constexpr int FOLD = vrc_mode_fold( MODE );
+    constexpr bool FLOAT_M = vrc_mode_base( MODE ) == VRC_MODE_MIP_TRILINEAR || sizeof( ATLAS_T ) == 4;
     const vrc_ray r = vrc_setup_ray( f, px, f.rowMap ? f.rowMap[py] : py );
     const uint32_t pixelPos = py * f.width + px;
     const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
     uint32_t bits = VRC_MIP_EMPTY;
+    uint32_t meanLo = 0u, meanHi = 0u, meanCount = 0u; /* (the mean fold's state; an integer 0 and a double 0 alike) */
     if( r.hit )
     {
-        if( !f.mipFirst )
-            bits = f.mipMax[pixelPos];
         vrc_f4 state = zero;
-        if( bits != VRC_MIP_EMPTY )
+        const uint32_t before = nSamples;
+        if constexpr( FOLD == VRC_FOLD_MEAN )
         {
-            state.x = vrc_bits_float( bits );
-            state.y = 1.0f;
+            if( !f.mipFirst )
+            {
+                const unsigned long long b = f.meanSum[pixelPos];
+                meanLo = (uint32_t)b;
+                meanHi = (uint32_t)( b >> 32 );
+                meanCount = f.meanCount[pixelPos];
+            }
+            state.x = vrc_bits_float( meanLo );
+            state.y = vrc_bits_float( meanHi );
         }
-        else if( MODE == VRC_MODE_MIP_TRILINEAR || sizeof( ATLAS_T ) == 4 )
-            state.x = vrc_bits_float( 0xFF800000u ); /* a float M starts at -infinity */
+        else
+        {
+            if( !f.mipFirst )
+                bits = f.mipMax[pixelPos];
+            if( bits != VRC_MIP_EMPTY )
+            {
+                state.x = vrc_bits_float( bits );
+                state.y = 1.0f;
+            }
+            else if( FOLD == VRC_FOLD_MIN )
+                state.x = vrc_bits_float( FLOAT_M ? 0x7F800000u : 0xFFFFFFFFu ); /* +infinity, or above every voxel */
+            else if( FLOAT_M )
+                state.x = vrc_bits_float( 0xFF800000u ); /* a float M starts at -infinity */
+        }
         if constexpr( DDA )
             vrc_ray_grid_dda< CLAMP, true, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, r, nodes, gridTable, atlas, tfp, cls, state,
                                                                              nSamples );
@@ -3088,20 +3472,39 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
                 vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, state, nSamples );
             }
         }
-        bits = state.y != 0.0f ? vrc_float_bits( state.x ) : VRC_MIP_EMPTY;
-    }
-    f.mipMax[pixelPos] = bits;
-    if( bits != VRC_MIP_EMPTY )
-    {
-        float d;
-        if constexpr( MODE == VRC_MODE_MIP && sizeof( ATLAS_T ) != 4 )
-            d = (float)bits;
+        if constexpr( FOLD == VRC_FOLD_MEAN )
+        {
+            meanLo = vrc_float_bits( state.x );
+            meanHi = vrc_float_bits( state.y );
+            meanCount += nSamples - before;
+        }
         else
-            d = vrc_bits_float( bits );
-        pixelBuffer[pixelPos] = vrc_classify_mip( tfp, d, cls );
+            bits = state.y != 0.0f ? vrc_float_bits( state.x ) : VRC_MIP_EMPTY;
     }
-    else if( f.clearFirst )
-        pixelBuffer[pixelPos] = zero;
+    if constexpr( FOLD == VRC_FOLD_MEAN )
+    {
+        f.meanSum[pixelPos] = ( (unsigned long long)meanHi << 32 ) | meanLo;
+        f.meanCount[pixelPos] = meanCount;
+        if( meanCount != 0u )
+            pixelBuffer[pixelPos] = vrc_classify_mip( tfp, vrc_mean_value< !FLOAT_M >( meanLo, meanHi, meanCount, 0.0 ), cls );
+        else if( f.clearFirst )
+            pixelBuffer[pixelPos] = zero;
+    }
+    else
+    {
+        f.mipMax[pixelPos] = bits;
+        if( bits != VRC_MIP_EMPTY )
+        {
+            float d;
+            if constexpr( !FLOAT_M )
+                d = (float)bits;
+            else
+                d = vrc_bits_float( bits );
+            pixelBuffer[pixelPos] = vrc_classify_mip( tfp, d, cls );
+        }
+        else if( f.clearFirst )
+            pixelBuffer[pixelPos] = zero;
+    }
 }
 
 #endif /* VRC_CORE_H */

@@ -73,11 +73,13 @@ hipError_t vrc_launch_build_lut( const float* tf, vrc_f4* lut, vrc_lut_params p,
  * slotInfo (may be NULL): the slot's uniformity word (vrc_core.h: VRC_SLOT_*), which the caller zeroed on `stream`
  * before this call; the kernel ORs into it what it finds.
  * slotMax (may be NULL): the slot's largest stored value (vrc_core.h: vrc_frame::slotMax), zeroed by the caller in the
- * same way; the kernel leaves the word of the voxels it wrote (padding copies repeat voxels of the brick). */
+ * same way; the kernel leaves the word of the voxels it wrote (padding copies repeat voxels of the brick).
+ * slotMin (may be NULL): the same for the slot's smallest stored value (vrc_frame::slotMin). */
 hipError_t vrc_launch_repack_brick( const void* srcRowMajor, void* slot, uint32_t elemBytes,
                                     const uint32_t size[3], const uint32_t slotDim[3],
                                     hipStream_t stream, uint32_t* slotInfo = nullptr,
-                                    uint32_t xform = VRC_XF_NONE, uint32_t* slotMax = nullptr );
+                                    uint32_t xform = VRC_XF_NONE, uint32_t* slotMax = nullptr,
+                                    uint32_t* slotMin = nullptr );
 
 /* atlas -> tap-packed atlas (vrc_core.h): the packed texels of elements [firstElem, firstElem + nElems) of the atlas of
  * 8- or 16-bit voxels (whole slots; the packed atlas holds vrc_packed_elems( atlas elements ) texels of
@@ -159,6 +161,25 @@ hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream );
 /* maximum-intensity projection (vrc_kernels_mip.hip): point or trilinear (a.linear) samples by gathers, reference-order
  * loop or grid walk (a.gridDda); lut = the padded transfer function; frame.mipMax set */
 hipError_t vrc_launch_raycast_mip( const vrc_raycast_args& a, hipStream_t stream );
+/* ... and its other folds (VRC_OPT_MIP_FOLD; vrc_kernels_minip.hip, vrc_kernels_meanip.hip): the minimum meets in
+ * frame.mipMax as the maximum does and skips by frame.slotMin; the mean needs frame.meanSum and frame.meanCount */
+hipError_t vrc_launch_raycast_minip( const vrc_raycast_args& a, hipStream_t stream );
+hipError_t vrc_launch_raycast_meanip( const vrc_raycast_args& a, hipStream_t stream );
+
+/* the per-pixel state a MIP frame's passes left, as vrc_get_projection_values returns it (vrc_kernels_meanip.hip):
+ * values[i] = M of pixel i in the volume's own units (shift: what an offset-binary atlas added to every voxel), counts[i]
+ * = the mean's sample count, or whether a maximum / minimum exists.  Device pointers, `pixels` entries each */
+struct vrc_projection_state
+{
+    const uint32_t* mipMax;            /* maximum and minimum */
+    const unsigned long long* meanSum; /* mean */
+    const uint32_t* meanCount;
+    uint32_t pixels;
+    uint32_t fold;       /* VRC_FOLD_* */
+    uint32_t floatState; /* M is a float / the sum a double (the float atlas, trilinear samples); else integers */
+    float shift;
+};
+hipError_t vrc_launch_projection_values( const vrc_projection_state& st, float* values, uint32_t* counts, hipStream_t stream );
 
 /* LDS-staged form (vrc_kernels_lds.hip): needs gridTable, !clamp, 8x8 tiles */
 hipError_t vrc_launch_raycast_lds( const vrc_raycast_args& a, hipStream_t stream );

@@ -106,6 +106,37 @@ __device__ inline void vrc_leave_slot_max( uint32_t* __restrict__ max, uint32_t 
     if( ( threadIdx.x & 63u ) == 0u && key != 0u )
         atomicMax( max, key );
 }
+/* The slot's smallest stored value (vrc_frame::slotMin, what the minimum fold of a MIP frame skips bricks by), beside
+ * the largest and in the same way: the key is complemented (vrc_slot_min_key), so the smallest voxel has the largest key
+ * and the same atomicMax folds it, 0 still means "nothing known"; a float brick's first thread also leaves the key of
+ * +infinity, the word of a brick whose voxels are all NaN. */
+template < typename T >
+__device__ inline uint32_t vrc_voxel_min_key( T stored )
+{
+    if constexpr( sizeof( T ) == 4 )
+    {
+        const float v = vrc_bits_float( (uint32_t)stored );
+        return v != v ? 0u : vrc_slot_min_key( v );
+    }
+    else
+        return vrc_slot_min_key( (uint32_t)stored );
+}
+template < typename T >
+__device__ inline void vrc_leave_slot_min( uint32_t* __restrict__ min, uint32_t key )
+{
+    if( min == nullptr )
+        return;
+    if( sizeof( T ) == 4 && blockIdx.x == 0u && threadIdx.x == 0u )
+        key = key > vrc_slot_min_key( vrc_bits_float( 0x7F800000u ) ) ? key : vrc_slot_min_key( vrc_bits_float( 0x7F800000u ) );
+#pragma unroll
+    for( int off = 32; off > 0; off >>= 1 )
+    {
+        const uint32_t o = (uint32_t)__shfl_xor( (int)key, off, 64 );
+        key = key > o ? key : o;
+    }
+    if( ( threadIdx.x & 63u ) == 0u && key != 0u )
+        atomicMax( min, key );
+}
 /* 16-bit voxels: the uniformity word as vrc_k_repack_u8x8 leaves it (first = the brick's first stored voxel) */
 template < typename T >
 __device__ inline void vrc_leave_slot_info( uint32_t* __restrict__ info, bool mixed, uint32_t first )
@@ -129,13 +160,15 @@ __device__ inline void vrc_leave_slot_info( uint32_t* __restrict__ info, bool mi
 template < bool FLIP >
 __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __restrict__ slot,
                                    uint32_t sx8, uint32_t sy, uint32_t sz, uint32_t sbx,
-                                   uint32_t sby, uint32_t* __restrict__ info, uint32_t* __restrict__ max )
+                                   uint32_t sby, uint32_t* __restrict__ info, uint32_t* __restrict__ max,
+                                   uint32_t* __restrict__ min )
 {
     const uint32_t total = sx8 * sy * sz;
     constexpr uint32_t flip = FLIP ? 0x80808080u : 0u;
     const uint32_t first = ( src[0].x ^ flip ) & 0xFFu, all = first * 0x01010101u;
     bool mixed = false;
     uint32_t top = 0u; /* largest byte this thread moved, + 1 */
+    uint32_t low = 0x101u; /* smallest byte this thread moved, + 1 (0x101: none) */
     for( uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += gridDim.x * blockDim.x )
     {
@@ -154,9 +187,12 @@ __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __res
             const uint32_t lo = ( ( v.x >> b ) & 0xFFu ) + 1u, hi = ( ( v.y >> b ) & 0xFFu ) + 1u;
             top = top > lo ? top : lo;
             top = top > hi ? top : hi;
+            low = low < lo ? low : lo;
+            low = low < hi ? low : hi;
         }
     }
     vrc_leave_slot_max< uint8_t >( max, top );
+    vrc_leave_slot_min< uint8_t >( min, low != 0x101u ? vrc_slot_min_key( low - 1u ) : 0u );
     if( info != nullptr )
     {
         if( __builtin_amdgcn_ballot_w64( mixed ) != 0ull && ( threadIdx.x & 63u ) == 0u )
@@ -170,12 +206,13 @@ __global__ void vrc_k_repack_u8x8( const uint2* __restrict__ src, uint8_t* __res
 template < typename T, int XF = VRC_XF_NONE >
 __global__ void vrc_k_repack_generic( const T* __restrict__ src, T* __restrict__ slot,
                                       uint32_t sx, uint32_t sy, uint32_t sz, uint32_t sbx,
-                                      uint32_t sby, uint32_t* __restrict__ info, uint32_t* __restrict__ max )
+                                      uint32_t sby, uint32_t* __restrict__ info, uint32_t* __restrict__ max,
+                                      uint32_t* __restrict__ min )
 {
     const size_t total = (size_t)sx * sy * sz;
     const T first = vrc_voxel_xform< XF, T >( src[0] );
     bool mixed = false;
-    uint32_t top = 0u;
+    uint32_t top = 0u, low = 0u; /* keys: the largest voxel's, and the smallest's */
     for( size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (size_t)gridDim.x * blockDim.x )
     {
@@ -185,10 +222,12 @@ __global__ void vrc_k_repack_generic( const T* __restrict__ src, T* __restrict__
         const T v = vrc_voxel_xform< XF, T >( src[i] );
         slot[vrc_slot_local_index( x, y, z, sbx, sby )] = v;
         mixed = mixed || v != first;
-        const uint32_t key = vrc_voxel_max_key< T >( v );
+        const uint32_t key = vrc_voxel_max_key< T >( v ), keyMin = vrc_voxel_min_key< T >( v );
         top = top > key ? top : key;
+        low = low > keyMin ? low : keyMin;
     }
     vrc_leave_slot_max< T >( max, top );
+    vrc_leave_slot_min< T >( min, low );
     vrc_leave_slot_info< T >( info, mixed, (uint32_t)first );
 }
 
@@ -199,13 +238,14 @@ __global__ void vrc_k_repack_generic( const T* __restrict__ src, T* __restrict__
 template < typename T, int XF = VRC_XF_NONE >
 __global__ void vrc_k_repack_padded( const T* __restrict__ src, T* __restrict__ slot, uint32_t sx,
                                      uint32_t sy, uint32_t sz, uint32_t dx, uint32_t dy,
-                                     uint32_t dz, uint32_t* __restrict__ info, uint32_t* __restrict__ max )
+                                     uint32_t dz, uint32_t* __restrict__ info, uint32_t* __restrict__ max,
+                                     uint32_t* __restrict__ min )
 {
     const size_t total = (size_t)dx * dy * dz;
     const uint32_t sbx = dx >> VRC_MB_SHIFT, sby = dy >> VRC_MB_SHIFT;
     const T first = vrc_voxel_xform< XF, T >( src[0] );
     bool mixed = false;
-    uint32_t top = 0u;
+    uint32_t top = 0u, low = 0u; /* keys: the largest voxel's, and the smallest's */
     for( size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (size_t)gridDim.x * blockDim.x )
     {
@@ -216,10 +256,12 @@ __global__ void vrc_k_repack_padded( const T* __restrict__ src, T* __restrict__ 
         const T v = vrc_voxel_xform< XF, T >( src[( (size_t)cz * sy + cy ) * sx + cx] );
         slot[vrc_slot_local_index( x, y, z, sbx, sby )] = v;
         mixed = mixed || v != first;
-        const uint32_t key = vrc_voxel_max_key< T >( v );
+        const uint32_t key = vrc_voxel_max_key< T >( v ), keyMin = vrc_voxel_min_key< T >( v );
         top = top > key ? top : key;
+        low = low > keyMin ? low : keyMin;
     }
     vrc_leave_slot_max< T >( max, top );
+    vrc_leave_slot_min< T >( min, low );
     vrc_leave_slot_info< T >( info, mixed, (uint32_t)first );
 }
 
@@ -448,12 +490,13 @@ static uint32_t grid_for( size_t total, uint32_t block )
 
 hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBytes,
                                     const uint32_t size[3], const uint32_t slotDim[3],
-                                    hipStream_t stream, uint32_t* slotInfo, uint32_t xform, uint32_t* slotMax )
+                                    hipStream_t stream, uint32_t* slotInfo, uint32_t xform, uint32_t* slotMax,
+                                    uint32_t* slotMin )
 {
     /* slotInfo: of 1-byte voxels only the kernel that fills a whole slot tests for a uniform brick; after the others
      * the (zeroed) word says "nothing known" and the brick takes the general march.  Bricks of 2-byte voxels are
      * tested by the kernels that move them (the MIP march reads their word; the composite march does not).
-     * slotMax: left by every kernel */
+     * slotMax, slotMin: left by every kernel */
     const size_t total = (size_t)size[0] * size[1] * size[2];
     if( total == 0 )
         return hipSuccess;
@@ -468,7 +511,7 @@ hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBy
         const dim3 g( grid_for( all, 256 ) ), b( 256 );
 #define VRC_PADDED( T, XF )                                                                                       \
     hipLaunchKernelGGL( ( vrc_k_repack_padded< T, XF > ), g, b, 0, stream, (const T*)src, (T*)slot, size[0], size[1], \
-                        size[2], slotDim[0], slotDim[1], slotDim[2], slotInfo, slotMax )
+                        size[2], slotDim[0], slotDim[1], slotDim[2], slotInfo, slotMax, slotMin )
         if( elemBytes == 1 && xform == VRC_XF_FLIP )
             VRC_PADDED( uint8_t, VRC_XF_FLIP );
         else if( elemBytes == 1 )
@@ -490,7 +533,7 @@ hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBy
     }
 #define VRC_GENERIC( T, XF )                                                                                          \
     hipLaunchKernelGGL( ( vrc_k_repack_generic< T, XF > ), dim3( grid_for( total, 256 ) ), dim3( 256 ), 0, stream,     \
-                        (const T*)src, (T*)slot, size[0], size[1], size[2], sbx, sby, slotInfo, slotMax )
+                        (const T*)src, (T*)slot, size[0], size[1], size[2], sbx, sby, slotInfo, slotMax, slotMin )
     /* (the experimental layout 5 has no 8-voxel runs along x: generic kernel) */
     if( VRC_LAYOUT != 5 && elemBytes == 1 && ( size[0] % 8u ) == 0 && ( ( (uintptr_t)src ) % 8u ) == 0 &&
         ( ( (uintptr_t)slot ) % 8u ) == 0 && total / 8 < 0xFFFFFFFFull )
@@ -499,11 +542,11 @@ hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBy
         if( xform == VRC_XF_FLIP )
             hipLaunchKernelGGL( vrc_k_repack_u8x8< true >, dim3( grid_for( total / 8, 256 ) ), dim3( 256 ), 0,
                                 stream, (const uint2*)src, (uint8_t*)slot, sx8, size[1], size[2], sbx,
-                                sby, slotInfo, slotMax );
+                                sby, slotInfo, slotMax, slotMin );
         else
             hipLaunchKernelGGL( vrc_k_repack_u8x8< false >, dim3( grid_for( total / 8, 256 ) ), dim3( 256 ), 0,
                                 stream, (const uint2*)src, (uint8_t*)slot, sx8, size[1], size[2], sbx,
-                                sby, slotInfo, slotMax );
+                                sby, slotInfo, slotMax, slotMin );
     }
     else if( elemBytes == 1 && xform == VRC_XF_FLIP )
         VRC_GENERIC( uint8_t, VRC_XF_FLIP );

@@ -1,0 +1,196 @@
+/*
+ * vrc_kernels_mip.h -- the kernel of a MIP frame and its launchers, as templates: included by the translation unit of
+ * every fold (vrc_kernels_mip.hip the maximum, vrc_kernels_minip.hip the minimum, vrc_kernels_meanip.hip the mean), each
+ * of which instantiates its own fold's instances and nothing else -- the instances of one fold take about half a minute
+ * to compile, and a change to one fold's code does not rebuild the others'.
+ *
+ * The frame of the composite kernel (vrc_kernels.hip: vrc_k_raycast) around another march body: one wave64 = one
+ * 8x8 pixel tile in Morton lane order, four tiles of a schedule unit per workgroup, the tile schedule, the tile
+ * culling of the reference-order loop, the per-axis address tables of the fixed-point stepping.  What it does not
+ * have: a table in LDS (the pixel is classified once per ray, from the padded transfer function in global memory),
+ * a transmittance, an early-exit test.  Per sample: the address, the gather and half a v_max3 (minimum: v_min3; mean:
+ * half a v_add3, or one v_add_f64).
+ *
+ * Samples are always counted in a register (one add per group); the counter is only added to where the caller asked
+ * for it -- half the instances of a COUNT template argument.
+ */
+#ifndef VRC_KERNELS_MIP_H
+#define VRC_KERNELS_MIP_H
+
+#include "vrc_internal.h"
+
+#include <type_traits>
+
+#define VRC_MIP_WG_THREADS ( 64u * VRC_WAVES_PER_GROUP )
+
+/* Waves per SIMD the compiler plans registers for (amdgpu_waves_per_eu is a register budget, not a residency limit).
+ * Without the classified table the LDS need is 3 KiB of address tables (plus 8 KiB of tile candidates in the
+ * reference-order form) per workgroup of four waves: LDS admits more than the 8 waves a SIMD holds, so the registers an
+ * instance ends up with decide how many waves are resident.
+ *   point samples, fixed-point stepping, 32-bit slot bases: (5, 5), the composite gather kernel's choice.  They come out
+ *     at 62-72 VGPRs, so 7-8 waves are resident; whether they want a limit of 5, as the composite gather kernel did
+ *     (its sixth wave thrashes the vector L1), is not measured, and nothing enforces one.
+ *   everything else (trilinear: 32 gathers and 4 x 12 address parts in flight; the float position chain; the clamped
+ *     sampler; 64-bit slot bases): at least 4, as the composite forms that spilled at 5. */
+#define VRC_MIP_MIN_WAVES ( ( vrc_mode_base( MODE ) == VRC_MODE_MIP && FIXED && !CLAMP && !BIG ) ? 5 : 4 )
+#define VRC_MIP_MAX_WAVES ( ( vrc_mode_base( MODE ) == VRC_MODE_MIP && FIXED && !CLAMP && !BIG ) ? 5 : 8 )
+
+template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
+__global__ __launch_bounds__( VRC_MIP_WG_THREADS ) __attribute__( ( amdgpu_waves_per_eu( VRC_MIP_MIN_WAVES, VRC_MIP_MAX_WAVES ) ) ) void vrc_k_raycast_mip(
+    const vrc_frame f, const vrc_dev_node* __restrict__ nodes, const int32_t* __restrict__ gridTable,
+    const ATLAS_T* __restrict__ atlas, const vrc_f4* __restrict__ tfp, const vrc_classifier cls,
+    vrc_f4* __restrict__ pixelBuffer, unsigned long long* __restrict__ sampleCounter,
+    const uint32_t* __restrict__ tileOrder, const uint32_t tilesX, const uint32_t nTiles )
+{
+    __shared__ uint16_t tileCand[DDA ? 1u : VRC_WAVES_PER_GROUP * VRC_TILE_CANDIDATES];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+#if defined( VRC_ADDR_TABLES )
+    if( FIXED )
+    {
+        const vrc_lay lay = vrc_make_lay( f.sbx, f.sby );
+        for( uint32_t u = tid; u < 256u; u += VRC_MIP_WG_THREADS )
+        {
+            vrc_addr_tab[u] = vrc_lay_x( lay, u );
+            vrc_addr_tab[256u + u] = vrc_lay_y( lay, u );
+            vrc_addr_tab[512u + u] = vrc_lay_z( lay, u );
+        }
+        __syncthreads();
+    }
+#endif
+    /* from here on the waves of the workgroup are independent */
+    const uint32_t slotIndex = blockIdx.x * VRC_WAVES_PER_GROUP + ( tid >> 6 );
+    const uint32_t tilesY = nTiles / tilesX;
+    if( slotIndex >= vrc_schedule_slots( tilesX, tilesY ) )
+        return;
+    const uint32_t tile = vrc_slot_tile( tileOrder, slotIndex, tilesX, tilesY );
+    if( tile == VRC_NO_TILE )
+        return;
+    const uint32_t tx = tile % tilesX, ty = tile / tilesX;
+    /* Morton lane order: four consecutive lanes are a 2x2 pixel quad (vrc_k_raycast) */
+    const uint32_t lx = ( lane & 1u ) | ( ( lane >> 1 ) & 2u ) | ( ( lane >> 2 ) & 4u );
+    const uint32_t ly = ( ( lane >> 1 ) & 1u ) | ( ( lane >> 2 ) & 2u ) | ( ( lane >> 3 ) & 4u );
+    const uint32_t px = tx * VRC_TILE_W + lx;
+    const uint32_t py = ty * VRC_TILE_H + ly;
+
+    uint32_t nSamples = 0;
+    /* reference-order loop: the bricks this tile's rays can hit at all, found once per wave (vrc_core.h, "tile
+     * culling"; a brick that is not hit is a `continue`, so leaving it out changes no sample) */
+    const uint16_t* cand = nullptr;
+    uint32_t nCand = 0;
+    if( !DDA && f.nodeCount > 8u && f.nodeCount <= 65535u )
+    {
+        uint16_t* const mine = tileCand + ( tid >> 6 ) * VRC_TILE_CANDIDATES;
+        float r0 = 1e30f, r1 = -1e30f;
+        for( uint32_t j = 0; j < VRC_TILE_H; ++j )
+        {
+            const uint32_t row = ty * VRC_TILE_H + j;
+            if( row < f.height )
+            {
+                const float fr = (float)( f.rowMap ? f.rowMap[row] : row );
+                r0 = fminf( r0, fr );
+                r1 = fmaxf( r1, fr );
+            }
+        }
+        const vrc_tile_pyramid pyr = vrc_make_tile_pyramid( f, (float)( tx * VRC_TILE_W ) - 1.0f, r0 - 1.0f,
+                                                           (float)( tx * VRC_TILE_W + VRC_TILE_W ), r1 + 1.0f );
+        for( uint32_t base = 0; base < f.nodeCount; base += 64u )
+        {
+            const uint32_t i = base + lane;
+            bool in = false;
+            if( i < f.nodeCount )
+                in = vrc_pyramid_may_hit( pyr, nodes[i].aabbMin, nodes[i].aabbSize );
+            const uint64_t m = __builtin_amdgcn_ballot_w64( in );
+            const uint32_t at = nCand + __builtin_amdgcn_mbcnt_hi( (uint32_t)( m >> 32 ),
+                                                                   __builtin_amdgcn_mbcnt_lo( (uint32_t)m, 0u ) );
+            if( in && at < VRC_TILE_CANDIDATES )
+                mine[at] = (uint16_t)i;
+            nCand += (uint32_t)__builtin_popcountll( m );
+        }
+        __builtin_amdgcn_fence( __ATOMIC_RELEASE, "wavefront" );
+        __builtin_amdgcn_wave_barrier();
+        if( nCand <= VRC_TILE_CANDIDATES )
+            cand = mine;
+    }
+    if( px < f.width && py < f.height )
+        vrc_pixel_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, VRC_GROUP, BIG >( f, nodes, gridTable, atlas, tfp, cls, pixelBuffer,
+                                                                         px, py, nSamples, cand, nCand );
+    if( sampleCounter != nullptr )
+    {
+        /* wave64 reduction, one atomic per wave */
+        unsigned long long s = nSamples;
+#pragma unroll
+        for( int off = 32; off > 0; off >>= 1 )
+            s += __shfl_down( s, off, 64 );
+        if( lane == 0 && s != 0 )
+            atomicAdd( sampleCounter, s );
+    }
+}
+
+template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
+static hipError_t launch_mip( const vrc_raycast_args& a, hipStream_t stream )
+{
+    const uint32_t tilesX = ( a.frame.width + VRC_TILE_W - 1 ) / VRC_TILE_W;
+    const uint32_t tilesY = ( a.frame.height + VRC_TILE_H - 1 ) / VRC_TILE_H;
+    const uint32_t nTiles = tilesX * tilesY;
+    if( nTiles == 0 )
+        return hipSuccess;
+    vrc_internal_note_kernel( "vrc_k_raycast_mip<%s,%s,%s,%d,%s,%s>", DDA ? "true" : "false", CLAMP ? "true" : "false",
+                              FIXED ? "true" : "false", (int)MODE,
+                              std::is_same< ATLAS_T, float >::value ? "float" : sizeof( ATLAS_T ) == 1 ? "unsigned char" : "unsigned short",
+                              BIG ? "true" : "false" );
+    vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >,
+                                 (int)VRC_MIP_WG_THREADS, 0 );
+    hipLaunchKernelGGL( ( vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG > ),
+                        dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WAVES_PER_GROUP - 1u ) / VRC_WAVES_PER_GROUP ),
+                        dim3( VRC_MIP_WG_THREADS ), 0, stream, a.frame, a.nodes, a.gridTable, (const ATLAS_T*)a.atlas,
+                        a.lut, a.classifier, a.pixelBuffer, a.sampleCounter, a.tileOrder, tilesX, nTiles );
+    return hipGetLastError();
+}
+
+/* the sampler of the composite forms: fixed-point stepping where the slot has an overlap and fits eight bits a side
+ * (point samples), the float chain with or without clamped addressing otherwise; the trilinear gather form always
+ * steps in float, as vrc_march_segment_linear does */
+template < int MODE, typename ATLAS_T, bool BIG >
+static hipError_t launch_mip_sampler( const vrc_raycast_args& a, hipStream_t stream )
+{
+    if constexpr( vrc_mode_base( MODE ) == VRC_MODE_MIP )
+        if( a.fixedStepping && !a.clamp )
+            return a.gridDda ? launch_mip< true, false, true, MODE, ATLAS_T, BIG >( a, stream )
+                             : launch_mip< false, false, true, MODE, ATLAS_T, BIG >( a, stream );
+    if( a.clamp )
+        return a.gridDda ? launch_mip< true, true, false, MODE, ATLAS_T, BIG >( a, stream )
+                         : launch_mip< false, true, false, MODE, ATLAS_T, BIG >( a, stream );
+    return a.gridDda ? launch_mip< true, false, false, MODE, ATLAS_T, BIG >( a, stream )
+                     : launch_mip< false, false, false, MODE, ATLAS_T, BIG >( a, stream );
+}
+
+template < int FOLD, typename ATLAS_T >
+static hipError_t launch_mip_atlas( const vrc_raycast_args& a, hipStream_t stream )
+{
+    constexpr int POINT = VRC_MODE_WITH_FOLD( VRC_MODE_MIP, FOLD ), TRILINEAR = VRC_MODE_WITH_FOLD( VRC_MODE_MIP_TRILINEAR, FOLD );
+    if( a.linear )
+        return a.bigAtlas ? launch_mip_sampler< TRILINEAR, ATLAS_T, true >( a, stream )
+                          : launch_mip_sampler< TRILINEAR, ATLAS_T, false >( a, stream );
+    return a.bigAtlas ? launch_mip_sampler< POINT, ATLAS_T, true >( a, stream )
+                      : launch_mip_sampler< POINT, ATLAS_T, false >( a, stream );
+}
+
+/* the instances of one fold: what a translation unit's entry point is */
+template < int FOLD >
+static hipError_t launch_mip_fold( const vrc_raycast_args& a, hipStream_t stream )
+{
+    if( VRC_TILE_W != 8u || a.lut == nullptr )
+        return hipErrorInvalidValue;
+    if( FOLD == VRC_FOLD_MEAN ? ( a.frame.meanSum == nullptr || a.frame.meanCount == nullptr ) : a.frame.mipMax == nullptr )
+        return hipErrorInvalidValue;
+    switch( a.elemBytes )
+    {
+    case 1: return launch_mip_atlas< FOLD, uint8_t >( a, stream );
+    case 2: return launch_mip_atlas< FOLD, uint16_t >( a, stream );
+    case 4: return launch_mip_atlas< FOLD, float >( a, stream );
+    default: return hipErrorInvalidValue;
+    }
+}
+
+#endif

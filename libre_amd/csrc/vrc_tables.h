@@ -340,6 +340,9 @@ inline void vrc_fill_frame( vrc_frame& f, const vrc_view_data& view, const vrc_r
     f.slotMax = nullptr;
     f.mipMax = nullptr;
     f.mipFirst = 0u;
+    f.slotMin = nullptr;
+    f.meanSum = nullptr;
+    f.meanCount = nullptr;
     f.samplesPerPixel = 1u; /* the caller sets it for the glRaycaster variant */
     f.lodLevels = 0;
     f.lodBase = 0.f;

@@ -36,7 +36,7 @@ struct lvh_app
     RenderStatistics lastStats;
     std::vector< uint32_t > rowMap; /* lvh_app_set_bands */
     std::vector< std::unique_ptr< Renderer > > extraRenderers; /* frames in flight beyond the first */
-    std::map< int, int64_t > projectionOptions; /* VRC_OPT_PROJECTION / VRC_OPT_MIP_SKIP as set: for renderers made later */
+    std::map< int, int64_t > projectionOptions; /* VRC_OPT_PROJECTION / VRC_OPT_MIP_SKIP / VRC_OPT_MIP_FOLD as set: for renderers made later */
     uint32_t slot = 0;
     std::string rendererName;
     float dataRange[2] = { 0.0f, 0.0f }; /* lvh_app_set_data_range; empty = the voxel type's range */
@@ -315,7 +315,7 @@ int lvh_app_select_slot( lvh_app* app, uint32_t slot )
 int lvh_app_set_option( lvh_app* app, int option, int64_t value )
 {
     if( !app ) return fail( "NULL argument" );
-    if( option == VRC_OPT_PROJECTION || option == VRC_OPT_MIP_SKIP )
+    if( option == VRC_OPT_PROJECTION || option == VRC_OPT_MIP_SKIP || option == VRC_OPT_MIP_FOLD )
     {
         /* how the app forms its pixels: every renderer it has, and every one it makes later (lvh_app_set_frames_in_flight) */
         try

@@ -759,7 +759,7 @@ void HipRaycastRenderer::setStream( void* s ) { throwOnVrcError( vrc_ctx_set_str
 void HipRaycastRenderer::setOption( int o, int64_t v )
 {
     throwOnVrcError( vrc_set_option( _ctx, o, v ), "vrc_set_option" );
-    if( o == VRC_OPT_PROJECTION )
+    if( o == VRC_OPT_PROJECTION ) /* (whichever VRC_OPT_MIP_FOLD: every fold of a MIP frame takes the per-brick cut) */
         _mip = v == VRC_PROJECTION_MIP;
 }
 void HipRaycastRenderer::synchronize() { throwOnVrcError( vrc_synchronize( _ctx ), "vrc_synchronize" ); }

@@ -11,8 +11,9 @@ LIB_PATH = os.path.join(_HERE, "lib", "libvrc_hip.so")
 
 VRC_OK, VRC_EINVAL, VRC_EHIP, VRC_EFULL, VRC_ENOMEM, VRC_EUNSUPPORTED, VRC_EHIERARCHY, VRC_ECOMM = range(8)
 OPT_KERNEL, OPT_FILTER, OPT_TF_FRAC_BITS, OPT_COUNT_SAMPLES, OPT_TILE_ORDER, OPT_STEPPING, OPT_VARIANT, OPT_KERNEL_USED, OPT_KERNEL_TIMING, OPT_DEPTH_SPLIT, OPT_ERT_COMPACTION, OPT_GREY_TABLE, OPT_PACKED_ATLAS, OPT_GRID_WALK_USED, OPT_UNIFORM_BRICKS = range(1, 16)
-OPT_PROJECTION, OPT_MIP_SKIP = 16, 17
+OPT_PROJECTION, OPT_MIP_SKIP, OPT_MIP_FOLD = 16, 17, 18
 PROJECTION_COMPOSITE, PROJECTION_MIP = 0, 1
+MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2
 VARIANT_CUDARAYCASTER, VARIANT_GLRAYCASTER = 0, 1
 FILTER_NEAREST, FILTER_TRILINEAR = 0, 1
 KERNEL_AUTO, KERNEL_REFERENCE_ORDER, KERNEL_GRID_DDA, KERNEL_LDS, KERNEL_RAY_LOD, KERNEL_PACKED = 0, 1, 2, 3, 4, 5
@@ -62,7 +63,7 @@ EXPORTS = [
     "vrc_pool_release_slot", "vrc_pool_info", "vrc_pool_synchronize", "vrc_pool_read_region",
     "vrc_pool_histogram", "vrc_pool_enable_histograms", "vrc_frame_histogram", "vrc_get_frame_histogram",
     "vrc_update", "vrc_pre_render", "vrc_set_row_map", "vrc_set_framebuffer", "vrc_get_framebuffer", "vrc_render",
-    "vrc_post_render", "vrc_synchronize", "vrc_get_stats", "vrc_get_ray_counts", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
+    "vrc_post_render", "vrc_synchronize", "vrc_get_stats", "vrc_get_ray_counts", "vrc_get_projection_values", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
     "vrc_comm_unique_id", "vrc_comm_create", "vrc_comm_destroy", "vrc_comm_info", "vrc_gather_tiles",
 ]
 COMM_ID_BYTES = 128
@@ -131,6 +132,8 @@ def load_library(path=None):
     L.vrc_synchronize.argtypes = [vp]
     L.vrc_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.vrc_get_ray_counts.argtypes = [vp, C.POINTER(C.c_uint32 * 8), C.POINTER(C.c_int)]
+    if hasattr(L, "vrc_get_projection_values"):  # (a symbol newer than ABI 4: an older library, e.g. a developer A/B build, lacks it)
+        L.vrc_get_projection_values.argtypes = [vp, vp, vp]
     L.vrc_comm_unique_id.argtypes = [C.c_char_p]
     L.vrc_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     L.vrc_comm_destroy.argtypes = [vp]

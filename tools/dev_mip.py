@@ -6,7 +6,12 @@ volume.  Kernel ms from the library's HIP events (mean per frame over --steps fr
 counted frame each.  The report goes to standard output and to --out (profiles/mip_projection.txt).
 
 Under rocprofv3 (a counter run is kept apart from any tracing) pass --only to keep the run to one row, e.g.
---only noise:off_axis:nearest:mip_skip0 --steps 1 --warmup 0."""
+--only noise:off_axis:nearest:mip_skip0 --steps 1 --warmup 0.
+
+--fold (VRC_OPT_MIP_FOLD): the same workloads for the minimum and the mean beside the maximum.  Per volume, camera and
+filter: composite, the maximum with skipping off three times (their spread is what a difference has to exceed to mean
+anything), the minimum with skipping off and on, the mean; every row against the composite kernel and against the
+first maximum run.  The report then goes to profiles/fold_projection.txt."""
 import argparse
 import os
 import sys
@@ -18,8 +23,13 @@ sys.path.insert(0, ROOT)
 from libre_amd import driver, vrc  # noqa: E402
 
 CAMERAS = (("default", (0.0, 0.0)), ("off_axis", (0.5235988, 0.3490659)))
-# (row, VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP)
-ROWS = (("composite", vrc.PROJECTION_COMPOSITE, 1), ("mip_skip0", vrc.PROJECTION_MIP, 0), ("mip_skip1", vrc.PROJECTION_MIP, 1))
+# (row, VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP, VRC_OPT_MIP_FOLD)
+ROWS = (("composite", vrc.PROJECTION_COMPOSITE, 1, vrc.MIP_FOLD_MAX), ("mip_skip0", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MAX),
+        ("mip_skip1", vrc.PROJECTION_MIP, 1, vrc.MIP_FOLD_MAX))
+FOLD_ROWS = (("composite", vrc.PROJECTION_COMPOSITE, 1, vrc.MIP_FOLD_MAX), ("max_skip0", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MAX),
+             ("max_skip0_b", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MAX), ("max_skip0_c", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MAX),
+             ("min_skip0", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MIN), ("min_skip1", vrc.PROJECTION_MIP, 1, vrc.MIP_FOLD_MIN),
+             ("mean", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MEAN))
 
 
 def linear_ramp(alpha):
@@ -57,8 +67,11 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--only", default=None, help="volume:camera:filter:row, e.g. noise:off_axis:nearest:mip_skip0")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mip_projection.txt"))
+    ap.add_argument("--fold", action="store_true", help="the minimum and the mean beside the maximum (profiles/fold_projection.txt)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    rows = FOLD_ROWS if a.fold else ROWS
+    a.out = a.out or os.path.join(ROOT, "profiles", "fold_projection.txt" if a.fold else "mip_projection.txt")
     driver.load_library()
     lines = []
 
@@ -68,7 +81,8 @@ def main():
 
     say("# tools/dev_mip.py: %d^3 voxels in %d^3 bricks, %dx%d viewport, alpha %.3g, %d frames after %d warm-up" % (
         a.voxels, a.block, a.viewport, a.viewport, a.alpha, a.steps, a.warmup))
-    say("# volume camera filter row: kernel, kernel ms per frame, samples per frame, Gsamples/s, ms against composite")
+    say("# volume camera filter row: kernel, kernel ms per frame, samples per frame, Gsamples/s, ms against composite%s" % (
+        ", ms against the first maximum run" if a.fold else ""))
     for volume, scheme, filters in (("C2", "mem", (0,)), ("noise", "hash", (0, 1))):
         uri = "%s://#%d,%d,%d,%d" % (scheme, a.voxels, a.voxels, a.voxels, a.block)
         with driver.App(uri, a.viewport, a.viewport, synchronous=True, gpu_cache_mb=3072) as probe:
@@ -80,21 +94,24 @@ def main():
                 for flt in filters:
                     fname = "trilinear" if flt else "nearest"
                     app.set_option(vrc.OPT_FILTER, vrc.FILTER_TRILINEAR if flt else vrc.FILTER_NEAREST)
-                    base = None
-                    for row, projection, skip in ROWS:
+                    base = first_max = None
+                    for row, projection, skip, fold in rows:
                         if a.only and a.only != "%s:%s:%s:%s" % (volume, camera, fname, row):
                             continue
                         app.set_option(vrc.OPT_PROJECTION, projection)
                         app.set_option(vrc.OPT_MIP_SKIP, skip)
+                        app.set_option(vrc.OPT_MIP_FOLD, fold)
                         n = count_samples(app)
                         ms = time_kernel(app, a.warmup, a.steps)
                         kernel = (vrc.load_library().vrc_last_kernel() or b"").decode()
                         base = ms if row == "composite" else base
-                        say("%-5s %-8s %-9s %-9s %-34s %8.3f ms %13d samples %7.2f Gsamples/s %s" % (
+                        first_max = ms if row == "max_skip0" else first_max
+                        say("%-5s %-8s %-9s %-11s %-34s %8.3f ms %13d samples %7.2f Gsamples/s %s%s" % (
                             volume, camera, fname, row, kernel, ms, n, n / ms / 1e6,
-                            "x%.3f" % (ms / base) if base else "-"))
+                            "x%.3f" % (ms / base) if base else "-", " x%.3f" % (ms / first_max) if first_max else ""))
                     app.set_option(vrc.OPT_PROJECTION, vrc.PROJECTION_COMPOSITE)
                     app.set_option(vrc.OPT_MIP_SKIP, 1)
+                    app.set_option(vrc.OPT_MIP_FOLD, vrc.MIP_FOLD_MAX)
             app.set_option(vrc.OPT_FILTER, vrc.FILTER_NEAREST)
     if not a.only:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
