@@ -63,7 +63,8 @@ int lvh_app_set_clip_planes( lvh_app* app, const float* planes, uint32_t n );
 /* sort-first row bands rendered by this process in one launch: bands (y0[i], h[i]) of the full
  * frame, stacked in that order in its pixel buffer (replaces params.tile; n = 0 -> back to it) */
 int lvh_app_set_bands( lvh_app* app, const uint32_t* y0, const uint32_t* h, uint32_t n );
-/* vrc_set_option on the renderer of the selected slot.  VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP and VRC_OPT_MIP_FOLD say how
+/* vrc_set_option on the renderer of the selected slot.  VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP, VRC_OPT_MIP_FOLD,
+ * VRC_OPT_MIP_DEPTH and VRC_OPT_MIP_DEPTH_CUE say how
  * the app forms its pixels: they reach every renderer of the app, those of extra slots and those made later included.
  * With VRC_PROJECTION_MIP, whichever fold (maximum, minimum, mean), a frame that asks for per-ray LOD
  * (lvh_app_set_ray_lod) renders its per-brick cut. */
@@ -107,6 +108,17 @@ int lvh_app_set_histogram( lvh_app* app, int enable );
  * frame's area and the frame's id.  An error while the histogram is off or before such a frame. */
 int lvh_app_frame_histogram( lvh_app* app, uint64_t* bins, uint32_t capacity, uint32_t* bin_count, float range[2],
                              float* area, uint64_t* frame_id );
+/* Pick in a MIP frame rendered with depth tracking (VRC_OPT_MIP_DEPTH = 1 or VRC_OPT_MIP_DEPTH_CUE > 0; maximum or
+ * minimum): what lies behind pixel (x, y) of the window in the selected slot's last frame.  *hit = 1 if the pixel's ray
+ * took a sample, *value = the projected value M in the volume's own units, *t = the ray parameter D of the nearest sample
+ * that equals M, xyz = its position origin + D * dir (vrc_get_projection_values / vrc_get_projection_depths of that
+ * pixel; any of the four may be NULL; value, t and xyz are unspecified without a hit).  An error, with a message: no
+ * frame yet; the frame was composite, a MIP frame without depth tracking, or the mean fold; (x, y) outside the window
+ * or the tile of this process; in band mode (lvh_app_set_bands), a row this process did not render.
+ * Every call reads the whole frame's values, counts, depths and positions back (24 bytes a pixel, two small kernels, one
+ * synchronisation) and returns one entry: meant for a click, not for a loop over the window -- a caller that wants many
+ * pixels takes vrc_get_projection_values / vrc_get_projection_depths once. */
+int lvh_app_pick( lvh_app* app, uint32_t x, uint32_t y, int* hit, float* value, float* t, float xyz[3] );
 /* introspection used by the parity tests */
 int lvh_app_volume_info( lvh_app* app, uint32_t voxels[3], uint32_t max_block[3],
                          uint32_t overlap[3], float world_size[3], uint32_t* depth,

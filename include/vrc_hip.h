@@ -171,6 +171,14 @@ typedef struct
 #define VRC_MIP_FOLD_MIN 1
 #define VRC_MIP_FOLD_MEAN 2
 
+#define VRC_OPT_MIP_DEPTH 19        /* 0 (default) | 1.  MIP only, VRC_MIP_FOLD_MAX and _MIN: keep, beside M, the depth D of
+                                    * the sample M was found at ("The depth of a MIP frame" below) for
+                                    * vrc_get_projection_depths.  The frame and the values are bit for bit those of 0.
+                                    * Any other value: VRC_EINVAL */
+#define VRC_OPT_MIP_DEPTH_CUE 20    /* 0 (default) ... 1000: the strength of the depth cue in thousandths.  Above 0 the
+                                    * frame tracks depth whatever VRC_OPT_MIP_DEPTH says, and a pixel is darkened by
+                                    * where D lies in its ray's interval.  Anything else: VRC_EINVAL */
+
 /* A MIP frame (VRC_OPT_PROJECTION = VRC_PROJECTION_MIP).
  *   Sample set.  A ray's sample set S is exactly what the composite march takes with a transfer function whose alpha
  *     is 0 everywhere: the same ray set-up, global-box and clip-plane interval and near plane; the same node list
@@ -226,6 +234,33 @@ typedef struct
  * the passes of one MIP frame, whatever the fold: the library does not check it, and the frame and the read-back values
  * are unspecified if it does.
  * vrc_get_projection_values returns M itself. */
+
+/* The depth of a MIP frame (VRC_OPT_MIP_DEPTH, VRC_OPT_MIP_DEPTH_CUE).  Both options are read only when
+ * VRC_OPT_PROJECTION = VRC_PROJECTION_MIP and the fold is VRC_MIP_FOLD_MAX or _MIN; under VRC_MIP_FOLD_MEAN they do
+ * nothing: the mean has no position.  Changing either between vrc_pre_render and vrc_post_render: the next vrc_render
+ * returns VRC_EINVAL and names the option, as a changed fold does.  With both at 0 a frame launches the kernel instances
+ * it launched before the options existed.
+ *   Depth of a sample.  The sample set S is the MIP frame's, unchanged.  Sample j (0-based, in march order) of a brick
+ *     segment has t_j = tNear + (float)j * stepSize in float32, the product and the sum each rounded (no fused multiply-
+ *     add); tNear is the ray parameter of the segment's first sample.  The same formula for VRC_OPT_STEPPING 0 and 1
+ *     and for both filters: the depth labels the sample's index, it does not re-derive the position chain.
+ *   Depth of a ray.  D = the smallest t_j over the samples of S whose value equals M.  On float atlases that is ==, so a
+ *     NaN sample never qualifies; a ray whose samples are all NaN has M = -/+infinity with no sample attaining it, and
+ *     D = +infinity.  Equivalently the ray's state (M, D) is folded lexicographically: a strictly better M replaces
+ *     both, an equal M replaces D only by a smaller t -- between two samples inside one voxel, between the bricks of
+ *     the reference-order loop (whose list order is no visibility order) and between the passes of one frame.
+ *   Passes.  The context owns one running depth word per pixel beside the running M: same ownership, same invalidation
+ *     by vrc_pre_render, not read by the first pass.  Later passes merge (M, D) by the rule above: after every pass the
+ *     pair is that of the passes so far, whatever the split.
+ *   VRC_OPT_MIP_SKIP, VRC_OPT_UNIFORM_BRICKS.  With depth on a brick is skipped only if no sample of it can reach M at
+ *     all (strictly; for trilinear samples "can equal M" within the interpolation's rounding margin counts as "must be
+ *     marched"), or if it cannot beat M and its tNear is not below the D the ray holds.  A uniform slot folds
+ *     (value, tNear) by the lexicographic rule and adds the step count without fetching.  Frame, values and depths are
+ *     bit-identical with either option on or off; only vrc_stats.samples may differ.
+ *   Depth cue.  After the classification t = TF(M) the stored pixel is w * (t.rgb * t.a, t.a), w = 1 - strength * u,
+ *     u = clamp((D - tNearGlobal) / (tFarGlobal - tNearGlobal), 0, 1), the interval being the ray's own (global box and
+ *     clip planes), the one S is taken from; u = 0 where that interval is empty, u = 1 for D = +infinity.  Float32,
+ *     operations in the order written.  Strength 0 is the uncued frame bit for bit. */
 
 #define VRC_VARIANT_CUDARAYCASTER 0 /* renderers/cudaRaycaster/cuda/Renderer.cu:95-230 */
 #define VRC_VARIANT_GLRAYCASTER 1   /* renderers/glRaycaster/shaders/fragRaycast.glsl:113-215: pixel centre
@@ -435,6 +470,15 @@ int vrc_get_ray_counts( vrc_ctx* ctx, uint32_t counts[8], int* parts );
  * after a composite frame). */
 int vrc_get_projection_values( vrc_ctx* ctx, float* host_values, uint32_t* host_counts );
 
+/* The depths of a MIP frame rendered with depth tracking (VRC_OPT_MIP_DEPTH = 1 or VRC_OPT_MIP_DEPTH_CUE > 0; fold
+ * _MAX or _MIN).  Validity, synchronisation and buffer geometry are those of vrc_get_projection_values; VRC_EINVAL,
+ * naming the reason, also when the frame's MIP passes ran without depth tracking or with the mean fold.
+ *   host_t[i]    D, the ray parameter of the nearest sample that equals M; +infinity where S is empty (and for a ray
+ *                whose samples are all NaN: the counts of vrc_get_projection_values tell the two apart).
+ *   host_xyz     (may be NULL; W x H x 3)  origin + D * dir of the pixel's ray in float32, product and sum each rounded,
+ *                for the frame row the pixel shows under a row map; unspecified where D is not finite. */
+int vrc_get_projection_depths( vrc_ctx* ctx, float* host_t, float* host_xyz );
+
 /* ---- sort-first tile exchange (multi-GPU) ------------------------------------------------------- */
 /* One process per GPU renders row bands of the frame (vrc_set_row_map); the display rank receives
  * them over RCCL (xGMI inside a node) directly at their rows of the full frame.  This is the step
@@ -483,8 +527,9 @@ int vrc_last_kernel_occupancy( int* workgroups_per_cu, int* threads_per_workgrou
 /* ABI version of this header */
 #define VRC_ABI_VERSION 4 /* 3: vrc_gather_tiles takes the frame height; 4: VRC_KERNEL_PACKED, VRC_OPT_PACKED_ATLAS, vrc_last_kernel_occupancy
                            * (added since without a new number, as symbols a caller may bind weakly: the frame histogram,
-                           * vrc_pool_create_typed / vrc_pool_voxel_type, vrc_get_projection_values; as option values only:
-                           * VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP, VRC_OPT_MIP_FOLD) */
+                           * vrc_pool_create_typed / vrc_pool_voxel_type, vrc_get_projection_values,
+                           * vrc_get_projection_depths; as option values only: VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP,
+                           * VRC_OPT_MIP_FOLD, VRC_OPT_MIP_DEPTH, VRC_OPT_MIP_DEPTH_CUE) */
 /* = VRC_ABI_VERSION for the product build; -VRC_ABI_VERSION for a developer build of the library (compiled with
  * -DVRC_DEV_BUILD: experiment switches, statistics, ablations that render wrong pixels on purpose) */
 int vrc_abi_version( void );

@@ -229,6 +229,23 @@ struct vrc_ctx
     vrc_projection_state projState = { nullptr, nullptr, nullptr, 0u, 0u, 0u, 0.0f };
     float* dProjOut = nullptr;
     size_t dProjOutPixels = 0;
+    /* the depth of the projected sample (include/vrc_hip.h, "The depth of a MIP frame") */
+    int64_t optMipDepth = 0;    /* VRC_OPT_MIP_DEPTH */
+    int64_t optMipDepthCue = 0; /* VRC_OPT_MIP_DEPTH_CUE, thousandths */
+    /* one running D per pixel beside dMipMax (vrc_frame::mipDepth): allocated by the first frame that tracks depth, grown
+     * and invalidated where dMipMax is; frameDepth / frameCue: what the frame's first MIP vrc_render read of the two
+     * options (-1 = none yet), as frameFold is its fold */
+    float* dMipDepth = nullptr;
+    size_t dMipDepthPixels = 0;
+    int64_t frameDepth = -1;
+    int64_t frameCue = -1;
+    /* what vrc_get_projection_depths reads: did the frame's last MIP pass track depth, the frame it marched (camera,
+     * pixel buffer geometry) with the row map it had, and the device buffer of the read-back (t | xyz | rows) */
+    bool depthValid = false;
+    vrc_frame depthFrame = {};
+    std::vector< uint32_t > depthRows;
+    float* dDepthOut = nullptr;
+    size_t dDepthOutWords = 0;
     uint32_t* dRayList = nullptr; /* counts | two ray lists (vrc_internal.h) */
     size_t dRayListCap = 0;       /* pixels */
     int lastErtParts = 0;         /* of the last vrc_render */
@@ -371,6 +388,8 @@ void vrc_ctx_destroy( vrc_ctx* c )
     if( c->dMeanSum ) (void)hipFree( c->dMeanSum );
     if( c->dMeanCount ) (void)hipFree( c->dMeanCount );
     if( c->dProjOut ) (void)hipFree( c->dProjOut );
+    if( c->dMipDepth ) (void)hipFree( c->dMipDepth );
+    if( c->dDepthOut ) (void)hipFree( c->dDepthOut );
     if( c->dRowMap ) (void)hipFree( c->dRowMap );
     if( c->dCounter ) (void)hipFree( c->dCounter );
     if( c->hCounter ) (void)hipHostFree( c->hCounter );
@@ -439,6 +458,16 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_MIP_FOLD is 0 (maximum), 1 (minimum) or 2 (mean)" );
         c->optMipFold = value;
         return VRC_OK;
+    case VRC_OPT_MIP_DEPTH:
+        if( value != 0 && value != 1 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_MIP_DEPTH is 0 (off) or 1 (keep the depth of the projected sample)" );
+        c->optMipDepth = value;
+        return VRC_OK;
+    case VRC_OPT_MIP_DEPTH_CUE:
+        if( value < 0 || value > 1000 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_MIP_DEPTH_CUE is the cue strength in thousandths, 0 (off) to 1000" );
+        c->optMipDepthCue = value;
+        return VRC_OK;
     case VRC_OPT_ERT_COMPACTION:
         if( value < 0 || value > VRC_MAX_ERT_PARTS )
             return fail( VRC_EINVAL, "VRC_OPT_ERT_COMPACTION: 0 (off) or 2.." + std::to_string( VRC_MAX_ERT_PARTS ) +
@@ -475,6 +504,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_PROJECTION: *value = c->optProjection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->optMipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->optMipFold; return VRC_OK;
+    case VRC_OPT_MIP_DEPTH: *value = c->optMipDepth; return VRC_OK;
+    case VRC_OPT_MIP_DEPTH_CUE: *value = c->optMipDepthCue; return VRC_OK;
     case VRC_OPT_VARIANT: *value = c->optVariant; return VRC_OK;
     case VRC_OPT_KERNEL_USED: *value = c->stats.kernel_variant; return VRC_OK;
     case VRC_OPT_GRID_WALK_USED: *value = c->gridWalkUsed; return VRC_OK;
@@ -1283,6 +1314,9 @@ int vrc_pre_render( vrc_ctx* c, const vrc_view_data* view )
     c->mipFirst = true;
     c->frameProjection = -1;
     c->frameFold = -1;
+    c->frameDepth = -1;
+    c->frameCue = -1;
+    c->depthValid = false;
     c->projState.pixels = 0u; /* vrc_get_projection_values: nothing to read until a MIP pass of this frame */
     return VRC_OK;
 }
@@ -1427,6 +1461,17 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     if( mip && c->frameFold >= 0 && c->frameFold != c->optMipFold )
         return fail( VRC_EINVAL, "vrc_render: VRC_OPT_MIP_FOLD changed between vrc_pre_render and vrc_post_render; the "
                                  "passes of one frame take one fold" );
+    /* depth tracking: the maximum and the minimum only; the mean reads neither option */
+    const bool mipDepth = mip && c->optMipFold != VRC_MIP_FOLD_MEAN && ( c->optMipDepth != 0 || c->optMipDepthCue > 0 );
+    if( mip && c->optMipFold != VRC_MIP_FOLD_MEAN )
+    {
+        if( c->frameDepth >= 0 && c->frameDepth != c->optMipDepth )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_MIP_DEPTH changed between vrc_pre_render and vrc_post_render; the "
+                                     "passes of one frame all keep the depth or none does" );
+        if( c->frameCue >= 0 && c->frameCue != c->optMipDepthCue )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_MIP_DEPTH_CUE changed between vrc_pre_render and vrc_post_render; "
+                                     "the passes of one frame take one cue strength" );
+    }
     if( mip )
     {
         /* what the maximum-intensity projection is not defined for (include/vrc_hip.h) */
@@ -1729,6 +1774,31 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         f.slotMin = c->optMipSkip ? pool->dSlotMin : nullptr;
         f.meanSum = mean ? c->dMeanSum : nullptr;
         f.meanCount = mean ? c->dMeanCount : nullptr;
+        if( mipDepth && pixels > c->dMipDepthPixels )
+        {
+            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+            if( c->dMipDepth ) VRC_HIP_CHECK( hipFree( c->dMipDepth ) );
+            c->dMipDepth = nullptr;
+            c->dMipDepthPixels = 0;
+            VRC_HIP_CHECK( hipMalloc( &c->dMipDepth, pixels * sizeof( float ) ) );
+            c->dMipDepthPixels = pixels;
+            if( !c->mipFirst ) /* a later pass (the pixel buffer grew, or dMipMax was large enough from an earlier frame
+                                * and keeps the passes so far): no sample equals M yet as far as this buffer knows */
+                VRC_HIP_CHECK( hipMemsetD32Async( reinterpret_cast< hipDeviceptr_t >( c->dMipDepth ), 0x7F800000, pixels, c->stream ) );
+        }
+        f.mipDepth = mipDepth ? c->dMipDepth : nullptr;
+        f.mipCue = mipDepth ? (float)c->optMipDepthCue / 1000.0f : 0.0f;
+        if( !mean )
+        {
+            c->frameDepth = c->optMipDepth;
+            c->frameCue = c->optMipDepthCue;
+        }
+        c->depthValid = mipDepth;
+        if( mipDepth )
+        {
+            c->depthFrame = f;
+            c->depthRows = c->rowMap;
+        }
         c->mipFirst = false;
         c->frameFold = c->optMipFold;
         /* what this pass leaves for vrc_get_projection_values */
@@ -1839,7 +1909,8 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     vrc_internal_note_kernel_fn( nullptr, 0, 0 ); /* set again by the launchers that report their occupancy */
     if( c->optTiming )
         VRC_HIP_CHECK( hipEventRecord( evp.first, c->stream ) );
-    VRC_HIP_CHECK( mip         ? ( c->optMipFold == VRC_MIP_FOLD_MIN    ? vrc_launch_raycast_minip( a, c->stream )
+    VRC_HIP_CHECK( mipDepth    ? vrc_launch_raycast_mip_depth( a, (int)c->optMipFold, c->stream )
+                   : mip       ? ( c->optMipFold == VRC_MIP_FOLD_MIN    ? vrc_launch_raycast_minip( a, c->stream )
                                    : c->optMipFold == VRC_MIP_FOLD_MEAN ? vrc_launch_raycast_meanip( a, c->stream )
                                                                         : vrc_launch_raycast_mip( a, c->stream ) )
                    : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
@@ -1924,6 +1995,53 @@ int vrc_get_projection_values( vrc_ctx* c, float* hostValues, uint32_t* hostCoun
     VRC_HIP_CHECK( hipMemcpyAsync( hostValues, c->dProjOut, pixels * sizeof( float ), hipMemcpyDeviceToHost, c->stream ) );
     if( hostCounts )
         VRC_HIP_CHECK( hipMemcpyAsync( hostCounts, dCounts, pixels * sizeof( uint32_t ), hipMemcpyDeviceToHost, c->stream ) );
+    VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+    return VRC_OK;
+}
+
+int vrc_get_projection_depths( vrc_ctx* c, float* hostT, float* hostXyz )
+{
+    if( !c || !hostT )
+        return fail( VRC_EINVAL, "vrc_get_projection_depths: NULL argument" );
+    if( c->projState.pixels == 0u )
+        return fail( VRC_EINVAL, "vrc_get_projection_depths: no VRC_OPT_PROJECTION = MIP vrc_render since the last "
+                                 "vrc_pre_render; the depths exist from a frame's first MIP pass until the next frame" );
+    if( c->projState.fold == (uint32_t)VRC_MIP_FOLD_MEAN )
+        return fail( VRC_EINVAL, "vrc_get_projection_depths: the frame's fold is VRC_MIP_FOLD_MEAN (VRC_OPT_MIP_FOLD); the mean "
+                                 "has no position" );
+    if( !c->depthValid )
+        return fail( VRC_EINVAL, "vrc_get_projection_depths: the frame's MIP passes ran without depth tracking "
+                                 "(VRC_OPT_MIP_DEPTH = 0 and VRC_OPT_MIP_DEPTH_CUE = 0)" );
+    VRC_HIP_CHECK( hipSetDevice( c->device ) );
+    const size_t pixels = c->projState.pixels;
+    vrc_frame f = c->depthFrame;
+    if( pixels != (size_t)f.width * f.height || ( !c->depthRows.empty() && c->depthRows.size() != f.height ) )
+        return fail( VRC_EINVAL, "vrc_get_projection_depths: the frame's geometry does not match its state" );
+    const size_t words = pixels * 4u + f.height;
+    if( words > c->dDepthOutWords )
+    {
+        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+        if( c->dDepthOut ) VRC_HIP_CHECK( hipFree( c->dDepthOut ) );
+        c->dDepthOut = nullptr;
+        c->dDepthOutWords = 0;
+        VRC_HIP_CHECK( hipMalloc( &c->dDepthOut, words * sizeof( float ) ) );
+        c->dDepthOutWords = words;
+    }
+    float* const dXyz = c->dDepthOut + pixels;
+    uint32_t* const dRows = reinterpret_cast< uint32_t* >( c->dDepthOut + pixels * 4u );
+    f.rowMap = nullptr;
+    if( !c->depthRows.empty() )
+    {
+        /* the rows the frame was marched with, whatever vrc_set_row_map has done since */
+        VRC_HIP_CHECK( hipMemcpyAsync( dRows, c->depthRows.data(), c->depthRows.size() * sizeof( uint32_t ),
+                                       hipMemcpyHostToDevice, c->stream ) );
+        f.rowMap = dRows;
+    }
+    VRC_HIP_CHECK( vrc_launch_projection_depths( f, c->dMipDepth, (uint32_t)pixels, c->dDepthOut, hostXyz ? dXyz : nullptr,
+                                                 c->stream ) );
+    VRC_HIP_CHECK( hipMemcpyAsync( hostT, c->dDepthOut, pixels * sizeof( float ), hipMemcpyDeviceToHost, c->stream ) );
+    if( hostXyz )
+        VRC_HIP_CHECK( hipMemcpyAsync( hostXyz, dXyz, pixels * 3u * sizeof( float ), hipMemcpyDeviceToHost, c->stream ) );
     VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
     return VRC_OK;
 }

@@ -209,6 +209,13 @@ struct vrc_frame
     const uint32_t* slotMin;
     unsigned long long* meanSum;
     uint32_t* meanCount;
+    /* the depth of the projected sample (VRC_OPT_MIP_DEPTH, the depth-tracking instances of the maximum and the minimum;
+     * at the end: no field above moves).  mipDepth: the context's running D per pixel of the pixel buffer beside mipMax --
+     * the smallest t_j = seg.tNear + (float)j * stepSize over the samples that equal M, +infinity where none does -- owned,
+     * invalidated and not read by a first pass as mipMax is; NULL in every other frame.  mipCue: the strength of the
+     * depth cue in [0, 1] (VRC_OPT_MIP_DEPTH_CUE / 1000), 0 = the pixel is the classification of M as it is */
+    float* mipDepth;
+    float mipCue;
 };
 
 /* Atlas memory layout.  The logical atlas is the reference's 3-D array of slots
@@ -2037,7 +2044,11 @@ VRC_HD bool vrc_march_segment_packed( const vrc_frame& f, const vrc_dev_node& n,
 #define VRC_FOLD_MEAN 2
 #define VRC_MODE_WITH_FOLD( mode, fold ) ( ( mode ) + 16 * ( fold ) )
 VRC_HD constexpr int vrc_mode_base( int mode ) { return mode & 15; }
-VRC_HD constexpr int vrc_mode_fold( int mode ) { return mode >> 4; }
+VRC_HD constexpr int vrc_mode_fold( int mode ) { return ( mode >> 4 ) & 3; }
+/* Depth tracking (VRC_OPT_MIP_DEPTH) rides above the fold: VRC_MODE_WITH_FOLD( mode, fold + VRC_FOLD_DEPTH ), for the
+ * maximum and the minimum.  Without it a mode is the number, and its instances the code, they were before. */
+#define VRC_FOLD_DEPTH 4
+VRC_HD constexpr bool vrc_mode_depth( int mode ) { return ( ( mode >> 6 ) & 1 ) != 0; }
 VRC_HD constexpr bool vrc_mode_is_mip( int mode )
 {
     return vrc_mode_base( mode ) == VRC_MODE_MIP || vrc_mode_base( mode ) == VRC_MODE_MIP_TRILINEAR;
@@ -2167,6 +2178,93 @@ VRC_HD bool vrc_mip_cannot_lower( uint32_t word, float m )
     return m <= bottom;
 }
 
+/* Depth tracking: can no sample of the slot even EQUAL M?  The two tests above with the comparison made strict.  A brick
+ * that cannot beat M but can equal it holds the ray's depth if it lies nearer, and has to be marched then.  Trilinear
+ * samples: the margin bounds them from above (below), and a sample can sit on the bound itself (a slot of zeros), so
+ * only an M strictly beyond the bound rules a tie out. */
+template < int FOLD, bool TRILINEAR, typename ATLAS_T >
+VRC_HD bool vrc_mip_cannot_reach( uint32_t word, uint32_t m )
+{
+    static_assert( !TRILINEAR, "a trilinear M is a float" );
+    if constexpr( FOLD == VRC_FOLD_MIN )
+        return m < vrc_slot_min_value( word );
+    else
+        return m >= word; /* word = the largest stored value + 1 */
+}
+template < int FOLD, bool TRILINEAR, typename ATLAS_T >
+VRC_HD bool vrc_mip_cannot_reach( uint32_t word, float m )
+{
+    float bound;
+    if constexpr( FOLD == VRC_FOLD_MIN )
+    {
+        if constexpr( sizeof( ATLAS_T ) == 4 )
+            bound = vrc_slot_min_float( word );
+        else
+            bound = (float)vrc_slot_min_value( word );
+        if constexpr( TRILINEAR )
+        {
+            VRC_STRICT_FP
+            bound = bound - fabsf( bound ) * 1e-6f;
+        }
+        return m < bound;
+    }
+    else
+    {
+        if constexpr( sizeof( ATLAS_T ) == 4 )
+            bound = vrc_slot_max_float( word );
+        else
+            bound = (float)( word - 1u );
+        if constexpr( TRILINEAR )
+        {
+            VRC_STRICT_FP
+            bound = bound + fabsf( bound ) * 1e-6f;
+        }
+        return m > bound;
+    }
+}
+
+/* The depth of a ray beside its M: D = the smallest t_j = seg.tNear + (float)j * stepSize (the product and the sum each
+ * rounded) over the samples that equal M, j the sample's index in its segment; +infinity while no sample equals M.  (M, D)
+ * is folded lexicographically: a strictly better M replaces both, an equal M replaces D only by a smaller t.
+ *   tNear  the segment's;  index: samples of the segment taken so far
+ *   tie    M has not changed in this segment and an equal sample of it could still lie nearer than D (seg.tNear < D).
+ *          Once the segment set D, or an equal sample came out no nearer, every later sample of it lies farther.
+ * The marches fold a group as they did and look for the index only in a group that changed M or may hold such a tie. */
+struct vrc_mip_depth
+{
+    float d;
+    float tNear;
+    uint32_t index;
+    bool tie;
+};
+VRC_HD float vrc_mip_sample_t( float tNear, uint32_t j, float stepSize )
+{
+    VRC_STRICT_FP
+    const float along = (float)j * stepSize;
+    return tNear + along;
+}
+/* after a group of N samples d[] (taken[k]: sample k belongs to S) was folded into m, which was m0 before */
+template < int N, typename D >
+VRC_HD void vrc_mip_depth_group( vrc_mip_depth& z, D m0, D m, const D* d, const bool* taken, float stepSize )
+{
+    const bool changed = m != m0;
+    if( changed || z.tie )
+    {
+        int first = -1;
+#pragma unroll
+        for( int k = N - 1; k >= 0; --k )
+            first = ( taken[k] && d[k] == m ) ? k : first;
+        if( first >= 0 )
+        {
+            const float t = vrc_mip_sample_t( z.tNear, z.index + (uint32_t)first, stepSize );
+            if( changed || t < z.d )
+                z.d = t;
+            z.tie = false;
+        }
+    }
+    z.index += (uint32_t)N;
+}
+
 /* trips of the reference's `for( ; travel > 0; travel -= stepSize )` (travel > 0): in integers where that is exact
  * (vrc_exact_step_count), else by the float chain itself */
 VRC_HD uint32_t vrc_step_count( float travel, float stepSize )
@@ -2181,9 +2279,9 @@ VRC_HD uint32_t vrc_step_count( float travel, float stepSize )
 }
 
 /* point samples of one brick segment (travel > 0 or nothing is taken): vrc_march_segment_as without table, blend and exit */
-template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename D, int FOLD = VRC_FOLD_MAX >
+template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename D, int FOLD = VRC_FOLD_MAX, bool DEPTH = false >
 VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
-                                   const ATLAS_T* __restrict__ atlas, D& m, uint32_t& nSamples )
+                                   const ATLAS_T* __restrict__ atlas, D& m, uint32_t& nSamples, vrc_mip_depth* z = nullptr )
 {
     const float stepSize = f.stepSize;
     const vrc_sampler sm = vrc_make_sampler( n, f );
@@ -2208,12 +2306,21 @@ VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, co
 #pragma unroll
         for( int k = 0; k < GROUP; ++k )
             d[k] = (D)vrc_gather( atlas, idx[k] );
+        const D m0 = m;
 #pragma unroll
         for( int k = 0; k + 1 < GROUP; k += 2 )
             m = vrc_mip_fold3< FOLD >( m, d[k], d[k + 1] );
         if( GROUP & 1 )
             m = vrc_mip_fold< FOLD >( m, d[GROUP - 1] );
         nSamples += GROUP;
+        if constexpr( DEPTH )
+        {
+            bool taken[GROUP];
+#pragma unroll
+            for( int k = 0; k < GROUP; ++k )
+                taken[k] = true;
+            vrc_mip_depth_group< GROUP >( *z, m0, m, d, taken, stepSize );
+        }
     }
     constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
     D none;
@@ -2237,17 +2344,55 @@ VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, co
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
             d[k] = (D)vrc_gather( atlas, idx[k] );
+        const D m0 = m;
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
             m = vrc_mip_fold< FOLD >( m, (uint32_t)k < cnt ? d[k] : none );
         nSamples += cnt;
+        if constexpr( DEPTH )
+        {
+            bool taken[TAILG];
+#pragma unroll
+            for( int k = 0; k < TAILG; ++k )
+                taken[k] = (uint32_t)k < cnt;
+            vrc_mip_depth_group< TAILG >( *z, m0, m, d, taken, stepSize );
+        }
     }
 }
 
+/* vrc_trilerp with its fused multiply-adds written out, for the depth-tracking instances: a frame has to come out with the
+ * same M, bit for bit, with depth tracking on and off, and under contract(fast) the compiler is free to fuse either
+ * product of a (1 - w) + b w -- which one it takes depends on the code around the expression (it keeps as a product the
+ * one with more uses).  Read off the gfx950 code of the instances without depth tracking, all of them:
+ *   8- and 16-bit atlases  the first product is fused, fma( a, 1 - w, b * w ), at all three levels of every sample;
+ *   the float atlas        the same, but for the first interpolation along x (c00) of the first sample of a group,
+ *                          which comes out as fma( b, w, a * (1 - w) ) -- firstOfFloatGroup.
+ * tests/test_depth.py holds the two kinds of instance to each other on the GPU, every atlas type, both folds, the grid
+ * walk and the reference-order loop, with and without the clamped sampler.  The host build contracts nothing, either
+ * way. */
+VRC_HD float vrc_trilerp_fused_as_plain( const float v[8], float wx, float wy, float wz, bool firstOfFloatGroup )
+{
+#if defined( __HIP_DEVICE_COMPILE__ )
+    VRC_STRICT_FP
+    const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
+    const float c00 = firstOfFloatGroup ? __builtin_fmaf( v[1], wx, v[0] * ux ) : __builtin_fmaf( v[0], ux, v[1] * wx );
+    const float c10 = __builtin_fmaf( v[2], ux, v[3] * wx );
+    const float c01 = __builtin_fmaf( v[4], ux, v[5] * wx );
+    const float c11 = __builtin_fmaf( v[6], ux, v[7] * wx );
+    const float c0 = __builtin_fmaf( c00, uy, c10 * wy );
+    const float c1 = __builtin_fmaf( c01, uy, c11 * wy );
+    return __builtin_fmaf( c0, uz, c1 * wz );
+#else
+    (void)firstOfFloatGroup;
+    return vrc_trilerp( v, wx, wy, wz );
+#endif
+}
+
 /* trilinear samples of one brick segment: vrc_march_segment_linear without classification, blend and exit */
-template < bool CLAMP, typename ATLAS_T, int FOLD = VRC_FOLD_MAX >
+template < bool CLAMP, typename ATLAS_T, int FOLD = VRC_FOLD_MAX, bool DEPTH = false >
 VRC_HD void vrc_mip_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
-                                       const ATLAS_T* __restrict__ atlas, float& m, uint32_t& nSamples )
+                                       const ATLAS_T* __restrict__ atlas, float& m, uint32_t& nSamples,
+                                       vrc_mip_depth* z = nullptr )
 {
     const float stepSize = f.stepSize;
     const vrc_sampler sm = vrc_make_sampler( n, f );
@@ -2285,15 +2430,21 @@ VRC_HD void vrc_mip_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n
 #pragma unroll
         for( int k = 0; k < VRC_LGROUP; ++k )
         {
+            if constexpr( DEPTH )
+                d[k] = vrc_trilerp_fused_as_plain( v[k], t[k].wx, t[k].wy, t[k].wz, k == 0 && sizeof( ATLAS_T ) == 4 );
+            else
             d[k] = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
             d[k] = valid[k] ? d[k] : none;
             nSamples += valid[k] ? 1u : 0u;
         }
+        const float m0 = m;
 #pragma unroll
         for( int k = 0; k + 1 < VRC_LGROUP; k += 2 )
             m = vrc_mip_fold3< FOLD >( m, d[k], d[k + 1] );
         if( VRC_LGROUP & 1 )
             m = vrc_mip_fold< FOLD >( m, d[VRC_LGROUP - 1] );
+        if constexpr( DEPTH )
+            vrc_mip_depth_group< VRC_LGROUP >( *z, m0, m, d, valid, stepSize );
     }
 }
 
@@ -2561,8 +2712,10 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
 {
     constexpr bool TRILINEAR = vrc_mode_base( MODE ) == VRC_MODE_MIP_TRILINEAR;
     constexpr int FOLD = vrc_mode_fold( MODE );
+    constexpr bool DEPTH = vrc_mode_depth( MODE );
     if constexpr( FOLD == VRC_FOLD_MEAN )
     {
+        static_assert( !DEPTH, "the mean has no position" );
         vrc_mean_brick< CLAMP, FIXED, TRILINEAR, ATLAS_T, GROUP, BIG >( f, n, s, atlas, state, nSamples );
         return;
     }
@@ -2572,6 +2725,8 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
     vrc_mip_from_bits( vrc_float_bits( state.x ), m );
     bool has = state.y != 0.0f;
     bool march = s.dist > 0.0f;
+    /* depth tracking: z of the state = D; could an equal sample of this brick lie nearer? */
+    vrc_mip_depth z = { state.z, s.tNear, 0u, DEPTH && s.tNear < state.z };
     if( march && n.slotInfoIndex != 0u )
     {
         if constexpr( FOLD == VRC_FOLD_MIN )
@@ -2579,6 +2734,14 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
             if( f.slotMin != nullptr && has )
             {
                 const uint32_t word = f.slotMin[n.slotInfoIndex - 1u];
+                if constexpr( DEPTH )
+                {
+                    /* skipped: no sample can equal M, or none can beat it and none lies nearer than D */
+                    if( word != 0u && vrc_mip_cannot_lower< TRILINEAR, ATLAS_T >( word, m ) &&
+                        ( !z.tie || vrc_mip_cannot_reach< FOLD, TRILINEAR, ATLAS_T >( word, m ) ) )
+                        march = false;
+                }
+                else
                 if( word != 0u && vrc_mip_cannot_lower< TRILINEAR, ATLAS_T >( word, m ) )
                     march = false;
             }
@@ -2586,6 +2749,13 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
         else if( f.slotMax != nullptr && has )
         {
             const uint32_t word = f.slotMax[n.slotInfoIndex - 1u];
+            if constexpr( DEPTH )
+            {
+                if( word != 0u && vrc_mip_cannot_raise< TRILINEAR, ATLAS_T >( word, m ) &&
+                    ( !z.tie || vrc_mip_cannot_reach< FOLD, TRILINEAR, ATLAS_T >( word, m ) ) )
+                    march = false;
+            }
+            else
             if( word != 0u && vrc_mip_cannot_raise< TRILINEAR, ATLAS_T >( word, m ) )
                 march = false;
         }
@@ -2596,6 +2766,15 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
                 const uint32_t word = f.slotInfo[n.slotInfoIndex - 1u];
                 if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) == VRC_SLOT_KNOWN )
                 {
+                    if constexpr( DEPTH )
+                    {
+                        /* (value, seg.tNear): the segment's first sample, j = 0, is the nearest of its equal ones */
+                        const D m0 = m;
+                        m = vrc_mip_fold< FOLD >( m, (D)( word & VRC_SLOT_VALUE_MASK ) );
+                        if( m != m0 || ( z.tie && m == (D)( word & VRC_SLOT_VALUE_MASK ) ) )
+                            z.d = s.tNear;
+                    }
+                    else
                     m = vrc_mip_fold< FOLD >( m, (D)( word & VRC_SLOT_VALUE_MASK ) );
                     has = true;
                     nSamples += vrc_step_count( s.dist, f.stepSize );
@@ -2619,6 +2798,14 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
             local.slotBase = 0u;
             slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
         }
+        if constexpr( DEPTH )
+        {
+            if constexpr( TRILINEAR )
+                vrc_mip_segment_trilinear< CLAMP, ATLAS_T, FOLD, true >( f, local, s, travel, slot, m, nSamples, &z );
+            else
+                vrc_mip_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, D, FOLD, true >( f, local, s, travel, slot, m, nSamples, &z );
+        }
+        else
         if constexpr( TRILINEAR )
             vrc_mip_segment_trilinear< CLAMP, ATLAS_T, FOLD >( f, local, s, travel, slot, m, nSamples );
         else
@@ -2627,6 +2814,8 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
     }
     state.x = vrc_bits_float( vrc_mip_bits( m ) );
     state.y = has ? 1.0f : 0.0f;
+    if constexpr( DEPTH )
+        state.z = z.d;
 }
 
 /* the pixel of a maximum M: TF((M - r0) / (r1 - r0)) as vrc_classify fetches it (256 texels, linear, the weight in
@@ -3395,6 +3584,23 @@ VRC_HD void vrc_pixel_ray_lod( const vrc_frame& f, const vrc_dev_node* __restric
     pixelBuffer[pixelPos] = color;
 }
 
+/* the depth cue of a MIP pixel: w = 1 - strength * u, u = where D lies in the ray's own interval [tNearGlobal, tFarGlobal]
+ * (vrc_setup_ray's), clamped to [0, 1]; u = 0 where that interval is empty, 1 for D = +infinity.  Float, in this order. */
+VRC_HD float vrc_mip_cue_weight( float strength, float depth, float tNearGlobal, float tFarGlobal )
+{
+    VRC_STRICT_FP
+    const float span = tFarGlobal - tNearGlobal;
+    float u = 0.0f;
+    if( span > 0.0f )
+    {
+        u = ( depth - tNearGlobal ) / span;
+        u = u > 0.0f ? u : 0.0f; /* (a NaN -- an infinite interval -- reads 0) */
+        u = u < 1.0f ? u : 1.0f;
+    }
+    const float su = strength * u;
+    return 1.0f - su;
+}
+
 /* ------------------------------------------------------------------------------------------
  * MIP pixel: the bricks of the ray as the composite pixel finds them (DDA: the grid walk; else the list in its order,
  * with the reference's `break` where a brick's tNear lies beyond the ray's interval, which is part of the sample set's
@@ -3415,10 +3621,13 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
     static_assert( vrc_mode_is_mip( MODE ), "a MIP mode" );
     constexpr int FOLD = vrc_mode_fold( MODE );
     constexpr bool FLOAT_M = vrc_mode_base( MODE ) == VRC_MODE_MIP_TRILINEAR || sizeof( ATLAS_T ) == 4;
+    constexpr bool DEPTH = vrc_mode_depth( MODE );
+    static_assert( !DEPTH || FOLD != VRC_FOLD_MEAN, "the mean has no position" );
     const vrc_ray r = vrc_setup_ray( f, px, f.rowMap ? f.rowMap[py] : py );
     const uint32_t pixelPos = py * f.width + px;
     const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
     uint32_t bits = VRC_MIP_EMPTY;
+    float depth = vrc_bits_float( 0x7F800000u ); /* (depth tracking: D, +infinity while no sample equals M) */
     uint32_t meanLo = 0u, meanHi = 0u, meanCount = 0u; /* (the mean fold's state; an integer 0 and a double 0 alike) */
     if( r.hit )
     {
@@ -3444,11 +3653,15 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
             {
                 state.x = vrc_bits_float( bits );
                 state.y = 1.0f;
+                if constexpr( DEPTH )
+                    depth = f.mipDepth[pixelPos]; /* (a later pass: the first has bits = VRC_MIP_EMPTY here) */
             }
             else if( FOLD == VRC_FOLD_MIN )
                 state.x = vrc_bits_float( FLOAT_M ? 0x7F800000u : 0xFFFFFFFFu ); /* +infinity, or above every voxel */
             else if( FLOAT_M )
                 state.x = vrc_bits_float( 0xFF800000u ); /* a float M starts at -infinity */
+            if constexpr( DEPTH )
+                state.z = depth;
         }
         if constexpr( DDA )
             vrc_ray_grid_dda< CLAMP, true, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, r, nodes, gridTable, atlas, tfp, cls, state,
@@ -3479,7 +3692,11 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
             meanCount += nSamples - before;
         }
         else
+        {
             bits = state.y != 0.0f ? vrc_float_bits( state.x ) : VRC_MIP_EMPTY;
+            if constexpr( DEPTH )
+                depth = state.y != 0.0f ? state.z : depth;
+        }
     }
     if constexpr( FOLD == VRC_FOLD_MEAN )
     {
@@ -3500,10 +3717,30 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
                 d = (float)bits;
             else
                 d = vrc_bits_float( bits );
+            if constexpr( DEPTH )
+            {
+                f.mipDepth[pixelPos] = depth;
+                vrc_f4 e = vrc_classify_mip( tfp, d, cls );
+                if( f.mipCue > 0.0f )
+                {
+                    const float w = vrc_mip_cue_weight( f.mipCue, depth, r.tNearGlobal, r.tFarGlobal );
+                    e.x = w * e.x;
+                    e.y = w * e.y;
+                    e.z = w * e.z;
+                    e.w = w * e.w;
+                }
+                pixelBuffer[pixelPos] = e;
+            }
+            else
             pixelBuffer[pixelPos] = vrc_classify_mip( tfp, d, cls );
         }
-        else if( f.clearFirst )
-            pixelBuffer[pixelPos] = zero;
+        else
+        {
+            if constexpr( DEPTH )
+                f.mipDepth[pixelPos] = vrc_bits_float( 0x7F800000u );
+            if( f.clearFirst )
+                pixelBuffer[pixelPos] = zero;
+        }
     }
 }
 

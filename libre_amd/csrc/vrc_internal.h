@@ -181,6 +181,14 @@ struct vrc_projection_state
 };
 hipError_t vrc_launch_projection_values( const vrc_projection_state& st, float* values, uint32_t* counts, hipStream_t stream );
 
+/* the maximum and the minimum with the depth of the projected sample (vrc_kernels_mipdepth.hip; VRC_OPT_MIP_DEPTH,
+ * VRC_OPT_MIP_DEPTH_CUE): fold = VRC_FOLD_MAX or VRC_FOLD_MIN, frame.mipDepth set beside frame.mipMax ... */
+hipError_t vrc_launch_raycast_mip_depth( const vrc_raycast_args& a, int fold, hipStream_t stream );
+/* ... and what vrc_get_projection_depths returns of it: t[i] = D of pixel i, xyz (or NULL) = origin + D * dir of the
+ * pixel's ray in the frame f of the last pass (its camera, pixel buffer geometry and row map).  Device pointers */
+hipError_t vrc_launch_projection_depths( const vrc_frame& f, const float* depth, uint32_t pixels, float* t, float* xyz,
+                                         hipStream_t stream );
+
 /* LDS-staged form (vrc_kernels_lds.hip): needs gridTable, !clamp, 8x8 tiles */
 hipError_t vrc_launch_raycast_lds( const vrc_raycast_args& a, hipStream_t stream );
 

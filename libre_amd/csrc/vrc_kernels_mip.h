@@ -31,8 +31,13 @@
  *     at 62-72 VGPRs, so 7-8 waves are resident; whether they want a limit of 5, as the composite gather kernel did
  *     (its sixth wave thrashes the vector L1), is not measured, and nothing enforces one.
  *   everything else (trilinear: 32 gathers and 4 x 12 address parts in flight; the float position chain; the clamped
- *     sampler; 64-bit slot bases): at least 4, as the composite forms that spilled at 5. */
-#define VRC_MIP_MIN_WAVES ( ( vrc_mode_base( MODE ) == VRC_MODE_MIP && FIXED && !CLAMP && !BIG ) ? 5 : 4 )
+ *     sampler; 64-bit slot bases): at least 4, as the composite forms that spilled at 5.
+ *   trilinear samples with depth tracking (vrc_kernels_mipdepth.hip): at least 3.  The group's eight samples stay live
+ *     past the fold for the index search, and at 4 (128 VGPRs) the grid-walk forms with the clamped sampler spilled
+ *     12-16 bytes a lane; at 3 none does (DESIGN.md section 4.6 has the table). */
+#define VRC_MIP_MIN_WAVES                                                                                          \
+    ( ( vrc_mode_base( MODE ) == VRC_MODE_MIP && FIXED && !CLAMP && !BIG )                            ? 5          \
+      : ( vrc_mode_depth( MODE ) && vrc_mode_base( MODE ) == VRC_MODE_MIP_TRILINEAR ) ? 3 : 4 )
 #define VRC_MIP_MAX_WAVES ( ( vrc_mode_base( MODE ) == VRC_MODE_MIP && FIXED && !CLAMP && !BIG ) ? 5 : 8 )
 
 template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >

@@ -29,7 +29,7 @@ EXPORTS = [
     "lvh_app_set_modelview", "lvh_app_set_time_step", "lvh_datasource_frame_range", "lvh_app_set_colormap", "lvh_app_set_clip_planes",
     "lvh_app_set_bands", "lvh_app_set_frames_in_flight", "lvh_app_select_slot", "lvh_app_set_option", "lvh_app_set_data_range", "lvh_app_set_ray_lod", "lvh_app_set_stream", "lvh_app_set_framebuffer", "lvh_app_render_frame",
     "lvh_app_get_stats", "lvh_app_wait_uploads", "lvh_app_synchronize", "lvh_app_volume_info",
-    "lvh_app_set_histogram", "lvh_app_frame_histogram",
+    "lvh_app_set_histogram", "lvh_app_frame_histogram", "lvh_app_pick",
     "lvh_comm_unique_id", "lvh_app_comm_create", "lvh_app_set_layout", "lvh_app_gather_tiles",
     "lvh_app_visible_set", "lvh_app_node_order", "lvh_app_view_matrices", "lvh_app_cache_stats", "lvh_select_visibles",
     "lvh_selftest_cache", "lvh_selftest_plugin_factory", "lvh_selftest_camera",
@@ -71,6 +71,8 @@ def load_library():
     L.lvh_app_set_histogram.argtypes = [vp, C.c_int]
     L.lvh_app_frame_histogram.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                           C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+    L.lvh_app_pick.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                               C.c_float * 3]
     L.lvh_app_volume_info.argtypes = [vp, C.c_uint32 * 3, C.c_uint32 * 3, C.c_uint32 * 3,
                                       C.c_float * 3, C.POINTER(C.c_uint32), C.c_uint32 * 3]
     L.lvh_app_visible_set.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
@@ -192,6 +194,14 @@ class App:
         check(self.L, self.L.lvh_app_frame_histogram(self.h, bins.ctypes.data, n.value, C.byref(n), rng,
                                                       C.byref(area), C.byref(fid)))
         return bins, (float(rng[0]), float(rng[1])), float(area.value), int(fid.value)
+
+    def pick(self, x, y):
+        """What lies behind pixel (x, y) of the window in the selected slot's last frame -- a MIP frame (maximum or
+        minimum) rendered with VRC_OPT_MIP_DEPTH or a depth cue: (hit, value, t, (x, y, z)); value is the projected
+        value in the volume's own units, t the ray parameter of the nearest sample that has it, xyz its position."""
+        hit, value, t, xyz = C.c_int(), C.c_float(), C.c_float(), (C.c_float * 3)()
+        check(self.L, self.L.lvh_app_pick(self.h, int(x), int(y), C.byref(hit), C.byref(value), C.byref(t), xyz))
+        return bool(hit.value), float(value.value), float(t.value), (float(xyz[0]), float(xyz[1]), float(xyz[2]))
 
     def wait_uploads(self):
         check(self.L, self.L.lvh_app_wait_uploads(self.h))

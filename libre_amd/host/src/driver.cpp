@@ -9,6 +9,11 @@
 
 #include "livre_hip/hip.h"
 
+/* the read-backs of a MIP frame are newer than ABI 4 and bound weakly: a device layer without them (the CPU stand-in of
+ * the host sanitizer builds, an older libvrc_hip.so) still loads, and lvh_app_pick says so */
+#pragma weak vrc_get_projection_values
+#pragma weak vrc_get_projection_depths
+
 using namespace livre;
 
 namespace
@@ -36,7 +41,14 @@ struct lvh_app
     RenderStatistics lastStats;
     std::vector< uint32_t > rowMap; /* lvh_app_set_bands */
     std::vector< std::unique_ptr< Renderer > > extraRenderers; /* frames in flight beyond the first */
-    std::map< int, int64_t > projectionOptions; /* VRC_OPT_PROJECTION / VRC_OPT_MIP_SKIP / VRC_OPT_MIP_FOLD as set: for renderers made later */
+    std::map< int, int64_t > projectionOptions; /* VRC_OPT_PROJECTION / VRC_OPT_MIP_SKIP / _FOLD / _DEPTH / _DEPTH_CUE as set: for renderers made later */
+    struct PickFrame /* per renderer slot: where its last frame's pixel buffer lies in the window (lvh_app_pick) */
+    {
+        bool valid = false;
+        uint32_t tile[4] = { 0, 0, 0, 0 };
+        std::vector< uint32_t > rowMap;
+    };
+    PickFrame pickFrames[8];
     uint32_t slot = 0;
     std::string rendererName;
     float dataRange[2] = { 0.0f, 0.0f }; /* lvh_app_set_data_range; empty = the voxel type's range */
@@ -293,6 +305,7 @@ int lvh_app_set_frames_in_flight( lvh_app* app, uint32_t n )
         while( app->extraRenderers.size() + 1 > n )
         {
             app->histFrames[app->extraRenderers.size()] = lvh_app::HistogramFrame();
+            app->pickFrames[app->extraRenderers.size()] = lvh_app::PickFrame();
             app->extraRenderers.pop_back();
         }
         if( app->slot >= n )
@@ -315,7 +328,8 @@ int lvh_app_select_slot( lvh_app* app, uint32_t slot )
 int lvh_app_set_option( lvh_app* app, int option, int64_t value )
 {
     if( !app ) return fail( "NULL argument" );
-    if( option == VRC_OPT_PROJECTION || option == VRC_OPT_MIP_SKIP || option == VRC_OPT_MIP_FOLD )
+    if( option == VRC_OPT_PROJECTION || option == VRC_OPT_MIP_SKIP || option == VRC_OPT_MIP_FOLD ||
+        option == VRC_OPT_MIP_DEPTH || option == VRC_OPT_MIP_DEPTH_CUE )
     {
         /* how the app forms its pixels: every renderer it has, and every one it makes later (lvh_app_set_frames_in_flight) */
         try
@@ -407,10 +421,67 @@ int lvh_app_render_frame( lvh_app* app, float* host, lvh_frame_stats* stats )
             hf.frameId = app->frameId;
         }
         ++app->frameId;
+        {
+            lvh_app::PickFrame& pf = app->pickFrames[app->slot];
+            pf.valid = true;
+            app->tile( pf.tile );
+            pf.rowMap = app->rowMap;
+        }
         if( host )
             app->renderer().readFrame( host );
         if( stats )
             fillStats( app, stats, false );
+        return 0;
+    }
+    catch( const std::exception& e )
+    {
+        return fail( e.what() );
+    }
+}
+
+int lvh_app_pick( lvh_app* app, uint32_t x, uint32_t y, int* hit, float* value, float* t, float xyz[3] )
+{
+    if( !app ) return fail( "NULL argument" );
+    const lvh_app::PickFrame& pf = app->pickFrames[app->slot];
+    if( !pf.valid )
+        return fail( "lvh_app_pick: no frame rendered in this slot yet" );
+    if( x >= app->params.width || y >= app->params.height )
+        return fail( "lvh_app_pick: (x, y) outside the window" );
+    /* window -> pixel buffer of that frame: its tile of the window, or the rows of its bands in their order */
+    uint32_t bx = x, by = y, rows = pf.tile[3];
+    if( !pf.rowMap.empty() )
+    {
+        const auto at = std::find( pf.rowMap.begin(), pf.rowMap.end(), y );
+        if( at == pf.rowMap.end() )
+            return fail( "lvh_app_pick: row " + std::to_string( y ) + " is not in the bands this process rendered (lvh_app_set_bands)" );
+        by = uint32_t( at - pf.rowMap.begin() );
+        rows = uint32_t( pf.rowMap.size() );
+    }
+    else
+    {
+        if( x < pf.tile[0] || x >= pf.tile[0] + pf.tile[2] || y < pf.tile[1] || y >= pf.tile[1] + pf.tile[3] )
+            return fail( "lvh_app_pick: (x, y) is outside the tile this process rendered" );
+        bx = x - pf.tile[0];
+        by = y - pf.tile[1];
+    }
+    try
+    {
+        if( !vrc_get_projection_values || !vrc_get_projection_depths )
+            return fail( "lvh_app_pick: the device layer has no vrc_get_projection_depths" );
+        vrc_ctx* const ctx = app->renderer().deviceContext();
+        const size_t pixels = size_t( pf.tile[2] ) * rows, i = size_t( by ) * pf.tile[2] + bx;
+        std::vector< float > values( pixels ), depths( pixels ), pos( pixels * 3 );
+        std::vector< uint32_t > counts( pixels );
+        /* (the depths first: their refusal says why a frame has none -- composite, no depth tracking, the mean) */
+        if( vrc_get_projection_depths( ctx, depths.data(), pos.data() ) != VRC_OK ||
+            vrc_get_projection_values( ctx, values.data(), counts.data() ) != VRC_OK )
+            return fail( std::string( "lvh_app_pick: the slot's last frame has no depth to pick from: " ) + vrc_last_error() );
+        if( hit ) *hit = counts[i] != 0u ? 1 : 0;
+        if( value ) *value = values[i];
+        if( t ) *t = depths[i];
+        if( xyz )
+            for( int a = 0; a < 3; ++a )
+                xyz[a] = pos[3 * i + a];
         return 0;
     }
     catch( const std::exception& e )

@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libvrc_hip.so")
 VRC_OK, VRC_EINVAL, VRC_EHIP, VRC_EFULL, VRC_ENOMEM, VRC_EUNSUPPORTED, VRC_EHIERARCHY, VRC_ECOMM = range(8)
 OPT_KERNEL, OPT_FILTER, OPT_TF_FRAC_BITS, OPT_COUNT_SAMPLES, OPT_TILE_ORDER, OPT_STEPPING, OPT_VARIANT, OPT_KERNEL_USED, OPT_KERNEL_TIMING, OPT_DEPTH_SPLIT, OPT_ERT_COMPACTION, OPT_GREY_TABLE, OPT_PACKED_ATLAS, OPT_GRID_WALK_USED, OPT_UNIFORM_BRICKS = range(1, 16)
 OPT_PROJECTION, OPT_MIP_SKIP, OPT_MIP_FOLD = 16, 17, 18
+OPT_MIP_DEPTH, OPT_MIP_DEPTH_CUE = 19, 20
 PROJECTION_COMPOSITE, PROJECTION_MIP = 0, 1
 MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2
 VARIANT_CUDARAYCASTER, VARIANT_GLRAYCASTER = 0, 1
@@ -63,7 +64,7 @@ EXPORTS = [
     "vrc_pool_release_slot", "vrc_pool_info", "vrc_pool_synchronize", "vrc_pool_read_region",
     "vrc_pool_histogram", "vrc_pool_enable_histograms", "vrc_frame_histogram", "vrc_get_frame_histogram",
     "vrc_update", "vrc_pre_render", "vrc_set_row_map", "vrc_set_framebuffer", "vrc_get_framebuffer", "vrc_render",
-    "vrc_post_render", "vrc_synchronize", "vrc_get_stats", "vrc_get_ray_counts", "vrc_get_projection_values", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
+    "vrc_post_render", "vrc_synchronize", "vrc_get_stats", "vrc_get_ray_counts", "vrc_get_projection_values", "vrc_get_projection_depths", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
     "vrc_comm_unique_id", "vrc_comm_create", "vrc_comm_destroy", "vrc_comm_info", "vrc_gather_tiles",
 ]
 COMM_ID_BYTES = 128
@@ -134,6 +135,8 @@ def load_library(path=None):
     L.vrc_get_ray_counts.argtypes = [vp, C.POINTER(C.c_uint32 * 8), C.POINTER(C.c_int)]
     if hasattr(L, "vrc_get_projection_values"):  # (a symbol newer than ABI 4: an older library, e.g. a developer A/B build, lacks it)
         L.vrc_get_projection_values.argtypes = [vp, vp, vp]
+    if hasattr(L, "vrc_get_projection_depths"):
+        L.vrc_get_projection_depths.argtypes = [vp, vp, vp]
     L.vrc_comm_unique_id.argtypes = [C.c_char_p]
     L.vrc_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     L.vrc_comm_destroy.argtypes = [vp]
@@ -149,3 +152,16 @@ def load_library(path=None):
 def check(L, rc):
     if rc != VRC_OK:
         raise VrcError(rc, (L.vrc_last_error() or b"").decode("utf-8", "replace"))
+
+
+def projection_depths(L, ctx, width, height, xyz=True):
+    """vrc_get_projection_depths of the frame just rendered with depth tracking: (t, xyz) as float32 arrays of
+    height x width and height x width x 3 (xyz None if not asked for).  height: the rows of the pixel buffer -- the
+    mapped rows under a row map.  t is +infinity where the ray took no sample."""
+    import numpy as np
+    if not hasattr(L, "vrc_get_projection_depths"):
+        raise VrcError(VRC_EUNSUPPORTED, "this libvrc_hip.so has no vrc_get_projection_depths")
+    t = np.empty((height, width), dtype=np.float32)
+    p = np.empty((height, width, 3), dtype=np.float32) if xyz else None
+    check(L, L.vrc_get_projection_depths(ctx, t.ctypes.data, p.ctypes.data if xyz else None))
+    return t, p

@@ -11,7 +11,13 @@ Under rocprofv3 (a counter run is kept apart from any tracing) pass --only to ke
 --fold (VRC_OPT_MIP_FOLD): the same workloads for the minimum and the mean beside the maximum.  Per volume, camera and
 filter: composite, the maximum with skipping off three times (their spread is what a difference has to exceed to mean
 anything), the minimum with skipping off and on, the mean; every row against the composite kernel and against the
-first maximum run.  The report then goes to profiles/fold_projection.txt."""
+first maximum run.  The report then goes to profiles/fold_projection.txt.
+
+--depth (VRC_OPT_MIP_DEPTH, VRC_OPT_MIP_DEPTH_CUE): depth tracking against the same frame without it, all in this one
+process.  Per volume (mem://, hash://), camera, filter (point and trilinear samples on both volumes) and fold (maximum,
+minimum), skipping on: depth off three times (their spread is what a ratio has to exceed to mean anything), depth on,
+depth on with a cue of 0.5; the last two against the first depth-off run.  A library without the two options (the
+parent of the change that added them) runs the depth-off rows alone.  The report goes to profiles/mip_depth.txt."""
 import argparse
 import os
 import sys
@@ -30,6 +36,53 @@ FOLD_ROWS = (("composite", vrc.PROJECTION_COMPOSITE, 1, vrc.MIP_FOLD_MAX), ("max
              ("max_skip0_b", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MAX), ("max_skip0_c", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MAX),
              ("min_skip0", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MIN), ("min_skip1", vrc.PROJECTION_MIP, 1, vrc.MIP_FOLD_MIN),
              ("mean", vrc.PROJECTION_MIP, 0, vrc.MIP_FOLD_MEAN))
+# (row, VRC_OPT_MIP_DEPTH, VRC_OPT_MIP_DEPTH_CUE)
+DEPTH_ROWS = (("off", 0, 0), ("off_b", 0, 0), ("off_c", 0, 0), ("depth", 1, 0), ("depth_cue", 1, 500))
+OPT_MIP_DEPTH, OPT_MIP_DEPTH_CUE = getattr(vrc, "OPT_MIP_DEPTH", 19), getattr(vrc, "OPT_MIP_DEPTH_CUE", 20)
+
+
+def depth_report(a, say):
+    """--depth: see the module's text."""
+    say("# volume camera filter fold row: kernel, kernel ms per frame, samples per frame, ms against the first depth-off run")
+    for volume, scheme in (("C2", "mem"), ("noise", "hash")):
+        uri = "%s://#%d,%d,%d,%d" % (scheme, a.voxels, a.voxels, a.voxels, a.block)
+        with driver.App(uri, a.viewport, a.viewport, synchronous=True, gpu_cache_mb=3072) as probe:
+            leaf = probe.volume_info()["depth"] - 1
+        with driver.App(uri, a.viewport, a.viewport, synchronous=True, min_lod=leaf, max_lod=leaf, gpu_cache_mb=3072) as app:
+            app.set_colormap(linear_ramp(a.alpha))
+            app.set_option(vrc.OPT_PROJECTION, vrc.PROJECTION_MIP)
+            app.set_option(vrc.OPT_MIP_SKIP, 1)
+            try:
+                app.set_option(OPT_MIP_DEPTH, 0)
+                have = True
+            except driver.DriverError:
+                have = False
+                say("# this library has no VRC_OPT_MIP_DEPTH: depth-off rows only")
+            for camera, spin in CAMERAS:
+                app.set_camera(spin=spin)
+                for flt in (0, 1):
+                    fname = "trilinear" if flt else "nearest"
+                    app.set_option(vrc.OPT_FILTER, vrc.FILTER_TRILINEAR if flt else vrc.FILTER_NEAREST)
+                    for fold, foldname in ((vrc.MIP_FOLD_MAX, "max"), (vrc.MIP_FOLD_MIN, "min")):
+                        app.set_option(vrc.OPT_MIP_FOLD, fold)
+                        first = None
+                        for row, depth, cue in DEPTH_ROWS:
+                            if a.only and a.only != "%s:%s:%s:%s:%s" % (volume, camera, fname, foldname, row):
+                                continue
+                            if (depth or cue) and not have:
+                                continue
+                            if have:
+                                app.set_option(OPT_MIP_DEPTH, depth)
+                                app.set_option(OPT_MIP_DEPTH_CUE, cue)
+                            n = count_samples(app)
+                            ms = time_kernel(app, a.warmup, a.steps)
+                            kernel = (vrc.load_library().vrc_last_kernel() or b"").decode()
+                            first = ms if row == "off" else first
+                            say("%-5s %-8s %-9s %-3s %-9s %-62s %8.3f ms %13d samples %s" % (
+                                volume, camera, fname, foldname, row, kernel, ms, n, "x%.3f" % (ms / first) if first else "-"))
+                        if have:
+                            app.set_option(OPT_MIP_DEPTH, 0)
+                            app.set_option(OPT_MIP_DEPTH_CUE, 0)
 
 
 def linear_ramp(alpha):
@@ -38,14 +91,13 @@ def linear_ramp(alpha):
 
 
 def time_kernel(app, n_warm, n_timed):
-    import torch
     for _ in range(n_warm):
         app.render_frame(readback=False)
-    torch.cuda.synchronize()
+    app.synchronize()
     app.stats()
     for _ in range(n_timed):
         app.render_frame(readback=False)
-    torch.cuda.synchronize()
+    app.synchronize()  # (the renderer's own stream; torch, imported after the library, would find no device)
     st = app.stats()
     return st.kernel_ms_sum / max(1, st.kernel_launches)
 
@@ -68,10 +120,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--only", default=None, help="volume:camera:filter:row, e.g. noise:off_axis:nearest:mip_skip0")
     ap.add_argument("--fold", action="store_true", help="the minimum and the mean beside the maximum (profiles/fold_projection.txt)")
+    ap.add_argument("--depth", action="store_true", help="depth tracking against the same frames without it (profiles/mip_depth.txt)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     rows = FOLD_ROWS if a.fold else ROWS
-    a.out = a.out or os.path.join(ROOT, "profiles", "fold_projection.txt" if a.fold else "mip_projection.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "mip_depth.txt" if a.depth else "fold_projection.txt" if a.fold else "mip_projection.txt")
     driver.load_library()
     lines = []
 
@@ -81,6 +134,13 @@ def main():
 
     say("# tools/dev_mip.py: %d^3 voxels in %d^3 bricks, %dx%d viewport, alpha %.3g, %d frames after %d warm-up" % (
         a.voxels, a.block, a.viewport, a.viewport, a.alpha, a.steps, a.warmup))
+    if a.depth:
+        depth_report(a, say)
+        if not a.only:
+            os.makedirs(os.path.dirname(a.out), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     say("# volume camera filter row: kernel, kernel ms per frame, samples per frame, Gsamples/s, ms against composite%s" % (
         ", ms against the first maximum run" if a.fold else ""))
     for volume, scheme, filters in (("C2", "mem", (0,)), ("noise", "hash", (0, 1))):
