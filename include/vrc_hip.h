@@ -179,6 +179,18 @@ typedef struct
                                     * frame tracks depth whatever VRC_OPT_MIP_DEPTH says, and a pixel is darkened by
                                     * where D lies in its ray's interval.  Anything else: VRC_EINVAL */
 
+#define VRC_OPT_STREAM_MARKERS 21   /* 0 (default) | 1.  What vrc_render puts on the stream besides the march.  0: the
+                                    * dispatch of a timed march that is one launch carries the second timing event as
+                                    * its own stop event, which is also what an upload that recycles a slot waits for,
+                                    * and the stream waits for the pool's uploads once per upload, not once per frame:
+                                    * a steady-state frame is one marker (the first timing event, or the fence of a
+                                    * march that is not timed) and the dispatch.  vrc_stats' times then end with the
+                                    * dispatch itself, not with a marker behind it.  1: a wait for the last upload, an
+                                    * event recorded before and one behind the march, and a fence recorded behind
+                                    * those, every frame (what the library did before the option existed; its times
+                                    * include the second marker's latency).  Frames, counts and the ordering against
+                                    * uploads are the same either way */
+
 /* A MIP frame (VRC_OPT_PROJECTION = VRC_PROJECTION_MIP).
  *   Sample set.  A ray's sample set S is exactly what the composite march takes with a transfer function whose alpha
  *     is 0 everywhere: the same ray set-up, global-box and clip-plane interval and near plane; the same node list

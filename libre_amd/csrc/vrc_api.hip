@@ -17,6 +17,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -42,6 +43,21 @@ int fail( int code, const std::string& msg )
 constexpr int kStagingSlots = 8;
 constexpr int kNodeStages = 4;
 } // namespace
+
+/* the timing events of a context: one pair per raycast launch since the last vrc_get_stats (ring, grows on demand).
+ * Shared with the render fences of the pools the context marched from (vrc_pool::RenderFence::keep) */
+struct vrc_event_ring
+{
+    std::vector< std::pair< hipEvent_t, hipEvent_t > > pairs;
+    ~vrc_event_ring()
+    {
+        for( auto& pr : pairs )
+        {
+            (void)hipEventDestroy( pr.first );
+            (void)hipEventDestroy( pr.second );
+        }
+    }
+};
 
 struct vrc_pool
 {
@@ -84,7 +100,12 @@ struct vrc_pool
     struct RenderFence
     {
         const vrc_ctx* ctx;
-        hipEvent_t event;
+        hipEvent_t event; /* the pool's own, recorded behind a march or a frame histogram, or a march's stop event */
+        /* what an upload waits for: `event`, or the stop event of the context's last march where the dispatch carried
+         * one of the context's timing events (VRC_OPT_STREAM_MARKERS = 0); `keep` holds those events alive for as long
+         * as this entry names one, whatever becomes of the context */
+        hipEvent_t last;
+        std::shared_ptr< vrc_event_ring > keep;
     };
     std::vector< RenderFence > renderFences; /* last march of every context that used this pool */
 
@@ -94,6 +115,7 @@ struct vrc_pool
     hipStream_t copyStream[2] = { nullptr, nullptr };
     hipEvent_t lastUpload = nullptr;
     bool hasUpload = false;
+    uint64_t uploadGen = 0; /* counts the records of lastUpload: a stream that has waited for this one need not again */
 
     struct Staging
     {
@@ -193,7 +215,9 @@ struct vrc_ctx
     unsigned long long* hCounter = nullptr; /* pinned */
 
     /* one event pair per raycast launch since the last vrc_get_stats (ring, grows on demand) */
-    std::vector< std::pair< hipEvent_t, hipEvent_t > > evPairs;
+    std::shared_ptr< vrc_event_ring > evRing = std::make_shared< vrc_event_ring >();
+    /* the upload this context's stream has waited for: pool and its vrc_pool::uploadGen (0 = none) */
+    uint64_t waitedPoolUid = 0, waitedGen = 0;
     size_t evUsed = 0;
     double evFoldedMs = 0.0;      /* pairs taken out of a full ring before anyone asked for the statistics */
     uint32_t evFoldedLaunches = 0;
@@ -208,6 +232,7 @@ struct vrc_ctx
     int64_t optErtParts = 0;     /* VRC_OPT_ERT_COMPACTION */
     int64_t optPackedAtlas = 1;  /* VRC_OPT_PACKED_ATLAS */
     int64_t optUniformBricks = 1; /* VRC_OPT_UNIFORM_BRICKS */
+    int64_t optStreamMarkers = 0; /* VRC_OPT_STREAM_MARKERS */
     int64_t optProjection = VRC_PROJECTION_COMPOSITE; /* VRC_OPT_PROJECTION */
     int64_t optMipSkip = 1;                           /* VRC_OPT_MIP_SKIP */
     int64_t optMipFold = VRC_MIP_FOLD_MAX;            /* VRC_OPT_MIP_FOLD */
@@ -399,11 +424,7 @@ void vrc_ctx_destroy( vrc_ctx* c )
     if( c->hHistRefs ) (void)hipHostFree( c->hHistRefs );
     for( hipEvent_t e : c->histRefsEvent )
         if( e ) (void)hipEventDestroy( e );
-    for( auto& pr : c->evPairs )
-    {
-        (void)hipEventDestroy( pr.first );
-        (void)hipEventDestroy( pr.second );
-    }
+    c->evRing.reset(); /* (the events live on while a pool's render fence names one) */
     if( c->ownStream ) (void)hipStreamDestroy( c->ownStream );
     delete c;
 }
@@ -415,6 +436,7 @@ int vrc_ctx_set_stream( vrc_ctx* c, void* s )
     VRC_HIP_CHECK( hipSetDevice( c->device ) );
     VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
     c->stream = s ? (hipStream_t)s : c->ownStream;
+    c->waitedPoolUid = c->waitedGen = 0; /* the new stream has waited for no upload */
     return VRC_OK;
 }
 
@@ -447,6 +469,7 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
     case VRC_OPT_GREY_TABLE: c->optGreyTable = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_PACKED_ATLAS: c->optPackedAtlas = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_UNIFORM_BRICKS: c->optUniformBricks = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_STREAM_MARKERS: c->optStreamMarkers = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_PROJECTION:
         if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite) or 1 (maximum intensity)" );
@@ -501,6 +524,7 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_GREY_TABLE: *value = c->optGreyTable; return VRC_OK;
     case VRC_OPT_PACKED_ATLAS: *value = c->optPackedAtlas; return VRC_OK;
     case VRC_OPT_UNIFORM_BRICKS: *value = c->optUniformBricks; return VRC_OK;
+    case VRC_OPT_STREAM_MARKERS: *value = c->optStreamMarkers; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->optProjection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->optMipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->optMipFold; return VRC_OK;
@@ -672,6 +696,7 @@ static int pool_create( vrc_ctx* c, int voxelType, const uint32_t maxBlock[3], s
     {
         e = hipEventRecord( p->lastUpload, p->uploadStream ); /* a render before any upload waits for the clear too */
         p->hasUpload = true;
+        ++p->uploadGen;
     }
     for( int k = 0; k < 2 && e == hipSuccess; ++k )
         e = hipStreamCreateWithFlags( &p->copyStream[k], hipStreamNonBlocking );
@@ -737,7 +762,63 @@ static int pool_take_slot( vrc_pool* p, float slot[3], std::vector< hipEvent_t >
     slot[2] = s[2];
     if( s[3] != 0.0f )
         for( const auto& f : p->renderFences )
-            fences.push_back( f.event );
+            fences.push_back( f.last );
+    return VRC_OK;
+}
+
+/* the render fence of context c on the pool, made on first use (caller holds the mutex); NULL: vrc_last_error is set */
+static vrc_pool::RenderFence* pool_render_fence( vrc_pool* p, const vrc_ctx* c )
+{
+    for( auto& f : p->renderFences )
+        if( f.ctx == c )
+            return &f;
+    hipEvent_t e = nullptr;
+    const hipError_t err = hipEventCreateWithFlags( &e, hipEventDisableTiming );
+    if( err != hipSuccess )
+    {
+        (void)fail( VRC_EHIP, std::string( "render fence: " ) + hipGetErrorString( err ) );
+        return nullptr;
+    }
+    p->renderFences.push_back( { c, e, e, nullptr } );
+    return &p->renderFences.back();
+}
+
+/* order the context's stream behind every upload the pool has issued so far.  The stream waits once for each record of
+ * lastUpload (uploadGen): a wait it has made already orders everything it runs later.  VRC_OPT_STREAM_MARKERS = 1 waits
+ * before every march, as the library always did */
+static int ctx_wait_uploads( vrc_ctx* c, vrc_pool* p )
+{
+    std::lock_guard< std::mutex > lock( p->mutex );
+    if( !p->hasUpload )
+        return VRC_OK;
+    if( !c->optStreamMarkers && c->waitedPoolUid == p->uid && c->waitedGen == p->uploadGen )
+        return VRC_OK;
+    VRC_HIP_CHECK( hipStreamWaitEvent( c->stream, p->lastUpload, 0 ) );
+    c->waitedPoolUid = p->uid;
+    c->waitedGen = p->uploadGen;
+    return VRC_OK;
+}
+
+/* the context's render fence on the pool (pool_upload waits for it before it overwrites a recycled slot) now stands
+ * behind the context's last work on its stream: `done`, one of the context's timing events that already does (the
+ * pool keeps the context's events alive while it names one), or NULL = record the pool's own event there */
+static int pool_fence_behind( vrc_pool* p, vrc_ctx* c, hipEvent_t done )
+{
+    std::lock_guard< std::mutex > lock( p->mutex );
+    vrc_pool::RenderFence* const f = pool_render_fence( p, c );
+    if( !f )
+        return VRC_EHIP;
+    if( !done )
+    {
+        VRC_HIP_CHECK( hipEventRecord( f->event, c->stream ) );
+        f->last = f->event;
+        f->keep.reset();
+    }
+    else
+    {
+        f->last = done;
+        f->keep = c->evRing;
+    }
     return VRC_OK;
 }
 
@@ -891,6 +972,7 @@ static int pool_upload( vrc_pool* p, const void* src, bool srcIsDevice, const ui
             {
                 e = hipEventRecord( p->lastUpload, p->uploadStream );
                 p->hasUpload = true;
+                ++p->uploadGen;
             }
         }
         st.used = true;
@@ -948,6 +1030,7 @@ static bool pool_enable_packed( vrc_pool* p )
     {
         e = hipEventRecord( p->lastUpload, p->uploadStream );
         p->hasUpload = true;
+        ++p->uploadGen;
     }
     if( e != hipSuccess )
     {
@@ -1193,7 +1276,10 @@ int vrc_pool_enable_histograms( vrc_pool* p, uint32_t binCount, const uint32_t o
     if( e == hipSuccess )
         e = hipEventRecord( p->lastUpload, p->uploadStream );
     if( e == hipSuccess )
+    {
         p->hasUpload = true;
+        ++p->uploadGen;
+    }
     if( dEntries )
     {
         const hipError_t e2 = hipStreamSynchronize( p->uploadStream ); /* the entries are read by the launch */
@@ -1874,23 +1960,23 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
 
     /* order the march after every brick upload issued so far (fixes quirk Q9) */
     {
-        std::lock_guard< std::mutex > lock( pool->mutex );
-        if( pool->hasUpload )
-            VRC_HIP_CHECK( hipStreamWaitEvent( c->stream, pool->lastUpload, 0 ) );
+        const int rc = ctx_wait_uploads( c, pool );
+        if( rc != VRC_OK )
+            return rc;
     }
     if( c->optCount )
         VRC_HIP_CHECK( hipMemsetAsync( c->dCounter, 0, sizeof( unsigned long long ), c->stream ) );
-    if( c->optTiming && c->evUsed == c->evPairs.size() )
+    if( c->optTiming && c->evUsed == c->evRing->pairs.size() )
     {
-        if( c->evPairs.size() >= 4096 )
+        if( c->evRing->pairs.size() >= 4096 )
         {
             /* nobody has read the timings for 4096 launches: fold them into running sums (waits for the
              * launches still in flight, once per 4096) so that vrc_get_stats still accounts for every one */
-            VRC_HIP_CHECK( hipEventSynchronize( c->evPairs[c->evUsed - 1].second ) );
+            VRC_HIP_CHECK( hipEventSynchronize( c->evRing->pairs[c->evUsed - 1].second ) );
             for( size_t i = 0; i < c->evUsed; ++i )
             {
                 float ms = 0.f;
-                VRC_HIP_CHECK( hipEventElapsedTime( &ms, c->evPairs[i].first, c->evPairs[i].second ) );
+                VRC_HIP_CHECK( hipEventElapsedTime( &ms, c->evRing->pairs[i].first, c->evRing->pairs[i].second ) );
                 c->evFoldedMs += ms;
             }
             c->evFoldedLaunches += (uint32_t)c->evUsed;
@@ -1901,12 +1987,23 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             hipEvent_t a0 = nullptr, a1 = nullptr;
             VRC_HIP_CHECK( hipEventCreate( &a0 ) );
             VRC_HIP_CHECK( hipEventCreate( &a1 ) );
-            c->evPairs.push_back( { a0, a1 } );
+            c->evRing->pairs.push_back( { a0, a1 } );
         }
     }
     const std::pair< hipEvent_t, hipEvent_t > evp =
-        c->optTiming ? c->evPairs[c->evUsed++] : std::pair< hipEvent_t, hipEvent_t >( nullptr, nullptr );
+        c->optTiming ? c->evRing->pairs[c->evUsed++] : std::pair< hipEvent_t, hipEvent_t >( nullptr, nullptr );
     vrc_internal_note_kernel_fn( nullptr, 0, 0 ); /* set again by the launchers that report their occupancy */
+    /* VRC_OPT_STREAM_MARKERS = 0: the dispatch of a timed march that is one launch carries the pair's second event as its
+     * stop event, and that event is also what an upload that recycles a slot waits for.  The pair's first event is
+     * recorded in front of the dispatch: the runtime puts a marker on the queue for an attached start event all the
+     * same, and a dispatch that carries one holds up a copy queued behind it (profiles/r8_frame_packets.txt).  A
+     * launcher says whether it attached the event; the marches of several launches (depth split, ray compaction) do
+     * not, and theirs is recorded behind the sequence.  VRC_OPT_STREAM_MARKERS = 1, and a march that is not timed,
+     * record the pool's own fence behind the march */
+    const bool pairFences = c->optTiming && !c->optStreamMarkers;
+    bool attached = false;
+    a.stopEvent = pairFences ? evp.second : nullptr;
+    a.attached = &attached;
     if( c->optTiming )
         VRC_HIP_CHECK( hipEventRecord( evp.first, c->stream ) );
     VRC_HIP_CHECK( mipDepth    ? vrc_launch_raycast_mip_depth( a, (int)c->optMipFold, c->stream )
@@ -1916,21 +2013,12 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                    : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
                    : c->rayLod ? vrc_launch_raycast_raylod( a, c->stream )
                                : vrc_launch_raycast( a, c->stream ) );
-    if( c->optTiming )
+    if( c->optTiming && !attached ) /* (also a frame without tiles, which launches nothing) */
         VRC_HIP_CHECK( hipEventRecord( evp.second, c->stream ) );
     {
-        /* render fence of this context on the pool (see pool_upload) */
-        std::lock_guard< std::mutex > lock( pool->mutex );
-        hipEvent_t fence = nullptr;
-        for( const auto& f : pool->renderFences )
-            if( f.ctx == c )
-                fence = f.event;
-        if( !fence )
-        {
-            VRC_HIP_CHECK( hipEventCreateWithFlags( &fence, hipEventDisableTiming ) );
-            pool->renderFences.push_back( { c, fence } );
-        }
-        VRC_HIP_CHECK( hipEventRecord( fence, c->stream ) );
+        const int rc = pool_fence_behind( pool, c, pairFences ? evp.second : nullptr );
+        if( rc != VRC_OK )
+            return rc;
     }
     if( c->optCount )
         VRC_HIP_CHECK( hipMemcpyAsync( c->hCounter, c->dCounter, sizeof( unsigned long long ),
@@ -2086,11 +2174,11 @@ int vrc_get_stats( vrc_ctx* c, vrc_stats* out )
     c->stats.kernel_launches = 0;
     if( c->evUsed > 0 )
     {
-        VRC_HIP_CHECK( hipEventSynchronize( c->evPairs[c->evUsed - 1].second ) );
+        VRC_HIP_CHECK( hipEventSynchronize( c->evRing->pairs[c->evUsed - 1].second ) );
         float ms = 0.f;
         for( size_t i = 0; i < c->evUsed; ++i )
         {
-            VRC_HIP_CHECK( hipEventElapsedTime( &ms, c->evPairs[i].first, c->evPairs[i].second ) );
+            VRC_HIP_CHECK( hipEventElapsedTime( &ms, c->evRing->pairs[i].first, c->evRing->pairs[i].second ) );
             c->stats.kernel_ms_sum += ms;
         }
         c->stats.kernel_launches = (uint32_t)c->evUsed;
@@ -2184,9 +2272,9 @@ int vrc_frame_histogram( vrc_ctx* c, vrc_pool* pool, const float* slots, const u
     }
     /* the rows are written on the pool's upload stream */
     {
-        std::lock_guard< std::mutex > lock( pool->mutex );
-        if( pool->hasUpload )
-            VRC_HIP_CHECK( hipStreamWaitEvent( c->stream, pool->lastUpload, 0 ) );
+        const int rc = ctx_wait_uploads( c, pool );
+        if( rc != VRC_OK )
+            return rc;
     }
     if( n )
     {
@@ -2206,17 +2294,9 @@ int vrc_frame_histogram( vrc_ctx* c, vrc_pool* pool, const float* slots, const u
     {
         /* the context's render fence on the pool (pool_upload) now stands behind this reduction too: an upload that
          * recycles one of these slots does not overwrite its row while the reduction reads it */
-        std::lock_guard< std::mutex > lock( pool->mutex );
-        hipEvent_t fence = nullptr;
-        for( const auto& f : pool->renderFences )
-            if( f.ctx == c )
-                fence = f.event;
-        if( !fence )
-        {
-            VRC_HIP_CHECK( hipEventCreateWithFlags( &fence, hipEventDisableTiming ) );
-            pool->renderFences.push_back( { c, fence } );
-        }
-        VRC_HIP_CHECK( hipEventRecord( fence, c->stream ) );
+        const int rc = pool_fence_behind( pool, c, nullptr );
+        if( rc != VRC_OK )
+            return rc;
     }
     return VRC_OK;
 }

@@ -4,6 +4,7 @@
 #define VRC_INTERNAL_H
 
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #include "vrc_core.h"
@@ -148,7 +149,30 @@ struct vrc_raycast_args
                       * scalar base + 32-bit offset (BIG instances) */
     bool depthSplit; /* two waves per tile, near / far half of every ray (vrc_k_raycast_split): set by the host
                       * only when early ray termination cannot occur in this frame and the frame is cleared */
+    /* VRC_OPT_STREAM_MARKERS = 0: the event the march's own dispatch carries as its stop event (NULL = none), and where
+     * the launcher says that it did: a launcher whose march is one dispatch hands the event to it (vrc_launch_march) and
+     * sets *attached; the forms of several launches (depth split, ray compaction) leave both alone, and vrc_render
+     * records the event behind the sequence */
+    hipEvent_t stopEvent;
+    bool* attached;
 };
+
+/* the one dispatch of a single-launch march: with a's stop event if it has one (the dispatch then carries its own
+ * completion and end timestamp: no marker packet behind it), else the plain launch */
+template < typename... KArgs, typename... Args >
+static inline void vrc_launch_march( const vrc_raycast_args& a, void ( *kernel )( KArgs... ), dim3 grid, dim3 block,
+                                     uint32_t dynamicLds, hipStream_t stream, Args&&... args )
+{
+    static_assert( sizeof...( KArgs ) == sizeof...( Args ), "one argument per kernel parameter" );
+    if( a.stopEvent )
+    {
+        hipExtLaunchKernelGGL< KArgs... >( kernel, grid, block, dynamicLds, stream, nullptr, a.stopEvent, 0u,
+                                           static_cast< KArgs >( args )... );
+        *a.attached = true;
+    }
+    else
+        hipLaunchKernelGGL( kernel, grid, block, dynamicLds, stream, static_cast< KArgs >( args )... );
+}
 
 /* the frame's tile schedule (above): order: vrc_schedule_slots() uint32; scratch: VRC_TILE_SCRATCH_WORDS uint32;
  * bucket: one byte per super-tile (at most one per schedule slot) */

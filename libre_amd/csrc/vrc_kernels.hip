@@ -1037,11 +1037,11 @@ static hipError_t launch_variant( const vrc_raycast_args& a, hipStream_t stream 
                               (int)GROUP, BIG ? "true" : "false" );
     vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast< DDA, CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >,
                                  (int)VRC_WG_THREADS, 0 );
-    hipLaunchKernelGGL( ( vrc_k_raycast< DDA, CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG > ),
-                        dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WAVES_PER_WG - 1u ) / VRC_WAVES_PER_WG ),
-                        dim3( VRC_WG_THREADS ), 0, stream, a.frame, a.nodes, a.gridTable,
-                        (const ATLAS_T*)a.atlas, a.lut, a.classifier, a.pixelBuffer,
-                        a.sampleCounter, a.tileOrder, tilesX, nTiles );
+    vrc_launch_march( a, &vrc_k_raycast< DDA, CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >,
+                      dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WAVES_PER_WG - 1u ) / VRC_WAVES_PER_WG ),
+                      dim3( VRC_WG_THREADS ), 0, stream, a.frame, a.nodes, a.gridTable,
+                      (const ATLAS_T*)a.atlas, a.lut, a.classifier, a.pixelBuffer,
+                      a.sampleCounter, a.tileOrder, tilesX, nTiles );
     return hipGetLastError();
 }
 

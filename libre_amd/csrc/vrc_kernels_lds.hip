@@ -1340,9 +1340,9 @@ hipError_t launch_lds( const vrc_raycast_args& a, hipStream_t stream )
                               a.greyTable ? "true" : "false", RAYLOD ? "true" : "false",
                               sizeof( V ) == 1 ? "unsigned char" : "unsigned short", BIG ? "true" : "false" );
 #define VRC_LDS_LAUNCH( COUNT, GREY )                                                                             \
-    hipLaunchKernelGGL( ( vrc_k_raycast_lds< COUNT, LINEAR, GREY, RAYLOD, V, BIG > ), grid, block, 0, stream, a.frame, \
-                        a.nodes, a.gridTable, (const V*)a.atlas, a.lut, a.classifier, a.pixelBuffer,              \
-                        a.sampleCounter, a.tileOrder, tilesX, nTiles )
+    vrc_launch_march( a, &vrc_k_raycast_lds< COUNT, LINEAR, GREY, RAYLOD, V, BIG >, grid, block, 0, stream, a.frame,  \
+                      a.nodes, a.gridTable, (const V*)a.atlas, a.lut, a.classifier, a.pixelBuffer,                \
+                      a.sampleCounter, a.tileOrder, tilesX, nTiles )
     if( a.greyTable )
     {
         if( count ) VRC_LDS_LAUNCH( true, true ); else VRC_LDS_LAUNCH( false, true );

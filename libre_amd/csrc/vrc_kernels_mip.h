@@ -146,10 +146,10 @@ static hipError_t launch_mip( const vrc_raycast_args& a, hipStream_t stream )
                               BIG ? "true" : "false" );
     vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >,
                                  (int)VRC_MIP_WG_THREADS, 0 );
-    hipLaunchKernelGGL( ( vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG > ),
-                        dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WAVES_PER_GROUP - 1u ) / VRC_WAVES_PER_GROUP ),
-                        dim3( VRC_MIP_WG_THREADS ), 0, stream, a.frame, a.nodes, a.gridTable, (const ATLAS_T*)a.atlas,
-                        a.lut, a.classifier, a.pixelBuffer, a.sampleCounter, a.tileOrder, tilesX, nTiles );
+    vrc_launch_march( a, &vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >,
+                      dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WAVES_PER_GROUP - 1u ) / VRC_WAVES_PER_GROUP ),
+                      dim3( VRC_MIP_WG_THREADS ), 0, stream, a.frame, a.nodes, a.gridTable, (const ATLAS_T*)a.atlas,
+                      a.lut, a.classifier, a.pixelBuffer, a.sampleCounter, a.tileOrder, tilesX, nTiles );
     return hipGetLastError();
 }
 

@@ -128,13 +128,13 @@ static hipError_t launch_raylod( const vrc_raycast_args& a, hipStream_t stream )
                               FIXED ? "true" : "false", (int)MODE,
                               std::is_same< ATLAS_T, float >::value ? "float" : sizeof( ATLAS_T ) == 1 ? "unsigned char" : ( sizeof( ATLAS_T ) == 2 ? "unsigned short" : ( sizeof( ATLAS_T ) == 4 ? "unsigned int" : "unsigned long" ) ),
                               BIG ? "true" : "false" );
-    hipLaunchKernelGGL( ( vrc_k_raycast_raylod< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG > ),
-                        dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_RL_WAVES - 1u ) / VRC_RL_WAVES ),
-                        dim3( VRC_RL_THREADS ),
-                        lutEntries * ( MODE == VRC_MODE_GREY ? sizeof( vrc_f2 ) : sizeof( vrc_f4 ) ), stream, a.frame,
-                        a.nodes, a.gridTable,
-                        (const ATLAS_T*)a.atlas, a.lut, lutEntries, a.classifier, a.pixelBuffer,
-                        a.sampleCounter, a.tileOrder, tilesX, nTiles );
+    vrc_launch_march( a, &vrc_k_raycast_raylod< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG >,
+                      dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_RL_WAVES - 1u ) / VRC_RL_WAVES ),
+                      dim3( VRC_RL_THREADS ),
+                      (uint32_t)( lutEntries * ( MODE == VRC_MODE_GREY ? sizeof( vrc_f2 ) : sizeof( vrc_f4 ) ) ), stream,
+                      a.frame, a.nodes, a.gridTable,
+                      (const ATLAS_T*)a.atlas, a.lut, lutEntries, a.classifier, a.pixelBuffer,
+                      a.sampleCounter, a.tileOrder, tilesX, nTiles );
     return hipGetLastError();
 }
 

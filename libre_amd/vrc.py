@@ -13,6 +13,7 @@ VRC_OK, VRC_EINVAL, VRC_EHIP, VRC_EFULL, VRC_ENOMEM, VRC_EUNSUPPORTED, VRC_EHIER
 OPT_KERNEL, OPT_FILTER, OPT_TF_FRAC_BITS, OPT_COUNT_SAMPLES, OPT_TILE_ORDER, OPT_STEPPING, OPT_VARIANT, OPT_KERNEL_USED, OPT_KERNEL_TIMING, OPT_DEPTH_SPLIT, OPT_ERT_COMPACTION, OPT_GREY_TABLE, OPT_PACKED_ATLAS, OPT_GRID_WALK_USED, OPT_UNIFORM_BRICKS = range(1, 16)
 OPT_PROJECTION, OPT_MIP_SKIP, OPT_MIP_FOLD = 16, 17, 18
 OPT_MIP_DEPTH, OPT_MIP_DEPTH_CUE = 19, 20
+OPT_STREAM_MARKERS = 21
 PROJECTION_COMPOSITE, PROJECTION_MIP = 0, 1
 MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2
 VARIANT_CUDARAYCASTER, VARIANT_GLRAYCASTER = 0, 1

@@ -6,12 +6,18 @@ Forms of the uniform march against each other (the product carries no switch for
 tools/build_variants.sh NAME "-DVRC_NO_UNIFORM_INT_STEPS" / "-DVRC_UNIFORM_GROUP=8", or an older commit's library):
        python tools/uniform_ab.py --libs parent=variants/libvrc_hip_parent.so new=libre_amd/lib/libvrc_hip.so ...
 renders the frame with every library, option on (compared bit for bit with the first one's, counts included), and
-times them in alternating rounds in this one process."""
+times them in alternating rounds in this one process.
+VRC_OPT_STREAM_MARKERS (what vrc_render puts on the stream besides the march) in one process:
+       python tools/uniform_ab.py --markers [--steps 2000] [--rounds 3]
+renders the frame with the option at 1 and at 0 (compared bit for bit), then in alternating rounds runs --steps frames
+back to back and reports the wall time per frame of the synchronised loop beside the library's mean kernel time.  The
+wall time is the figure to compare: the kernel time ends with a marker behind the march at 1 and with the dispatch itself at 0."""
 import argparse
 import ctypes as C
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -55,6 +61,49 @@ def several(a):
         g.close()
 
 
+def markers(a):
+    """--markers: VRC_OPT_STREAM_MARKERS 1 against 0, the same context and pool."""
+    s = orc.build_scene(voxels=(a.voxels,) * 3, block=a.block, viewport=(a.viewport,) * 2, volume=a.volume,
+                        spin=tuple(a.spin), spr=a.spr)
+    L = vrc.load_library(a.lib) if a.lib else vrc.load_library()
+    g = GpuScene(s, lib=L)
+    frames = {}
+    for v in (1, 0):
+        vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_STREAM_MARKERS, v))
+        frames[v] = g.render(count=True)[:2]
+    assert (frames[0][0] == frames[1][0]).all() and frames[0][1] == frames[1][1], "frames differ"
+    g.render(count=False)
+    view = C.cast(C.byref(s.view), C.POINTER(vrc.ViewData))
+    render = C.cast(C.byref(s.render), C.POINTER(vrc.RenderData))
+    nodes = C.cast(s.nodes, C.POINTER(vrc.NodeData))
+    stats = vrc.Stats()
+
+    def run(n):
+        for _ in range(n):
+            vrc.check(L, L.vrc_pre_render(g.ctx, view))
+            vrc.check(L, L.vrc_render(g.ctx, view, nodes, s.n_nodes, render, g.pool))
+        vrc.check(L, L.vrc_synchronize(g.ctx))
+
+    wall = {1: [], 0: []}
+    kernel = {1: [], 0: []}
+    for _ in range(a.rounds):
+        for v in (1, 0):
+            vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_STREAM_MARKERS, v))
+            run(max(40, a.steps // 10))  # warm-up: clocks, the tile schedule
+            vrc.check(L, L.vrc_get_stats(g.ctx, C.byref(stats)))
+            t0 = time.perf_counter()
+            run(a.steps)
+            wall[v].append(round((time.perf_counter() - t0) * 1e3 / a.steps, 5))
+            vrc.check(L, L.vrc_get_stats(g.ctx, C.byref(stats)))
+            assert stats.kernel_launches == a.steps
+            kernel[v].append(round(stats.kernel_ms_sum / stats.kernel_launches, 5))
+    print(json.dumps({"volume": a.volume, "spin": list(a.spin), "samples": frames[0][1],
+                      "kernel": L.vrc_last_kernel().decode(), "steps": a.steps,
+                      "wall_ms_per_frame": {"markers": wall[1], "lean": wall[0]},
+                      "kernel_ms_mean": {"markers": kernel[1], "lean": kernel[0]}, "frames_bit_identical": True}))
+    g.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=None)
@@ -67,7 +116,10 @@ def main():
     ap.add_argument("--spin", type=float, nargs=2, default=(0.0, 0.0))
     ap.add_argument("--spr", type=int, default=0, help="samples per ray (0 = the automatic value)")
     ap.add_argument("--libs", nargs="+", default=None, metavar="NAME=PATH")
+    ap.add_argument("--markers", action="store_true", help="A/B of VRC_OPT_STREAM_MARKERS instead (see above)")
     a = ap.parse_args()
+    if a.markers:
+        return markers(a)
     if a.libs:
         return several(a)
     s = orc.build_scene(voxels=(a.voxels,) * 3, block=a.block, viewport=(a.viewport,) * 2, volume=a.volume,
