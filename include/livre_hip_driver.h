@@ -65,10 +65,13 @@ int lvh_app_set_clip_planes( lvh_app* app, const float* planes, uint32_t n );
 int lvh_app_set_bands( lvh_app* app, const uint32_t* y0, const uint32_t* h, uint32_t n );
 /* vrc_set_option on the renderer of the selected slot.  VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP, VRC_OPT_MIP_FOLD,
  * VRC_OPT_MIP_DEPTH and VRC_OPT_MIP_DEPTH_CUE say how
- * the app forms its pixels: they reach every renderer of the app, those of extra slots and those made later included.
+ * the app forms its pixels: they reach every renderer of the app, those of extra slots and those made later included;
+ * so does VRC_OPT_RAY_CACHE (every renderer has a ray cache of its own).
  * With VRC_PROJECTION_MIP, whichever fold (maximum, minimum, mean), a frame that asks for per-ray LOD
  * (lvh_app_set_ray_lod) renders its per-brick cut. */
 int lvh_app_set_option( lvh_app* app, int vrc_option, int64_t value );
+/* vrc_get_option on the renderer of the selected slot (read-only options such as VRC_OPT_RAY_CACHE_USED included) */
+int lvh_app_get_option( lvh_app* app, int vrc_option, int64_t* value );
 /* RenderInputs::dataSourceRange, in the volume's own values, for volumes that are not uint8 (the reference forces
  * (0,255), livre/eq/Channel.cpp:284, and its CUDA renderer ignores the field; the other voxel types are an extension
  * here).  Without this call uint16 volumes take (0,65535), int8 (-128,127), int16 (-32768,32767): the type's range.

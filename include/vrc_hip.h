@@ -191,6 +191,25 @@ typedef struct
                                     * include the second marker's latency).  Frames, counts and the ordering against
                                     * uploads are the same either way */
 
+#define VRC_OPT_RAY_CACHE 22        /* 1 (default) | 0.  What a pixel's ray set-up computes -- direction, its reciprocal,
+                                    * the interval in the volume's box and the clip planes, the near plane -- depends on
+                                    * the camera, the viewport and its offset, the box, the clip planes, the row bands
+                                    * and the pixel buffer's size alone.  A vrc_render whose values of those equal the
+                                    * ones of the vrc_render before, bit for bit, stores its rays in device memory the
+                                    * context owns (40 bytes per pixel, whole 8x8 tiles), and the ones after that load
+                                    * them instead of computing them: later passes of a multi-pass frame, frames
+                                    * re-rendered while bricks stream in, transfer-function edits, a time series from a
+                                    * fixed camera.  The loaded ray is the stored bits: the same frame and sample count.
+                                    * A camera that moves every frame computes its rays as before and allocates
+                                    * nothing.  The tile-scheduled grid walk of the gather kernels only (GRID_DDA and
+                                    * PACKED on a grid-aligned node set): the reference-order loop, the LDS-staged,
+                                    * per-ray-LOD and MIP kernels, the depth split, ray compaction and the supersampled
+                                    * glRaycaster variant (jittered rays) always compute.  vrc_ctx_set_stream, a changed
+                                    * vrc_set_row_map and setting this option to another value start over.  0: always
+                                    * compute */
+#define VRC_OPT_RAY_CACHE_USED 23   /* read-only (vrc_get_option), no synchronisation: what the last vrc_render did with
+                                    * the ray cache -- 0 computed its rays, 1 computed and stored them, 2 loaded them */
+
 /* A MIP frame (VRC_OPT_PROJECTION = VRC_PROJECTION_MIP).
  *   Sample set.  A ray's sample set S is exactly what the composite march takes with a transfer function whose alpha
  *     is 0 everywhere: the same ray set-up, global-box and clip-plane interval and near plane; the same node list

@@ -206,6 +206,16 @@ struct vrc_ctx
     uint32_t tileOrderReused = 0; /* frames in a row that kept the schedule of a nearby view */
     vrc_frame tileOrderFrame;
     int64_t optTileOrder = 1;
+    /* ray cache (VRC_OPT_RAY_CACHE; vrc_core.h: vrc_frame::rayCache): the planes, regrown like dTileOrder; the frame
+     * constants of the vrc_render before (rayPrevSet: there was one that could have used the cache) and whether the
+     * planes hold the rays of exactly those constants; the mode the last vrc_render used (VRC_OPT_RAY_CACHE_USED) */
+    float* dRayCache = nullptr;
+    size_t dRayCacheCap = 0; /* words per plane */
+    bool rayCacheValid = false;
+    bool rayPrevSet = false;
+    vrc_frame rayPrevFrame;
+    int64_t optRayCache = 1;
+    int64_t rayCacheUsed = 0;
     int64_t optStepping = 1;
     int64_t optVariant = VRC_VARIANT_CUDARAYCASTER;
     bool rayLod = false; /* vrc_set_ray_lod */
@@ -408,6 +418,7 @@ void vrc_ctx_destroy( vrc_ctx* c )
     for( hipEvent_t e : c->stageEvent )
         if( e ) (void)hipEventDestroy( e );
     if( c->dTileOrder ) (void)hipFree( c->dTileOrder );
+    if( c->dRayCache ) (void)hipFree( c->dRayCache );
     if( c->dRayList ) (void)hipFree( c->dRayList );
     if( c->dMipMax ) (void)hipFree( c->dMipMax );
     if( c->dMeanSum ) (void)hipFree( c->dMeanSum );
@@ -437,6 +448,7 @@ int vrc_ctx_set_stream( vrc_ctx* c, void* s )
     VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
     c->stream = s ? (hipStream_t)s : c->ownStream;
     c->waitedPoolUid = c->waitedGen = 0; /* the new stream has waited for no upload */
+    c->rayCacheValid = c->rayPrevSet = false; /* (the planes were written on the stream before) */
     return VRC_OK;
 }
 
@@ -470,6 +482,11 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
     case VRC_OPT_PACKED_ATLAS: c->optPackedAtlas = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_UNIFORM_BRICKS: c->optUniformBricks = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_STREAM_MARKERS: c->optStreamMarkers = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_RAY_CACHE:
+        if( c->optRayCache != ( value ? 1 : 0 ) )
+            c->rayCacheValid = c->rayPrevSet = false;
+        c->optRayCache = value ? 1 : 0;
+        return VRC_OK;
     case VRC_OPT_PROJECTION:
         if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite) or 1 (maximum intensity)" );
@@ -525,6 +542,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_PACKED_ATLAS: *value = c->optPackedAtlas; return VRC_OK;
     case VRC_OPT_UNIFORM_BRICKS: *value = c->optUniformBricks; return VRC_OK;
     case VRC_OPT_STREAM_MARKERS: *value = c->optStreamMarkers; return VRC_OK;
+    case VRC_OPT_RAY_CACHE: *value = c->optRayCache; return VRC_OK;
+    case VRC_OPT_RAY_CACHE_USED: *value = c->rayCacheUsed; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->optProjection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->optMipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->optMipFold; return VRC_OK;
@@ -1334,6 +1353,23 @@ int vrc_update( vrc_ctx* c, const float tf[256 * 4], const float* planes, uint32
 
 static vrc_f4* ctx_fb( vrc_ctx* c ) { return c->fbExt ? c->fbExt : c->fbOwn; }
 
+/* Do two frames cast the same rays?  Exactly the frame constants vrc_setup_ray_at reads (vrc_core.h) and the pixel
+ * buffer's shape, bit for bit -- no tolerance, unlike the tile schedule's: a ray cache entry stands for the computed
+ * ray.  (The contents of the row map: vrc_set_row_map forgets the frame before when they change.) */
+static bool ray_constants_equal( const vrc_frame& a, const vrc_frame& b )
+{
+    return a.width == b.width && a.height == b.height && a.rowMap == b.rowMap && a.variant == b.variant &&
+           a.nPlanes == b.nPlanes && std::memcmp( &a.vpX, &b.vpX, 4 * sizeof( float ) ) == 0 &&
+           std::memcmp( &a.pixelOffX, &b.pixelOffX, 2 * sizeof( float ) ) == 0 &&
+           std::memcmp( &a.nearPlane, &b.nearPlane, sizeof( float ) ) == 0 &&
+           std::memcmp( a.eye, b.eye, sizeof( a.eye ) ) == 0 &&
+           std::memcmp( a.invProj, b.invProj, sizeof( a.invProj ) ) == 0 &&
+           std::memcmp( a.invView, b.invView, sizeof( a.invView ) ) == 0 &&
+           std::memcmp( a.aabbMin, b.aabbMin, sizeof( a.aabbMin ) ) == 0 &&
+           std::memcmp( a.aabbMax, b.aabbMax, sizeof( a.aabbMax ) ) == 0 &&
+           std::memcmp( a.planes, b.planes, sizeof( a.planes ) ) == 0;
+}
+
 int vrc_set_row_map( vrc_ctx* c, const uint32_t* rows, uint32_t n )
 {
     if( !c || ( n && !rows ) )
@@ -1354,6 +1390,7 @@ int vrc_set_row_map( vrc_ctx* c, const uint32_t* rows, uint32_t n )
         VRC_HIP_CHECK( hipMemcpy( c->dRowMap, rows, n * sizeof( uint32_t ), hipMemcpyHostToDevice ) );
     c->rowMap.assign( rows, rows + n );
     c->tileOrderValid = false;
+    c->rayCacheValid = c->rayPrevSet = false;
     return VRC_OK;
 }
 
@@ -1954,6 +1991,47 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         a.rayList = c->dRayList;
     }
     c->lastErtParts = a.ertParts;
+    /* ray cache (VRC_OPT_RAY_CACHE): the tile-scheduled grid walk of vrc_k_raycast only (vrc_pixel_grid_dda; the
+     * supersampled GL variant, whose rays are jittered, is not a grid walk).  A frame whose ray constants differ from
+     * those of the vrc_render before computes its rays (a moving camera pays nothing); the first that repeats them
+     * also stores them, and the ones after that load them.  The kernel-visible fields are set here, after the tile
+     * schedule compared frames */
+    c->rayCacheUsed = 0;
+    {
+        const size_t tiles = (size_t)( ( c->fbW + VRC_TILE_W - 1 ) / VRC_TILE_W ) * ( ( c->fbH + VRC_TILE_H - 1 ) / VRC_TILE_H );
+        const size_t plane = tiles * 64u; /* whole tiles */
+        const bool eligible = c->optRayCache && useDda && !useLds && !c->rayLod && !mip && !glSuper && !a.depthSplit &&
+                              a.ertParts <= 1 && VRC_TILE_W * VRC_TILE_H == 64u &&
+                              plane * VRC_RAY_CACHE_PLANES <= 0xFFFFFFFFull; /* (32-bit word offsets in the kernel) */
+        if( !eligible )
+            c->rayCacheValid = c->rayPrevSet = false;
+        else
+        {
+            const bool same = c->rayPrevSet && ray_constants_equal( c->rayPrevFrame, f );
+            if( !same )
+                c->rayCacheValid = false;
+            else if( !c->rayCacheValid )
+            {
+                if( plane > c->dRayCacheCap )
+                {
+                    VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+                    if( c->dRayCache ) VRC_HIP_CHECK( hipFree( c->dRayCache ) );
+                    c->dRayCache = nullptr;
+                    c->dRayCacheCap = 0;
+                    VRC_HIP_CHECK( hipMalloc( &c->dRayCache, plane * VRC_RAY_CACHE_PLANES * sizeof( float ) ) );
+                    c->dRayCacheCap = plane;
+                }
+                c->rayCacheUsed = VRC_RAY_STORE; /* (valid once the march is on the stream, below) */
+            }
+            else
+                c->rayCacheUsed = VRC_RAY_LOAD;
+            std::memcpy( &c->rayPrevFrame, &f, sizeof( f ) );
+            c->rayPrevSet = true;
+        }
+        f.rayMode = (uint32_t)c->rayCacheUsed;
+        f.rayCache = c->rayCacheUsed ? c->dRayCache : nullptr;
+        f.rayCachePlane = c->rayCacheUsed ? (uint32_t)plane : 0u;
+    }
     /* grey transfer function, frame starting from zero: two-float table entries, the same bits (VRC_MODE_GREY) */
     a.greyTable = c->optGreyTable && c->tfGrey && f.clearFirst && !glSuper; /* (a sub-ray starts from the pixel so far) */
     a.classifier = vrc_make_classifier( lp );
@@ -2013,6 +2091,8 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                    : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
                    : c->rayLod ? vrc_launch_raycast_raylod( a, c->stream )
                                : vrc_launch_raycast( a, c->stream ) );
+    if( c->rayCacheUsed == VRC_RAY_STORE )
+        c->rayCacheValid = true;
     if( c->optTiming && !attached ) /* (also a frame without tiles, which launches nothing) */
         VRC_HIP_CHECK( hipEventRecord( evp.second, c->stream ) );
     {

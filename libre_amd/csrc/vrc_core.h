@@ -216,7 +216,25 @@ struct vrc_frame
      * depth cue in [0, 1] (VRC_OPT_MIP_DEPTH_CUE / 1000), 0 = the pixel is the classification of M as it is */
     float* mipDepth;
     float mipCue;
+    /* the ray cache (VRC_OPT_RAY_CACHE; at the end: no field above moves).  What vrc_setup_ray returns depends on the
+     * camera, the viewport, the global box and the clip planes alone, so a view that stands still -- the passes of a
+     * multi-pass frame, frames re-rendered while bricks stream in, transfer-function edits, a time series -- need not
+     * compute it again.  rayCache: VRC_RAY_CACHE_PLANES planes of rayCachePlane words each, the context's; a plane holds
+     * one component of vrc_ray for every pixel, indexed tile * 64 + lane in the kernel's own tile and lane order (whole
+     * tiles: a wave's load of one component is one run of 256 bytes).  rayMode: VRC_RAY_COMPUTE (0: the ray is computed,
+     * nothing else is read), VRC_RAY_STORE (computed and stored), VRC_RAY_LOAD (loaded: the bits that were stored).
+     * Read by vrc_pixel_grid_dda only -- the tile-scheduled grid walk of every vrc_k_raycast instance; the
+     * reference-order loop, the LDS-staged, per-ray-LOD and MIP kernels, the depth split and ray compaction compute
+     * their rays whatever these say (the host leaves rayMode 0 for them) */
+    float* rayCache;
+    uint32_t rayCachePlane;
+    uint32_t rayMode;
 };
+#define VRC_RAY_COMPUTE 0u
+#define VRC_RAY_STORE 1u
+#define VRC_RAY_LOAD 2u
+/* planes of vrc_frame::rayCache: dir, invDir, tNearGlobal, tFarGlobal, tNearPlane, hit (a word: 0 or 1); origin is the eye */
+#define VRC_RAY_CACHE_PLANES 10u
 
 /* Atlas memory layout.  The logical atlas is the reference's 3-D array of slots
  * (cuda/TexturePool.cu:128-150); physically every slot is one contiguous run of
@@ -564,8 +582,20 @@ struct vrc_segment
     float tNear;  /* ray parameter of rayStart */
 };
 
-VRC_HD bool vrc_brick_segment( const vrc_frame& f, const vrc_ray& r, const vrc_dev_node& n,
-                               float stepSize, vrc_segment* s, bool* stop )
+/* The segment in two parts.  The interval part is everything of Renderer.cu:179-194 -- the slab test, the global
+ * interval, the near plane, and for the GLSL twin the lattice snap and the per-brick clip planes -- up to the final
+ * tNear / tFar, `stop` and the early returns.  The completion part (Renderer.cu:195-201) makes pos, step, dist and
+ * tNear of it.  vrc_brick_segment is the two in a row, statement for statement what it was as one function.  A march
+ * that needs less completes less: the uniform march reads dist alone (vrc_segment_dist: the same expressions in the
+ * same order, so the same bits) and leaves the division and the three products of `step` to the marches that step
+ * (vrc_march_brick on an interval, below). */
+struct vrc_interval
+{
+    float tNear, tFar;
+};
+
+VRC_HD bool vrc_brick_interval( const vrc_frame& f, const vrc_ray& r, const vrc_dev_node& n,
+                                float stepSize, vrc_interval* iv, bool* stop )
 {
     VRC_STRICT_FP
     const vrc_f3 boxMin = { n.aabbMin[0], n.aabbMin[1], n.aabbMin[2] };
@@ -620,7 +650,30 @@ VRC_HD bool vrc_brick_segment( const vrc_frame& f, const vrc_ray& r, const vrc_d
         if( tNear > tFar )
             return false;
     }
+    iv->tNear = tNear;
+    iv->tFar = tFar;
+    return true;
+}
 
+/* dist of the completed segment, and nothing else of it */
+VRC_HD float vrc_segment_dist( const vrc_ray& r, const vrc_interval& iv )
+{
+    VRC_STRICT_FP
+    const float tNear = iv.tNear, tFar = iv.tFar;
+    const vrc_f3 rayStart = { r.origin.x + r.dir.x * tNear, r.origin.y + r.dir.y * tNear,
+                              r.origin.z + r.dir.z * tNear };
+    const vrc_f3 rayStop = { r.origin.x + r.dir.x * tFar, r.origin.y + r.dir.y * tFar,
+                             r.origin.z + r.dir.z * tFar };
+    const vrc_f3 diff = { rayStop.x - rayStart.x, rayStop.y - rayStart.y,
+                          rayStop.z - rayStart.z };
+    const float d2 = vrc_dot( diff, diff );
+    return sqrtf( d2 );
+}
+
+VRC_HD void vrc_segment_complete( const vrc_ray& r, const vrc_interval& iv, float stepSize, vrc_segment* s )
+{
+    VRC_STRICT_FP
+    const float tNear = iv.tNear, tFar = iv.tFar;
     const vrc_f3 rayStart = { r.origin.x + r.dir.x * tNear, r.origin.y + r.dir.y * tNear,
                               r.origin.z + r.dir.z * tNear };
     const vrc_f3 rayStop = { r.origin.x + r.dir.x * tFar, r.origin.y + r.dir.y * tFar,
@@ -645,8 +698,45 @@ VRC_HD bool vrc_brick_segment( const vrc_frame& f, const vrc_ray& r, const vrc_d
     s->step.z = diff.z * invLen * stepSize;
     s->dist = sqrtf( d2 );
     s->tNear = tNear;
+}
+
+VRC_HD bool vrc_brick_segment( const vrc_frame& f, const vrc_ray& r, const vrc_dev_node& n,
+                               float stepSize, vrc_segment* s, bool* stop )
+{
+    vrc_interval iv;
+    if( !vrc_brick_interval( f, r, n, stepSize, &iv, stop ) )
+        return false;
+    vrc_segment_complete( r, iv, stepSize, s );
     return true;
 }
+
+/* Where a march takes its segment from: one that is complete already, or the interval it is completed from at the
+ * place it is used (vrc_march_brick).  full(): the segment; distOnly(): dist and tNear of it, the rest zero -- all the
+ * uniform march reads */
+struct vrc_segment_ready
+{
+    const vrc_segment& s;
+    VRC_HD const vrc_segment& full() const { return s; }
+    VRC_HD const vrc_segment& distOnly() const { return s; }
+};
+struct vrc_segment_from_interval
+{
+    const vrc_ray& r;
+    const vrc_interval& iv;
+    float stepSize;
+    VRC_HD vrc_segment full() const
+    {
+        vrc_segment s;
+        vrc_segment_complete( r, iv, stepSize, &s );
+        return s;
+    }
+    VRC_HD vrc_segment distOnly() const
+    {
+        const vrc_f3 zero = { 0.0f, 0.0f, 0.0f };
+        vrc_segment s = { zero, zero, vrc_segment_dist( r, iv ), iv.tNear };
+        return s;
+    }
+};
 
 /* 24-bit multiply (v_mul_u32_u24 / v_mad_u32_u24 on gfx950: full rate, where a 32-bit
  * multiply is quarter rate). */
@@ -2863,14 +2953,17 @@ VRC_HD vrc_f4 vrc_classify_mip( const vrc_f4* tfp, float d, const vrc_classifier
 /* BIG: the atlas holds more than 2^32 voxels.  Offsets inside a slot stay 32-bit; the slot's
  * 64-bit base moves into the lane's atlas pointer (one 64-bit add per gather instead of a 32-bit
  * one), so the default kernels keep their scalar base + 32-bit offset addressing. */
-template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, int GROUP = VRC_GROUP, bool BIG = false >
-VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s,
-                             const ATLAS_T* __restrict__ atlas, const vrc_f4* lut,
-                             const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples,
-                             float levelStep = 0.0f )
+/* SRC: vrc_segment_ready or vrc_segment_from_interval.  One body for both: the slot word, its ballot and every march are
+ * where they were; only the place the segment's arithmetic is done differs */
+template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, int GROUP, bool BIG, typename SRC >
+VRC_HD bool vrc_march_brick_from( const vrc_frame& f, const vrc_dev_node& n, const SRC& src,
+                                  const ATLAS_T* __restrict__ atlas, const vrc_f4* lut,
+                                  const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples,
+                                  float levelStep )
 {
     if constexpr( MODE == VRC_MODE_PACKED || MODE == VRC_MODE_PACKED_GREY )
     {
+        const vrc_segment& s = src.full();
         /* (BIG here: a packed atlas of more than 4 GiB, or of an atlas of more than 2^32 voxels -- 64-bit lane pointers.
          * ATLAS_T is a tag: uint32_t = the packed form of 8-bit voxels, uint64_t = of 16-bit voxels) */
         static_assert( ( sizeof( ATLAS_T ) == 4 || sizeof( ATLAS_T ) == 8 ) && !CLAMP, "the packed atlas: overlap >= 1" );
@@ -2892,8 +2985,8 @@ VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vr
         vrc_dev_node local = n;
         local.slotBase = 0u;
         const ATLAS_T* slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
-        return vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, false >( f, local, s, slot, lut, cls,
-                                                                                color, nSamples, levelStep );
+        return vrc_march_brick_from< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, false, SRC >( f, local, src, slot, lut, cls,
+                                                                                          color, nSamples, levelStep );
     }
     if constexpr( ( MODE == VRC_MODE_TABLE || MODE == VRC_MODE_GREY ) && sizeof( ATLAS_T ) == 1 )
     {
@@ -2911,6 +3004,7 @@ VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vr
 #endif
         if( !general )
         {
+            const vrc_segment& s = src.distOnly();
             const uint32_t v = word & 0xFFu;
             if constexpr( MODE == VRC_MODE_GREY )
             {
@@ -2927,6 +3021,7 @@ VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vr
                     f, n, s, atlas, lut, color, nSamples, levelStep, nullptr, lut[v] );
         }
     }
+    const vrc_segment& s = src.full();
     if constexpr( MODE == VRC_MODE_GREY )
         return vrc_march_segment< CLAMP, COUNT, FIXED, ATLAS_T, GROUP, true >( f, n, s, atlas, lut, color, nSamples,
                                                                              levelStep );
@@ -2952,6 +3047,28 @@ VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vr
     else
         return vrc_march_segment< CLAMP, COUNT, FIXED, ATLAS_T, GROUP >( f, n, s, atlas, lut, color, nSamples,
                                                                        levelStep );
+}
+
+template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, int GROUP = VRC_GROUP, bool BIG = false >
+VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s,
+                             const ATLAS_T* __restrict__ atlas, const vrc_f4* lut,
+                             const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples,
+                             float levelStep = 0.0f )
+{
+    const vrc_segment_ready src = { s };
+    return vrc_march_brick_from< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG, vrc_segment_ready >(
+        f, n, src, atlas, lut, cls, color, nSamples, levelStep );
+}
+
+/* ... on a brick interval of the frame's step: the segment is completed where the march needs it */
+template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, int GROUP = VRC_GROUP, bool BIG = false >
+VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_ray& r, const vrc_interval& iv,
+                             const ATLAS_T* __restrict__ atlas, const vrc_f4* lut,
+                             const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples )
+{
+    const vrc_segment_from_interval src = { r, iv, f.stepSize };
+    return vrc_march_brick_from< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG, vrc_segment_from_interval >(
+        f, n, src, atlas, lut, cls, color, nSamples, 0.0f );
 }
 
 /* ---- tile culling for the reference-order loop -------------------------------------------------------------
@@ -3243,9 +3360,9 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
             recent[1] = recent[0];
             recent[0] = node;
             const vrc_dev_node n = nodes[node];
-            vrc_segment s;
+            vrc_interval iv;
             bool stop;
-            if( vrc_brick_segment( f, r, n, f.stepSize, &s, &stop ) )
+            if( vrc_brick_interval( f, r, n, f.stepSize, &iv, &stop ) )
             {
                 if( part >= 0 )
                 {
@@ -3255,7 +3372,7 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                          * inside the grid -- halves of equal length for every ray (what the depth split wants: the
                          * longer half is the latency), at the price that the lanes of a wave disagree about the
                          * brick the middle falls into */
-                        sp = s.tNear < 0.5f * ( t0 + t1 ) ? 0 : 1;
+                        sp = iv.tNear < 0.5f * ( t0 + t1 ) ? 0 : 1; /* (the segment's tNear) */
                     else
                     {
                         const int ax = partDir & 3;
@@ -3271,9 +3388,13 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                         return; /* another part's brick */
                 }
                 if constexpr( vrc_mode_is_mip( MODE ) )
+                {
+                    vrc_segment s;
+                    vrc_segment_complete( r, iv, f.stepSize, &s );
                     vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, color, nSamples ); /* (color: the ray's MIP state) */
-                else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, lut, cls, color,
-                                                                                  nSamples ) )
+                }
+                else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, r, iv, atlas, lut, cls, color,
+                                                                                       nSamples ) )
                     finished = true;
             }
             else if( stop )
@@ -3361,11 +3482,62 @@ VRC_HD void vrc_pixel_grid_dda( const vrc_frame& f, const vrc_dev_node* __restri
                                 const ATLAS_T* __restrict__ atlas, const vrc_f4* lut,
                                 const vrc_classifier& cls,
                                 vrc_f4* __restrict__ pixelBuffer, uint32_t px, uint32_t py,
-                                uint32_t& nSamples )
+                                uint32_t& nSamples, uint32_t rayIndex = 0u )
 {
-    const vrc_ray r = vrc_setup_ray( f, px, f.rowMap ? f.rowMap[py] : py );
+    /* rayIndex: tile * 64 + lane, the pixel's word in every plane of the ray cache (vrc_frame::rayCache; read only when
+     * f.rayMode is not 0).  The mode is a frame constant, so the whole wave takes one side.  Both sides end in the same
+     * `r` and run into the same code below -- no second exit: a loaded wave without a hit skips the other nine loads
+     * and leaves through the miss path as a computed one does (an early return here cost every grid-walk instance
+     * three registers, and the ones at their occupancy's limit scratch or a wave) */
     const uint32_t pixelPos = py * f.width + px;
     const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
+    vrc_ray r;
+    if( f.rayMode == VRC_RAY_LOAD )
+    {
+        const float* const rc = f.rayCache + rayIndex;
+        const uint32_t P = f.rayCachePlane;
+        r.hit = vrc_float_bits( rc[9u * P] ) != 0u;
+        bool any = r.hit;
+#if defined( __HIP_DEVICE_COMPILE__ )
+        any = __builtin_amdgcn_ballot_w64( any ) != 0ull;
+#endif
+        r.origin.x = f.eye[0];
+        r.origin.y = f.eye[1];
+        r.origin.z = f.eye[2];
+        r.dir.x = r.dir.y = r.dir.z = r.invDir.x = r.invDir.y = r.invDir.z = 0.0f;
+        r.tNearGlobal = r.tFarGlobal = r.tNearPlane = 0.0f;
+        if( any ) /* (a wave whose rays all miss the volume reads nothing else of them) */
+        {
+            r.dir.x = rc[0];
+            r.dir.y = rc[P];
+            r.dir.z = rc[2u * P];
+            r.invDir.x = rc[3u * P];
+            r.invDir.y = rc[4u * P];
+            r.invDir.z = rc[5u * P];
+            r.tNearGlobal = rc[6u * P];
+            r.tFarGlobal = rc[7u * P];
+            r.tNearPlane = rc[8u * P];
+        }
+    }
+    else
+    {
+        r = vrc_setup_ray( f, px, f.rowMap ? f.rowMap[py] : py );
+        if( f.rayMode == VRC_RAY_STORE )
+        {
+            float* const rc = f.rayCache + rayIndex;
+            const uint32_t P = f.rayCachePlane;
+            rc[0] = r.dir.x;
+            rc[P] = r.dir.y;
+            rc[2u * P] = r.dir.z;
+            rc[3u * P] = r.invDir.x;
+            rc[4u * P] = r.invDir.y;
+            rc[5u * P] = r.invDir.z;
+            rc[6u * P] = r.tNearGlobal;
+            rc[7u * P] = r.tFarGlobal;
+            rc[8u * P] = r.tNearPlane;
+            rc[9u * P] = vrc_bits_float( r.hit ? 1u : 0u );
+        }
+    }
     if( !r.hit )
     {
         if( f.clearFirst )

@@ -1005,7 +1005,7 @@ __global__ __launch_bounds__( VRC_WG_THREADS ) __attribute__( ( amdgpu_waves_per
     {
         if( DDA )
             vrc_pixel_grid_dda< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >(
-                f, nodes, gridTable, atlas, lut, cls, pixelBuffer, px, py, nSamples );
+                f, nodes, gridTable, atlas, lut, cls, pixelBuffer, px, py, nSamples, tile * 64u + lane );
         else
             vrc_pixel_reference_order< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >(
                 f, nodes, atlas, lut, cls, pixelBuffer, px, py, nSamples, cand, nCand );

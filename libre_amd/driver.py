@@ -27,7 +27,7 @@ class FrameStats(C.Structure):  # lvh_frame_stats
 EXPORTS = [
     "lvh_last_error", "lvh_app_create", "lvh_app_destroy", "lvh_app_set_camera",
     "lvh_app_set_modelview", "lvh_app_set_time_step", "lvh_datasource_frame_range", "lvh_app_set_colormap", "lvh_app_set_clip_planes",
-    "lvh_app_set_bands", "lvh_app_set_frames_in_flight", "lvh_app_select_slot", "lvh_app_set_option", "lvh_app_set_data_range", "lvh_app_set_ray_lod", "lvh_app_set_stream", "lvh_app_set_framebuffer", "lvh_app_render_frame",
+    "lvh_app_set_bands", "lvh_app_set_frames_in_flight", "lvh_app_select_slot", "lvh_app_set_option", "lvh_app_get_option", "lvh_app_set_data_range", "lvh_app_set_ray_lod", "lvh_app_set_stream", "lvh_app_set_framebuffer", "lvh_app_render_frame",
     "lvh_app_get_stats", "lvh_app_wait_uploads", "lvh_app_synchronize", "lvh_app_volume_info",
     "lvh_app_set_histogram", "lvh_app_frame_histogram", "lvh_app_pick",
     "lvh_comm_unique_id", "lvh_app_comm_create", "lvh_app_set_layout", "lvh_app_gather_tiles",
@@ -60,6 +60,7 @@ def load_library():
     L.lvh_app_set_frames_in_flight.argtypes = [vp, C.c_uint32]
     L.lvh_app_select_slot.argtypes = [vp, C.c_uint32]
     L.lvh_app_set_option.argtypes = [vp, C.c_int, C.c_int64]
+    L.lvh_app_get_option.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
     L.lvh_app_set_data_range.argtypes = [vp, C.c_float, C.c_float]
     L.lvh_app_set_ray_lod.argtypes = [vp, C.c_int]
     L.lvh_app_set_stream.argtypes = [vp, vp]
@@ -154,6 +155,11 @@ class App:
 
     def set_option(self, option, value):
         check(self.L, self.L.lvh_app_set_option(self.h, option, value))
+
+    def get_option(self, option):
+        v = C.c_int64()
+        check(self.L, self.L.lvh_app_get_option(self.h, option, C.byref(v)))
+        return int(v.value)
 
     def set_data_range(self, lo, hi):
         """dataSourceRange of a volume that is not uint8 (extension), in the volume's own values.  uint16, int8 and

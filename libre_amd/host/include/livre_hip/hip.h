@@ -91,6 +91,7 @@ public:
     void setFrameBuffer( void* deviceRgba, uint32_t width, uint32_t height );
     void setStream( void* hipStream );
     void setOption( int option, int64_t value );
+    int64_t getOption( int option ) const;
     /** VRC_OPT_PROJECTION = VRC_PROJECTION_MIP was set: the maximum-intensity projection has no per-ray LOD form, a frame
      *  that asks for per-ray LOD is then rendered with its per-brick cut (the path taken on VRC_EHIERARCHY) */
     bool projectionIsMip() const { return _mip; }

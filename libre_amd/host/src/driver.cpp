@@ -329,7 +329,7 @@ int lvh_app_set_option( lvh_app* app, int option, int64_t value )
 {
     if( !app ) return fail( "NULL argument" );
     if( option == VRC_OPT_PROJECTION || option == VRC_OPT_MIP_SKIP || option == VRC_OPT_MIP_FOLD ||
-        option == VRC_OPT_MIP_DEPTH || option == VRC_OPT_MIP_DEPTH_CUE )
+        option == VRC_OPT_MIP_DEPTH || option == VRC_OPT_MIP_DEPTH_CUE || option == VRC_OPT_RAY_CACHE )
     {
         /* how the app forms its pixels: every renderer it has, and every one it makes later (lvh_app_set_frames_in_flight) */
         try
@@ -346,6 +346,11 @@ int lvh_app_set_option( lvh_app* app, int option, int64_t value )
         }
     }
     LVH_TRY( app->renderer().setOption( option, value ) )
+}
+int lvh_app_get_option( lvh_app* app, int option, int64_t* value )
+{
+    if( !app || !value ) return fail( "NULL argument" );
+    LVH_TRY( *value = app->renderer().getOption( option ) )
 }
 int lvh_app_set_data_range( lvh_app* app, float lo, float hi )
 {

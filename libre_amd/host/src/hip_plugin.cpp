@@ -762,6 +762,12 @@ void HipRaycastRenderer::setOption( int o, int64_t v )
     if( o == VRC_OPT_PROJECTION ) /* (whichever VRC_OPT_MIP_FOLD: every fold of a MIP frame takes the per-brick cut) */
         _mip = v == VRC_PROJECTION_MIP;
 }
+int64_t HipRaycastRenderer::getOption( int o ) const
+{
+    int64_t v = 0;
+    throwOnVrcError( vrc_get_option( _ctx, o, &v ), "vrc_get_option" );
+    return v;
+}
 void HipRaycastRenderer::synchronize() { throwOnVrcError( vrc_synchronize( _ctx ), "vrc_synchronize" ); }
 void HipRaycastRenderer::kernelStats( float* lastMs, double* sumMs, uint32_t* launches, uint64_t* samples )
 {

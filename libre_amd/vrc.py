@@ -14,6 +14,7 @@ OPT_KERNEL, OPT_FILTER, OPT_TF_FRAC_BITS, OPT_COUNT_SAMPLES, OPT_TILE_ORDER, OPT
 OPT_PROJECTION, OPT_MIP_SKIP, OPT_MIP_FOLD = 16, 17, 18
 OPT_MIP_DEPTH, OPT_MIP_DEPTH_CUE = 19, 20
 OPT_STREAM_MARKERS = 21
+OPT_RAY_CACHE, OPT_RAY_CACHE_USED = 22, 23
 PROJECTION_COMPOSITE, PROJECTION_MIP = 0, 1
 MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2
 VARIANT_CUDARAYCASTER, VARIANT_GLRAYCASTER = 0, 1

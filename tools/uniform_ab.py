@@ -11,7 +11,10 @@ VRC_OPT_STREAM_MARKERS (what vrc_render puts on the stream besides the march) in
        python tools/uniform_ab.py --markers [--steps 2000] [--rounds 3]
 renders the frame with the option at 1 and at 0 (compared bit for bit), then in alternating rounds runs --steps frames
 back to back and reports the wall time per frame of the synchronised loop beside the library's mean kernel time.  The
-wall time is the figure to compare: the kernel time ends with a marker behind the march at 1 and with the dispatch itself at 0."""
+wall time is the figure to compare: the kernel time ends with a marker behind the march at 1 and with the dispatch itself at 0.
+VRC_OPT_RAY_CACHE (rays computed every frame against rays loaded from the context's cache) the same way:
+       python tools/uniform_ab.py --ray-cache [--steps 2000] [--rounds 3]
+With --steps of 200 or more, --libs reports the wall time per frame and the mean kernel time of such a loop as well."""
 import argparse
 import ctypes as C
 import json
@@ -25,6 +28,34 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import orc  # noqa: E402
 from gpu_run import GpuScene  # noqa: E402
 from libre_amd import vrc  # noqa: E402
+
+
+def frame_loop(g, s):
+    """run(n): n frames back to back (vrc_pre_render + vrc_render, nothing read back), then a synchronise."""
+    L = g.L
+    view = C.cast(C.byref(s.view), C.POINTER(vrc.ViewData))
+    render = C.cast(C.byref(s.render), C.POINTER(vrc.RenderData))
+    nodes = C.cast(s.nodes, C.POINTER(vrc.NodeData))
+
+    def run(n):
+        for _ in range(n):
+            vrc.check(L, L.vrc_pre_render(g.ctx, view))
+            vrc.check(L, L.vrc_render(g.ctx, view, nodes, s.n_nodes, render, g.pool))
+        vrc.check(L, L.vrc_synchronize(g.ctx))
+    return run
+
+
+def timed_loop(g, run, steps):
+    """(wall ms per frame, mean kernel ms) of `steps` frames after a warm-up (clocks, the tile schedule, the ray cache)."""
+    stats = vrc.Stats()
+    run(max(40, steps // 10))
+    vrc.check(g.L, g.L.vrc_get_stats(g.ctx, C.byref(stats)))
+    t0 = time.perf_counter()
+    run(steps)
+    wall = (time.perf_counter() - t0) * 1e3 / steps
+    vrc.check(g.L, g.L.vrc_get_stats(g.ctx, C.byref(stats)))
+    assert stats.kernel_launches == steps
+    return round(wall, 5), round(stats.kernel_ms_sum / stats.kernel_launches, 5)
 
 
 def several(a):
@@ -44,10 +75,19 @@ def several(a):
             first = (fb, n)
         assert (fb == first[0]).all() and n == first[1], "%s: frame or count differs from %s" % (name, names[0])
     ms = {name: [] for name in names}
+    wall = {name: [] for name in names}
+    mean = {name: [] for name in names}
     kernels = {}
     for _ in range(a.rounds):
         for name in names:
             g = scenes[name]
+            if a.steps >= 200:  # a loop long enough for a wall time
+                g.render(count=False)
+                w, k = timed_loop(g, frame_loop(g, s), a.steps)
+                wall[name].append(w)
+                mean[name].append(k)
+                kernels[name] = g.L.vrc_last_kernel().decode()
+                continue
             g.render(count=False)  # warm-up: the tile schedule
             best = None
             for _ in range(a.steps):
@@ -56,51 +96,43 @@ def several(a):
             ms[name].append(round(best, 4))
             kernels[name] = g.L.vrc_last_kernel().decode()
     print(json.dumps({"volume": a.volume, "spin": list(a.spin), "spr": s.render.samplesPerRay, "samples": first[1],
-                      "kernel": kernels, "kernel_ms_min_per_round": ms, "frames_bit_identical": True}))
+                      "kernel": kernels, "kernel_ms_min_per_round": ms, "wall_ms_per_frame": wall,
+                      "kernel_ms_mean": mean, "frames_bit_identical": True}))
     for g in scenes.values():
         g.close()
 
 
-def markers(a):
-    """--markers: VRC_OPT_STREAM_MARKERS 1 against 0, the same context and pool."""
+def markers(a, option=None, names=("lean", "markers")):
+    """--markers: VRC_OPT_STREAM_MARKERS 1 against 0, the same context and pool (--ray-cache: VRC_OPT_RAY_CACHE)."""
+    option = vrc.OPT_STREAM_MARKERS if option is None else option
     s = orc.build_scene(voxels=(a.voxels,) * 3, block=a.block, viewport=(a.viewport,) * 2, volume=a.volume,
                         spin=tuple(a.spin), spr=a.spr)
     L = vrc.load_library(a.lib) if a.lib else vrc.load_library()
     g = GpuScene(s, lib=L)
     frames = {}
     for v in (1, 0):
-        vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_STREAM_MARKERS, v))
-        frames[v] = g.render(count=True)[:2]
+        vrc.check(L, L.vrc_set_option(g.ctx, option, v))
+        for _ in range(3):  # (the ray cache: computed, stored, loaded)
+            frames[v] = g.render(count=True)[:2]
+        used = C.c_int64(0)
+        if option == vrc.OPT_RAY_CACHE:
+            vrc.check(L, L.vrc_get_option(g.ctx, vrc.OPT_RAY_CACHE_USED, C.byref(used)))
+            assert used.value == (2 if v else 0), "the third frame did not load its rays"
     assert (frames[0][0] == frames[1][0]).all() and frames[0][1] == frames[1][1], "frames differ"
     g.render(count=False)
-    view = C.cast(C.byref(s.view), C.POINTER(vrc.ViewData))
-    render = C.cast(C.byref(s.render), C.POINTER(vrc.RenderData))
-    nodes = C.cast(s.nodes, C.POINTER(vrc.NodeData))
-    stats = vrc.Stats()
-
-    def run(n):
-        for _ in range(n):
-            vrc.check(L, L.vrc_pre_render(g.ctx, view))
-            vrc.check(L, L.vrc_render(g.ctx, view, nodes, s.n_nodes, render, g.pool))
-        vrc.check(L, L.vrc_synchronize(g.ctx))
-
+    run = frame_loop(g, s)
     wall = {1: [], 0: []}
     kernel = {1: [], 0: []}
     for _ in range(a.rounds):
         for v in (1, 0):
-            vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_STREAM_MARKERS, v))
-            run(max(40, a.steps // 10))  # warm-up: clocks, the tile schedule
-            vrc.check(L, L.vrc_get_stats(g.ctx, C.byref(stats)))
-            t0 = time.perf_counter()
-            run(a.steps)
-            wall[v].append(round((time.perf_counter() - t0) * 1e3 / a.steps, 5))
-            vrc.check(L, L.vrc_get_stats(g.ctx, C.byref(stats)))
-            assert stats.kernel_launches == a.steps
-            kernel[v].append(round(stats.kernel_ms_sum / stats.kernel_launches, 5))
+            vrc.check(L, L.vrc_set_option(g.ctx, option, v))
+            w, k = timed_loop(g, run, a.steps)
+            wall[v].append(w)
+            kernel[v].append(k)
     print(json.dumps({"volume": a.volume, "spin": list(a.spin), "samples": frames[0][1],
                       "kernel": L.vrc_last_kernel().decode(), "steps": a.steps,
-                      "wall_ms_per_frame": {"markers": wall[1], "lean": wall[0]},
-                      "kernel_ms_mean": {"markers": kernel[1], "lean": kernel[0]}, "frames_bit_identical": True}))
+                      "wall_ms_per_frame": {names[1]: wall[1], names[0]: wall[0]},
+                      "kernel_ms_mean": {names[1]: kernel[1], names[0]: kernel[0]}, "frames_bit_identical": True}))
     g.close()
 
 
@@ -117,9 +149,12 @@ def main():
     ap.add_argument("--spr", type=int, default=0, help="samples per ray (0 = the automatic value)")
     ap.add_argument("--libs", nargs="+", default=None, metavar="NAME=PATH")
     ap.add_argument("--markers", action="store_true", help="A/B of VRC_OPT_STREAM_MARKERS instead (see above)")
+    ap.add_argument("--ray-cache", action="store_true", help="A/B of VRC_OPT_RAY_CACHE instead (see above)")
     a = ap.parse_args()
     if a.markers:
         return markers(a)
+    if a.ray_cache:
+        return markers(a, vrc.OPT_RAY_CACHE, ("computed", "cached"))
     if a.libs:
         return several(a)
     s = orc.build_scene(voxels=(a.voxels,) * 3, block=a.block, viewport=(a.viewport,) * 2, volume=a.volume,
