@@ -70,6 +70,11 @@ int lvh_app_set_bands( lvh_app* app, const uint32_t* y0, const uint32_t* h, uint
  * With VRC_PROJECTION_MIP, whichever fold (maximum, minimum, mean), a frame that asks for per-ray LOD
  * (lvh_app_set_ray_lod) renders its per-brick cut. */
 int lvh_app_set_option( lvh_app* app, int vrc_option, int64_t value );
+/* vrc_set_isosurface on every renderer of the app, those of extra slots and those made later included, as the projection
+ * options are handed on: the isovalue (in the volume's own units) and the ambient share in [0, 1] of the frames rendered
+ * under VRC_OPT_PROJECTION = VRC_PROJECTION_ISO, which lvh_app_set_option accepts only after this call.  An error, with the device layer's message, for a NaN or an ambient
+ * share outside [0, 1]. */
+int lvh_app_set_isosurface( lvh_app* app, float iso_value, float ambient );
 /* vrc_get_option on the renderer of the selected slot (read-only options such as VRC_OPT_RAY_CACHE_USED included) */
 int lvh_app_get_option( lvh_app* app, int vrc_option, int64_t* value );
 /* RenderInputs::dataSourceRange, in the volume's own values, for volumes that are not uint8 (the reference forces
@@ -112,7 +117,9 @@ int lvh_app_set_histogram( lvh_app* app, int enable );
 int lvh_app_frame_histogram( lvh_app* app, uint64_t* bins, uint32_t capacity, uint32_t* bin_count, float range[2],
                              float* area, uint64_t* frame_id );
 /* Pick in a MIP frame rendered with depth tracking (VRC_OPT_MIP_DEPTH = 1 or VRC_OPT_MIP_DEPTH_CUE > 0; maximum or
- * minimum): what lies behind pixel (x, y) of the window in the selected slot's last frame.  *hit = 1 if the pixel's ray
+ * minimum) or in an isosurface frame (VRC_PROJECTION_ISO, which always tracks depth: *hit = 1 where the ray reached
+ * the isovalue, *value = V of the first sample that did, *t = its D, xyz = the surface point):
+ * what lies behind pixel (x, y) of the window in the selected slot's last frame.  *hit = 1 if the pixel's ray
  * took a sample, *value = the projected value M in the volume's own units, *t = the ray parameter D of the nearest sample
  * that equals M, xyz = its position origin + D * dir (vrc_get_projection_values / vrc_get_projection_depths of that
  * pixel; any of the four may be NULL; value, t and xyz are unspecified without a hit).  An error, with a message: no

@@ -154,9 +154,13 @@ typedef struct
 
 #define VRC_OPT_PROJECTION 16       /* how a pixel is formed from its ray's samples: VRC_PROJECTION_COMPOSITE (default: the
                                     * reference's emission/absorption compositing with early ray termination) |
-                                    * VRC_PROJECTION_MIP (maximum-intensity projection, an extension: see below) */
+                                    * VRC_PROJECTION_MIP (maximum-intensity projection, an extension: see below) |
+                                    * VRC_PROJECTION_ISO (shaded isosurface, an extension: "An isosurface frame" below;
+                                    * VRC_EINVAL, naming vrc_set_isosurface, on a context that has not called it yet: such
+                                    * a context accepts and refuses the values it did before the projection existed) */
 #define VRC_PROJECTION_COMPOSITE 0
 #define VRC_PROJECTION_MIP 1
+#define VRC_PROJECTION_ISO 2
 #define VRC_OPT_MIP_SKIP 17         /* 1 (default) | 0.  MIP only: a ray does not march a brick whose largest voxel cannot
                                     * beat the maximum the ray already holds (every upload notes it per slot).  The
                                     * maximum does not depend on the order or on samples that cannot raise it: the same
@@ -292,6 +296,53 @@ typedef struct
  *     u = clamp((D - tNearGlobal) / (tFarGlobal - tNearGlobal), 0, 1), the interval being the ray's own (global box and
  *     clip planes), the one S is taken from; u = 0 where that interval is empty, u = 1 for D = +infinity.  Float32,
  *     operations in the order written.  Strength 0 is the uncued frame bit for bit. */
+
+/* An isosurface frame (VRC_OPT_PROJECTION = VRC_PROJECTION_ISO; vrc_set_isosurface gives iso_value and ambient).  The
+ * pixel shows the first place along its ray where the sampled density reaches iso_value, lit by the volume's gradient
+ * there.  VRC_OPT_MIP_FOLD, _DEPTH and _DEPTH_CUE are not read; VRC_OPT_MIP_SKIP is.
+ *   Sample set.  S is the MIP frame's, unchanged: the same rays, interval, list-order quirk, restart per brick and sample
+ *     positions, for VRC_OPT_STEPPING 0 and 1.
+ *   Hit.  A sample hits when its value, as vrc_get_projection_values would report it, is >= iso_value.  For point
+ *     samples of the 8- and 16-bit atlases that is an integer comparison of the stored voxel against one threshold formed
+ *     once per frame: the ceiling of iso_value plus the offset-binary shift, clamped to the type (and one above the
+ *     type's largest value where iso_value lies above it: no voxel hits).  It is exact.  On float atlases and for
+ *     trilinear samples it is >= in float32 (for trilinear samples of an offset-binary atlas: against the smallest
+ *     stored float whose reported value is >= iso_value, which is the same set), so a NaN sample never hits.
+ *   Ray.  D = the smallest t_j = tNear + (float)j * stepSize ("The depth of a MIP frame") over the hitting samples, V
+ *     that sample's value.  Two hitting samples with bit-equal t keep the larger V; if V is equal too, either gradient
+ *     may stand.  (D, V) is the same whatever the brick loop and however the node list is split into passes, in any
+ *     order.  A ray that takes no hitting sample has D = +infinity and its pixel keeps its cleared value.
+ *   Gradient.  (x, y, z) = the slot-local voxel the hit sample was read from; for a trilinear sample the voxel the point
+ *     sampler addresses at that position, the floor of the brick's voxel coordinate.  g_a = v(a+1) - v(a-1) along each
+ *     axis, of stored voxels, indices clamped to the slot (slotDim - 1, as the clamped sampler clamps).  Integer voxels
+ *     are differenced in integers (exact; the offset-binary shift cancels), a float atlas in float32 (a NaN tap gives a
+ *     NaN component).  G_a = (float)g_a * voxPerWorld_a of the brick's node, one rounded multiply: a world-space
+ *     gradient, right across LOD cuts and anisotropic voxels.  The six gathers happen once per ray and pass, after the
+ *     march, only for a ray whose D this pass lowered, in that pass's nodes and atlas.
+ *   Pixel.  c = TF((iso_value - r0) / (r1 - r0)), fetched as a MIP pixel's is; s = ambient + (1 - ambient) *
+ *     |G.dir| / |G|, two-sided, a headlight; s = 1 where |G| is 0 or not finite.  Float32, operations in the order
+ *     written (the sums of three left to right), nothing fused.  The stored pixel is (c.rgb * c.a * s, c.a).
+ *   Passes.  The context keeps V, D and G per pixel of the pixel buffer, owned and invalidated as the running maximum
+ *     and depth of a MIP frame are.  Changing iso_value, ambient or VRC_OPT_PROJECTION between vrc_pre_render and
+ *     vrc_post_render: the next vrc_render returns VRC_EINVAL, as a changed fold does.  A vrc_render under
+ *     VRC_PROJECTION_ISO before the first vrc_set_isosurface: VRC_EINVAL, naming the function -- and so is the
+ *     vrc_set_option that would select the projection on such a context, so that no render gets that far.
+ *   Read-backs, valid from the frame's first ISO pass until the next vrc_pre_render.  vrc_get_projection_values: V,
+ *     with count 1 where the ray hit and 0 elsewhere.  vrc_get_projection_depths: D and origin + D * dir; depth is
+ *     always tracked.  vrc_get_projection_gradients: G, 0 where there is no hit.
+ *   VRC_OPT_MIP_SKIP, a run-time value of the same kernel instance.  1: a ray does not march a brick whose slot cannot
+ *     reach the threshold (every upload notes the slot's largest voxel; trilinear samples with the interpolation's
+ *     rounding margin), nor one whose tNear lies strictly above the D it holds -- the grid walk, which meets bricks by
+ *     increasing tNear, ends the ray there (once tNear clears D by the walk's own tie tolerance) -- and it leaves a
+ *     segment in front of the first group of samples whose t lies strictly above D.  0: every sample of S is taken, and
+ *     vrc_stats.samples is |S| summed over the rays.  Frame, V, D and G are bit-identical either way.
+ *   VRC_OPT_UNIFORM_BRICKS.  A slot known to hold one value hits at its segment's first sample or not at all, without
+ *     fetching (point samples of 8- and 16-bit voxels); its gradient is 0.  Bit-identical on and off, counts included.
+ * Served and refused exactly as a MIP frame: all seven voxel types, both filters (trilinear by gathers), AUTO /
+ * REFERENCE_ORDER / GRID_DDA, atlases of more than 2^32 voxels, row maps, caller-owned frame buffers; VRC_EINVAL naming
+ * the option for an explicit VRC_KERNEL_LDS or _PACKED, vrc_set_ray_lod on and VRC_VARIANT_GLRAYCASTER;
+ * VRC_OPT_DEPTH_SPLIT and VRC_OPT_ERT_COMPACTION are silently the plain kernel.  A depth cue, a "<=" surface, smooth
+ * (trilinear) gradients and several isovalues are not part of it. */
 
 #define VRC_VARIANT_CUDARAYCASTER 0 /* renderers/cudaRaycaster/cuda/Renderer.cu:95-230 */
 #define VRC_VARIANT_GLRAYCASTER 1   /* renderers/glRaycaster/shaders/fragRaycast.glsl:113-215: pixel centre
@@ -510,6 +561,15 @@ int vrc_get_projection_values( vrc_ctx* ctx, float* host_values, uint32_t* host_
  *                for the frame row the pixel shows under a row map; unspecified where D is not finite. */
 int vrc_get_projection_depths( vrc_ctx* ctx, float* host_t, float* host_xyz );
 
+/* The isosurface of VRC_PROJECTION_ISO frames ("An isosurface frame" above).  iso_value: in the volume's own units, as
+ * dataSourceRange is (signed types un-shifted); ambient: the unlit share of the shading, in [0, 1].  VRC_EINVAL, naming
+ * the argument, for a NaN or an ambient outside that range; the values set before stay. */
+int vrc_set_isosurface( vrc_ctx* ctx, float iso_value, float ambient );
+/* The gradients of an isosurface frame: host_g[3 i + a] = G_a of pixel i, 0 where the ray did not hit.  Validity,
+ * synchronisation and buffer geometry are those of vrc_get_projection_values; VRC_EINVAL after a frame of another
+ * projection. */
+int vrc_get_projection_gradients( vrc_ctx* ctx, float* host_g /* W x H x 3 */ );
+
 /* ---- sort-first tile exchange (multi-GPU) ------------------------------------------------------- */
 /* One process per GPU renders row bands of the frame (vrc_set_row_map); the display rank receives
  * them over RCCL (xGMI inside a node) directly at their rows of the full frame.  This is the step
@@ -559,7 +619,8 @@ int vrc_last_kernel_occupancy( int* workgroups_per_cu, int* threads_per_workgrou
 #define VRC_ABI_VERSION 4 /* 3: vrc_gather_tiles takes the frame height; 4: VRC_KERNEL_PACKED, VRC_OPT_PACKED_ATLAS, vrc_last_kernel_occupancy
                            * (added since without a new number, as symbols a caller may bind weakly: the frame histogram,
                            * vrc_pool_create_typed / vrc_pool_voxel_type, vrc_get_projection_values,
-                           * vrc_get_projection_depths; as option values only: VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP,
+                           * vrc_get_projection_depths, vrc_set_isosurface, vrc_get_projection_gradients; as option
+                           * values only: VRC_PROJECTION_ISO, VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP,
                            * VRC_OPT_MIP_FOLD, VRC_OPT_MIP_DEPTH, VRC_OPT_MIP_DEPTH_CUE) */
 /* = VRC_ABI_VERSION for the product build; -VRC_ABI_VERSION for a developer build of the library (compiled with
  * -DVRC_DEV_BUILD: experiment switches, statistics, ablations that render wrong pixels on purpose) */

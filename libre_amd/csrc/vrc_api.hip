@@ -281,6 +281,19 @@ struct vrc_ctx
     std::vector< uint32_t > depthRows;
     float* dDepthOut = nullptr;
     size_t dDepthOutWords = 0;
+    /* an isosurface frame (include/vrc_hip.h, "An isosurface frame"): vrc_set_isosurface's two values (isoSet: called at
+     * all), what the frame's first ISO vrc_render read of them (frameIso: did one), the running G per pixel beside
+     * dMipMax and dMipDepth (vrc_frame::isoGrad, three floats a pixel: grown and invalidated where they are), and whether
+     * the frame's last pass left one (vrc_get_projection_gradients) */
+    bool isoSet = false;
+    float isoValue = 0.0f;
+    float isoAmbient = 0.0f;
+    bool frameIso = false;
+    float frameIsoValue = 0.0f;
+    float frameIsoAmbient = 0.0f;
+    float* dIsoGrad = nullptr;
+    size_t dIsoGradPixels = 0;
+    bool gradValid = false;
     uint32_t* dRayList = nullptr; /* counts | two ray lists (vrc_internal.h) */
     size_t dRayListCap = 0;       /* pixels */
     int lastErtParts = 0;         /* of the last vrc_render */
@@ -425,6 +438,7 @@ void vrc_ctx_destroy( vrc_ctx* c )
     if( c->dMeanCount ) (void)hipFree( c->dMeanCount );
     if( c->dProjOut ) (void)hipFree( c->dProjOut );
     if( c->dMipDepth ) (void)hipFree( c->dMipDepth );
+    if( c->dIsoGrad ) (void)hipFree( c->dIsoGrad );
     if( c->dDepthOut ) (void)hipFree( c->dDepthOut );
     if( c->dRowMap ) (void)hipFree( c->dRowMap );
     if( c->dCounter ) (void)hipFree( c->dCounter );
@@ -488,8 +502,12 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
         c->optRayCache = value ? 1 : 0;
         return VRC_OK;
     case VRC_OPT_PROJECTION:
-        if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP )
-            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite) or 1 (maximum intensity)" );
+        if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP && value != VRC_PROJECTION_ISO )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite), 1 (maximum intensity) or 2 (isosurface)" );
+        /* a context that never called vrc_set_isosurface keeps what it had before the isosurface projection existed: the
+         * value is refused, here and not only by the render it could not serve */
+        if( value == VRC_PROJECTION_ISO && !c->isoSet )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION = VRC_PROJECTION_ISO needs vrc_set_isosurface first" );
         c->optProjection = value;
         return VRC_OK;
     case VRC_OPT_MIP_SKIP: c->optMipSkip = value ? 1 : 0; return VRC_OK;
@@ -1440,6 +1458,8 @@ int vrc_pre_render( vrc_ctx* c, const vrc_view_data* view )
     c->frameDepth = -1;
     c->frameCue = -1;
     c->depthValid = false;
+    c->frameIso = false;
+    c->gradValid = false;
     c->projState.pixels = 0u; /* vrc_get_projection_values: nothing to read until a MIP pass of this frame */
     return VRC_OK;
 }
@@ -1577,16 +1597,24 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     if( pool->elemBytes == 4 && ( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED ) )
         return fail( VRC_EINVAL, "vrc_render: 32-bit and float voxels are marched by gathers; the LDS-staged and tap-packed "
                                  "forms take 8- and 16-bit voxels (VRC_OPT_KERNEL = AUTO, REFERENCE_ORDER or GRID_DDA)" );
-    const bool mip = c->optProjection == VRC_PROJECTION_MIP;
+    /* an isosurface frame is a MIP frame with the first-crossing fold: it reads none of the MIP frame's options but
+     * VRC_OPT_MIP_SKIP, and is served and refused as one */
+    const bool iso = c->optProjection == VRC_PROJECTION_ISO;
+    const bool mip = c->optProjection == VRC_PROJECTION_MIP || iso;
     if( c->frameProjection >= 0 && c->frameProjection != c->optProjection )
         return fail( VRC_EINVAL, "vrc_render: VRC_OPT_PROJECTION changed between vrc_pre_render and vrc_post_render; the "
                                  "passes of one frame take one projection" );
-    if( mip && c->frameFold >= 0 && c->frameFold != c->optMipFold )
+    if( iso && !c->isoSet )
+        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_PROJECTION = ISO needs vrc_set_isosurface first" );
+    if( iso && c->frameIso && ( c->frameIsoValue != c->isoValue || c->frameIsoAmbient != c->isoAmbient ) )
+        return fail( VRC_EINVAL, "vrc_render: vrc_set_isosurface changed iso_value or ambient between vrc_pre_render and "
+                                 "vrc_post_render; the passes of one frame take one isosurface" );
+    if( mip && !iso && c->frameFold >= 0 && c->frameFold != c->optMipFold )
         return fail( VRC_EINVAL, "vrc_render: VRC_OPT_MIP_FOLD changed between vrc_pre_render and vrc_post_render; the "
                                  "passes of one frame take one fold" );
     /* depth tracking: the maximum and the minimum only; the mean reads neither option */
-    const bool mipDepth = mip && c->optMipFold != VRC_MIP_FOLD_MEAN && ( c->optMipDepth != 0 || c->optMipDepthCue > 0 );
-    if( mip && c->optMipFold != VRC_MIP_FOLD_MEAN )
+    const bool mipDepth = iso || ( mip && c->optMipFold != VRC_MIP_FOLD_MEAN && ( c->optMipDepth != 0 || c->optMipDepthCue > 0 ) );
+    if( mip && !iso && c->optMipFold != VRC_MIP_FOLD_MEAN )
     {
         if( c->frameDepth >= 0 && c->frameDepth != c->optMipDepth )
             return fail( VRC_EINVAL, "vrc_render: VRC_OPT_MIP_DEPTH changed between vrc_pre_render and vrc_post_render; the "
@@ -1599,13 +1627,18 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     {
         /* what the maximum-intensity projection is not defined for (include/vrc_hip.h) */
         if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no maximum-intensity form; "
-                                     "VRC_OPT_PROJECTION = MIP is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
+            return fail( VRC_EINVAL, iso ? "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no isosurface form; "
+                                           "VRC_OPT_PROJECTION = ISO is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)"
+                                         : "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no maximum-intensity form; "
+                                           "VRC_OPT_PROJECTION = MIP is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
         if( c->rayLod )
-            return fail( VRC_EINVAL, "vrc_render: vrc_set_ray_lod is on; VRC_OPT_PROJECTION = MIP renders a per-brick cut" );
+            return fail( VRC_EINVAL, iso ? "vrc_render: vrc_set_ray_lod is on; VRC_OPT_PROJECTION = ISO renders a per-brick cut"
+                                         : "vrc_render: vrc_set_ray_lod is on; VRC_OPT_PROJECTION = MIP renders a per-brick cut" );
         if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_PROJECTION = MIP is defined on the "
-                                     "cudaRaycaster variant's sample set" );
+            return fail( VRC_EINVAL, iso ? "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_PROJECTION = ISO is defined on the "
+                                           "cudaRaycaster variant's sample set"
+                                         : "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_PROJECTION = MIP is defined on the "
+                                           "cudaRaycaster variant's sample set" );
     }
     const bool linear = c->optFilter == VRC_FILTER_TRILINEAR;
     /* samples classified one by one (padded transfer function in the table buffer) whenever the
@@ -1873,7 +1906,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             if( !c->mipFirst ) /* a later pass of a frame whose pixel buffer grew (vrc_set_framebuffer): nothing known */
                 VRC_HIP_CHECK( hipMemsetAsync( c->dMipMax, 0xFF, pixels * sizeof( uint32_t ), c->stream ) );
         }
-        const bool mean = c->optMipFold == VRC_MIP_FOLD_MEAN;
+        const bool mean = !iso && c->optMipFold == VRC_MIP_FOLD_MEAN;
         if( mean && pixels > c->dMeanPixels )
         {
             VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
@@ -1910,8 +1943,31 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                 VRC_HIP_CHECK( hipMemsetD32Async( reinterpret_cast< hipDeviceptr_t >( c->dMipDepth ), 0x7F800000, pixels, c->stream ) );
         }
         f.mipDepth = mipDepth ? c->dMipDepth : nullptr;
-        f.mipCue = mipDepth ? (float)c->optMipDepthCue / 1000.0f : 0.0f;
-        if( !mean )
+        f.mipCue = ( mipDepth && !iso ) ? (float)c->optMipDepthCue / 1000.0f : 0.0f;
+        if( iso )
+        {
+            if( pixels > c->dIsoGradPixels )
+            {
+                VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+                if( c->dIsoGrad ) VRC_HIP_CHECK( hipFree( c->dIsoGrad ) );
+                c->dIsoGrad = nullptr;
+                c->dIsoGradPixels = 0;
+                VRC_HIP_CHECK( hipMalloc( &c->dIsoGrad, pixels * 3u * sizeof( float ) ) );
+                c->dIsoGradPixels = pixels;
+                if( !c->mipFirst ) /* (as dMipDepth above: no hit yet as far as this buffer knows) */
+                    VRC_HIP_CHECK( hipMemsetAsync( c->dIsoGrad, 0, pixels * 3u * sizeof( float ), c->stream ) );
+            }
+            f.isoGrad = c->dIsoGrad;
+            f.isoThreshold = vrc_iso_int_threshold( c->isoValue, pool->rangeShift, pool->elemBytes == 1 ? 255u : 65535u );
+            f.isoStored = vrc_iso_float_threshold( c->isoValue, pool->rangeShift );
+            f.isoClassify = c->isoValue + pool->rangeShift;
+            f.isoAmbient = c->isoAmbient;
+            c->frameIso = true;
+            c->frameIsoValue = c->isoValue;
+            c->frameIsoAmbient = c->isoAmbient;
+        }
+        c->gradValid = iso;
+        if( !mean && !iso )
         {
             c->frameDepth = c->optMipDepth;
             c->frameCue = c->optMipDepthCue;
@@ -1923,13 +1979,14 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             c->depthRows = c->rowMap;
         }
         c->mipFirst = false;
-        c->frameFold = c->optMipFold;
+        if( !iso )
+            c->frameFold = c->optMipFold;
         /* what this pass leaves for vrc_get_projection_values */
         c->projState.mipMax = c->dMipMax;
         c->projState.meanSum = c->dMeanSum;
         c->projState.meanCount = c->dMeanCount;
         c->projState.pixels = (uint32_t)pixels;
-        c->projState.fold = (uint32_t)c->optMipFold;
+        c->projState.fold = iso ? (uint32_t)VRC_FOLD_FIRST : (uint32_t)c->optMipFold;
         c->projState.floatState = ( linear || pool->elemBytes == 4 ) ? 1u : 0u;
         c->projState.shift = pool->rangeShift;
     }
@@ -2084,7 +2141,8 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     a.attached = &attached;
     if( c->optTiming )
         VRC_HIP_CHECK( hipEventRecord( evp.first, c->stream ) );
-    VRC_HIP_CHECK( mipDepth    ? vrc_launch_raycast_mip_depth( a, (int)c->optMipFold, c->stream )
+    VRC_HIP_CHECK( iso         ? vrc_launch_raycast_iso( a, c->stream )
+                   : mipDepth  ? vrc_launch_raycast_mip_depth( a, (int)c->optMipFold, c->stream )
                    : mip       ? ( c->optMipFold == VRC_MIP_FOLD_MIN    ? vrc_launch_raycast_minip( a, c->stream )
                                    : c->optMipFold == VRC_MIP_FOLD_MEAN ? vrc_launch_raycast_meanip( a, c->stream )
                                                                         : vrc_launch_raycast_mip( a, c->stream ) )
@@ -2210,6 +2268,34 @@ int vrc_get_projection_depths( vrc_ctx* c, float* hostT, float* hostXyz )
     VRC_HIP_CHECK( hipMemcpyAsync( hostT, c->dDepthOut, pixels * sizeof( float ), hipMemcpyDeviceToHost, c->stream ) );
     if( hostXyz )
         VRC_HIP_CHECK( hipMemcpyAsync( hostXyz, dXyz, pixels * 3u * sizeof( float ), hipMemcpyDeviceToHost, c->stream ) );
+    VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+    return VRC_OK;
+}
+
+int vrc_set_isosurface( vrc_ctx* c, float isoValue, float ambient )
+{
+    if( !c )
+        return fail( VRC_EINVAL, "vrc_set_isosurface: ctx is NULL" );
+    if( isoValue != isoValue )
+        return fail( VRC_EINVAL, "vrc_set_isosurface: iso_value is not a number" );
+    if( !( ambient >= 0.0f && ambient <= 1.0f ) )
+        return fail( VRC_EINVAL, "vrc_set_isosurface: ambient lies in [0, 1]" );
+    c->isoSet = true;
+    c->isoValue = isoValue;
+    c->isoAmbient = ambient;
+    return VRC_OK;
+}
+
+int vrc_get_projection_gradients( vrc_ctx* c, float* hostG )
+{
+    if( !c || !hostG )
+        return fail( VRC_EINVAL, "vrc_get_projection_gradients: NULL argument" );
+    if( c->projState.pixels == 0u || !c->gradValid )
+        return fail( VRC_EINVAL, "vrc_get_projection_gradients: no VRC_OPT_PROJECTION = ISO vrc_render since the last "
+                                 "vrc_pre_render; the gradients exist from a frame's first ISO pass until the next frame" );
+    VRC_HIP_CHECK( hipSetDevice( c->device ) );
+    VRC_HIP_CHECK( hipMemcpyAsync( hostG, c->dIsoGrad, (size_t)c->projState.pixels * 3u * sizeof( float ),
+                                   hipMemcpyDeviceToHost, c->stream ) );
     VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
     return VRC_OK;
 }

@@ -229,6 +229,18 @@ struct vrc_frame
     float* rayCache;
     uint32_t rayCachePlane;
     uint32_t rayMode;
+    /* an isosurface frame (VRC_OPT_PROJECTION = VRC_PROJECTION_ISO, the VRC_FOLD_FIRST instances; at the end: no field
+     * above moves).  The passes of the frame meet in mipMax (the bits of V, VRC_MIP_EMPTY = no hit), mipDepth (D) and
+     * isoGrad: the context's running G, three floats per pixel of the pixel buffer, 0 where there is no hit -- owned,
+     * invalidated and not read by a first pass as mipDepth is; NULL in every other frame.  isoThreshold: what a stored
+     * voxel of an 8- or 16-bit atlas is compared against (vrc_iso_int_threshold); isoStored: what a float voxel and
+     * every trilinear sample is (vrc_iso_float_threshold); isoClassify: the isovalue as the classifier takes a density
+     * (the offset-binary shift added); isoAmbient: the ambient share of the shading in [0, 1] */
+    float* isoGrad;
+    uint32_t isoThreshold;
+    float isoStored;
+    float isoClassify;
+    float isoAmbient;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -1024,7 +1036,7 @@ VRC_HD uint32_t vrc_float_bits( float v )
     return __float_as_uint( v );
 #else
     uint32_t u;
-    memcpy( &u, &v, 4 );
+    __builtin_memcpy( &u, &v, 4 );
     return u;
 #endif
 }
@@ -1034,7 +1046,7 @@ VRC_HD float vrc_bits_float( uint32_t u )
     return __uint_as_float( u );
 #else
     float v;
-    memcpy( &v, &u, 4 );
+    __builtin_memcpy( &v, &u, 4 );
     return v;
 #endif
 }
@@ -2132,6 +2144,7 @@ VRC_HD bool vrc_march_segment_packed( const vrc_frame& f, const vrc_dev_node& n,
 #define VRC_FOLD_MAX 0
 #define VRC_FOLD_MIN 1
 #define VRC_FOLD_MEAN 2
+#define VRC_FOLD_FIRST 3 /* the first sample at or above a threshold: an isosurface frame (below, "the first-crossing fold") */
 #define VRC_MODE_WITH_FOLD( mode, fold ) ( ( mode ) + 16 * ( fold ) )
 VRC_HD constexpr int vrc_mode_base( int mode ) { return mode & 15; }
 VRC_HD constexpr int vrc_mode_fold( int mode ) { return ( mode >> 4 ) & 3; }
@@ -2789,6 +2802,428 @@ VRC_HD void vrc_mean_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc
     state.y = vrc_bits_float( vrc_mean_bits_hi( sum ) );
 }
 
+/* ---- the first-crossing fold (VRC_FOLD_FIRST): an isosurface frame ------------------------------------------------------
+ * include/vrc_hip.h has the definition ("An isosurface frame").  The sample set is the MIP frame's; the marches below are
+ * the two above once more -- groups, guard, travel chain, tails -- and what is kept per ray is the hitting sample of the
+ * smallest t_j (vrc_mip_sample_t): its value V, its depth D, and where it was read, for the gradient that is gathered once
+ * after the march.  A sample hits when it is >= the frame's threshold: an integer comparison of the stored voxel for point
+ * samples of the 8- and 16-bit atlases, a float comparison (false for a NaN) for everything else.
+ *
+ * t_j does not fall as j grows (the product (float)j * stepSize and the sum are each rounded, and rounding is monotone),
+ * but two neighbours can share a t where stepSize is below an ulp of tNear, and of two hits with one t the larger V
+ * stands.  So a ray that skips (VRC_OPT_MIP_SKIP) leaves a segment only in front of a group whose first t lies strictly
+ * above the D it holds: no sample from there on can change (D, V).  Without skipping the same test only saves the search
+ * of the group.  Either way every sample that is taken is computed by the same code: one kernel instance, and the
+ * frame, V, D and G are the same bits with skipping on and off. */
+VRC_HD uint32_t vrc_iso_int_threshold( float iso, float shift, uint32_t typeMax )
+{
+    /* the ceiling of iso + shift (exact in double), clamped to the type -- and one above it where no voxel can hit */
+    const double s = (double)iso + (double)shift;
+    if( !( s > 0.0 ) )
+        return 0u;
+    if( s > (double)typeMax )
+        return typeMax + 1u;
+    const uint32_t fl = (uint32_t)s;
+    return (double)fl < s ? fl + 1u : fl;
+}
+/* The threshold of a float sample in stored units: the smallest float d that vrc_get_projection_values would report as
+ * a value >= iso, i.e. (float)( (double)d - shift ) >= iso.  That report does not fall as d grows, so the hits are the
+ * floats from one d on: found by bisection over the floats in their order (vrc_slot_max_key).  iso is not NaN. */
+VRC_HD float vrc_iso_float_threshold( float iso, float shift )
+{
+    if( shift == 0.0f )
+        return iso;
+    uint32_t lo = vrc_slot_max_key( vrc_bits_float( 0xFF800000u ) ), hi = vrc_slot_max_key( vrc_bits_float( 0x7F800000u ) );
+    while( lo < hi ) /* (+infinity always reports >= iso) */
+    {
+        const uint32_t mid = lo + ( hi - lo ) / 2u;
+        const float d = vrc_slot_max_float( mid );
+        if( (float)( (double)d - (double)shift ) >= iso )
+            hi = mid;
+        else
+            lo = mid + 1u;
+    }
+    return vrc_slot_max_float( lo );
+}
+template < typename D >
+VRC_HD D vrc_iso_threshold( const vrc_frame& f );
+template <>
+VRC_HD uint32_t vrc_iso_threshold< uint32_t >( const vrc_frame& f ) { return f.isoThreshold; }
+template <>
+VRC_HD float vrc_iso_threshold< float >( const vrc_frame& f ) { return f.isoStored; }
+
+/* a ray inside one brick segment.  v, d: (V, D) so far; where: the atlas element the sample that set them was read
+ * from, valid once lowered; tGroup: t of the next group's first sample */
+template < typename D >
+struct vrc_iso_march
+{
+    D v;
+    float d;
+    uint32_t where;
+    bool lowered;
+    float tNear;
+    uint32_t index;
+    float tGroup;
+};
+/* after a group of N samples d[] (taken[k]: sample k belongs to S), gmax their maximum with NaN left out; elem( k ): the
+ * element sample k's gradient is centred on.  Returns true when nothing behind this group can change the ray. */
+template < int N, typename D, typename ELEM >
+VRC_HD bool vrc_iso_group( vrc_iso_march< D >& z, D thr, D gmax, const D* d, const bool* taken, float stepSize, ELEM elem )
+{
+    if( gmax >= thr && !( z.tGroup > z.d ) )
+    {
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+            if( taken[k] && d[k] >= thr )
+            {
+                const float t = vrc_mip_sample_t( z.tNear, z.index + (uint32_t)k, stepSize );
+                if( t < z.d || ( t == z.d && d[k] > z.v ) )
+                {
+                    z.d = t;
+                    z.v = d[k];
+                    z.where = elem( k );
+                    z.lowered = true;
+                }
+            }
+    }
+    z.index += (uint32_t)N;
+    z.tGroup = vrc_mip_sample_t( z.tNear, z.index, stepSize );
+    return z.tGroup > z.d;
+}
+
+/* point samples of one brick segment: vrc_mip_segment_point with the search in place of the fold */
+template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename D >
+VRC_HD void vrc_iso_segment_point( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
+                                   const ATLAS_T* __restrict__ atlas, D thr, bool skip, vrc_iso_march< D >& z,
+                                   uint32_t& nSamples )
+{
+    const float stepSize = f.stepSize;
+    const vrc_sampler sm = vrc_make_sampler( n, f );
+    vrc_f3 pos = s.pos;
+    if( !( travel > 0.0f ) )
+        return;
+    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
+    if( FIXED )
+        fp = vrc_fixpos_init( sm, pos, s.step );
+    const float guard = stepSize * (float)( GROUP + 1 );
+    while( travel > guard )
+    {
+        uint32_t idx[GROUP];
+        if( FIXED )
+            vrc_group_indices_fixed< GROUP >( sm, fp, idx );
+        else
+            vrc_group_indices< CLAMP, GROUP >( sm, pos, s.step, idx );
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            travel -= stepSize; /* same sequential subtraction as the reference */
+        D d[GROUP];
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            d[k] = (D)vrc_gather( atlas, idx[k] );
+        D gmax;
+        vrc_mip_identity( gmax );
+#pragma unroll
+        for( int k = 0; k + 1 < GROUP; k += 2 )
+            gmax = vrc_mip_max3( gmax, d[k], d[k + 1] );
+        if( GROUP & 1 )
+            gmax = vrc_mip_max( gmax, d[GROUP - 1] );
+        nSamples += GROUP;
+        bool taken[GROUP];
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            taken[k] = true;
+        if( vrc_iso_group< GROUP >( z, thr, gmax, d, taken, stepSize, [&]( int k ) { return idx[k]; } ) && skip )
+            travel = 0.0f;
+    }
+    constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
+    while( travel > 0.0f )
+    {
+        uint32_t idx[TAILG], cnt = 0;
+        D d[TAILG];
+        bool taken[TAILG];
+        if( FIXED )
+            vrc_group_indices_fixed< TAILG >( sm, fp, idx );
+        else
+            vrc_group_indices< CLAMP, TAILG >( sm, pos, s.step, idx );
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+        {
+            taken[k] = travel > 0.0f;
+            cnt += taken[k] ? 1u : 0u;
+            idx[k] = taken[k] ? idx[k] : 0u; /* a step the reference does not take reads element 0 and is not looked at */
+            travel -= stepSize;
+        }
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+            d[k] = (D)vrc_gather( atlas, idx[k] );
+        D gmax;
+        vrc_mip_identity( gmax );
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+            gmax = vrc_mip_max( gmax, taken[k] ? d[k] : gmax );
+        nSamples += cnt;
+        if( vrc_iso_group< TAILG >( z, thr, gmax, d, taken, stepSize, [&]( int k ) { return idx[k]; } ) && skip )
+            travel = 0.0f;
+    }
+}
+
+/* What the uniform-brick shortcut counts for a segment it does not march: the samples vrc_iso_segment_point would have
+ * taken -- all of them without skipping, and with it the groups up to the one in front of which the ray leaves, by the
+ * same travel chain.  d: the ray's D after the segment's first sample (a uniform segment changes it there or nowhere). */
+template < int GROUP >
+VRC_HD uint32_t vrc_iso_uniform_count( float travel, float stepSize, float tNear, float d, bool skip )
+{
+    if( !skip || !( d < vrc_bits_float( 0x7F800000u ) ) )
+        return vrc_step_count( travel, stepSize );
+    uint32_t n = 0u, index = 0u;
+    const float guard = stepSize * (float)( GROUP + 1 );
+    while( travel > guard )
+    {
+        for( int k = 0; k < GROUP; ++k )
+            travel -= stepSize;
+        n += GROUP;
+        index += GROUP;
+        if( vrc_mip_sample_t( tNear, index, stepSize ) > d )
+            return n;
+    }
+    constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
+    while( travel > 0.0f )
+    {
+        for( int k = 0; k < TAILG; ++k )
+        {
+            n += travel > 0.0f ? 1u : 0u;
+            travel -= stepSize;
+        }
+        index += TAILG;
+        if( vrc_mip_sample_t( tNear, index, stepSize ) > d )
+            return n;
+    }
+    return n;
+}
+
+/* trilinear samples of one brick segment: vrc_mip_segment_trilinear with the search in place of the fold.  The element
+ * a hit's gradient is centred on is the voxel the point sampler addresses at the sample's position, the floor of the
+ * slot-local coordinate l: of the two taps of an axis (floor( l - 0.5 ) and the next, clamped as the sampler clamps) it is
+ * the second exactly when the weight is >= 0.5 (l - 0.5 and the weight are exact for l >= 0.5; below, both taps are 0). */
+template < bool CLAMP, typename ATLAS_T >
+VRC_HD void vrc_iso_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
+                                       const ATLAS_T* __restrict__ atlas, float thr, bool skip, vrc_iso_march< float >& z,
+                                       uint32_t& nSamples )
+{
+    const float stepSize = f.stepSize;
+    const vrc_sampler sm = vrc_make_sampler( n, f );
+    vrc_f3 pos = s.pos;
+    while( travel > 0.0f )
+    {
+        bool valid[VRC_LGROUP];
+        vrc_taps t[VRC_LGROUP];
+#pragma unroll
+        for( int k = 0; k < VRC_LGROUP; ++k )
+        {
+            VRC_FAST_FP
+            valid[k] = travel > 0.0f;
+            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
+            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
+            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
+            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
+            pos.x += s.step.x;
+            pos.y += s.step.y;
+            pos.z += s.step.z;
+            travel -= stepSize;
+        }
+        float v[VRC_LGROUP][8];
+#pragma unroll
+        for( int k = 0; k < VRC_LGROUP; ++k )
+#pragma unroll
+            for( int c = 0; c < 8; ++c )
+            {
+                const uint32_t e = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
+                v[k][c] = (float)vrc_gather( atlas, valid[k] ? e : 0u );
+            }
+        float d[VRC_LGROUP];
+        float gmax = vrc_bits_float( 0xFF800000u );
+#pragma unroll
+        for( int k = 0; k < VRC_LGROUP; ++k )
+        {
+            d[k] = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
+            gmax = vrc_mip_max( gmax, valid[k] ? d[k] : gmax );
+            nSamples += valid[k] ? 1u : 0u;
+        }
+        if( vrc_iso_group< VRC_LGROUP >( z, thr, gmax, d, valid, stepSize, [&]( int k ) {
+                return t[k].ax[t[k].wx >= 0.5f ? 1 : 0] + t[k].ay[t[k].wy >= 0.5f ? 1 : 0] + t[k].az[t[k].wz >= 0.5f ? 1 : 0];
+            } ) && skip )
+            travel = 0.0f;
+    }
+}
+
+/* vrc_pixel_mip's state word of a hit in a uniform brick: there is nothing to gather, the gradient is 0 */
+#define VRC_ISO_WHERE_UNIFORM 0xFFFFFFFFu
+/* how far above D a brick's tNear has to lie for the grid walk to end the ray there.  The walk meets bricks by
+ * increasing tNear -- but for the bricks around an edge or a corner, which it hands over in a fixed order and which tie
+ * to within 2e-6 of t (vrc_ray_grid_dda: tolE); twice that */
+#define VRC_ISO_WALK_MARGIN 4e-6f
+
+/* One brick of one ray, first-crossing fold.  The state: x = the bits of V, z = D (+infinity: no hit yet), and, once
+ * this pass has set them, y = 1 + the slot-local element the hit was read from (VRC_ISO_WHERE_UNIFORM: a uniform brick;
+ * 0: this pass has not) and w = the bits of the node's index.
+ *   skipping (vrc_frame::slotMax, NULL = off)  a lane takes no sample of a brick whose tNear lies strictly above its D,
+ *     or whose slot cannot reach the threshold (vrc_mip_cannot_reach), and leaves a segment as described above;
+ *   uniform bricks  a slot known to hold one value hits at the segment's first sample or not at all.
+ * Returns true when the grid walk can end the ray. */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, typename ATLAS_T, int GROUP, bool BIG >
+VRC_HD bool vrc_iso_brick( const vrc_frame& f, const vrc_dev_node& n, uint32_t nodeIndex, const vrc_segment& s,
+                           const ATLAS_T* __restrict__ atlas, vrc_f4& state, uint32_t& nSamples )
+{
+    typedef typename vrc_density< ATLAS_T >::type P;
+    typedef typename std::conditional< TRILINEAR, float, P >::type D;
+    const D thr = vrc_iso_threshold< D >( f );
+    const bool skip = f.slotMax != nullptr;
+    vrc_iso_march< D > z;
+    vrc_mip_from_bits( vrc_float_bits( state.x ), z.v );
+    z.d = state.z;
+    z.where = 0u;
+    z.lowered = false;
+    z.tNear = s.tNear;
+    z.index = 0u;
+    z.tGroup = s.tNear;
+    bool march = s.dist > 0.0f;
+    bool beyond = false;
+    bool uniformHit = false;
+    if( skip && march )
+    {
+        if( s.tNear > z.d )
+        {
+            VRC_STRICT_FP
+            march = false;
+            const float margin = fabsf( z.d ) * VRC_ISO_WALK_MARGIN;
+            beyond = s.tNear > z.d + margin;
+        }
+        else if( n.slotInfoIndex != 0u )
+        {
+            const uint32_t word = f.slotMax[n.slotInfoIndex - 1u];
+            if( word != 0u && vrc_mip_cannot_reach< VRC_FOLD_MAX, TRILINEAR, ATLAS_T >( word, thr ) )
+                march = false;
+        }
+    }
+    if constexpr( !TRILINEAR && sizeof( ATLAS_T ) <= 2 )
+    {
+        if( march && n.slotInfoIndex != 0u && f.slotInfo != nullptr )
+        {
+            const uint32_t word = f.slotInfo[n.slotInfoIndex - 1u];
+            if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) == VRC_SLOT_KNOWN )
+            {
+                const D value = (D)( word & VRC_SLOT_VALUE_MASK );
+                if( value >= thr && ( s.tNear < z.d || ( s.tNear == z.d && value > z.v ) ) )
+                {
+                    z.d = s.tNear; /* (the segment's first sample: t_0 = tNear) */
+                    z.v = value;
+                    z.lowered = true;
+                    uniformHit = true;
+                }
+                nSamples += vrc_iso_uniform_count< GROUP >( s.dist, f.stepSize, s.tNear, z.d, skip );
+                march = false;
+            }
+        }
+    }
+    bool any = march;
+#if defined( __HIP_DEVICE_COMPILE__ )
+    any = __builtin_amdgcn_ballot_w64( march ) != 0ull;
+#endif
+    uint32_t base = n.slotBase;
+    if( any )
+    {
+        const float travel = march ? s.dist : 0.0f;
+        vrc_dev_node local = n;
+        const ATLAS_T* slot = atlas;
+        if( BIG )
+        {
+            local.slotBase = 0u;
+            base = 0u;
+            slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
+        }
+        if constexpr( TRILINEAR )
+            vrc_iso_segment_trilinear< CLAMP, ATLAS_T >( f, local, s, travel, slot, thr, skip, z, nSamples );
+        else
+            vrc_iso_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, D >( f, local, s, travel, slot, thr, skip, z, nSamples );
+    }
+    if( z.lowered )
+    {
+        state.x = vrc_bits_float( vrc_mip_bits( z.v ) );
+        state.y = vrc_bits_float( uniformHit ? VRC_ISO_WHERE_UNIFORM : z.where - base + 1u );
+        state.z = z.d;
+        state.w = vrc_bits_float( nodeIndex );
+    }
+    return beyond;
+}
+
+/* slot-local voxel of a slot-local element offset: vrc_slot_local_index read backwards (the product's layout) */
+VRC_HD void vrc_slot_local_voxel( uint32_t e, uint32_t sbx, uint32_t sby, uint32_t& x, uint32_t& y, uint32_t& z )
+{
+#if VRC_LAYOUT == 0
+    const uint32_t blk = e / VRC_MB_VOXELS, in = e % VRC_MB_VOXELS;
+    const uint32_t bx = blk % sbx, by = ( blk / sbx ) % sby, bz = blk / ( sbx * sby );
+    x = ( bx << VRC_MB_SHIFT ) | ( in & 7u );
+    y = ( by << VRC_MB_SHIFT ) | ( ( in >> 3 ) & 3u ) | ( ( in >> 5 ) & 4u );
+    z = ( bz << VRC_MB_SHIFT ) | ( ( in >> 5 ) & 3u ) | ( ( in >> 6 ) & 4u );
+#else
+    (void)e; (void)sbx; (void)sby;
+    x = y = z = 0u; /* the developer layouts have no isosurface frame (vrc_kernels_iso.hip refuses) */
+#endif
+}
+
+/* The gradient of a hit: central differences of stored voxels around slot-local element `where` of node n, indices
+ * clamped to the slot, times the node's voxels per world unit -- six gathers, once per ray and pass.  Integer voxels
+ * are differenced in integers (exact; an offset-binary shift cancels), float voxels in float. */
+template < typename ATLAS_T, bool BIG >
+VRC_HD void vrc_iso_gradient( const vrc_frame& f, const vrc_dev_node& n, const ATLAS_T* __restrict__ atlas, uint32_t where,
+                              float g[3] )
+{
+    VRC_STRICT_FP
+    const uint32_t sbx = f.sbx, sby = f.sby;
+    uint32_t c[3];
+    vrc_slot_local_voxel( where, sbx, sby, c[0], c[1], c[2] );
+    const ATLAS_T* slot = atlas;
+    uint32_t base = n.slotBase;
+    if( BIG )
+    {
+        base = 0u;
+        slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
+    }
+#pragma unroll
+    for( int a = 0; a < 3; ++a ) /* (a coordinate read back from a sample's own address lies inside the slot) */
+        c[a] = c[a] < f.slotDim[a] ? c[a] : f.slotDim[a] - 1u;
+#pragma unroll
+    for( int a = 0; a < 3; ++a )
+    {
+        uint32_t lo[3] = { c[0], c[1], c[2] }, hi[3] = { c[0], c[1], c[2] };
+        lo[a] = c[a] > 0u ? c[a] - 1u : 0u;
+        hi[a] = c[a] + 1u < f.slotDim[a] ? c[a] + 1u : f.slotDim[a] - 1u;
+        const ATLAS_T vHi = vrc_gather( slot, base + vrc_slot_local_index( hi[0], hi[1], hi[2], sbx, sby ) );
+        const ATLAS_T vLo = vrc_gather( slot, base + vrc_slot_local_index( lo[0], lo[1], lo[2], sbx, sby ) );
+        float diff;
+        if constexpr( sizeof( ATLAS_T ) == 4 )
+            diff = (float)vHi - (float)vLo;
+        else
+            diff = (float)( (int32_t)vHi - (int32_t)vLo );
+        g[a] = diff * n.voxPerWorld[a];
+    }
+}
+
+/* the headlight of an isosurface pixel: s = ambient + (1 - ambient) * |G.dir| / |G|, two-sided; 1 where |G| is 0 or not
+ * finite.  Float, in this order, nothing contracted. */
+VRC_HD float vrc_iso_shade( const float g[3], const vrc_f3& dir, float ambient )
+{
+    VRC_STRICT_FP
+    const float xx = g[0] * g[0], yy = g[1] * g[1], zz = g[2] * g[2];
+    const float len = sqrtf( ( xx + yy ) + zz );
+    if( !( len > 0.0f ) || !( len < vrc_bits_float( 0x7F800000u ) ) )
+        return 1.0f;
+    const float dx = g[0] * dir.x, dy = g[1] * dir.y, dz = g[2] * dir.z;
+    const float dot = fabsf( ( dx + dy ) + dz );
+    const float diffuse = ( ( 1.0f - ambient ) * dot ) / len;
+    return ambient + diffuse;
+}
+
 /* One brick of one ray.  The ray's state travels in the colour the brick walks hand on: x = the bits of M, y != 0 once
  * a sample was taken, w = 0 (no walk ever sees an opaque pixel).
  *   skipping (vrc_frame::slotMax)  a lane whose M no sample of the slot can raise takes none of them;
@@ -2797,8 +3232,8 @@ VRC_HD void vrc_mean_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc
  *     of equal voxels is the value only up to rounding: those are fetched);
  *   a wave none of whose lanes is left to march does not set the march up. */
 template < bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, int GROUP, bool BIG >
-VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s,
-                           const ATLAS_T* __restrict__ atlas, vrc_f4& state, uint32_t& nSamples )
+VRC_HD bool vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s,
+                           const ATLAS_T* __restrict__ atlas, vrc_f4& state, uint32_t& nSamples, uint32_t nodeIndex = 0u )
 {
     constexpr bool TRILINEAR = vrc_mode_base( MODE ) == VRC_MODE_MIP_TRILINEAR;
     constexpr int FOLD = vrc_mode_fold( MODE );
@@ -2807,8 +3242,16 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
     {
         static_assert( !DEPTH, "the mean has no position" );
         vrc_mean_brick< CLAMP, FIXED, TRILINEAR, ATLAS_T, GROUP, BIG >( f, n, s, atlas, state, nSamples );
-        return;
+        return false;
     }
+    else if constexpr( FOLD == VRC_FOLD_FIRST )
+    {
+        /* (nodeIndex: what only this fold keeps; true: the grid walk can end the ray) */
+        static_assert( !DEPTH, "the first crossing keeps its depth by itself" );
+        return vrc_iso_brick< CLAMP, FIXED, TRILINEAR, ATLAS_T, GROUP, BIG >( f, n, nodeIndex, s, atlas, state, nSamples );
+    }
+    else
+    {
     typedef typename vrc_density< ATLAS_T >::type P;
     typedef typename std::conditional< TRILINEAR, float, P >::type D;
     D m;
@@ -2906,6 +3349,8 @@ VRC_HD void vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
     state.y = has ? 1.0f : 0.0f;
     if constexpr( DEPTH )
         state.z = z.d;
+    return false;
+    }
 }
 
 /* the pixel of a maximum M: TF((M - r0) / (r1 - r0)) as vrc_classify fetches it (256 texels, linear, the weight in
@@ -3391,7 +3836,8 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                 {
                     vrc_segment s;
                     vrc_segment_complete( r, iv, f.stepSize, &s );
-                    vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, color, nSamples ); /* (color: the ray's MIP state) */
+                    if( vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, color, nSamples, (uint32_t)node ) ) /* (color: the ray's MIP state) */
+                        finished = true; /* (an isosurface frame: every brick from here on lies behind the ray's hit) */
                 }
                 else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, r, iv, atlas, lut, cls, color,
                                                                                        nSamples ) )
@@ -3801,6 +4247,7 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
     uint32_t bits = VRC_MIP_EMPTY;
     float depth = vrc_bits_float( 0x7F800000u ); /* (depth tracking: D, +infinity while no sample equals M) */
     uint32_t meanLo = 0u, meanHi = 0u, meanCount = 0u; /* (the mean fold's state; an integer 0 and a double 0 alike) */
+    uint32_t where = 0u, hitNode = 0u; /* (the first-crossing fold: where this pass's hit was read, vrc_iso_brick) */
     if( r.hit )
     {
         vrc_f4 state = zero;
@@ -3816,6 +4263,15 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
             }
             state.x = vrc_bits_float( meanLo );
             state.y = vrc_bits_float( meanHi );
+        }
+        else if constexpr( FOLD == VRC_FOLD_FIRST )
+        {
+            if( !f.mipFirst )
+                bits = f.mipMax[pixelPos];
+            if( bits != VRC_MIP_EMPTY )
+                depth = f.mipDepth[pixelPos];
+            state.x = vrc_bits_float( bits );
+            state.z = depth;
         }
         else
         {
@@ -3854,10 +4310,20 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
                         break;
                     continue;
                 }
-                vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, state, nSamples );
+                vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, state, nSamples, i );
             }
         }
-        if constexpr( FOLD == VRC_FOLD_MEAN )
+        if constexpr( FOLD == VRC_FOLD_FIRST )
+        {
+            where = vrc_float_bits( state.y );
+            if( where != 0u )
+            {
+                bits = vrc_float_bits( state.x );
+                depth = state.z;
+                hitNode = vrc_float_bits( state.w );
+            }
+        }
+        else if constexpr( FOLD == VRC_FOLD_MEAN )
         {
             meanLo = vrc_float_bits( state.x );
             meanHi = vrc_float_bits( state.y );
@@ -3870,7 +4336,41 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
                 depth = state.y != 0.0f ? state.z : depth;
         }
     }
-    if constexpr( FOLD == VRC_FOLD_MEAN )
+    if constexpr( FOLD == VRC_FOLD_FIRST )
+    {
+        /* the gradient: gathered where this pass lowered D (its nodes, its atlas), else what the passes before left */
+        float g[3] = { 0.0f, 0.0f, 0.0f };
+        if( where != 0u )
+        {
+            if( where != VRC_ISO_WHERE_UNIFORM && hitNode < f.nodeCount )
+                vrc_iso_gradient< ATLAS_T, BIG >( f, nodes[hitNode], atlas, where - 1u, g );
+        }
+        else if( bits != VRC_MIP_EMPTY )
+        {
+            g[0] = f.isoGrad[3u * pixelPos];
+            g[1] = f.isoGrad[3u * pixelPos + 1u];
+            g[2] = f.isoGrad[3u * pixelPos + 2u];
+        }
+        f.mipMax[pixelPos] = bits;
+        f.mipDepth[pixelPos] = depth;
+        f.isoGrad[3u * pixelPos] = g[0];
+        f.isoGrad[3u * pixelPos + 1u] = g[1];
+        f.isoGrad[3u * pixelPos + 2u] = g[2];
+        if( bits != VRC_MIP_EMPTY )
+        {
+            const vrc_f4 e = vrc_classify_mip( tfp, f.isoClassify, cls );
+            const float sh = vrc_iso_shade( g, r.dir, f.isoAmbient );
+            vrc_f4 p;
+            p.x = e.x * sh;
+            p.y = e.y * sh;
+            p.z = e.z * sh;
+            p.w = e.w;
+            pixelBuffer[pixelPos] = p;
+        }
+        else if( f.clearFirst )
+            pixelBuffer[pixelPos] = zero;
+    }
+    else if constexpr( FOLD == VRC_FOLD_MEAN )
     {
         f.meanSum[pixelPos] = ( (unsigned long long)meanHi << 32 ) | meanLo;
         f.meanCount[pixelPos] = meanCount;

@@ -213,6 +213,10 @@ hipError_t vrc_launch_raycast_mip_depth( const vrc_raycast_args& a, int fold, hi
 hipError_t vrc_launch_projection_depths( const vrc_frame& f, const float* depth, uint32_t pixels, float* t, float* xyz,
                                          hipStream_t stream );
 
+/* an isosurface frame (vrc_kernels_iso.hip; VRC_OPT_PROJECTION = VRC_PROJECTION_ISO): the first-crossing fold of the MIP
+ * kernel; frame.mipMax, frame.mipDepth and frame.isoGrad set, frame.slotMax = NULL: every sample is taken */
+hipError_t vrc_launch_raycast_iso( const vrc_raycast_args& a, hipStream_t stream );
+
 /* LDS-staged form (vrc_kernels_lds.hip): needs gridTable, !clamp, 8x8 tiles */
 hipError_t vrc_launch_raycast_lds( const vrc_raycast_args& a, hipStream_t stream );
 

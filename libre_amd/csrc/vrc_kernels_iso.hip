@@ -1,0 +1,18 @@
+/*
+ * vrc_kernels_iso.hip -- gfx950 kernels of an isosurface frame (VRC_OPT_PROJECTION = VRC_PROJECTION_ISO): the instances
+ * of vrc_kernels_mip.h's kernel for the first-crossing fold (vrc_core.h: VRC_FOLD_FIRST), and nothing else.  A composite
+ * or MIP frame launches nothing from this file.
+ */
+#include "vrc_kernels_mip.h"
+
+hipError_t vrc_launch_raycast_iso( const vrc_raycast_args& a, hipStream_t stream )
+{
+#if VRC_LAYOUT == 0
+    return launch_mip_fold< VRC_FOLD_FIRST >( a, stream );
+#else
+    /* (the gradient reads a sample's voxel back from its address, which is written for the product's layout alone) */
+    (void)a;
+    (void)stream;
+    return hipErrorInvalidValue;
+#endif
+}

@@ -34,10 +34,13 @@
  *     sampler; 64-bit slot bases): at least 4, as the composite forms that spilled at 5.
  *   trilinear samples with depth tracking (vrc_kernels_mipdepth.hip): at least 3.  The group's eight samples stay live
  *     past the fold for the index search, and at 4 (128 VGPRs) the grid-walk forms with the clamped sampler spilled
- *     12-16 bytes a lane; at 3 none does (DESIGN.md section 4.6 has the table). */
+ *     12-16 bytes a lane; at 3 none does (DESIGN.md section 4.6 has the table).
+ *   the first-crossing fold (vrc_kernels_iso.hip): as the fold-less rows above for point samples (74-101 VGPRs), at least
+ *     3 for trilinear samples as with depth tracking -- the group's samples and taps stay live for the search (116-140
+ *     VGPRs, no scratch; the table is in the same section). */
 #define VRC_MIP_MIN_WAVES                                                                                          \
     ( ( vrc_mode_base( MODE ) == VRC_MODE_MIP && FIXED && !CLAMP && !BIG )                            ? 5          \
-      : ( vrc_mode_depth( MODE ) && vrc_mode_base( MODE ) == VRC_MODE_MIP_TRILINEAR ) ? 3 : 4 )
+      : ( ( vrc_mode_depth( MODE ) || vrc_mode_fold( MODE ) == VRC_FOLD_FIRST ) && vrc_mode_base( MODE ) == VRC_MODE_MIP_TRILINEAR ) ? 3 : 4 )
 #define VRC_MIP_MAX_WAVES ( ( vrc_mode_base( MODE ) == VRC_MODE_MIP && FIXED && !CLAMP && !BIG ) ? 5 : 8 )
 
 template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
@@ -188,6 +191,8 @@ static hipError_t launch_mip_fold( const vrc_raycast_args& a, hipStream_t stream
     if( VRC_TILE_W != 8u || a.lut == nullptr )
         return hipErrorInvalidValue;
     if( FOLD == VRC_FOLD_MEAN ? ( a.frame.meanSum == nullptr || a.frame.meanCount == nullptr ) : a.frame.mipMax == nullptr )
+        return hipErrorInvalidValue;
+    if( FOLD == VRC_FOLD_FIRST && ( a.frame.mipDepth == nullptr || a.frame.isoGrad == nullptr ) )
         return hipErrorInvalidValue;
     switch( a.elemBytes )
     {

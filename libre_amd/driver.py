@@ -29,7 +29,7 @@ EXPORTS = [
     "lvh_app_set_modelview", "lvh_app_set_time_step", "lvh_datasource_frame_range", "lvh_app_set_colormap", "lvh_app_set_clip_planes",
     "lvh_app_set_bands", "lvh_app_set_frames_in_flight", "lvh_app_select_slot", "lvh_app_set_option", "lvh_app_get_option", "lvh_app_set_data_range", "lvh_app_set_ray_lod", "lvh_app_set_stream", "lvh_app_set_framebuffer", "lvh_app_render_frame",
     "lvh_app_get_stats", "lvh_app_wait_uploads", "lvh_app_synchronize", "lvh_app_volume_info",
-    "lvh_app_set_histogram", "lvh_app_frame_histogram", "lvh_app_pick",
+    "lvh_app_set_histogram", "lvh_app_frame_histogram", "lvh_app_pick", "lvh_app_set_isosurface",
     "lvh_comm_unique_id", "lvh_app_comm_create", "lvh_app_set_layout", "lvh_app_gather_tiles",
     "lvh_app_visible_set", "lvh_app_node_order", "lvh_app_view_matrices", "lvh_app_cache_stats", "lvh_select_visibles",
     "lvh_selftest_cache", "lvh_selftest_plugin_factory", "lvh_selftest_camera",
@@ -61,6 +61,7 @@ def load_library():
     L.lvh_app_select_slot.argtypes = [vp, C.c_uint32]
     L.lvh_app_set_option.argtypes = [vp, C.c_int, C.c_int64]
     L.lvh_app_get_option.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
+    L.lvh_app_set_isosurface.argtypes = [vp, C.c_float, C.c_float]
     L.lvh_app_set_data_range.argtypes = [vp, C.c_float, C.c_float]
     L.lvh_app_set_ray_lod.argtypes = [vp, C.c_int]
     L.lvh_app_set_stream.argtypes = [vp, vp]
@@ -156,6 +157,11 @@ class App:
     def set_option(self, option, value):
         check(self.L, self.L.lvh_app_set_option(self.h, option, value))
 
+    def set_isosurface(self, iso_value, ambient=0.2):
+        """The isosurface of frames rendered under VRC_OPT_PROJECTION = PROJECTION_ISO: the isovalue in the volume's own
+        units and the ambient share of the shading in [0, 1]; reaches every renderer slot."""
+        check(self.L, self.L.lvh_app_set_isosurface(self.h, float(iso_value), float(ambient)))
+
     def get_option(self, option):
         v = C.c_int64()
         check(self.L, self.L.lvh_app_get_option(self.h, option, C.byref(v)))
@@ -204,7 +210,9 @@ class App:
     def pick(self, x, y):
         """What lies behind pixel (x, y) of the window in the selected slot's last frame -- a MIP frame (maximum or
         minimum) rendered with VRC_OPT_MIP_DEPTH or a depth cue: (hit, value, t, (x, y, z)); value is the projected
-        value in the volume's own units, t the ray parameter of the nearest sample that has it, xyz its position."""
+        value in the volume's own units, t the ray parameter of the nearest sample that has it, xyz its position.
+        In an isosurface frame (PROJECTION_ISO): hit says whether the ray reached the isovalue, value, t and xyz are
+        those of the first sample that did -- the surface under the pixel."""
         hit, value, t, xyz = C.c_int(), C.c_float(), C.c_float(), (C.c_float * 3)()
         check(self.L, self.L.lvh_app_pick(self.h, int(x), int(y), C.byref(hit), C.byref(value), C.byref(t), xyz))
         return bool(hit.value), float(value.value), float(t.value), (float(xyz[0]), float(xyz[1]), float(xyz[2]))

@@ -92,7 +92,9 @@ public:
     void setStream( void* hipStream );
     void setOption( int option, int64_t value );
     int64_t getOption( int option ) const;
-    /** VRC_OPT_PROJECTION = VRC_PROJECTION_MIP was set: the maximum-intensity projection has no per-ray LOD form, a frame
+    /** vrc_set_isosurface: the isovalue (the volume's own units) and the ambient share of VRC_PROJECTION_ISO frames */
+    void setIsosurface( float isoValue, float ambient );
+    /** VRC_OPT_PROJECTION = VRC_PROJECTION_MIP or _ISO was set: neither projection has a per-ray LOD form, a frame
      *  that asks for per-ray LOD is then rendered with its per-brick cut (the path taken on VRC_EHIERARCHY) */
     bool projectionIsMip() const { return _mip; }
     /** kernel time (HIP events) of the last launch, sum and count since the previous call,

@@ -41,6 +41,8 @@ struct lvh_app
     RenderStatistics lastStats;
     std::vector< uint32_t > rowMap; /* lvh_app_set_bands */
     std::vector< std::unique_ptr< Renderer > > extraRenderers; /* frames in flight beyond the first */
+    bool isoSet = false; /* lvh_app_set_isosurface as called: for renderers made later */
+    float isoValue = 0.f, isoAmbient = 0.f;
     std::map< int, int64_t > projectionOptions; /* VRC_OPT_PROJECTION / VRC_OPT_MIP_SKIP / _FOLD / _DEPTH / _DEPTH_CUE as set: for renderers made later */
     struct PickFrame /* per renderer slot: where its last frame's pixel buffer lies in the window (lvh_app_pick) */
     {
@@ -297,6 +299,8 @@ int lvh_app_set_frames_in_flight( lvh_app* app, uint32_t n )
         while( app->extraRenderers.size() + 1 < n )
         {
             app->extraRenderers.emplace_back( new Renderer( app->rendererName ) );
+            if( app->isoSet ) /* (first: VRC_PROJECTION_ISO is refused on a context without an isosurface) */
+                static_cast< HipRaycastRenderer& >( app->extraRenderers.back()->getPlugin() ).setIsosurface( app->isoValue, app->isoAmbient );
             for( const auto& o : app->projectionOptions )
                 static_cast< HipRaycastRenderer& >( app->extraRenderers.back()->getPlugin() ).setOption( o.first, o.second );
             if( app->histogram )
@@ -346,6 +350,25 @@ int lvh_app_set_option( lvh_app* app, int option, int64_t value )
         }
     }
     LVH_TRY( app->renderer().setOption( option, value ) )
+}
+int lvh_app_set_isosurface( lvh_app* app, float iso_value, float ambient )
+{
+    if( !app ) return fail( "NULL argument" );
+    /* as the projection options: every renderer the app has, and every one it makes later */
+    try
+    {
+        static_cast< HipRaycastRenderer& >( app->pipeline->getRenderer().getPlugin() ).setIsosurface( iso_value, ambient );
+        for( auto& r : app->extraRenderers )
+            static_cast< HipRaycastRenderer& >( r->getPlugin() ).setIsosurface( iso_value, ambient );
+        app->isoSet = true;
+        app->isoValue = iso_value;
+        app->isoAmbient = ambient;
+        return 0;
+    }
+    catch( const std::exception& e )
+    {
+        return fail( e.what() );
+    }
 }
 int lvh_app_get_option( lvh_app* app, int option, int64_t* value )
 {

@@ -26,6 +26,8 @@
 /* ... and so is the typed pool (signed, 32-bit and float voxels): without it the pool comes from vrc_pool_create,
  * which makes unsigned 8- and 16-bit pools and refuses the rest */
 #pragma weak vrc_pool_create_typed
+/* ... and the isosurface of VRC_PROJECTION_ISO frames: without it setIsosurface says so */
+#pragma weak vrc_set_isosurface
 
 extern "C" int LunchboxPluginGetVersion() { return 1; } /* LIVRECORE_VERSION_ABI, CudaRaycastPipeline.cpp:50-51 */
 extern "C" bool LunchboxPluginRegister() { return true; } /* CudaRaycastPipeline.cpp:53-54 */
@@ -760,7 +762,13 @@ void HipRaycastRenderer::setOption( int o, int64_t v )
 {
     throwOnVrcError( vrc_set_option( _ctx, o, v ), "vrc_set_option" );
     if( o == VRC_OPT_PROJECTION ) /* (whichever VRC_OPT_MIP_FOLD: every fold of a MIP frame takes the per-brick cut) */
-        _mip = v == VRC_PROJECTION_MIP;
+        _mip = v == VRC_PROJECTION_MIP || v == VRC_PROJECTION_ISO; /* (an isosurface frame is served as a MIP frame is) */
+}
+void HipRaycastRenderer::setIsosurface( float isoValue, float ambient )
+{
+    if( vrc_set_isosurface == nullptr )
+        throw std::runtime_error( "vrc_set_isosurface: the device layer has no isosurface projection" );
+    throwOnVrcError( vrc_set_isosurface( _ctx, isoValue, ambient ), "vrc_set_isosurface" );
 }
 int64_t HipRaycastRenderer::getOption( int o ) const
 {

@@ -15,7 +15,7 @@ OPT_PROJECTION, OPT_MIP_SKIP, OPT_MIP_FOLD = 16, 17, 18
 OPT_MIP_DEPTH, OPT_MIP_DEPTH_CUE = 19, 20
 OPT_STREAM_MARKERS = 21
 OPT_RAY_CACHE, OPT_RAY_CACHE_USED = 22, 23
-PROJECTION_COMPOSITE, PROJECTION_MIP = 0, 1
+PROJECTION_COMPOSITE, PROJECTION_MIP, PROJECTION_ISO = 0, 1, 2
 MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2
 VARIANT_CUDARAYCASTER, VARIANT_GLRAYCASTER = 0, 1
 FILTER_NEAREST, FILTER_TRILINEAR = 0, 1
@@ -66,7 +66,8 @@ EXPORTS = [
     "vrc_pool_release_slot", "vrc_pool_info", "vrc_pool_synchronize", "vrc_pool_read_region",
     "vrc_pool_histogram", "vrc_pool_enable_histograms", "vrc_frame_histogram", "vrc_get_frame_histogram",
     "vrc_update", "vrc_pre_render", "vrc_set_row_map", "vrc_set_framebuffer", "vrc_get_framebuffer", "vrc_render",
-    "vrc_post_render", "vrc_synchronize", "vrc_get_stats", "vrc_get_ray_counts", "vrc_get_projection_values", "vrc_get_projection_depths", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
+    "vrc_post_render", "vrc_synchronize", "vrc_get_stats", "vrc_get_ray_counts", "vrc_get_projection_values", "vrc_get_projection_depths",
+    "vrc_set_isosurface", "vrc_get_projection_gradients", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
     "vrc_comm_unique_id", "vrc_comm_create", "vrc_comm_destroy", "vrc_comm_info", "vrc_gather_tiles",
 ]
 COMM_ID_BYTES = 128
@@ -139,6 +140,9 @@ def load_library(path=None):
         L.vrc_get_projection_values.argtypes = [vp, vp, vp]
     if hasattr(L, "vrc_get_projection_depths"):
         L.vrc_get_projection_depths.argtypes = [vp, vp, vp]
+    if hasattr(L, "vrc_set_isosurface"):
+        L.vrc_set_isosurface.argtypes = [vp, C.c_float, C.c_float]
+        L.vrc_get_projection_gradients.argtypes = [vp, vp]
     L.vrc_comm_unique_id.argtypes = [C.c_char_p]
     L.vrc_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     L.vrc_comm_destroy.argtypes = [vp]
@@ -167,3 +171,22 @@ def projection_depths(L, ctx, width, height, xyz=True):
     p = np.empty((height, width, 3), dtype=np.float32) if xyz else None
     check(L, L.vrc_get_projection_depths(ctx, t.ctypes.data, p.ctypes.data if xyz else None))
     return t, p
+
+
+def set_isosurface(L, ctx, iso_value, ambient=0.2):
+    """vrc_set_isosurface: the isovalue (in the volume's own units) and the ambient share in [0, 1] of the frames
+    rendered under VRC_OPT_PROJECTION = PROJECTION_ISO."""
+    if not hasattr(L, "vrc_set_isosurface"):
+        raise VrcError(VRC_EUNSUPPORTED, "this libvrc_hip.so has no vrc_set_isosurface")
+    check(L, L.vrc_set_isosurface(ctx, float(iso_value), float(ambient)))
+
+
+def projection_gradients(L, ctx, width, height):
+    """vrc_get_projection_gradients of the isosurface frame just rendered: a float32 array of height x width x 3, the
+    world-space gradient at every pixel's hit, 0 where the ray did not hit."""
+    import numpy as np
+    if not hasattr(L, "vrc_get_projection_gradients"):
+        raise VrcError(VRC_EUNSUPPORTED, "this libvrc_hip.so has no vrc_get_projection_gradients")
+    g = np.empty((height, width, 3), dtype=np.float32)
+    check(L, L.vrc_get_projection_gradients(ctx, g.ctypes.data))
+    return g
