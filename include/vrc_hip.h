@@ -214,6 +214,51 @@ typedef struct
 #define VRC_OPT_RAY_CACHE_USED 23   /* read-only (vrc_get_option), no synchronisation: what the last vrc_render did with
                                     * the ray cache -- 0 computed its rays, 1 computed and stored them, 2 loaded them */
 
+#define VRC_OPT_WALK_CACHE 24       /* 1 (default) | 0 | 2.  Which bricks a ray visits, and the interval of each, depend on
+                                    * the ray, the brick grid, the node list and the step size, the variant and the clip
+                                    * planes -- not on the transfer function, the voxels or early ray termination.  A
+                                    * view that stands still over an unchanged node list (transfer-function edits, the
+                                    * frames after the last brick arrived) walks the brick grid once: frames that load
+                                    * their rays (VRC_OPT_RAY_CACHE_USED = 2) first count the longest list (one small
+                                    * extra launch), then record every ray's visits in device memory the context owns
+                                    * (4 + 16 bytes per visit and pixel of whole 8x8 tiles, as many visits as the longest
+                                    * list has), and from then on march from the lists with a kernel that has no grid
+                                    * walk in it (vrc_last_kernel: vrc_k_raycast_replay<...>; vrc_stats.kernel_variant
+                                    * stays VRC_KERNEL_GRID_DDA).  The march receives the same bricks, intervals and
+                                    * distances in the same order: the same frame and sample count, bit for bit.  The
+                                    * two extra launches are no marches: vrc_stats neither times nor counts them.  Only
+                                    * the table-driven point-sampling march of 8-bit voxels (VRC_FILTER_NEAREST,
+                                    * VRC_OPT_STEPPING 1, bricks with an overlap, slots of at most 248 voxels a side, an
+                                    * atlas of at most 2^32 voxels) over a grid-aligned node set: every other frame
+                                    * walks.  A camera that moves every frame allocates nothing and launches nothing
+                                    * extra.  What starts over: anything that starts the ray cache over, a changed node
+                                    * list, step size, variant or clip plane, vrc_ctx_set_stream, a changed
+                                    * vrc_set_row_map, and setting this option or the budget to another value; the node
+                                    * list and the constants must have been those of the vrc_render before for the count
+                                    * to be taken, so passes over alternating node subsets and frames rendered while
+                                    * bricks stream in launch nothing extra.  Where a visit gathers voxels the replay
+                                    * gains nothing on the walk (measured 1 to 3 % slower), so at 1 the count pass also
+                                    * counts the visits whose brick is not known to be uniform, and a view more than
+                                    * half of whose visits are such records nothing and stays on the walk (_USED reads 0)
+                                    * until a brick upload into the pool or VRC_OPT_UNIFORM_BRICKS changes that; those
+                                    * two then also start a replaying view over.  VRC_WALK_CACHE_ALWAYS (2): replay
+                                    * whatever the bricks hold; uploads and VRC_OPT_UNIFORM_BRICKS start nothing over.
+                                    * 0: walk every frame.  Other values: VRC_EINVAL */
+#define VRC_WALK_CACHE_ALWAYS 2
+#define VRC_OPT_WALK_CACHE_USED 25  /* read-only (vrc_get_option), no synchronisation: what the last vrc_render did -- 0
+                                    * walked; 1 walked and ran the count pass; 2 walked, the count has not arrived yet;
+                                    * 3 walked and ran the record pass; 4 replayed the lists */
+#define VRC_OPT_WALK_CACHE_BUDGET 26 /* bytes of device memory the lists of this context may take, default
+                                    * VRC_WALK_CACHE_DEFAULT_BUDGET.  A view whose lists need more (or more than 2^32
+                                    * words) stays on the walk: VRC_OPT_WALK_CACHE_USED then reads 0 (1 and 2 while the
+                                    * count is taken, unless not even one visit per ray fits).  Negative: VRC_EINVAL */
+#define VRC_OPT_WALK_CACHE_BYTES 27 /* read-only: bytes of device memory the context's lists hold now */
+/* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
+ * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
+ * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots
+ * of the default view: 1176 MiB in all) */
+#define VRC_WALK_CACHE_DEFAULT_BUDGET ( 512ll << 20 )
+
 /* A MIP frame (VRC_OPT_PROJECTION = VRC_PROJECTION_MIP).
  *   Sample set.  A ray's sample set S is exactly what the composite march takes with a transfer function whose alpha
  *     is 0 everywhere: the same ray set-up, global-box and clip-plane interval and near plane; the same node list

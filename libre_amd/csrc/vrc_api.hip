@@ -216,6 +216,30 @@ struct vrc_ctx
     vrc_frame rayPrevFrame;
     int64_t optRayCache = 1;
     int64_t rayCacheUsed = 0;
+    /* walk cache (VRC_OPT_WALK_CACHE; vrc_core.h: vrc_frame::walkCache).  walkState: WALK_IDLE nothing known; WALK_COUNTING
+     * the count pass is on the stream, its result on the way to hWalkMax behind evWalk; WALK_VALID the planes hold the
+     * lists of walkFrame's constants over the node table as it is.  Nothing here exists before the first count pass: a
+     * camera that moves every frame allocates nothing.  The count pass runs only for a frame whose constants, node list
+     * and (option at 1) pool uploads are those of the vrc_render before, walkPrev*: what changes every call -- passes over
+     * different node subsets, bricks streaming in -- launches nothing extra.  Option at 1: a view whose visits mostly
+     * gather stays on the walk (walkGen, walkSlotInfo: the uploads and uniformity words that was decided under; when they
+     * change the view is counted again) */
+    enum { WALK_IDLE = 0, WALK_COUNTING = 1, WALK_VALID = 2 };
+    int walkState = WALK_IDLE;
+    uint32_t* dWalk = nullptr;
+    size_t dWalkWords = 0;        /* allocated */
+    uint32_t walkK = 0;           /* visits per ray the planes hold */
+    vrc_walk_count* dWalkMax = nullptr; /* the count pass's result, and its pinned copy */
+    vrc_walk_count* hWalkMax = nullptr;
+    hipEvent_t evWalk = nullptr;
+    vrc_frame walkFrame;
+    vrc_frame walkPrevFrame;
+    bool walkPrevSet = false;
+    uint64_t walkPrevGen = 0, walkGen = 0;
+    const uint32_t* walkSlotInfo = nullptr;
+    int64_t optWalkCache = 1;
+    int64_t optWalkBudget = VRC_WALK_CACHE_DEFAULT_BUDGET;
+    int64_t walkCacheUsed = 0;
     int64_t optStepping = 1;
     int64_t optVariant = VRC_VARIANT_CUDARAYCASTER;
     bool rayLod = false; /* vrc_set_ray_lod */
@@ -432,6 +456,10 @@ void vrc_ctx_destroy( vrc_ctx* c )
         if( e ) (void)hipEventDestroy( e );
     if( c->dTileOrder ) (void)hipFree( c->dTileOrder );
     if( c->dRayCache ) (void)hipFree( c->dRayCache );
+    if( c->dWalk ) (void)hipFree( c->dWalk );
+    if( c->dWalkMax ) (void)hipFree( c->dWalkMax );
+    if( c->hWalkMax ) (void)hipHostFree( c->hWalkMax );
+    if( c->evWalk ) (void)hipEventDestroy( c->evWalk );
     if( c->dRayList ) (void)hipFree( c->dRayList );
     if( c->dMipMax ) (void)hipFree( c->dMipMax );
     if( c->dMeanSum ) (void)hipFree( c->dMeanSum );
@@ -463,6 +491,7 @@ int vrc_ctx_set_stream( vrc_ctx* c, void* s )
     c->stream = s ? (hipStream_t)s : c->ownStream;
     c->waitedPoolUid = c->waitedGen = 0; /* the new stream has waited for no upload */
     c->rayCacheValid = c->rayPrevSet = false; /* (the planes were written on the stream before) */
+    c->walkState = vrc_ctx::WALK_IDLE;        /* (and so were the lists; a count pass in flight has ended above) */
     return VRC_OK;
 }
 
@@ -500,6 +529,20 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
         if( c->optRayCache != ( value ? 1 : 0 ) )
             c->rayCacheValid = c->rayPrevSet = false;
         c->optRayCache = value ? 1 : 0;
+        return VRC_OK;
+    case VRC_OPT_WALK_CACHE:
+        if( value < 0 || value > VRC_WALK_CACHE_ALWAYS )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_CACHE is 0 (off), 1 (on) or 2 (on for every view)" );
+        if( c->optWalkCache != value )
+            c->walkState = vrc_ctx::WALK_IDLE;
+        c->optWalkCache = value;
+        return VRC_OK;
+    case VRC_OPT_WALK_CACHE_BUDGET:
+        if( value < 0 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_CACHE_BUDGET is a number of bytes" );
+        if( c->optWalkBudget != value )
+            c->walkState = vrc_ctx::WALK_IDLE;
+        c->optWalkBudget = value;
         return VRC_OK;
     case VRC_OPT_PROJECTION:
         if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP && value != VRC_PROJECTION_ISO )
@@ -562,6 +605,10 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_STREAM_MARKERS: *value = c->optStreamMarkers; return VRC_OK;
     case VRC_OPT_RAY_CACHE: *value = c->optRayCache; return VRC_OK;
     case VRC_OPT_RAY_CACHE_USED: *value = c->rayCacheUsed; return VRC_OK;
+    case VRC_OPT_WALK_CACHE: *value = c->optWalkCache; return VRC_OK;
+    case VRC_OPT_WALK_CACHE_USED: *value = c->walkCacheUsed; return VRC_OK;
+    case VRC_OPT_WALK_CACHE_BUDGET: *value = c->optWalkBudget; return VRC_OK;
+    case VRC_OPT_WALK_CACHE_BYTES: *value = (int64_t)( c->dWalkWords * sizeof( uint32_t ) ); return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->optProjection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->optMipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->optMipFold; return VRC_OK;
@@ -1388,6 +1435,19 @@ static bool ray_constants_equal( const vrc_frame& a, const vrc_frame& b )
            std::memcmp( a.planes, b.planes, sizeof( a.planes ) ) == 0;
 }
 
+/* Do two frames of the same rays visit the same bricks over the same intervals?  What vrc_ray_grid_dda and
+ * vrc_brick_interval read beside the ray, bit for bit (the node table itself: vrc_render forgets the lists when the
+ * node list changes) */
+static bool walk_constants_equal( const vrc_frame& a, const vrc_frame& b )
+{
+    return ray_constants_equal( a, b ) && a.nodeCount == b.nodeCount &&
+           std::memcmp( &a.stepSize, &b.stepSize, sizeof( float ) ) == 0 &&
+           std::memcmp( a.gridMin, b.gridMin, sizeof( a.gridMin ) ) == 0 &&
+           std::memcmp( a.cellSize, b.cellSize, sizeof( a.cellSize ) ) == 0 &&
+           std::memcmp( a.invCellSize, b.invCellSize, sizeof( a.invCellSize ) ) == 0 &&
+           std::memcmp( a.gridDim, b.gridDim, sizeof( a.gridDim ) ) == 0;
+}
+
 int vrc_set_row_map( vrc_ctx* c, const uint32_t* rows, uint32_t n )
 {
     if( !c || ( n && !rows ) )
@@ -1409,6 +1469,7 @@ int vrc_set_row_map( vrc_ctx* c, const uint32_t* rows, uint32_t n )
     c->rowMap.assign( rows, rows + n );
     c->tileOrderValid = false;
     c->rayCacheValid = c->rayPrevSet = false;
+    c->walkState = vrc_ctx::WALK_IDLE; /* (the stream was synchronised above) */
     return VRC_OK;
 }
 
@@ -1683,6 +1744,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                                         nNodes * sizeof( vrc_node_data ) ) == 0;
     if( !sameNodes )
     {
+        c->walkState = vrc_ctx::WALK_IDLE; /* the walk cache's lists index the node table that is replaced here */
         vrc_host_tables t;
         vrc_atlas_geom geom;
         for( int a = 0; a < 3; ++a )
@@ -2091,6 +2153,101 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     }
     /* grey transfer function, frame starting from zero: two-float table entries, the same bits (VRC_MODE_GREY) */
     a.greyTable = c->optGreyTable && c->tfGrey && f.clearFirst && !glSuper; /* (a sub-ray starts from the pixel so far) */
+    /* walk cache (VRC_OPT_WALK_CACHE): a frame that loads its rays, of the instances the replay march exists for
+     * (vrc_internal.h: vrc_walk_replay_eligible).  The first such frame also runs the count pass; the first one after
+     * its result has arrived (polled, never waited for) sizes the planes and runs the record pass; the ones after that
+     * replay.  Both passes go on the stream in front of the march's timing pair and are no marches: not timed, not
+     * counted as launches.  Whatever the lists depend on starts over when it changes: walk_constants_equal here,
+     * the node list above, the stream, the row map and the options where they are set; the transfer function, the
+     * uniformity words and the pixel buffer's contents are not among them.  What the lists do not depend on may still
+     * decide whether they are worth using: where every visit gathers the replay is no faster than the walk, and by 1 to
+     * 3 % slower (profiles/r10_walk_cache.txt), so with the option at 1 a view more than half of whose visits gather, by
+     * the count pass and the uniformity words it read, is not recorded and stays on the walk until the pool's uploads or
+     * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold */
+    c->walkCacheUsed = 0;
+    f.walkCache = nullptr;
+    f.walkPlane = f.walkK = 0u;
+    bool walkCount = false, walkRecord = false;
+    {
+        const size_t tiles = (size_t)( ( c->fbW + VRC_TILE_W - 1 ) / VRC_TILE_W ) * ( ( c->fbH + VRC_TILE_H - 1 ) / VRC_TILE_H );
+        const size_t plane = tiles * 64u;
+        const auto fits = [&]( uint32_t k ) { /* the planes of k visits: 32-bit word offsets in the kernels, and the budget */
+            const unsigned long long words = ( 1ull + 4ull * k ) * plane;
+            return words <= 0xFFFFFFFFull && words * sizeof( uint32_t ) <= (unsigned long long)c->optWalkBudget;
+        };
+        const bool eligible = c->optWalkCache && c->rayCacheUsed == VRC_RAY_LOAD && vrc_walk_replay_eligible( a ) &&
+                              f.nodeCount > 0u && plane > 0u && fits( 1u );
+        const bool byContent = c->optWalkCache != VRC_WALK_CACHE_ALWAYS;
+        const uint64_t gen = pool->uploadGen; /* (compared only where the choice goes by the bricks' content) */
+        if( !eligible || ( c->walkState != vrc_ctx::WALK_IDLE &&
+                           ( !walk_constants_equal( c->walkFrame, f ) ||
+                             ( byContent && ( c->walkGen != gen || c->walkSlotInfo != f.slotInfo ) ) ) ) )
+            c->walkState = vrc_ctx::WALK_IDLE;
+        const bool repeats = sameNodes && c->walkPrevSet && ( !byContent || c->walkPrevGen == gen ) &&
+                             walk_constants_equal( c->walkPrevFrame, f );
+        std::memcpy( &c->walkPrevFrame, &f, sizeof( f ) );
+        c->walkPrevSet = true;
+        c->walkPrevGen = gen;
+        if( eligible )
+        {
+            if( c->walkState == vrc_ctx::WALK_IDLE && !repeats )
+                ; /* mode 0: the next call counts if it is this one again */
+            else if( c->walkState == vrc_ctx::WALK_IDLE )
+            {
+                if( !c->dWalkMax )
+                {
+                    VRC_HIP_CHECK( hipMalloc( &c->dWalkMax, sizeof( vrc_walk_count ) ) );
+                    VRC_HIP_CHECK( hipHostMalloc( &c->hWalkMax, sizeof( vrc_walk_count ) ) );
+                    VRC_HIP_CHECK( hipEventCreateWithFlags( &c->evWalk, hipEventDisableTiming ) );
+                }
+                walkCount = true;
+                c->walkGen = gen;
+                c->walkSlotInfo = f.slotInfo;
+                c->walkCacheUsed = 1;
+            }
+            else if( c->walkState == vrc_ctx::WALK_COUNTING )
+            {
+                c->walkCacheUsed = 2;
+                const hipError_t q = hipEventQuery( c->evWalk );
+                if( q == hipErrorNotReady )
+                    (void)hipGetLastError(); /* (not an error: nothing later may find it there) */
+                else if( q != hipSuccess )
+                    VRC_HIP_CHECK( q );
+                if( q == hipSuccess )
+                {
+                    const uint32_t k = c->hWalkMax->longest > 0u ? c->hWalkMax->longest : 1u;
+                    if( !fits( k ) )
+                        c->walkCacheUsed = 0; /* over the budget or the offset limit: this view stays on the walk */
+                    else if( byContent && 2u * c->hWalkMax->gathers > c->hWalkMax->visits )
+                        c->walkCacheUsed = 0; /* most visits gather: so does this one */
+                    else
+                    {
+                        const size_t words = ( 1u + 4u * (size_t)k ) * plane;
+                        if( words > c->dWalkWords )
+                        {
+                            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+                            if( c->dWalk ) VRC_HIP_CHECK( hipFree( c->dWalk ) );
+                            c->dWalk = nullptr;
+                            c->dWalkWords = 0;
+                            VRC_HIP_CHECK( hipMalloc( &c->dWalk, words * sizeof( uint32_t ) ) );
+                            c->dWalkWords = words;
+                        }
+                        c->walkK = k;
+                        walkRecord = true;
+                        c->walkCacheUsed = 3;
+                    }
+                }
+            }
+            else
+                c->walkCacheUsed = 4;
+        }
+        if( walkRecord || c->walkCacheUsed == 4 )
+        {
+            f.walkCache = c->dWalk;
+            f.walkPlane = (uint32_t)plane;
+            f.walkK = c->walkK;
+        }
+    }
     a.classifier = vrc_make_classifier( lp );
 
     /* order the march after every brick upload issued so far (fixes quirk Q9) */
@@ -2098,6 +2255,23 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         const int rc = ctx_wait_uploads( c, pool );
         if( rc != VRC_OK )
             return rc;
+    }
+    if( walkCount )
+    {
+        VRC_HIP_CHECK( hipMemsetAsync( c->dWalkMax, 0, sizeof( vrc_walk_count ), c->stream ) );
+        VRC_HIP_CHECK( vrc_launch_walk_record( a, c->dWalkMax, c->stream ) );
+        VRC_HIP_CHECK( hipMemcpyAsync( c->hWalkMax, c->dWalkMax, sizeof( vrc_walk_count ), hipMemcpyDeviceToHost, c->stream ) );
+        VRC_HIP_CHECK( hipEventRecord( c->evWalk, c->stream ) );
+        std::memcpy( &c->walkFrame, &f, sizeof( f ) );
+        c->walkState = vrc_ctx::WALK_COUNTING;
+    }
+    if( walkRecord )
+    {
+        VRC_HIP_CHECK( vrc_launch_walk_record( a, nullptr, c->stream ) );
+        c->walkState = vrc_ctx::WALK_VALID;
+        /* this frame still walks: the march below reads none of the planes */
+        f.walkCache = nullptr;
+        f.walkPlane = f.walkK = 0u;
     }
     if( c->optCount )
         VRC_HIP_CHECK( hipMemsetAsync( c->dCounter, 0, sizeof( unsigned long long ), c->stream ) );
@@ -2148,6 +2322,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                                                                         : vrc_launch_raycast_mip( a, c->stream ) )
                    : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
                    : c->rayLod ? vrc_launch_raycast_raylod( a, c->stream )
+                   : c->walkCacheUsed == 4 ? vrc_launch_raycast_replay( a, c->stream )
                                : vrc_launch_raycast( a, c->stream ) );
     if( c->rayCacheUsed == VRC_RAY_STORE )
         c->rayCacheValid = true;

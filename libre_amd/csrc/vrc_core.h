@@ -241,6 +241,19 @@ struct vrc_frame
     float isoStored;
     float isoClassify;
     float isoAmbient;
+    /* the walk cache (VRC_OPT_WALK_CACHE; at the end: no field above moves).  Which bricks a ray visits, and the interval
+     * of each, depend on the ray, the brick grid, the node table and the frame constants vrc_brick_interval and
+     * vrc_ray_grid_dda read -- not on the transfer function, the voxels or early termination -- so a view that stands
+     * still over a resident brick set need not walk the grid again.  walkCache: 1 + 4 * walkK planes of walkPlane words
+     * each, the context's, indexed tile * 64 + lane as rayCache is: plane 0 holds the ray's number of visits (0: the ray
+     * misses, meets no brick, or the lane lies outside the frame), planes 1 + 4 k ... 4 + 4 k the k-th visit in the order
+     * the walk makes them -- the index into the node table, the bits of vrc_segment_dist (all the uniform march reads
+     * of a segment), tNear and tFar of the interval (what every other march completes, vrc_segment_complete).  Written
+     * by the record form of the walk (VRC_MODE_WALK_RECORD, vrc_pixel_walk_record; walkK = 0: nothing is stored, the
+     * pass only counts) and read by vrc_pixel_walk_replay; no other kernel looks at these */
+    uint32_t* walkCache;
+    uint32_t walkPlane;
+    uint32_t walkK;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -3394,11 +3407,12 @@ VRC_HD vrc_f4 vrc_classify_mip( const vrc_f4* tfp, float d, const vrc_classifier
 #define VRC_MODE_PACKED 5      /* trilinear through the tap-packed atlas (vrc_march_segment_packed): ATLAS_T = uint32_t,
                                 * lut = the vrc_cls8_entry table */
 #define VRC_MODE_PACKED_GREY 6 /* the same for a grey transfer function: (grey, alpha) colours, paired table entries */
+#define VRC_MODE_WALK_RECORD 9 /* no march: the grid walk records its visits (vrc_frame::walkCache; 7 and 8 are the MIP modes) */
 
 /* BIG: the atlas holds more than 2^32 voxels.  Offsets inside a slot stay 32-bit; the slot's
  * 64-bit base moves into the lane's atlas pointer (one 64-bit add per gather instead of a 32-bit
  * one), so the default kernels keep their scalar base + 32-bit offset addressing. */
-/* SRC: vrc_segment_ready or vrc_segment_from_interval.  One body for both: the slot word, its ballot and every march are
+/* SRC: vrc_segment_ready, vrc_segment_from_interval or vrc_segment_from_walk.  One body for all: the slot word, its ballot and every march are
  * where they were; only the place the segment's arithmetic is done differs */
 template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, int GROUP, bool BIG, typename SRC >
 VRC_HD bool vrc_march_brick_from( const vrc_frame& f, const vrc_dev_node& n, const SRC& src,
@@ -3511,6 +3525,10 @@ VRC_HD bool vrc_march_brick( const vrc_frame& f, const vrc_dev_node& n, const vr
                              const ATLAS_T* __restrict__ atlas, const vrc_f4* lut,
                              const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples )
 {
+#if defined( VRC_WALK_VISIT_HOOK ) && !defined( __HIPCC__ )
+    /* host test builds only (tests/cpu_harness/walk_cache_harness.cpp): every visit the walk hands to a march */
+    VRC_WALK_VISIT_HOOK( n, r, iv );
+#endif
     const vrc_segment_from_interval src = { r, iv, f.stepSize };
     return vrc_march_brick_from< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG, vrc_segment_from_interval >(
         f, n, src, atlas, lut, cls, color, nSamples, 0.0f );
@@ -3730,8 +3748,9 @@ template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, int G
 VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_dev_node* __restrict__ nodes,
                               const int32_t* __restrict__ gridTable, const ATLAS_T* __restrict__ atlas,
                               const vrc_f4* lut, const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples,
-                              int part = -1, int parts = 2, int partDir = 2 )
+                              int part = -1, int parts = 2, int partDir = 2, uint32_t* walkOut = nullptr )
 {
+    /* (walkOut: VRC_MODE_WALK_RECORD only -- the ray's word of the walk cache's plane 0; nSamples then counts visits) */
     /* ray interval inside the brick grid */
     const vrc_f3 gmin = { f.gridMin[0], f.gridMin[1], f.gridMin[2] };
     const vrc_f3 gmax = { f.gridMin[0] + f.cellSize[0] * (float)f.gridDim[0],
@@ -3832,7 +3851,32 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                     if( sp != part )
                         return; /* another part's brick */
                 }
-                if constexpr( vrc_mode_is_mip( MODE ) )
+                if constexpr( MODE == VRC_MODE_WALK_RECORD )
+                {
+                    /* where every other mode marches: the visit is stored (the count pass, walkK = 0, stores none) and
+                     * counted; nothing ends the list but `stop` and the end of the walk */
+                    if( nSamples < f.walkK )
+                    {
+                        uint32_t* const w = walkOut + ( 1u + 4u * nSamples ) * f.walkPlane;
+                        w[0] = (uint32_t)node;
+                        w[f.walkPlane] = vrc_float_bits( vrc_segment_dist( r, iv ) );
+                        w[2u * f.walkPlane] = vrc_float_bits( iv.tNear );
+                        w[3u * f.walkPlane] = vrc_float_bits( iv.tFar );
+                    }
+                    else if( f.walkK == 0u )
+                    {
+                        /* the count pass also says how many of the visits meet a brick that vrc_march_brick_from would
+                         * gather (color.x, otherwise unused here, carries the number): the host keeps a view of mostly
+                         * such visits on the walk.  Nothing of the lists depends on it */
+                        uint32_t word = 0u;
+                        if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
+                            word = f.slotInfo[n.slotInfoIndex - 1u];
+                        if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN )
+                            color.x += 1.0f; /* (exact: a ray visits far fewer than 2^24 bricks) */
+                    }
+                    ++nSamples;
+                }
+                else if constexpr( vrc_mode_is_mip( MODE ) )
                 {
                     vrc_segment s;
                     vrc_segment_complete( r, iv, f.stepSize, &s );
@@ -3995,6 +4039,175 @@ VRC_HD void vrc_pixel_grid_dda( const vrc_frame& f, const vrc_dev_node* __restri
         return;
     vrc_ray_grid_dda< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, r, nodes, gridTable, atlas, lut, cls, color,
                                                                    nSamples );
+    pixelBuffer[pixelPos] = color;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * The walk cache (vrc_frame::walkCache): the grid walk recorded once, and the march replayed from the record.
+ * ---------------------------------------------------------------------------------------- */
+/* the ray of pixel rayIndex as the ray cache holds it (f.rayMode == VRC_RAY_LOAD): the bits vrc_setup_ray returned */
+VRC_HD vrc_ray vrc_ray_from_cache( const vrc_frame& f, uint32_t rayIndex )
+{
+    const float* const rc = f.rayCache + rayIndex;
+    const uint32_t P = f.rayCachePlane;
+    vrc_ray r;
+    r.origin.x = f.eye[0];
+    r.origin.y = f.eye[1];
+    r.origin.z = f.eye[2];
+    r.dir.x = rc[0];
+    r.dir.y = rc[P];
+    r.dir.z = rc[2u * P];
+    r.invDir.x = rc[3u * P];
+    r.invDir.y = rc[4u * P];
+    r.invDir.z = rc[5u * P];
+    r.tNearGlobal = rc[6u * P];
+    r.tFarGlobal = rc[7u * P];
+    r.tNearPlane = rc[8u * P];
+    r.hit = vrc_float_bits( rc[9u * P] ) != 0u;
+    return r;
+}
+
+/* Record form of vrc_pixel_grid_dda: the same walk of the same ray, whose visits are stored and counted instead of
+ * marched.  Returns the number of visits; the caller stores it in plane 0 (record pass) or folds it into the frame's
+ * maximum (count pass).  The pixel buffer is not read: a list is complete whatever the frame composites onto, and
+ * whatever the transfer function ends early.  gathers (count pass only): how many of the visits meet a brick that is not
+ * known to be uniform, by the slot words as they are now */
+VRC_HD uint32_t vrc_pixel_walk_record( const vrc_frame& f, const vrc_dev_node* __restrict__ nodes,
+                                       const int32_t* __restrict__ gridTable, uint32_t rayIndex,
+                                       uint32_t* gathers = nullptr )
+{
+    const vrc_ray r = vrc_ray_from_cache( f, rayIndex );
+    uint32_t count = 0u;
+    vrc_f4 none = { 0.f, 0.f, 0.f, 0.f };
+    if( r.hit )
+    {
+        const vrc_classifier cls = {};
+        vrc_ray_grid_dda< false, false, true, VRC_MODE_WALK_RECORD, uint8_t, VRC_GROUP, false >(
+            f, r, nodes, gridTable, nullptr, nullptr, cls, none, count, -1, 2, 2, f.walkCache + rayIndex );
+    }
+    if( gathers )
+        *gathers = (uint32_t)none.x;
+    return count;
+}
+
+/* The third segment source (beside vrc_segment_ready and vrc_segment_from_interval): visit `at` of a recorded list.
+ * distOnly(): the stored dist -- the uniform march needs no ray; full(): the stored interval completed from the ray of
+ * the ray cache, exactly as vrc_march_brick completes an interval of the walk (vrc_segment_complete reads the ray's
+ * origin and direction).  A wave whose bricks are all uniform never reads ray or interval.  `early`: the caller issued
+ * the five loads already, at the top of the visit and in front of the node and slot-word fetches that decide whether
+ * they are needed (vrc_pixel_walk_replay: it does so when the wave's visit before took the gather march); else they
+ * are made here, where the wave first needs them.  `gathered`: set when a march asked for the whole segment -- what
+ * the caller's next visit goes by; the uniform march never touches it */
+struct vrc_walk_early
+{
+    bool have;
+    float tNear, tFar;
+    vrc_f3 dir;
+};
+VRC_HD vrc_walk_early vrc_walk_load_early( const vrc_frame& f, uint32_t rayIndex, const uint32_t* at )
+{
+    const float* const rc = f.rayCache + rayIndex;
+    vrc_walk_early e;
+    e.have = true;
+    e.tNear = vrc_bits_float( at[2u * f.walkPlane] );
+    e.tFar = vrc_bits_float( at[3u * f.walkPlane] );
+    e.dir.x = rc[0];
+    e.dir.y = rc[f.rayCachePlane];
+    e.dir.z = rc[2u * f.rayCachePlane];
+    return e;
+}
+struct vrc_segment_from_walk
+{
+    const vrc_frame& f;
+    uint32_t rayIndex;
+    const uint32_t* at; /* the visit's word of its first plane (node) */
+    float dist;
+    const vrc_walk_early& early;
+    bool* gathered;
+    VRC_HD vrc_segment full() const
+    {
+        *gathered = true;
+        const vrc_walk_early e = early.have ? early : vrc_walk_load_early( f, rayIndex, at );
+        vrc_ray r;
+        r.origin.x = f.eye[0];
+        r.origin.y = f.eye[1];
+        r.origin.z = f.eye[2];
+        r.dir = e.dir;
+        r.invDir = e.dir; /* (not read by the completion) */
+        r.tNearGlobal = r.tFarGlobal = r.tNearPlane = 0.0f;
+        r.hit = true;
+        const vrc_interval iv = { e.tNear, e.tFar };
+        vrc_segment s;
+        vrc_segment_complete( r, iv, f.stepSize, &s );
+        return s;
+    }
+    VRC_HD vrc_segment distOnly() const
+    {
+        const vrc_f3 zero = { 0.0f, 0.0f, 0.0f };
+        vrc_segment s = { zero, zero, dist, 0.0f };
+        return s;
+    }
+};
+
+/* Replay form of vrc_pixel_grid_dda for the instances of the uniform-brick march (8-bit atlas, fixed-point stepping, no
+ * clamp, 32-bit slot bases): the pixel's clear, early exit and store are the walk's, and every recorded visit goes to
+ * the one visit body vrc_march_brick_from -- the slot word, its ballot, both uniform marches, the gather march and the
+ * early exit are that code.  A ray without visits leaves the pixel as the walk does: cleared where the frame clears,
+ * untouched where it does not (a hit ray that met no brick stored the colour it had loaded).  The count is clamped by
+ * walkK and the node index by the table, so no list content can run the loop away or reach past the node table.  The
+ * node and dist loads of visit k + 1 are issued before the march of visit k.  What only the gather march needs -- the
+ * interval and the ray's direction -- is loaded at the top of a visit when the wave's visit before took the gather march
+ * (bricks of a kind come in runs), so that those loads overlap the node and slot-word fetches; the prediction decides
+ * nothing but when five loads are issued, and costs a wave of uniform bricks nothing */
+template < bool COUNT, int MODE, int GROUP >
+VRC_HD void vrc_pixel_walk_replay( const vrc_frame& f, const vrc_dev_node* __restrict__ nodes,
+                                   const uint8_t* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
+                                   vrc_f4* __restrict__ pixelBuffer, uint32_t px, uint32_t py, uint32_t& nSamples,
+                                   uint32_t rayIndex )
+{
+    const uint32_t pixelPos = py * f.width + px;
+    const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
+    const uint32_t P = f.walkPlane;
+    const uint32_t* const wc = f.walkCache + rayIndex;
+    uint32_t count = wc[0];
+    count = count < f.walkK ? count : f.walkK;
+    if( count == 0u )
+    {
+        if( f.clearFirst )
+            pixelBuffer[pixelPos] = zero;
+        return;
+    }
+    vrc_f4 color = f.clearFirst ? zero : pixelBuffer[pixelPos];
+    if( color.w > VRC_EARLY_EXIT )
+        return;
+    const uint32_t lastNode = f.nodeCount - 1u;
+    const uint32_t* at = wc + P;
+    uint32_t node = at[0];
+    float dist = vrc_bits_float( at[P] );
+    bool gathered = false; /* did the visit before take the gather march?  (the whole wave takes it or none of it) */
+    for( uint32_t k = 0u; k < count; ++k )
+    {
+        const uint32_t* const next = at + 4u * P;
+        uint32_t nodeNext = 0u;
+        float distNext = 0.0f;
+        if( k + 1u < count )
+        {
+            nodeNext = next[0];
+            distNext = vrc_bits_float( next[P] );
+        }
+        vrc_walk_early early = { false, 0.0f, 0.0f, { 0.0f, 0.0f, 0.0f } };
+        if( gathered )
+            early = vrc_walk_load_early( f, rayIndex, at );
+        gathered = false;
+        const vrc_dev_node n = nodes[node < lastNode ? node : lastNode];
+        const vrc_segment_from_walk src = { f, rayIndex, at, dist, early, &gathered };
+        if( vrc_march_brick_from< false, COUNT, true, MODE, uint8_t, GROUP, false, vrc_segment_from_walk >(
+                f, n, src, atlas, lut, cls, color, nSamples, 0.0f ) )
+            break;
+        at = next;
+        node = nodeNext;
+        dist = distNext;
+    }
     pixelBuffer[pixelPos] = color;
 }
 

@@ -182,6 +182,50 @@ hipError_t vrc_launch_tile_order( const vrc_frame& f, uint32_t* order, uint32_t*
 
 hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream );
 
+/* The walk cache (vrc_kernels_walk.hip; VRC_OPT_WALK_CACHE).  The replay march exists for the frames vrc_launch_raycast
+ * hands to the tile-scheduled grid walk of the table-driven point-sampling march of 8-bit voxels with fixed-point
+ * stepping -- vrc_k_raycast<true,false,COUNT,true,VRC_MODE_TABLE or VRC_MODE_GREY,unsigned char,GROUP,false>, the
+ * instances the uniform-brick march exists for -- and takes the group size that launcher would (the sizes are defined
+ * here, once, for vrc_kernels.hip and vrc_kernels_walk.hip) */
+#ifndef VRC_GREY_GROUP
+/* samples a lane of the grey form keeps in flight: its two-float colours and table entries leave registers for 14 at
+ * five waves per SIMD (93 VGPRs with the sample counter, 82 without); measured on C2 against 8: 0.509 -> 0.481 ms
+ * (mem://), 0.512 -> 0.482 ms (noise); 12: 0.491 / 0.484; 16 (96 VGPRs): 0.487 */
+#define VRC_GREY_GROUP 14
+#endif
+#ifndef VRC_SMALL_GROUP
+#define VRC_SMALL_GROUP 24 /* samples in flight per lane in launches too small to fill the GPU (latency-bound: 16 -> 24: -5 % on a rank's share of an 8-rank frame, -4 % of a 4-rank frame; 32: -7 % / -3 %) */
+#endif
+/* launches of at most ~1.5 waves per SIMD slot (256 CUs x 4 SIMDs x 4 waves) are latency-bound:
+ * measured 0.153 -> 0.130 ms for an eighth of the C2 frame, 0.538 -> 0.562 ms for the whole */
+#ifndef VRC_SMALL_LAUNCH_TILES
+#define VRC_SMALL_LAUNCH_TILES 6144u /* (8192 = half a 1024^2 frame: one frame alone 0.303 -> 0.287 ms, three in flight 4428 -> 4365 frames/s: not taken) */
+#endif
+static inline bool vrc_walk_replay_eligible( const vrc_raycast_args& a )
+{
+    return a.gridDda && a.gridTable && !a.packed && !a.linear && a.elemBytes == 1 && !a.bigAtlas && !a.clamp &&
+           a.fixedStepping && a.ertParts <= 1 && !a.depthSplit && VRC_TILE_W == 8u;
+}
+static inline int vrc_walk_replay_group( const vrc_raycast_args& a )
+{
+    const uint32_t tiles = ( ( a.frame.width + VRC_TILE_W - 1 ) / VRC_TILE_W ) * ( ( a.frame.height + VRC_TILE_H - 1 ) / VRC_TILE_H );
+    return tiles <= VRC_SMALL_LAUNCH_TILES ? VRC_SMALL_GROUP : ( a.greyTable ? VRC_GREY_GROUP : VRC_GROUP );
+}
+/* what the count pass finds: the longest list of the frame, the visits of all its rays, and those of them whose brick
+ * is not known to be uniform (a.frame.slotInfo as it is on `stream`): visits that would take the gather march */
+struct vrc_walk_count
+{
+    uint32_t longest, pad;
+    unsigned long long visits, gathers;
+};
+/* the record form of the grid walk: a.frame.rayMode = VRC_RAY_LOAD; a.frame.walkK = 0: the count pass folds the frame
+ * into *result (device memory the caller zeroed on `stream`), nothing else is written; walkK > 0: the record pass fills
+ * a.frame.walkCache and result is not used.  Not a march: no kernel note, no stop event */
+hipError_t vrc_launch_walk_record( const vrc_raycast_args& a, vrc_walk_count* result, hipStream_t stream );
+/* the march of a frame whose lists are valid (a.frame.walkCache, walkPlane, walkK; rayMode = VRC_RAY_LOAD); a.gridTable
+ * is not read.  hipErrorInvalidValue for a frame outside the instance set */
+hipError_t vrc_launch_raycast_replay( const vrc_raycast_args& a, hipStream_t stream );
+
 /* maximum-intensity projection (vrc_kernels_mip.hip): point or trilinear (a.linear) samples by gathers, reference-order
  * loop or grid walk (a.gridDda); lut = the padded transfer function; frame.mipMax set */
 hipError_t vrc_launch_raycast_mip( const vrc_raycast_args& a, hipStream_t stream );

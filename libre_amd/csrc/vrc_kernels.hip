@@ -799,12 +799,7 @@ hipError_t vrc_launch_tile_order( const vrc_frame& f, uint32_t* order, uint32_t*
 /* ------------------------------------------------------------------------------------------
  * the raycast kernel
  * ---------------------------------------------------------------------------------------- */
-#ifndef VRC_GREY_GROUP
-/* samples a lane of the grey form keeps in flight: its two-float colours and table entries leave registers for 14 at
- * five waves per SIMD (93 VGPRs with the sample counter, 82 without); measured on C2 against 8: 0.509 -> 0.481 ms
- * (mem://), 0.512 -> 0.482 ms (noise); 12: 0.491 / 0.484; 16 (96 VGPRs): 0.487 */
-#define VRC_GREY_GROUP 14
-#endif
+/* (VRC_GREY_GROUP, VRC_SMALL_GROUP and VRC_SMALL_LAUNCH_TILES: vrc_internal.h, with their measurements) */
 #ifndef VRC_PACKED_WAVES
 #define VRC_PACKED_WAVES 3 /* (developer switch; 2 ... 6 measured on C2 with groups of 4 ... 24: the group decides, not the waves) */
 #endif
@@ -1440,16 +1435,9 @@ hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream )
     /* the clamped sampler (overlap 0) always uses the float position chain */
     const bool fixed = a.fixedStepping && !a.clamp;
     const int key = ( fixed ? 8 : 0 ) | ( a.gridDda ? 4 : 0 ) | ( a.clamp ? 2 : 0 ) | ( count ? 1 : 0 );
-    /* launches of at most ~1.5 waves per SIMD slot (256 CUs x 4 SIMDs x 4 waves) are latency-bound:
-     * measured 0.153 -> 0.130 ms for an eighth of the C2 frame, 0.538 -> 0.562 ms for the whole */
+    /* small launches are latency-bound and take larger groups (VRC_SMALL_GROUP, VRC_SMALL_LAUNCH_TILES: vrc_internal.h) */
     const uint32_t nTilesLaunch = ( ( a.frame.width + VRC_TILE_W - 1 ) / VRC_TILE_W ) *
                                   ( ( a.frame.height + VRC_TILE_H - 1 ) / VRC_TILE_H );
-#ifndef VRC_SMALL_GROUP
-#define VRC_SMALL_GROUP 24 /* samples in flight per lane in launches too small to fill the GPU (latency-bound: 16 -> 24: -5 % on a rank's share of an 8-rank frame, -4 % of a 4-rank frame; 32: -7 % / -3 %) */
-#endif
-#ifndef VRC_SMALL_LAUNCH_TILES
-#define VRC_SMALL_LAUNCH_TILES 6144u /* (8192 = half a 1024^2 frame: one frame alone 0.303 -> 0.287 ms, three in flight 4428 -> 4365 frames/s: not taken) */
-#endif
     const bool smallLaunch = nTilesLaunch <= VRC_SMALL_LAUNCH_TILES;
     if( a.ertParts > 1 && ( key == 12 || key == 13 ) && VRC_TILE_W == 8u )
         return count ? launch_parts< true >( a, stream ) : launch_parts< false >( a, stream );

@@ -1,0 +1,197 @@
+/*
+ * vrc_kernels_walk.hip -- the walk cache (VRC_OPT_WALK_CACHE; vrc_core.h: vrc_frame::walkCache).
+ *
+ * Which bricks a ray visits, and the interval of each, depend on the ray, the brick grid, the node table and the frame
+ * constants the slab test reads -- not on the transfer function, the voxels or early termination.  A view that stands
+ * still over a resident brick set therefore walks the grid once:
+ *   vrc_k_walk_record   the tile-scheduled grid walk (vrc_ray_grid_dda, the same tie cells, `pending`, `recent` and
+ *                       `stop`) whose visit stores (node, dist, tNear, tFar) instead of marching.  Run twice: with
+ *                       frame.walkK = 0 it only counts (vrc_walk_count, three atomics per wave), then the host sizes
+ *                       the planes and the second run fills them.  Never a march: not timed, not counted as a launch.
+ *   vrc_k_raycast_replay the march of a frame whose lists are valid: the tile schedule, lane order, pixel clear and
+ *                       store, and sample counter of vrc_k_raycast around vrc_pixel_walk_replay, which hands every
+ *                       recorded visit to the one visit body vrc_march_brick_from.  None of the walk's state (cell, tMax,
+ *                       tDelta, recent, pending) exists in it.
+ * Instances: the ones the uniform-brick march exists for -- the table-driven point-sampling march of 8-bit voxels with
+ * fixed-point stepping (VRC_MODE_TABLE, VRC_MODE_GREY), counted and uncounted, in the group sizes vrc_launch_raycast
+ * picks for them.  Every other frame keeps the walk.
+ */
+#include "vrc_internal.h"
+
+#define VRC_WALK_WAVES VRC_WAVES_PER_GROUP /* the four tiles of a schedule unit (vrc_internal.h) */
+#define VRC_WALK_THREADS ( 64u * VRC_WALK_WAVES )
+
+/* Morton lane order of vrc_k_raycast: the ray cache and the walk cache are indexed tile * 64 + lane in it */
+__device__ inline void vrc_walk_lane_pixel( uint32_t tile, uint32_t tilesX, uint32_t lane, uint32_t& px, uint32_t& py )
+{
+    const uint32_t tx = tile % tilesX, ty = tile / tilesX;
+    const uint32_t lx = ( lane & 1u ) | ( ( lane >> 1 ) & 2u ) | ( ( lane >> 2 ) & 4u );
+    const uint32_t ly = ( ( lane >> 1 ) & 1u ) | ( ( lane >> 2 ) & 2u ) | ( ( lane >> 3 ) & 4u );
+    px = tx * 8u + lx;
+    py = ty * 8u + ly;
+}
+
+/* one wave per tile, tiles in row-major order (the pass runs once per view: no schedule) */
+__global__ __launch_bounds__( VRC_WALK_THREADS ) void vrc_k_walk_record(
+    const vrc_frame f, const vrc_dev_node* __restrict__ nodes, const int32_t* __restrict__ gridTable,
+    vrc_walk_count* __restrict__ result, const uint32_t tilesX, const uint32_t nTiles )
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t tile = blockIdx.x * VRC_WALK_WAVES + ( threadIdx.x >> 6 );
+    if( tile >= nTiles )
+        return;
+    uint32_t px, py;
+    vrc_walk_lane_pixel( tile, tilesX, lane, px, py );
+    const uint32_t rayIndex = tile * 64u + lane;
+    uint32_t count = 0u, gathers = 0u;
+    if( px < f.width && py < f.height )
+        count = vrc_pixel_walk_record( f, nodes, gridTable, rayIndex, &gathers );
+    if( f.walkK != 0u )
+        f.walkCache[rayIndex] = count; /* (0 for a lane outside the frame: whole tiles) */
+    else
+    {
+        /* the count pass's result (vrc_walk_count): the longest list, and over the whole frame the visits and those of
+         * them that would gather; one atomic each per wave */
+        uint32_t m = count, sum = count, g = gathers; /* (64 lanes: the wave's sums fit 32 bits) */
+#pragma unroll
+        for( int off = 32; off > 0; off >>= 1 )
+        {
+            const uint32_t o = __shfl_down( m, off, 64 );
+            m = o > m ? o : m;
+            sum += __shfl_down( sum, off, 64 );
+            g += __shfl_down( g, off, 64 );
+        }
+        if( lane == 0u && m != 0u )
+        {
+            atomicMax( &result->longest, m );
+            atomicAdd( &result->visits, (unsigned long long)sum );
+            if( g != 0u )
+                atomicAdd( &result->gathers, (unsigned long long)g );
+        }
+    }
+}
+
+hipError_t vrc_launch_walk_record( const vrc_raycast_args& a, vrc_walk_count* result, hipStream_t stream )
+{
+    const uint32_t tilesX = ( a.frame.width + 7u ) / 8u, tilesY = ( a.frame.height + 7u ) / 8u;
+    const uint32_t nTiles = tilesX * tilesY;
+    if( nTiles == 0 )
+        return hipSuccess;
+    if( !a.gridTable || a.frame.rayMode != VRC_RAY_LOAD || ( a.frame.walkK != 0u ? !a.frame.walkCache : !result ) )
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL( vrc_k_walk_record, dim3( ( nTiles + VRC_WALK_WAVES - 1u ) / VRC_WALK_WAVES ), dim3( VRC_WALK_THREADS ),
+                        0, stream, a.frame, a.nodes, a.gridTable, result, tilesX, nTiles );
+    return hipGetLastError();
+}
+
+/* waves per SIMD, as vrc_k_raycast says them for the walking instances of the same march (vrc_kernels.hip) -- except that
+ * the grey form in groups of 14, the judged instance, is allowed a sixth wave.  The walking instance is held at five
+ * because six thrash the L1 under its gathers; the replay needs 76 registers (79 with the sample counter), and
+ * measured at five against six waves (profiles/r10_walk_cache.txt) the uniform-brick frame runs 8 % faster at six and
+ * the gather path no slower */
+#ifndef VRC_REPLAY_GREY_MAX_WAVES
+#define VRC_REPLAY_GREY_MAX_WAVES 6
+#endif
+/* GROUP: samples a lane of the gather march keeps in flight -- what vrc_launch_raycast picks for the walking instance */
+#define VRC_REPLAY_K_MIN_WAVES ( GROUP > VRC_GREY_GROUP ? 2 : 5 )
+#define VRC_REPLAY_K_MAX_WAVES ( GROUP > VRC_GREY_GROUP ? 8 : ( MODE == VRC_MODE_GREY ? VRC_REPLAY_GREY_MAX_WAVES : 5 ) )
+template < bool COUNT, int MODE, int GROUP >
+__global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_per_eu( VRC_REPLAY_K_MIN_WAVES, VRC_REPLAY_K_MAX_WAVES ) ) ) void vrc_k_raycast_replay(
+    const vrc_frame f, const vrc_dev_node* __restrict__ nodes, const uint8_t* __restrict__ atlas,
+    const vrc_f4* __restrict__ lutGlobal, const vrc_classifier cls, vrc_f4* __restrict__ pixelBuffer,
+    unsigned long long* __restrict__ sampleCounter, const uint32_t* __restrict__ tileOrder, const uint32_t tilesX,
+    const uint32_t nTiles )
+{
+    static_assert( MODE == VRC_MODE_TABLE || MODE == VRC_MODE_GREY, "the instances of the uniform-brick march" );
+    /* the classified table (257 entries), as vrc_k_raycast stages it */
+    __shared__ vrc_f4 lut[VRC_CLS8_ENTRIES];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    if( MODE == VRC_MODE_GREY )
+    {
+        vrc_f2* const lut2 = reinterpret_cast< vrc_f2* >( lut );
+        for( uint32_t i = tid; i < VRC_LUT_ENTRIES; i += VRC_WALK_THREADS )
+        {
+            const vrc_f4 e = lutGlobal[i];
+            lut2[i] = vrc_f2{ e.x, e.w };
+        }
+    }
+    else
+    {
+        for( uint32_t i = tid; i < VRC_TFP_ENTRIES; i += VRC_WALK_THREADS )
+            lut[i] = lutGlobal[i];
+    }
+#if defined( VRC_ADDR_TABLES )
+    {
+        const vrc_lay lay = vrc_make_lay( f.sbx, f.sby );
+        for( uint32_t u = tid; u < 256u; u += VRC_WALK_THREADS )
+        {
+            vrc_addr_tab[u] = vrc_lay_x( lay, u );
+            vrc_addr_tab[256u + u] = vrc_lay_y( lay, u );
+            vrc_addr_tab[512u + u] = vrc_lay_z( lay, u );
+        }
+    }
+#endif
+    __syncthreads();
+    /* from here on the waves of the workgroup are independent */
+    const uint32_t slotIndex = blockIdx.x * VRC_WALK_WAVES + ( tid >> 6 );
+    const uint32_t tilesY = nTiles / tilesX;
+    if( slotIndex >= vrc_schedule_slots( tilesX, tilesY ) )
+        return;
+    const uint32_t tile = vrc_slot_tile( tileOrder, slotIndex, tilesX, tilesY );
+    if( tile == VRC_NO_TILE )
+        return;
+    uint32_t px, py;
+    vrc_walk_lane_pixel( tile, tilesX, lane, px, py );
+
+    uint32_t nSamples = 0;
+    if( px < f.width && py < f.height )
+        vrc_pixel_walk_replay< COUNT, MODE, GROUP >( f, nodes, atlas, lut, cls, pixelBuffer, px, py, nSamples,
+                                                     tile * 64u + lane );
+    if( COUNT )
+    {
+        /* wave64 reduction, one atomic per wave */
+        unsigned long long s = nSamples;
+#pragma unroll
+        for( int off = 32; off > 0; off >>= 1 )
+            s += __shfl_down( s, off, 64 );
+        if( lane == 0 && s != 0 )
+            atomicAdd( sampleCounter, s );
+    }
+}
+
+template < bool COUNT, int MODE, int GROUP >
+static hipError_t launch_replay( const vrc_raycast_args& a, hipStream_t stream )
+{
+    const uint32_t tilesX = ( a.frame.width + 7u ) / 8u, tilesY = ( a.frame.height + 7u ) / 8u;
+    const uint32_t nTiles = tilesX * tilesY;
+    if( nTiles == 0 )
+        return hipSuccess;
+    vrc_internal_note_kernel( "vrc_k_raycast_replay<%s,%d,unsigned char,%d>", COUNT ? "true" : "false", (int)MODE, (int)GROUP );
+    vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_replay< COUNT, MODE, GROUP >, (int)VRC_WALK_THREADS, 0 );
+    vrc_launch_march( a, &vrc_k_raycast_replay< COUNT, MODE, GROUP >,
+                      dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WALK_WAVES - 1u ) / VRC_WALK_WAVES ),
+                      dim3( VRC_WALK_THREADS ), 0, stream, a.frame, a.nodes, (const uint8_t*)a.atlas, a.lut, a.classifier,
+                      a.pixelBuffer, a.sampleCounter, a.tileOrder, tilesX, nTiles );
+    return hipGetLastError();
+}
+
+template < int MODE, int GROUP >
+static hipError_t launch_replay( const vrc_raycast_args& a, hipStream_t stream )
+{
+    return a.sampleCounter ? launch_replay< true, MODE, GROUP >( a, stream ) : launch_replay< false, MODE, GROUP >( a, stream );
+}
+
+/* the frames vrc_launch_raycast would march with <true,false,COUNT,true,TABLE or GREY,unsigned char,GROUP,false>, in the
+ * group size it would take (vrc_walk_replay_group): anything else is the caller's mistake, not a frame to walk quietly */
+hipError_t vrc_launch_raycast_replay( const vrc_raycast_args& a, hipStream_t stream )
+{
+    if( !vrc_walk_replay_eligible( a ) || !a.frame.walkCache || a.frame.walkK == 0u || a.frame.rayMode != VRC_RAY_LOAD )
+        return hipErrorInvalidValue;
+    const int group = vrc_walk_replay_group( a );
+    if( a.greyTable )
+        return group == VRC_SMALL_GROUP ? launch_replay< VRC_MODE_GREY, VRC_SMALL_GROUP >( a, stream )
+                                             : launch_replay< VRC_MODE_GREY, VRC_GREY_GROUP >( a, stream );
+    return group == VRC_SMALL_GROUP ? launch_replay< VRC_MODE_TABLE, VRC_SMALL_GROUP >( a, stream )
+                                         : launch_replay< VRC_MODE_TABLE, VRC_GROUP >( a, stream );
+}

@@ -14,6 +14,10 @@ back to back and reports the wall time per frame of the synchronised loop beside
 wall time is the figure to compare: the kernel time ends with a marker behind the march at 1 and with the dispatch itself at 0.
 VRC_OPT_RAY_CACHE (rays computed every frame against rays loaded from the context's cache) the same way:
        python tools/uniform_ab.py --ray-cache [--steps 2000] [--rounds 3]
+VRC_OPT_WALK_CACHE (the brick grid walked every frame against the march replayed from the context's recorded lists):
+       python tools/uniform_ab.py --walk-cache [--steps 2000] [--rounds 3]
+Frames and sample counts at 0 and 1 are compared bit for bit, and the option at 1 must have reached the replay
+(VRC_OPT_WALK_CACHE_USED = 4), before anything is timed; the kernel instance of either side is reported.
 With --steps of 200 or more, --libs reports the wall time per frame and the mean kernel time of such a loop as well."""
 import argparse
 import ctypes as C
@@ -82,7 +86,8 @@ def several(a):
         for name in names:
             g = scenes[name]
             if a.steps >= 200:  # a loop long enough for a wall time
-                g.render(count=False)
+                for _ in range(6):  # synchronised frames: the tile schedule, the ray cache and the walk cache settle
+                    g.render(count=False)
                 w, k = timed_loop(g, frame_loop(g, s), a.steps)
                 wall[name].append(w)
                 mean[name].append(k)
@@ -110,11 +115,22 @@ def markers(a, option=None, names=("lean", "markers")):
     L = vrc.load_library(a.lib) if a.lib else vrc.load_library()
     g = GpuScene(s, lib=L)
     frames = {}
+    walk = option == vrc.OPT_WALK_CACHE
+    on = vrc.WALK_CACHE_ALWAYS if walk else 1  # (the replay on any volume: at 1 a view that gathers keeps the walk)
+    settle = 6 if walk else 3  # synchronised frames until the steady state (the ray cache: computed, stored, loaded;
+    #                            the walk cache: counted, recorded and replayed behind that)
+
+    def walk_mode():
+        used = C.c_int64(-1)
+        vrc.check(L, L.vrc_get_option(g.ctx, vrc.OPT_WALK_CACHE_USED, C.byref(used)))
+        return used.value
     for v in (1, 0):
-        vrc.check(L, L.vrc_set_option(g.ctx, option, v))
-        for _ in range(3):  # (the ray cache: computed, stored, loaded)
+        vrc.check(L, L.vrc_set_option(g.ctx, option, on if v else 0))
+        for _ in range(settle):
             frames[v] = g.render(count=True)[:2]
         used = C.c_int64(0)
+        if walk:
+            assert walk_mode() == (4 if v else 0), "the frame compared was not replayed"
         if option == vrc.OPT_RAY_CACHE:
             vrc.check(L, L.vrc_get_option(g.ctx, vrc.OPT_RAY_CACHE_USED, C.byref(used)))
             assert used.value == (2 if v else 0), "the third frame did not load its rays"
@@ -123,14 +139,22 @@ def markers(a, option=None, names=("lean", "markers")):
     run = frame_loop(g, s)
     wall = {1: [], 0: []}
     kernel = {1: [], 0: []}
+    ran = {}
     for _ in range(a.rounds):
         for v in (1, 0):
-            vrc.check(L, L.vrc_set_option(g.ctx, option, v))
+            vrc.check(L, L.vrc_set_option(g.ctx, option, on if v else 0))
+            if walk:  # the option starts the lists over: back to the replay before the clock runs
+                for _ in range(settle):
+                    g.render(count=False)
+                assert walk_mode() == (4 if v else 0)
             w, k = timed_loop(g, run, a.steps)
+            if walk:
+                assert walk_mode() == (4 if v else 0)
             wall[v].append(w)
             kernel[v].append(k)
+            ran[names[v]] = L.vrc_last_kernel().decode()
     print(json.dumps({"volume": a.volume, "spin": list(a.spin), "samples": frames[0][1],
-                      "kernel": L.vrc_last_kernel().decode(), "steps": a.steps,
+                      "kernel": ran if walk else L.vrc_last_kernel().decode(), "steps": a.steps,
                       "wall_ms_per_frame": {names[1]: wall[1], names[0]: wall[0]},
                       "kernel_ms_mean": {names[1]: kernel[1], names[0]: kernel[0]}, "frames_bit_identical": True}))
     g.close()
@@ -150,11 +174,14 @@ def main():
     ap.add_argument("--libs", nargs="+", default=None, metavar="NAME=PATH")
     ap.add_argument("--markers", action="store_true", help="A/B of VRC_OPT_STREAM_MARKERS instead (see above)")
     ap.add_argument("--ray-cache", action="store_true", help="A/B of VRC_OPT_RAY_CACHE instead (see above)")
+    ap.add_argument("--walk-cache", action="store_true", help="A/B of VRC_OPT_WALK_CACHE instead (see above)")
     a = ap.parse_args()
     if a.markers:
         return markers(a)
     if a.ray_cache:
         return markers(a, vrc.OPT_RAY_CACHE, ("computed", "cached"))
+    if a.walk_cache:
+        return markers(a, vrc.OPT_WALK_CACHE, ("walked", "replayed"))
     if a.libs:
         return several(a)
     s = orc.build_scene(voxels=(a.voxels,) * 3, block=a.block, viewport=(a.viewport,) * 2, volume=a.volume,
