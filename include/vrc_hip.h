@@ -253,6 +253,14 @@ typedef struct
                                     * words) stays on the walk: VRC_OPT_WALK_CACHE_USED then reads 0 (1 and 2 while the
                                     * count is taken, unless not even one visit per ray fits).  Negative: VRC_EINVAL */
 #define VRC_OPT_WALK_CACHE_BYTES 27 /* read-only: bytes of device memory the context's lists hold now */
+#define VRC_OPT_WALK_LEAN_USED 28   /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render replayed
+                                    * lean lists (vrc_last_kernel: vrc_k_raycast_replay<...,lean>), 0 if it did anything
+                                    * else.  Where the step size is a power of two, the pool has fewer than 2^20 slots
+                                    * and no visit of the view takes 4096 samples or more, a visit's list entry holds
+                                    * its sample count and its brick's slot index instead of the segment's length, so
+                                    * the replay of a uniform brick neither fetches the node nor counts the steps again.
+                                    * Same layout, same bytes, same frame and sample count; every other view records
+                                    * and replays the lists as before */
 /* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
  * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
  * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots

@@ -240,6 +240,12 @@ struct vrc_ctx
     int64_t optWalkCache = 1;
     int64_t optWalkBudget = VRC_WALK_CACHE_DEFAULT_BUDGET;
     int64_t walkCacheUsed = 0;
+    /* the form of the lists (vrc_core.h: vrc_frame::walkLean).  walkLeanAsked: what the host saw when the count pass went
+     * out -- a step that vrc_exact_step_count counts, a pool whose slot indices fit the word -- and so what that pass was
+     * asked to check; part of what the lists are valid for.  walkLean: the form the record pass wrote.  walkLeanUsed:
+     * VRC_OPT_WALK_LEAN_USED */
+    bool walkLeanAsked = false, walkLean = false;
+    int64_t walkLeanUsed = 0;
     int64_t optStepping = 1;
     int64_t optVariant = VRC_VARIANT_CUDARAYCASTER;
     bool rayLod = false; /* vrc_set_ray_lod */
@@ -609,6 +615,7 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_WALK_CACHE_USED: *value = c->walkCacheUsed; return VRC_OK;
     case VRC_OPT_WALK_CACHE_BUDGET: *value = c->optWalkBudget; return VRC_OK;
     case VRC_OPT_WALK_CACHE_BYTES: *value = (int64_t)( c->dWalkWords * sizeof( uint32_t ) ); return VRC_OK;
+    case VRC_OPT_WALK_LEAN_USED: *value = c->walkLeanUsed; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->optProjection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->optMipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->optMipFold; return VRC_OK;
@@ -2165,10 +2172,20 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * the count pass and the uniformity words it read, is not recorded and stays on the walk until the pool's uploads or
      * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold */
     c->walkCacheUsed = 0;
+    c->walkLeanUsed = 0;
     f.walkCache = nullptr;
     f.walkPlane = f.walkK = 0u;
+    f.walkLean = f.walkSlots = 0u;
     bool walkCount = false, walkRecord = false;
     {
+        /* the form of the lists.  A lean list (vrc_core.h: vrc_frame::walkLean) holds every visit's step count and slot
+         * index in one word of 12 + 20 bits.  What the host can see of that: the step is one vrc_exact_step_count counts
+         * (its own test, asked here with a travel that passes it), and the pool's slot indices fit.  The rest -- no
+         * visit whose count is inexact or takes more than 12 bits -- the count pass reports with the count */
+        uint32_t one = 0u;
+        const size_t nSlots = pool->resident.size();
+        const bool leanAsked = vrc_exact_step_count( f.stepSize, f.stepSize, &one ) && nSlots >= 1u &&
+                               nSlots < ( (size_t)1u << VRC_WALK_LEAN_INDEX_BITS );
         const size_t tiles = (size_t)( ( c->fbW + VRC_TILE_W - 1 ) / VRC_TILE_W ) * ( ( c->fbH + VRC_TILE_H - 1 ) / VRC_TILE_H );
         const size_t plane = tiles * 64u;
         const auto fits = [&]( uint32_t k ) { /* the planes of k visits: 32-bit word offsets in the kernels, and the budget */
@@ -2181,6 +2198,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         const uint64_t gen = pool->uploadGen; /* (compared only where the choice goes by the bricks' content) */
         if( !eligible || ( c->walkState != vrc_ctx::WALK_IDLE &&
                            ( !walk_constants_equal( c->walkFrame, f ) ||
+                             leanAsked != c->walkLeanAsked ||
                              ( byContent && ( c->walkGen != gen || c->walkSlotInfo != f.slotInfo ) ) ) ) )
             c->walkState = vrc_ctx::WALK_IDLE;
         const bool repeats = sameNodes && c->walkPrevSet && ( !byContent || c->walkPrevGen == gen ) &&
@@ -2201,6 +2219,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                     VRC_HIP_CHECK( hipEventCreateWithFlags( &c->evWalk, hipEventDisableTiming ) );
                 }
                 walkCount = true;
+                c->walkLeanAsked = leanAsked;
                 c->walkGen = gen;
                 c->walkSlotInfo = f.slotInfo;
                 c->walkCacheUsed = 1;
@@ -2233,6 +2252,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                             c->dWalkWords = words;
                         }
                         c->walkK = k;
+                        c->walkLean = c->walkLeanAsked && c->hWalkMax->notLean == 0u;
                         walkRecord = true;
                         c->walkCacheUsed = 3;
                     }
@@ -2246,7 +2266,12 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             f.walkCache = c->dWalk;
             f.walkPlane = (uint32_t)plane;
             f.walkK = c->walkK;
+            f.walkLean = c->walkLean ? 1u : 0u;
+            f.walkSlots = (uint32_t)nSlots;
+            c->walkLeanUsed = ( c->walkLean && c->walkCacheUsed == 4 ) ? 1 : 0;
         }
+        else if( walkCount )
+            f.walkLean = leanAsked ? 1u : 0u; /* (the count pass: check every visit) */
     }
     a.classifier = vrc_make_classifier( lp );
 
@@ -2264,6 +2289,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         VRC_HIP_CHECK( hipEventRecord( c->evWalk, c->stream ) );
         std::memcpy( &c->walkFrame, &f, sizeof( f ) );
         c->walkState = vrc_ctx::WALK_COUNTING;
+        f.walkLean = 0u; /* (asked of the count pass alone) */
     }
     if( walkRecord )
     {
@@ -2272,6 +2298,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         /* this frame still walks: the march below reads none of the planes */
         f.walkCache = nullptr;
         f.walkPlane = f.walkK = 0u;
+        f.walkLean = f.walkSlots = 0u;
     }
     if( c->optCount )
         VRC_HIP_CHECK( hipMemsetAsync( c->dCounter, 0, sizeof( unsigned long long ), c->stream ) );

@@ -27,6 +27,7 @@
     defined( VRC_SETPRIO ) || \
     defined( VRC_INT_STEPS ) || defined( VRC_WG_TIMELINE ) || \
     defined( VRC_NO_UNIFORM_INT_STEPS ) || defined( VRC_UNIFORM_GROUP ) || defined( VRC_UNIFORM_SMALL_GROUP ) || \
+    defined( VRC_LEAN_REMAINDER ) || defined( VRC_LEAN_GROUP ) || \
     defined( VRC_PIPELINE ) || \
     defined( VRC_LAYOUT ) || \
     defined( VRC_LAYOUT_PADX ) || \
@@ -254,6 +255,14 @@ struct vrc_frame
     uint32_t* walkCache;
     uint32_t walkPlane;
     uint32_t walkK;
+    /* the lean form of the lists (at the end: no field above moves).  walkLean != 0: a visit's second plane holds, where
+     * the other form holds the bits of dist, the word vrc_walk_lean_word packs -- the visit's exact step count and its
+     * node's slotInfoIndex, what the uniform march would otherwise fetch and compute again in every frame -- and the
+     * replay is vrc_pixel_walk_replay_lean.  In the count pass (walkK = 0) it asks whether every visit can be packed.
+     * walkSlots: the words of slotInfo, what an index read from a list is clamped by.  The host sets both
+     * (vrc_render); a frame that leaves them 0 records and replays the other form */
+    uint32_t walkLean;
+    uint32_t walkSlots;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -1169,6 +1178,85 @@ VRC_HD bool vrc_march_uniform_counted( E& color, const E ue, uint32_t nLeft, uin
             return true;
     }
     return false;
+}
+
+/* The uniform march of the lean replay (vrc_pixel_walk_replay_lean): n samples of one entry, n < 4096 known from the
+ * list.  Whole groups as above, of VRC_LEAN_GROUP samples: with the remainder in bodies a larger group no longer pays
+ * in single samples, and on C2 groups of 32 beat 16 by 4 % and 64 by 3 % of the kernel, an opaque table and a rotated
+ * view included.  What is left below a group is, by VRC_LEAN_REMAINDER,
+ *   0  the single-sample loop of vrc_march_uniform_counted, a test after every sample;
+ *   1  a saved colour, the samples left in a loop without a test, one test;
+ *   2  a saved colour, bodies of 16, 8, 4, 2 and 1 samples by the bits of the number left, one test (taken);
+ * and where that one test fires -- the threshold was crossed somewhere in the remainder -- the colour goes back and
+ * the single-sample loop replays it and stops after the crossing sample: the reference's exit, as for a whole group.
+ * The same composites in the same order and the same count in every form.  The bodies are confined to the lean
+ * instances, which is why they can be here and not in vrc_march_uniform_counted (see above).  Measured:
+ * profiles/r11_lean_visit.txt */
+#ifndef VRC_LEAN_REMAINDER
+#define VRC_LEAN_REMAINDER 2
+#endif
+#ifndef VRC_LEAN_GROUP
+#define VRC_LEAN_GROUP 32 /* samples per whole group of the lean march: a power of two */
+#endif
+template < bool COUNT, typename E >
+VRC_HD bool vrc_march_uniform_lean( E& color, const E ue, uint32_t nLeft, uint32_t& nSamples )
+{
+    static_assert( VRC_LEAN_GROUP >= 2 && ( VRC_LEAN_GROUP & ( VRC_LEAN_GROUP - 1 ) ) == 0,
+                   "the bodies below are the bits of a count below the group" );
+    const bool crossed = vrc_uniform_groups< COUNT, VRC_LEAN_GROUP, E >( color, ue, nLeft, nSamples );
+    if( VRC_LEAN_REMAINDER != 0 && !crossed )
+    {
+        const E saved = color;
+        if( VRC_LEAN_REMAINDER == 1 )
+        {
+            for( uint32_t k = 0u; k < nLeft; ++k )
+                vrc_composite( color, ue );
+        }
+        else
+        {
+#pragma unroll
+            for( int body = VRC_LEAN_GROUP / 2; body > 0; body >>= 1 )
+                if( nLeft & (uint32_t)body )
+                {
+#pragma unroll
+                    for( int k = 0; k < body; ++k )
+                        vrc_composite( color, ue );
+                }
+        }
+        if( !( color.w > VRC_EARLY_EXIT ) )
+        {
+            if( COUNT )
+                nSamples += nLeft;
+            return false;
+        }
+        color = saved;
+    }
+    for( ; nLeft > 0u; --nLeft )
+    {
+        vrc_composite( color, ue );
+        if( COUNT )
+            nSamples += 1u;
+        if( color.w > VRC_EARLY_EXIT )
+            return true;
+    }
+    return false;
+}
+
+/* The second plane of a lean list's visit (vrc_frame::walkLean): n << 20 | slotInfoIndex, n = the samples of the
+ * uniform march over `dist` -- what vrc_exact_step_count returns, 0 where the march takes none -- and the node's own
+ * slotInfoIndex (0: none, else ordinal + 1).  false: the visit cannot be packed -- the count is not exact, or does not
+ * fit 12 bits, or the index does not fit 20 -- and the view keeps the other form */
+#define VRC_WALK_LEAN_INDEX_BITS 20u
+#define VRC_WALK_LEAN_MAX_STEPS 4096u /* n below this */
+VRC_HD bool vrc_walk_lean_word( float dist, float stepSize, uint32_t slotInfoIndex, uint32_t* word )
+{
+    uint32_t n = 0u;
+    bool ok = true;
+    if( dist > 0.0f )
+        ok = vrc_exact_step_count( dist, stepSize, &n );
+    ok = ok && n < VRC_WALK_LEAN_MAX_STEPS && slotInfoIndex < ( 1u << VRC_WALK_LEAN_INDEX_BITS );
+    *word = ( n << VRC_WALK_LEAN_INDEX_BITS ) | ( slotInfoIndex & ( ( 1u << VRC_WALK_LEAN_INDEX_BITS ) - 1u ) );
+    return ok;
 }
 
 /* UNIFORM: every voxel a sample of this brick can reach holds one value (the slot's uniformity word,
@@ -3859,7 +3947,11 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                     {
                         uint32_t* const w = walkOut + ( 1u + 4u * nSamples ) * f.walkPlane;
                         w[0] = (uint32_t)node;
-                        w[f.walkPlane] = vrc_float_bits( vrc_segment_dist( r, iv ) );
+                        const float dist = vrc_segment_dist( r, iv );
+                        uint32_t second = vrc_float_bits( dist );
+                        if( f.walkLean != 0u ) /* (the count pass found that every visit packs) */
+                            (void)vrc_walk_lean_word( dist, f.stepSize, n.slotInfoIndex, &second );
+                        w[f.walkPlane] = second;
                         w[2u * f.walkPlane] = vrc_float_bits( iv.tNear );
                         w[3u * f.walkPlane] = vrc_float_bits( iv.tFar );
                     }
@@ -3873,6 +3965,11 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                             word = f.slotInfo[n.slotInfoIndex - 1u];
                         if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN )
                             color.x += 1.0f; /* (exact: a ray visits far fewer than 2^24 bricks) */
+                        /* ... and, asked by walkLean, whether a visit fails to pack (color.y != 0) */
+                        uint32_t packed;
+                        if( f.walkLean != 0u &&
+                            !vrc_walk_lean_word( vrc_segment_dist( r, iv ), f.stepSize, n.slotInfoIndex, &packed ) )
+                            color.y = 1.0f;
                     }
                     ++nSamples;
                 }
@@ -4071,10 +4168,11 @@ VRC_HD vrc_ray vrc_ray_from_cache( const vrc_frame& f, uint32_t rayIndex )
  * marched.  Returns the number of visits; the caller stores it in plane 0 (record pass) or folds it into the frame's
  * maximum (count pass).  The pixel buffer is not read: a list is complete whatever the frame composites onto, and
  * whatever the transfer function ends early.  gathers (count pass only): how many of the visits meet a brick that is not
- * known to be uniform, by the slot words as they are now */
+ * known to be uniform, by the slot words as they are now; notLean (count pass of a frame with walkLean set): 1 when a
+ * visit of the ray does not pack (vrc_walk_lean_word) */
 VRC_HD uint32_t vrc_pixel_walk_record( const vrc_frame& f, const vrc_dev_node* __restrict__ nodes,
                                        const int32_t* __restrict__ gridTable, uint32_t rayIndex,
-                                       uint32_t* gathers = nullptr )
+                                       uint32_t* gathers = nullptr, uint32_t* notLean = nullptr )
 {
     const vrc_ray r = vrc_ray_from_cache( f, rayIndex );
     uint32_t count = 0u;
@@ -4087,6 +4185,8 @@ VRC_HD uint32_t vrc_pixel_walk_record( const vrc_frame& f, const vrc_dev_node* _
     }
     if( gathers )
         *gathers = (uint32_t)none.x;
+    if( notLean )
+        *notLean = none.y != 0.0f ? 1u : 0u;
     return count;
 }
 
@@ -4209,6 +4309,111 @@ VRC_HD void vrc_pixel_walk_replay( const vrc_frame& f, const vrc_dev_node* __res
         dist = distNext;
     }
     pixelBuffer[pixelPos] = color;
+}
+
+/* The replay of a lean list (vrc_frame::walkLean): the pixel's clear, early exit and store, the order of the visits,
+ * the slot word's rule (0 without slotInfo or without an index), its ballot and the gather march are
+ * vrc_pixel_walk_replay's; what a frame cannot change is read from the list instead of being fetched and computed
+ * again.  The slot word's address comes from the list, so the node is not fetched in front of the ballot, and a
+ * uniform visit marches the n of its word: no node, no dist, no vrc_exact_step_count, no second ballot (every visit of
+ * a lean list counts exactly, so the wave would always have taken the counted form).  A visit that gathers fetches its
+ * node, interval and ray as the other form does and runs the same march on the same segment.  In flight before the
+ * march of visit k: the list word of visit k + 2 and the slot word of visit k + 1.  The index is clamped by walkSlots
+ * as the node is by the table, so no list content reaches past slotInfo.  The colour stays in the march's own form
+ * (two floats under a grey table) across the visits and is widened once, at the store: what every march of the
+ * other form does on its way out */
+template < int MODE > struct vrc_lean_colour { typedef vrc_f4 type; };
+template <> struct vrc_lean_colour< VRC_MODE_GREY > { typedef vrc_f2 type; };
+VRC_HD vrc_f2 vrc_lean_narrow( const vrc_f4& c, const vrc_f2* ) { return vrc_f2{ c.x, c.w }; }
+VRC_HD vrc_f4 vrc_lean_narrow( const vrc_f4& c, const vrc_f4* ) { return c; }
+VRC_HD vrc_f4 vrc_lean_widen( const vrc_f2& c ) { return vrc_f4{ c.x, c.x, c.x, c.w }; }
+VRC_HD vrc_f4 vrc_lean_widen( const vrc_f4& c ) { return c; }
+/* the slot word of a list word, in two steps so that the load can be issued a visit ahead and nothing waits for it
+ * before the visit that reads it: the load (always from a word of slotInfo: index clamped), and the rule */
+VRC_HD uint32_t vrc_lean_slot_load( const vrc_frame& f, uint32_t packed )
+{
+    const uint32_t idx = packed & ( ( 1u << VRC_WALK_LEAN_INDEX_BITS ) - 1u );
+    if( f.slotInfo == nullptr )
+        return 0u;
+    const uint32_t last = f.walkSlots - 1u; /* (a lean frame: walkSlots >= 1) */
+    const uint32_t i = idx != 0u ? idx - 1u : 0u;
+    return f.slotInfo[i < last ? i : last];
+}
+VRC_HD uint32_t vrc_lean_slot_word( uint32_t packed, uint32_t loaded )
+{
+    return ( packed & ( ( 1u << VRC_WALK_LEAN_INDEX_BITS ) - 1u ) ) != 0u ? loaded : 0u;
+}
+
+template < bool COUNT, int MODE, int GROUP >
+VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* __restrict__ nodes,
+                                        const uint8_t* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
+                                        vrc_f4* __restrict__ pixelBuffer, uint32_t px, uint32_t py, uint32_t& nSamples,
+                                        uint32_t rayIndex )
+{
+    typedef typename vrc_lean_colour< MODE >::type E;
+    (void)cls;
+    const E* const tab = reinterpret_cast< const E* >( lut );
+    const uint32_t pixelPos = py * f.width + px;
+    const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
+    const size_t P = f.walkPlane;
+    const uint32_t* const wc = f.walkCache;
+    uint32_t count = wc[rayIndex];
+    count = count < f.walkK ? count : f.walkK;
+    if( count == 0u )
+    {
+        if( f.clearFirst )
+            pixelBuffer[pixelPos] = zero;
+        return;
+    }
+    const vrc_f4 start = f.clearFirst ? zero : pixelBuffer[pixelPos];
+    if( start.w > VRC_EARLY_EXIT )
+        return;
+    E color = vrc_lean_narrow( start, (const E*)nullptr );
+    const uint32_t lastNode = f.nodeCount - 1u;
+    /* pre: the word of visit k + 2 (its second plane); the visit's own first plane lies 9 planes in front of it */
+    size_t pre = (size_t)rayIndex + 2u * P;
+    uint32_t packed = wc[pre];
+    uint32_t packedNext = count > 1u ? wc[pre + 4u * P] : 0u;
+    pre += 8u * P;
+    uint32_t loaded = vrc_lean_slot_load( f, packed );
+    bool gathered = false; /* did the visit before take the gather march?  (the whole wave takes it or none of it) */
+    for( uint32_t k = 0u; k < count; ++k )
+    {
+        /* (the slot word first: its address is a list word that arrived a visit ago) */
+        const uint32_t loadedNext = vrc_lean_slot_load( f, packedNext );
+        uint32_t packedAfter = 0u;
+        if( k + 2u < count )
+            packedAfter = wc[pre];
+        const uint32_t* const at = wc + ( pre - 9u * P );
+        vrc_walk_early early; /* (only `have` is set where nothing was loaded: the rest is then not read) */
+        early.have = false;
+        if( gathered )
+            early = vrc_walk_load_early( f, rayIndex, at );
+        gathered = false;
+        const uint32_t word = vrc_lean_slot_word( packed, loaded );
+        bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
+#if defined( __HIP_DEVICE_COMPILE__ )
+        general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
+#endif
+        bool done;
+        if( !general )
+            done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], packed >> VRC_WALK_LEAN_INDEX_BITS, nSamples );
+        else
+        {
+            const uint32_t node = at[0];
+            const vrc_dev_node n = nodes[node < lastNode ? node : lastNode];
+            const vrc_segment_from_walk src = { f, rayIndex, at, 0.0f, early, &gathered };
+            done = vrc_march_segment_as< false, COUNT, true, uint8_t, GROUP, E >( f, n, src.full(), atlas, tab, color,
+                                                                                  nSamples, 0.0f );
+        }
+        if( done )
+            break;
+        pre += 4u * P;
+        packed = packedNext;
+        packedNext = packedAfter;
+        loaded = loadedNext;
+    }
+    pixelBuffer[pixelPos] = vrc_lean_widen( color );
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -212,10 +212,11 @@ static inline int vrc_walk_replay_group( const vrc_raycast_args& a )
     return tiles <= VRC_SMALL_LAUNCH_TILES ? VRC_SMALL_GROUP : ( a.greyTable ? VRC_GREY_GROUP : VRC_GROUP );
 }
 /* what the count pass finds: the longest list of the frame, the visits of all its rays, and those of them whose brick
- * is not known to be uniform (a.frame.slotInfo as it is on `stream`): visits that would take the gather march */
+ * is not known to be uniform (a.frame.slotInfo as it is on `stream`): visits that would take the gather march.  notLean
+ * (a.frame.walkLean set): 1 when a visit does not pack into a lean list's word (vrc_core.h: vrc_walk_lean_word) */
 struct vrc_walk_count
 {
-    uint32_t longest, pad;
+    uint32_t longest, notLean;
     unsigned long long visits, gathers;
 };
 /* the record form of the grid walk: a.frame.rayMode = VRC_RAY_LOAD; a.frame.walkK = 0: the count pass folds the frame

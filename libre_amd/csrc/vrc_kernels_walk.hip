@@ -6,12 +6,16 @@
  * still over a resident brick set therefore walks the grid once:
  *   vrc_k_walk_record   the tile-scheduled grid walk (vrc_ray_grid_dda, the same tie cells, `pending`, `recent` and
  *                       `stop`) whose visit stores (node, dist, tNear, tFar) instead of marching.  Run twice: with
- *                       frame.walkK = 0 it only counts (vrc_walk_count, three atomics per wave), then the host sizes
+ *                       frame.walkK = 0 it only counts (vrc_walk_count, up to four atomics per wave), then the host sizes
  *                       the planes and the second run fills them.  Never a march: not timed, not counted as a launch.
  *   vrc_k_raycast_replay the march of a frame whose lists are valid: the tile schedule, lane order, pixel clear and
  *                       store, and sample counter of vrc_k_raycast around vrc_pixel_walk_replay, which hands every
  *                       recorded visit to the one visit body vrc_march_brick_from.  None of the walk's state (cell, tMax,
- *                       tDelta, recent, pending) exists in it.
+ *                       tDelta, recent, pending) exists in it.  Its LEAN instances replay the lean form of the lists
+ *                       (vrc_frame::walkLean: a visit's second plane holds its step count and slot index instead of
+ *                       dist) through vrc_pixel_walk_replay_lean, which neither fetches the node of a uniform visit nor
+ *                       counts its steps again; the host picks the form per view (vrc_render), the count pass
+ *                       reports whether every visit packs.
  * Instances: the ones the uniform-brick march exists for -- the table-driven point-sampling march of 8-bit voxels with
  * fixed-point stepping (VRC_MODE_TABLE, VRC_MODE_GREY), counted and uncounted, in the group sizes vrc_launch_raycast
  * picks for them.  Every other frame keeps the walk.
@@ -43,15 +47,16 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) void vrc_k_walk_record(
     uint32_t px, py;
     vrc_walk_lane_pixel( tile, tilesX, lane, px, py );
     const uint32_t rayIndex = tile * 64u + lane;
-    uint32_t count = 0u, gathers = 0u;
+    uint32_t count = 0u, gathers = 0u, notLean = 0u;
     if( px < f.width && py < f.height )
-        count = vrc_pixel_walk_record( f, nodes, gridTable, rayIndex, &gathers );
+        count = vrc_pixel_walk_record( f, nodes, gridTable, rayIndex, &gathers, &notLean );
     if( f.walkK != 0u )
         f.walkCache[rayIndex] = count; /* (0 for a lane outside the frame: whole tiles) */
     else
     {
-        /* the count pass's result (vrc_walk_count): the longest list, and over the whole frame the visits and those of
-         * them that would gather; one atomic each per wave */
+        /* the count pass's result (vrc_walk_count): the longest list, and over the whole frame the visits, those of
+         * them that would gather, and whether one of them does not pack into a lean list's word; one atomic each per
+         * wave */
         uint32_t m = count, sum = count, g = gathers; /* (64 lanes: the wave's sums fit 32 bits) */
 #pragma unroll
         for( int off = 32; off > 0; off >>= 1 )
@@ -61,12 +66,15 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) void vrc_k_walk_record(
             sum += __shfl_down( sum, off, 64 );
             g += __shfl_down( g, off, 64 );
         }
+        const bool anyNotLean = __builtin_amdgcn_ballot_w64( notLean != 0u ) != 0ull;
         if( lane == 0u && m != 0u )
         {
             atomicMax( &result->longest, m );
             atomicAdd( &result->visits, (unsigned long long)sum );
             if( g != 0u )
                 atomicAdd( &result->gathers, (unsigned long long)g );
+            if( anyNotLean )
+                atomicOr( &result->notLean, 1u );
         }
     }
 }
@@ -95,7 +103,9 @@ hipError_t vrc_launch_walk_record( const vrc_raycast_args& a, vrc_walk_count* re
 /* GROUP: samples a lane of the gather march keeps in flight -- what vrc_launch_raycast picks for the walking instance */
 #define VRC_REPLAY_K_MIN_WAVES ( GROUP > VRC_GREY_GROUP ? 2 : 5 )
 #define VRC_REPLAY_K_MAX_WAVES ( GROUP > VRC_GREY_GROUP ? 8 : ( MODE == VRC_MODE_GREY ? VRC_REPLAY_GREY_MAX_WAVES : 5 ) )
-template < bool COUNT, int MODE, int GROUP >
+/* LEAN: the replay of a lean list (vrc_frame::walkLean, vrc_pixel_walk_replay_lean); everything around the pixel is
+ * the same kernel */
+template < bool COUNT, int MODE, int GROUP, bool LEAN = false >
 __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_per_eu( VRC_REPLAY_K_MIN_WAVES, VRC_REPLAY_K_MAX_WAVES ) ) ) void vrc_k_raycast_replay(
     const vrc_frame f, const vrc_dev_node* __restrict__ nodes, const uint8_t* __restrict__ atlas,
     const vrc_f4* __restrict__ lutGlobal, const vrc_classifier cls, vrc_f4* __restrict__ pixelBuffer,
@@ -146,8 +156,14 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_p
 
     uint32_t nSamples = 0;
     if( px < f.width && py < f.height )
-        vrc_pixel_walk_replay< COUNT, MODE, GROUP >( f, nodes, atlas, lut, cls, pixelBuffer, px, py, nSamples,
-                                                     tile * 64u + lane );
+    {
+        if constexpr( LEAN )
+            vrc_pixel_walk_replay_lean< COUNT, MODE, GROUP >( f, nodes, atlas, lut, cls, pixelBuffer, px, py, nSamples,
+                                                              tile * 64u + lane );
+        else
+            vrc_pixel_walk_replay< COUNT, MODE, GROUP >( f, nodes, atlas, lut, cls, pixelBuffer, px, py, nSamples,
+                                                         tile * 64u + lane );
+    }
     if( COUNT )
     {
         /* wave64 reduction, one atomic per wave */
@@ -160,33 +176,40 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_p
     }
 }
 
-template < bool COUNT, int MODE, int GROUP >
+template < bool COUNT, int MODE, int GROUP, bool LEAN >
 static hipError_t launch_replay( const vrc_raycast_args& a, hipStream_t stream )
 {
     const uint32_t tilesX = ( a.frame.width + 7u ) / 8u, tilesY = ( a.frame.height + 7u ) / 8u;
     const uint32_t nTiles = tilesX * tilesY;
     if( nTiles == 0 )
         return hipSuccess;
-    vrc_internal_note_kernel( "vrc_k_raycast_replay<%s,%d,unsigned char,%d>", COUNT ? "true" : "false", (int)MODE, (int)GROUP );
-    vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_replay< COUNT, MODE, GROUP >, (int)VRC_WALK_THREADS, 0 );
-    vrc_launch_march( a, &vrc_k_raycast_replay< COUNT, MODE, GROUP >,
+    vrc_internal_note_kernel( "vrc_k_raycast_replay<%s,%d,unsigned char,%d%s>", COUNT ? "true" : "false", (int)MODE, (int)GROUP,
+                              LEAN ? ",lean" : "" );
+    vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_replay< COUNT, MODE, GROUP, LEAN >, (int)VRC_WALK_THREADS, 0 );
+    vrc_launch_march( a, &vrc_k_raycast_replay< COUNT, MODE, GROUP, LEAN >,
                       dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WALK_WAVES - 1u ) / VRC_WALK_WAVES ),
                       dim3( VRC_WALK_THREADS ), 0, stream, a.frame, a.nodes, (const uint8_t*)a.atlas, a.lut, a.classifier,
                       a.pixelBuffer, a.sampleCounter, a.tileOrder, tilesX, nTiles );
     return hipGetLastError();
 }
 
+/* (the form of the lists and the sample counter: run-time choices among instances) */
 template < int MODE, int GROUP >
 static hipError_t launch_replay( const vrc_raycast_args& a, hipStream_t stream )
 {
-    return a.sampleCounter ? launch_replay< true, MODE, GROUP >( a, stream ) : launch_replay< false, MODE, GROUP >( a, stream );
+    if( a.frame.walkLean != 0u )
+        return a.sampleCounter ? launch_replay< true, MODE, GROUP, true >( a, stream )
+                               : launch_replay< false, MODE, GROUP, true >( a, stream );
+    return a.sampleCounter ? launch_replay< true, MODE, GROUP, false >( a, stream )
+                           : launch_replay< false, MODE, GROUP, false >( a, stream );
 }
 
 /* the frames vrc_launch_raycast would march with <true,false,COUNT,true,TABLE or GREY,unsigned char,GROUP,false>, in the
  * group size it would take (vrc_walk_replay_group): anything else is the caller's mistake, not a frame to walk quietly */
 hipError_t vrc_launch_raycast_replay( const vrc_raycast_args& a, hipStream_t stream )
 {
-    if( !vrc_walk_replay_eligible( a ) || !a.frame.walkCache || a.frame.walkK == 0u || a.frame.rayMode != VRC_RAY_LOAD )
+    if( !vrc_walk_replay_eligible( a ) || !a.frame.walkCache || a.frame.walkK == 0u || a.frame.rayMode != VRC_RAY_LOAD ||
+        ( a.frame.walkLean != 0u && a.frame.walkSlots == 0u ) )
         return hipErrorInvalidValue;
     const int group = vrc_walk_replay_group( a );
     if( a.greyTable )
