@@ -1092,7 +1092,7 @@ static int pool_upload( vrc_pool* p, const void* src, bool srcIsDevice, const ui
  * 16 bits, or not enough device memory (tried once). */
 static bool pool_packed_possible( const vrc_pool* p )
 {
-    return ( p->elemBytes == 1 || p->elemBytes == 2 ) && VRC_LAYOUT == 0;
+    return p->elemBytes == 1 || p->elemBytes == 2;
 }
 /* bytes of the pool's packed atlas (+ 8: a pair is read as 4 / 8 bytes at the last texel) */
 static uint64_t pool_packed_bytes( const vrc_pool* p )
@@ -1304,8 +1304,6 @@ int vrc_pool_enable_histograms( vrc_pool* p, uint32_t binCount, const uint32_t o
     if( binCount != 0 && ( !overlap || binCount > VRC_HIST_MAX_BINS || typeRange % binCount != 0 ) )
         return fail( VRC_EINVAL, "vrc_pool_enable_histograms: bin count must divide the voxel type's range (max 4096), "
                                  "overlap must be given" );
-    if( binCount != 0 && VRC_LAYOUT != 0 )
-        return fail( VRC_EUNSUPPORTED, "vrc_pool_enable_histograms: needs the product's atlas layout" );
     if( binCount != 0 )
         for( int a = 0; a < 3; ++a )
             if( overlap[a] >= p->slotDim[a] )

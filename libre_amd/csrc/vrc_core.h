@@ -15,32 +15,18 @@
 
 /* ---- one guard for every compile-time switch of the kernels (round 3) ------------------------------------------
  * The product is built with NONE of them on the command line (__graft_entry__.build()).  Timing ablations that
- * render wrong pixels on purpose (VRC_ABLATE_*), alternative layouts and schedules, statistics builds, the biased
+ * render wrong pixels on purpose (VRC_ABLATE_NO_FETCH, VRC_PACKED_ABLATE), statistics and timeline builds, the biased
  * negative control of the parity tests and every tuning value live behind VRC_DEV_BUILD: a stray -DVRC_... without
  * it does not compile, and a library built with it says so (vrc_abi_version() < 0, vrc_is_dev_build() = 1;
  * bench.py refuses it).  tools/build_variants.sh and the test harnesses pass -DVRC_DEV_BUILD. */
 #if !defined( VRC_DEV_BUILD ) && ( \
     defined( VRC_ABLATE_NO_FETCH ) || \
-    defined( VRC_ABLATE_HALF_FETCH ) || \
-    defined( VRC_ABLATE_QUARTER_FETCH ) || \
-    defined( VRC_ZRUN ) || \
-    defined( VRC_SETPRIO ) || \
-    defined( VRC_INT_STEPS ) || defined( VRC_WG_TIMELINE ) || \
-    defined( VRC_NO_UNIFORM_INT_STEPS ) || defined( VRC_UNIFORM_GROUP ) || defined( VRC_UNIFORM_SMALL_GROUP ) || \
-    defined( VRC_LEAN_REMAINDER ) || defined( VRC_LEAN_GROUP ) || \
-    defined( VRC_PIPELINE ) || \
-    defined( VRC_LAYOUT ) || \
-    defined( VRC_LAYOUT_PADX ) || \
-    defined( VRC_LANES_ROWMAJOR ) || \
-    defined( VRC_NO_SERIAL_STEPS ) || \
-    defined( VRC_NO_ADDR_TABLES ) || \
-    defined( VRC_ADDR_TABLES ) || \
+    defined( VRC_WG_TIMELINE ) || \
+    defined( VRC_UNIFORM_GROUP ) || \
+    defined( VRC_LEAN_GROUP ) || \
     defined( VRC_TEST_BIAS_ENTRY ) || \
-    defined( VRC_DEV_KNOBS ) || \
     defined( VRC_LDS_STATS ) || defined( VRC_LDS_STATS2 ) || \
     defined( VRC_LDS_TIMING ) || \
-    defined( VRC_LDS_ABLATE_GATHER ) || \
-    defined( VRC_LDS_NO_STEP_CAP ) || defined( VRC_LDS_LOAD_ALL ) || \
     defined( VRC_LDS_PASSES ) || defined( VRC_LDS_ROWS ) || defined( VRC_LDS_OCC ) || defined( VRC_LDS_STAGE_N ) || \
     defined( VRC_LDS_ROWS16 ) || defined( VRC_LDS_OCC16 ) || defined( VRC_LDS_STAGE_N16 ) || \
     defined( VRC_LDS_KMAX ) || \
@@ -52,8 +38,7 @@
     defined( VRC_LDS_REFILL ) || defined( VRC_LDS_SOON ) || \
     defined( VRC_GROUP ) || \
     defined( VRC_GREY_GROUP ) || \
-    defined( VRC_GREY_MAX_WAVES ) || \
-    defined( VRC_TAIL_GROUP ) || \
+    defined( VRC_GREY_MAX_WAVES ) || defined( VRC_REPLAY_GREY_MAX_WAVES ) || \
     defined( VRC_LGROUP ) || \
     defined( VRC_PGROUP ) || defined( VRC_PGROUP16 ) || defined( VRC_PACKED_WAVES ) || defined( VRC_PACKED_ABLATE ) || \
     defined( VRC_SPLIT_GROUP ) || \
@@ -283,21 +268,11 @@ struct vrc_layout
 };
 
 /* ---- slot-local layout: element offset = LX(x) + LY(y) + LZ(z), one part per axis ---------------
- * VRC_LAYOUT 0 (the product's layout): 8x8x8 micro-blocks, blocks x-fastest inside the slot; inside a block the
- * 64 x-rows of 8 voxels lie in the order y & 3, z & 3, y >> 2, z >> 2, so that a 128-byte line -- what an L2 fetches
+ * 8x8x8 micro-blocks, blocks x-fastest inside the slot; inside a block the 64 x-rows of 8 voxels lie in the order y & 3, z & 3, y >> 2, z >> 2, so that a 128-byte line -- what an L2 fetches
  * from HBM -- is a block of 8 x 4 x 4 voxels and the lines a tile touches per step are the same for views along every
  * axis (round 4; rounds 1-3 had the rows in the order y, z -- lines of 8 x 8 x 2 -- and ran views along x and y
  * 17 % / 7 % slower than along z: profiles/r4_byte_atlas_line_shapes.txt).  Rows y and y + 1 (y even) stay neighbours.
- * Other values are developer experiments (tools/dev_layouts.sh): only the table-driven point-sampling
- * kernel understands them.
- *   1: micro-blocks 576 B apart and block rows padded to 3 mod 8 blocks: the 64-B lines of x/y
- *      neighbour blocks fall into different 64-B phases of a 512-B period
- *   2: row-major (x fastest), pitch slotDim.x + VRC_LAYOUT_PADX
- *   3: 64-B lines of 32 x 2 voxels      4: 64-B lines of 16 x 4 voxels
- *   5: 64-B lines of 4 x 4 x 4 voxels, z fastest (a dword = four voxels along z); with VRC_ZRUN the fast groups of
- *      the march keep a lane's dword and reload it only when the voxel column or the 4-voxel block changes
- *   6: micro-blocks with the rows in the order y, z (rounds 1-3: lines of 8 x 8 x 2)
- *   7: ... in the order y & 1, z, y >> 1 (lines of 8 x 2 x 8) */
+ * The layouts measured against it and retired: DESIGN_HISTORY.md and profiles/r4_byte_atlas_line_shapes.txt. */
 /* in-block offset of row y / slice z (bits 0-2 of u count) */
 VRC_HD uint32_t vrc_mb_y( uint32_t u ) { return ( ( u & 3u ) << 3 ) | ( ( u & 4u ) << 5 ); }
 VRC_HD uint32_t vrc_mb_z( uint32_t u ) { return ( ( u & 3u ) << 5 ) | ( ( u & 4u ) << 6 ); }
@@ -305,115 +280,41 @@ VRC_HD uint32_t vrc_mb_z( uint32_t u ) { return ( ( u & 3u ) << 5 ) | ( ( u & 4u
  * vrc_mb_z( u ) = 64 (u & 7) - VRC_MB_FIX_Z( u ) -- what the arithmetic address paths add to 8 y + 64 z */
 #define VRC_MB_FIX_Y( u ) ( 96u * ( ( ( u ) >> 2 ) & 1u ) )
 #define VRC_MB_FIX_Z( u ) ( 32u * ( ( u ) & 3u ) )
-#ifndef VRC_LAYOUT
-#define VRC_LAYOUT 0
-#endif
-#ifndef VRC_LAYOUT_PADX
-#define VRC_LAYOUT_PADX 0
-#endif
 struct vrc_lay
 {
-    uint32_t a, b, c; /* meaning depends on the layout */
+    uint32_t a, b, c; /* what a step to the next micro-block adds along x, y, z beyond the plain 1, 8, 64 per voxel */
 };
 VRC_HD vrc_lay vrc_make_lay( uint32_t sbx, uint32_t sby )
 {
     vrc_lay l;
-#if VRC_LAYOUT == 0 || VRC_LAYOUT == 6
     l.a = 504u; l.b = sbx * VRC_MB_VOXELS - 64u; l.c = sbx * sby * VRC_MB_VOXELS - 512u;
-#elif VRC_LAYOUT == 1
-    const uint32_t sbxp = sbx + ( ( 3u - sbx ) & 7u );
-    l.a = 576u; l.b = 576u * sbxp; l.c = 576u * sbxp * sby;
-#elif VRC_LAYOUT == 2
-    l.a = 1u; l.b = sbx * 8u + VRC_LAYOUT_PADX; l.c = l.b * sby * 8u;
-#elif VRC_LAYOUT == 3
-    l.a = 64u; l.b = 64u * ( ( sbx * 8u + 31u ) / 32u ); l.c = l.b * sby * 4u;
-#elif VRC_LAYOUT == 5
-    l.a = 64u; l.b = 64u * sbx * 2u; l.c = l.b * sby * 2u;
-#elif VRC_LAYOUT == 7
-    l.a = 504u; l.b = sbx * VRC_MB_VOXELS; l.c = sbx * sby * VRC_MB_VOXELS;
-#else
-    l.a = 64u; l.b = 64u * ( ( sbx * 8u + 15u ) / 16u ); l.c = l.b * sby * 2u;
-#endif
     return l;
 }
 VRC_HD uint32_t vrc_lay_x( const vrc_lay& l, uint32_t u )
 {
-#if VRC_LAYOUT == 0 || VRC_LAYOUT == 6 || VRC_LAYOUT == 7
     return u + l.a * ( u >> 3 );
-#elif VRC_LAYOUT == 1
-    return ( u & 7u ) + l.a * ( u >> 3 );
-#elif VRC_LAYOUT == 2
-    return u;
-#elif VRC_LAYOUT == 3
-    return ( u & 31u ) + l.a * ( u >> 5 );
-#elif VRC_LAYOUT == 5
-    return 16u * ( u & 3u ) + l.a * ( u >> 2 );
-#else
-    return ( u & 15u ) + l.a * ( u >> 4 );
-#endif
 }
 VRC_HD uint32_t vrc_lay_y( const vrc_lay& l, uint32_t u )
 {
-#if VRC_LAYOUT == 0
     return 8u * u + l.b * ( u >> 3 ) + VRC_MB_FIX_Y( u );
-#elif VRC_LAYOUT == 6
-    return 8u * u + l.b * ( u >> 3 );
-#elif VRC_LAYOUT == 1
-    return 8u * ( u & 7u ) + l.b * ( u >> 3 );
-#elif VRC_LAYOUT == 2
-    return l.b * u;
-#elif VRC_LAYOUT == 3
-    return 32u * ( u & 1u ) + l.b * ( u >> 1 );
-#elif VRC_LAYOUT == 5
-    return 4u * ( u & 3u ) + l.b * ( u >> 2 );
-#elif VRC_LAYOUT == 7
-    return 8u * ( ( u & 1u ) | ( ( ( u >> 1 ) & 3u ) << 4 ) ) + l.b * ( u >> 3 );
-#else
-    return 16u * ( u & 3u ) + l.b * ( u >> 2 );
-#endif
 }
 VRC_HD uint32_t vrc_lay_z( const vrc_lay& l, uint32_t u )
 {
-#if VRC_LAYOUT == 0
     return 64u * u + l.c * ( u >> 3 ) - VRC_MB_FIX_Z( u );
-#elif VRC_LAYOUT == 6
-    return 64u * u + l.c * ( u >> 3 );
-#elif VRC_LAYOUT == 1
-    return 64u * ( u & 7u ) + l.c * ( u >> 3 );
-#elif VRC_LAYOUT == 5
-    return ( u & 3u ) + l.c * ( u >> 2 );
-#elif VRC_LAYOUT == 7
-    return 8u * ( ( u & 7u ) << 1 ) + l.c * ( u >> 3 );
-#else
-    return l.c * u;
-#endif
 }
 /* physical elements of one slot */
 VRC_HD uint64_t vrc_slot_elems( uint32_t sdx, uint32_t sdy, uint32_t sdz )
 {
-#if VRC_LAYOUT == 0 || VRC_LAYOUT == 6 || VRC_LAYOUT == 7
     return (uint64_t)sdx * sdy * sdz;
-#elif VRC_LAYOUT == 1
-    return (uint64_t)vrc_make_lay( sdx >> 3, sdy >> 3 ).c * ( sdz >> 3 );
-#elif VRC_LAYOUT == 5
-    return (uint64_t)vrc_make_lay( sdx >> 3, sdy >> 3 ).c * ( sdz >> 2 );
-#else
-    return (uint64_t)vrc_make_lay( sdx >> 3, sdy >> 3 ).c * sdz;
-#endif
 }
 
 /* element offset of voxel (x,y,z), local to a slot of sbx x sby x * micro-blocks */
 VRC_HD uint32_t vrc_slot_local_index( uint32_t x, uint32_t y, uint32_t z, uint32_t sbx, uint32_t sby )
 {
-#if VRC_LAYOUT == 0
     const uint32_t blk = ( ( z >> VRC_MB_SHIFT ) * sby + ( y >> VRC_MB_SHIFT ) ) * sbx +
                          ( x >> VRC_MB_SHIFT );
     const uint32_t inner = vrc_mb_z( z ) | vrc_mb_y( y ) | ( x & 7u );
     return blk * VRC_MB_VOXELS + inner;
-#else
-    const vrc_lay l = vrc_make_lay( sbx, sby );
-    return vrc_lay_x( l, x ) + vrc_lay_y( l, y ) + vrc_lay_z( l, z );
-#endif
 }
 
 /* element offset of slot (i,j,k): 64 bits, an atlas may hold more than 2^32 voxels (it is sized
@@ -913,21 +814,19 @@ VRC_HD vrc_fixpos vrc_fixpos_init( const vrc_sampler& s, const vrc_f3& pos, cons
     return p;
 }
 
-#if !defined( VRC_NO_ADDR_TABLES ) && !defined( VRC_ADDR_TABLES )
-#define VRC_ADDR_TABLES /* measured 4 % faster on C2 than the arithmetic form */
-#endif
-#if defined( __HIPCC__ ) && defined( VRC_ADDR_TABLES )
+#if defined( __HIPCC__ )
 /* Per-axis address parts of vrc_voxel_address as three 256-entry tables in LDS (filled by the
  * raycast kernel): TX[u] = u + 504 (u>>3), TY[u] = 8u + cyy (u>>3) + FIX_Y(u), TZ[u] = 64u + czz (u>>3) - FIX_Z(u).
  * Replaces 3 shifts + 3 24-bit multiply-adds + 2 shift-adds (the slow VALU classes) by 3 masks
- * + 3 LDS reads + one 3-input add per sample. */
+ * + 3 LDS reads + one 3-input add per sample (measured 4 % faster on C2 than the arithmetic form, which the host
+ * build keeps). */
 __shared__ uint32_t vrc_addr_tab[3 * 256];
 #endif
 
 template < int N >
 VRC_HD void vrc_group_indices_fixed( const vrc_sampler& s, vrc_fixpos& p, uint32_t* idx )
 {
-#if defined( __HIP_DEVICE_COMPILE__ ) && defined( VRC_ADDR_TABLES )
+#if defined( __HIP_DEVICE_COMPILE__ )
     uint32_t tx[N], ty[N], tz[N];
 #pragma unroll
     for( int k = 0; k < N; ++k )
@@ -939,12 +838,10 @@ VRC_HD void vrc_group_indices_fixed( const vrc_sampler& s, vrc_fixpos& p, uint32
         p.x += p.dx;
         p.y += p.dy;
         p.z += p.dz;
-#if !defined( VRC_NO_SERIAL_STEPS )
         /* keep the three additions per step: left alone, hipcc rewrites the chain as p + k * d with a
          * v_mul_lo_u32 or a shift-add per step and axis (the slow integer classes, profiles/r1_ubench_valu_issue_costs.txt)
          * to shorten a dependency that the other waves hide anyway */
         asm( "" : "+v"( p.x ), "+v"( p.y ), "+v"( p.z ) );
-#endif
     }
 #pragma unroll
     for( int k = 0; k < N; ++k )
@@ -1133,9 +1030,6 @@ extern uint64_t vrc_uniform_form_taken[2];
 #ifndef VRC_UNIFORM_GROUP
 #define VRC_UNIFORM_GROUP 16
 #endif
-#ifndef VRC_UNIFORM_SMALL_GROUP
-#define VRC_UNIFORM_SMALL_GROUP 0 /* a second round of smaller groups before the single samples: 0 = none */
-#endif
 
 /* Whole groups of G while nLeft >= G: all G samples are the reference's, the early-exit test comes once at the end
  * (alpha never decreases).  Crossed inside a group: the colour goes back to the group's start and nLeft becomes G --
@@ -1165,10 +1059,8 @@ VRC_HD bool vrc_uniform_groups( E& color, const E ue, uint32_t& nLeft, uint32_t&
 template < bool COUNT, typename E >
 VRC_HD bool vrc_march_uniform_counted( E& color, const E ue, uint32_t nLeft, uint32_t& nSamples )
 {
-    bool crossed = vrc_uniform_groups< COUNT, VRC_UNIFORM_GROUP, E >( color, ue, nLeft, nSamples );
-    if constexpr( VRC_UNIFORM_SMALL_GROUP > 0 )
-        crossed = crossed || vrc_uniform_groups< COUNT, VRC_UNIFORM_SMALL_GROUP, E >( color, ue, nLeft, nSamples );
-    (void)crossed;
+    /* (crossed or not, the loop below runs what is left: the remainder, or the group to replay) */
+    (void)vrc_uniform_groups< COUNT, VRC_UNIFORM_GROUP, E >( color, ue, nLeft, nSamples );
     for( ; nLeft > 0u; --nLeft )
     {
         vrc_composite( color, ue );
@@ -1183,18 +1075,13 @@ VRC_HD bool vrc_march_uniform_counted( E& color, const E ue, uint32_t nLeft, uin
 /* The uniform march of the lean replay (vrc_pixel_walk_replay_lean): n samples of one entry, n < 4096 known from the
  * list.  Whole groups as above, of VRC_LEAN_GROUP samples: with the remainder in bodies a larger group no longer pays
  * in single samples, and on C2 groups of 32 beat 16 by 4 % and 64 by 3 % of the kernel, an opaque table and a rotated
- * view included.  What is left below a group is, by VRC_LEAN_REMAINDER,
- *   0  the single-sample loop of vrc_march_uniform_counted, a test after every sample;
- *   1  a saved colour, the samples left in a loop without a test, one test;
- *   2  a saved colour, bodies of 16, 8, 4, 2 and 1 samples by the bits of the number left, one test (taken);
- * and where that one test fires -- the threshold was crossed somewhere in the remainder -- the colour goes back and
- * the single-sample loop replays it and stops after the crossing sample: the reference's exit, as for a whole group.
- * The same composites in the same order and the same count in every form.  The bodies are confined to the lean
- * instances, which is why they can be here and not in vrc_march_uniform_counted (see above).  Measured:
- * profiles/r11_lean_visit.txt */
-#ifndef VRC_LEAN_REMAINDER
-#define VRC_LEAN_REMAINDER 2
-#endif
+ * view included.  What is left below a group is a saved colour, bodies of 16, 8, 4, 2 and 1 samples by the bits of the
+ * number left, and one test; where that test fires -- the threshold was crossed somewhere in the remainder -- the
+ * colour goes back and the single-sample loop replays it and stops after the crossing sample: the reference's exit, as
+ * for a whole group.  The same composites in the same order and the same count as vrc_march_uniform_counted.  The
+ * bodies are confined to the lean instances, which is why they can be here and not there (see above).  Two other forms
+ * of the remainder -- that single-sample loop alone, and the samples left in one loop without a test -- were measured
+ * and lost: profiles/r11_lean_visit.txt */
 #ifndef VRC_LEAN_GROUP
 #define VRC_LEAN_GROUP 32 /* samples per whole group of the lean march: a power of two */
 #endif
@@ -1204,25 +1091,17 @@ VRC_HD bool vrc_march_uniform_lean( E& color, const E ue, uint32_t nLeft, uint32
     static_assert( VRC_LEAN_GROUP >= 2 && ( VRC_LEAN_GROUP & ( VRC_LEAN_GROUP - 1 ) ) == 0,
                    "the bodies below are the bits of a count below the group" );
     const bool crossed = vrc_uniform_groups< COUNT, VRC_LEAN_GROUP, E >( color, ue, nLeft, nSamples );
-    if( VRC_LEAN_REMAINDER != 0 && !crossed )
+    if( !crossed )
     {
         const E saved = color;
-        if( VRC_LEAN_REMAINDER == 1 )
-        {
-            for( uint32_t k = 0u; k < nLeft; ++k )
-                vrc_composite( color, ue );
-        }
-        else
-        {
 #pragma unroll
-            for( int body = VRC_LEAN_GROUP / 2; body > 0; body >>= 1 )
-                if( nLeft & (uint32_t)body )
-                {
+        for( int body = VRC_LEAN_GROUP / 2; body > 0; body >>= 1 )
+            if( nLeft & (uint32_t)body )
+            {
 #pragma unroll
-                    for( int k = 0; k < body; ++k )
-                        vrc_composite( color, ue );
-                }
-        }
+                for( int k = 0; k < body; ++k )
+                    vrc_composite( color, ue );
+            }
         if( !( color.w > VRC_EARLY_EXIT ) )
         {
             if( COUNT )
@@ -1282,7 +1161,6 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
     bool done = false;
     if( !( travel > 0.0f ) )
         return false;
-#if !defined( VRC_NO_UNIFORM_INT_STEPS )
     if constexpr( UNIFORM )
     {
         /* counted in integers where that is the float chain's count exactly (vrc_exact_step_count); taken, like the
@@ -1298,7 +1176,6 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
         if( counted )
             return vrc_march_uniform_counted< COUNT, E >( color, ue, nLeft, nSamples );
     }
-#endif
     vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
     if( FIXED && !UNIFORM )
         fp = vrc_fixpos_init( sm, pos, s.step );
@@ -1307,88 +1184,7 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
      * GROUP steps remain (the sequentially rounded travel differs from the exact one by
      * far less than one step) */
     const float guard = stepSize * (float)( GROUP + 1 );
-#if defined( VRC_PIPELINE ) && defined( __HIP_DEVICE_COMPILE__ )
-    /* Two groups in flight: the gathers of the NEXT group are issued before the table reads and blends of the
-     * current one.  Every wave's life is a chain of groups, each as long as its slowest gather (with every voxel
-     * line touched once per frame, some lane of every group goes all the way to HBM); with the next group's
-     * gathers already on their way that wait overlaps the current group's work instead of following it.  Same
-     * samples in the same order: only when the loads are issued changes. */
-    if( !UNIFORM && travel > guard )
-    {
-        uint32_t idx[GROUP], d[GROUP];
-        if( FIXED )
-            vrc_group_indices_fixed< GROUP >( sm, fp, idx );
-        else
-            vrc_group_indices< CLAMP, GROUP >( sm, pos, s.step, idx );
-#pragma unroll
-        for( int k = 0; k < GROUP; ++k )
-            d[k] = (uint32_t)atlas[idx[k]];
-        for( ;; )
-        {
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-                travel -= stepSize; /* same sequential subtraction as the reference */
-            const bool next = travel > guard; /* another whole group follows: fetch it now */
-            uint32_t dn[GROUP];
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-                dn[k] = 0u;
-            if( next )
-            {
-                if( FIXED )
-                    vrc_group_indices_fixed< GROUP >( sm, fp, idx );
-                else
-                    vrc_group_indices< CLAMP, GROUP >( sm, pos, s.step, idx );
-#pragma unroll
-                for( int k = 0; k < GROUP; ++k )
-                    dn[k] = (uint32_t)atlas[idx[k]];
-            }
-            E e[GROUP];
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-                e[k] = lut[d[k]];
-            const E saved = color;
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-                vrc_composite( color, e[k] );
-            if( COUNT )
-                nSamples += GROUP;
-            if( color.w > VRC_EARLY_EXIT )
-            {
-                /* crossed inside this group: replay it with the reference's per-sample exit */
-                color = saved;
-                if( COUNT )
-                    nSamples -= GROUP;
-#pragma unroll
-                for( int k = 0; k < GROUP; ++k )
-                {
-                    vrc_composite( color, e[k], done );
-                    if( COUNT )
-                        nSamples += done ? 0u : 1u;
-                    done = done || ( color.w > VRC_EARLY_EXIT );
-                }
-                return true;
-            }
-            if( !next )
-                break;
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-                d[k] = dn[k];
-        }
-    }
-#endif
-#if defined( VRC_ZRUN )
-    uint32_t zrunTag = 0xFFFFFFFFu, zrunWord = 0u;
-#endif
-#if defined( VRC_INT_STEPS ) /* developer measurement (round 3): the fast groups counted in integers.
-                              * Only equal to the reference's float chain when the step is a power of two (every
-                              * subtraction is then exact); measured on C2, where it is (1/1024): see DESIGN.md section 4 */
-    uint32_t fastLeft = (uint32_t)( travel / stepSize ); /* exact for a power-of-two step */
-    float travelDone = 0.0f;
-    while( fastLeft > (uint32_t)( GROUP + 1 ) )
-#else
     while( travel > guard )
-#endif
     {
         uint32_t idx[GROUP];
         if constexpr( UNIFORM )
@@ -1397,47 +1193,10 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
             vrc_group_indices_fixed< GROUP >( sm, fp, idx );
         else
             vrc_group_indices< CLAMP, GROUP >( sm, pos, s.step, idx );
-#if defined( VRC_INT_STEPS )
-        fastLeft -= (uint32_t)GROUP;
-        travelDone += stepSize * (float)GROUP;
-#else
 #pragma unroll
         for( int k = 0; k < GROUP; ++k )
             travel -= stepSize; /* same sequential subtraction as the reference */
-#endif
-#if defined( VRC_SETPRIO ) && defined( __HIP_DEVICE_COMPILE__ ) /* developer measurement */
-        __builtin_amdgcn_s_setprio( 3 );
-#endif
         E e[GROUP];
-#if defined( VRC_ZRUN ) && defined( __HIP_DEVICE_COMPILE__ ) && VRC_LAYOUT == 5
-        /* developer experiment (tools/dev_layouts.sh): a lane keeps the dword of its voxel
-         * column (four voxels along z) and loads a new one only when its dword address changes; the other lanes'
-         * loads are out of range of the buffer descriptor and touch nothing */
-        if( sizeof( ATLAS_T ) == 1 && !UNIFORM )
-        {
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast< ATLAS_T* >( atlas ), (short)0, (int)0xFFFFFFFEu, 0x00020000 );
-            uint32_t w[GROUP];
-            uint32_t tag = zrunTag;
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-            {
-                const uint32_t t = idx[k] >> 2;
-                const bool need = t != tag;
-                tag = t;
-                w[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32( rsrc, need ? (int32_t)( idx[k] & ~3u ) : -1, 0, 0 );
-                idx[k] = ( idx[k] & 3u ) | ( need ? 4u : 0u );
-            }
-            zrunTag = tag;
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-            {
-                zrunWord = ( idx[k] & 4u ) ? w[k] : zrunWord;
-                e[k] = lut[( zrunWord >> ( ( idx[k] & 3u ) * 8u ) ) & 0xFFu];
-            }
-        }
-        else
-#endif
 #pragma unroll
         for( int k = 0; k < GROUP; ++k )
         {
@@ -1446,17 +1205,10 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
             else
 #if defined( VRC_ABLATE_NO_FETCH ) /* timing experiment only */
                 e[k] = lut[64u + ( idx[k] >> 31 )];
-#elif defined( VRC_ABLATE_HALF_FETCH ) /* timing experiment only: every other gather dropped */
-                e[k] = lut[(uint32_t)atlas[idx[k & ~1]] + ( idx[k] >> 31 )];
-#elif defined( VRC_ABLATE_QUARTER_FETCH ) /* timing experiment only */
-                e[k] = lut[(uint32_t)atlas[idx[k & ~3]] + ( idx[k] >> 31 )];
 #else
                 e[k] = vrc_entry< PERSAMPLE, E >( lut, (D)atlas[idx[k]], cls );
 #endif
         }
-#if defined( VRC_SETPRIO ) && defined( __HIP_DEVICE_COMPILE__ )
-        __builtin_amdgcn_s_setprio( 0 );
-#endif
         const E saved = color;
 #pragma unroll
         for( int k = 0; k < GROUP; ++k )
@@ -1481,13 +1233,7 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
         }
     }
 
-#if defined( VRC_INT_STEPS )
-    travel -= travelDone; /* exact for a power-of-two step */
-#endif
     /* tail: general form, in smaller groups (fewer slots wasted on steps no lane takes) */
-#if defined( VRC_TAIL_GROUP )
-    constexpr int TAILG = VRC_TAIL_GROUP;
-#else
     /* measured on C2 (groups of 8): tail groups of 8 / 4 / 2 / 1: 0.500 / 0.491 / 0.484 / 0.502 ms relative:
      * fewer gather slots spent on steps no lane takes, until the dependent round trips of a short group
      * cost more than the slots did */
@@ -1496,7 +1242,6 @@ VRC_HD bool vrc_march_segment_as( const vrc_frame& f, const vrc_dev_node& n, vrc
     /* groups of 14: tails of 2 / 3 / 4 / 5 / 7: 0.492 / 0.489 / 0.479 / 0.485 / 0.485 ms (C2), 0.622 / 0.615 / 0.587 / 0.580 /
      * 0.582 ms (noise, 30/20 degrees) */
     constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
-#endif
     while( travel > 0.0f && !done )
     {
         uint32_t idx[TAILG], cnt = 0;
@@ -2017,10 +1762,6 @@ VRC_HD float vrc_trilerp_packed( const vrc_pk_taps< 4 >& t, uint32_t fx, uint32_
  * device the pointer is typed as global memory, so the compiler emits global_load_dword / _dwordx2. */
 VRC_HD vrc_pk_taps< 2 > vrc_packed_load( const vrc_pk_taps< 2 >*, const uint8_t* slot, uint32_t byteOffset, uint32_t byteOffsetY1 )
 {
-#if defined( VRC_PACKED_ABLATE ) && VRC_PACKED_ABLATE == 3 /* timing experiment only: 4-byte-aligned (wrong) addresses */
-    byteOffset &= ~2u;
-    byteOffsetY1 &= ~2u;
-#endif
 #if defined( __HIP_DEVICE_COMPILE__ )
     typedef uint32_t u32_a2 __attribute__( ( aligned( 2 ) ) );
     typedef __attribute__( ( address_space( 1 ) ) ) const u32_a2 g_t;
@@ -2059,7 +1800,7 @@ VRC_HD uint32_t vrc_pk_taps_mix( const vrc_pk_taps< 4 >& t ) { return t.a0 ^ t.a
 template < int N, int TB >
 VRC_HD void vrc_packed_offsets( const vrc_sampler& s, vrc_fixpos& p, uint32_t bias, uint32_t* off, uint32_t* offY1 )
 {
-#if defined( __HIP_DEVICE_COMPILE__ ) && defined( VRC_ADDR_TABLES )
+#if defined( __HIP_DEVICE_COMPILE__ )
     (void)s;
 #pragma unroll
     for( int k = 0; k < N; ++k )
@@ -3257,19 +2998,14 @@ VRC_HD bool vrc_iso_brick( const vrc_frame& f, const vrc_dev_node& n, uint32_t n
     return beyond;
 }
 
-/* slot-local voxel of a slot-local element offset: vrc_slot_local_index read backwards (the product's layout) */
+/* slot-local voxel of a slot-local element offset: vrc_slot_local_index read backwards */
 VRC_HD void vrc_slot_local_voxel( uint32_t e, uint32_t sbx, uint32_t sby, uint32_t& x, uint32_t& y, uint32_t& z )
 {
-#if VRC_LAYOUT == 0
     const uint32_t blk = e / VRC_MB_VOXELS, in = e % VRC_MB_VOXELS;
     const uint32_t bx = blk % sbx, by = ( blk / sbx ) % sby, bz = blk / ( sbx * sby );
     x = ( bx << VRC_MB_SHIFT ) | ( in & 7u );
     y = ( by << VRC_MB_SHIFT ) | ( ( in >> 3 ) & 3u ) | ( ( in >> 5 ) & 4u );
     z = ( bz << VRC_MB_SHIFT ) | ( ( in >> 5 ) & 3u ) | ( ( in >> 6 ) & 4u );
-#else
-    (void)e; (void)sbx; (void)sby;
-    x = y = z = 0u; /* the developer layouts have no isosurface frame (vrc_kernels_iso.hip refuses) */
-#endif
 }
 
 /* The gradient of a hit: central differences of stored voxels around slot-local element `where` of node n, indices

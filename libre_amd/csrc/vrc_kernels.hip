@@ -288,7 +288,7 @@ __global__ void vrc_k_read_region( const T* __restrict__ atlas, T* __restrict__ 
  * when a brick lands (or for every resident brick when the feature is turned on), and the one
  * region of vrc_pool_histogram.
  *
- * The slot is read in its physical order (VRC_LAYOUT 0, vrc_core.h): 8x8x8 micro-blocks, inside
+ * The slot is read in its physical order (vrc_core.h): 8x8x8 micro-blocks, inside
  * a block 64 rows of 8 voxels.  A lane loads 16 bytes = two rows (y, y + 1) of 8-bit voxels or
  * one row of 16-bit voxels and masks out the voxels outside the region; only the micro-blocks
  * that meet the region are read.  Equal neighbours inside a lane's 16 bytes are counted as one
@@ -412,7 +412,7 @@ hipError_t vrc_launch_bin_bricks( const void* atlas, uint32_t elemBytes, const u
         return hipSuccess;
     const uint32_t range = elemBytes == 1 ? 256u : 65536u;
     if( ( elemBytes != 1 && elemBytes != 2 ) || binCount == 0 || binCount > VRC_HIST_MAX_BINS ||
-        range % binCount != 0 || VRC_LAYOUT != 0 || nEntries > 65535u )
+        range % binCount != 0 || nEntries > 65535u )
         return hipErrorInvalidValue;
     uint32_t shift = 0;
     while( ( binCount << shift ) < range )
@@ -534,8 +534,7 @@ hipError_t vrc_launch_repack_brick( const void* src, void* slot, uint32_t elemBy
 #define VRC_GENERIC( T, XF )                                                                                          \
     hipLaunchKernelGGL( ( vrc_k_repack_generic< T, XF > ), dim3( grid_for( total, 256 ) ), dim3( 256 ), 0, stream,     \
                         (const T*)src, (T*)slot, size[0], size[1], size[2], sbx, sby, slotInfo, slotMax, slotMin )
-    /* (the experimental layout 5 has no 8-voxel runs along x: generic kernel) */
-    if( VRC_LAYOUT != 5 && elemBytes == 1 && ( size[0] % 8u ) == 0 && ( ( (uintptr_t)src ) % 8u ) == 0 &&
+    if( elemBytes == 1 && ( size[0] % 8u ) == 0 && ( ( (uintptr_t)src ) % 8u ) == 0 &&
         ( ( (uintptr_t)slot ) % 8u ) == 0 && total / 8 < 0xFFFFFFFFull )
     {
         const uint32_t sx8 = size[0] / 8u;
@@ -903,7 +902,6 @@ __global__ __launch_bounds__( VRC_WG_THREADS ) __attribute__( ( amdgpu_waves_per
         if( tid < VRC_TFP_ENTRIES - 256u )
             lut[256u + tid] = lutGlobal[256u + tid];
     }
-#if defined( VRC_ADDR_TABLES )
     if( MODE == VRC_MODE_PACKED || MODE == VRC_MODE_PACKED_GREY )
     {
         /* per-axis BYTE offsets of the packed atlas's texels (vrc_core.h: vrc_pk_x / y / z) */
@@ -930,7 +928,6 @@ __global__ __launch_bounds__( VRC_WG_THREADS ) __attribute__( ( amdgpu_waves_per
             }
         }
     }
-#endif
     __syncthreads();
     /* from here on the waves of the workgroup are independent */
     const uint32_t slotIndex = blockIdx.x * VRC_WAVES_PER_WG + ( tid >> 6 );
@@ -945,7 +942,7 @@ __global__ __launch_bounds__( VRC_WG_THREADS ) __attribute__( ( amdgpu_waves_per
     if( tile == VRC_NO_TILE )
         return;
     const uint32_t tx = tile % tilesX, ty = tile / tilesX;
-#if defined( VRC_LANES_ROWMAJOR ) || VRC_TILE_W != 8
+#if VRC_TILE_W != 8
     const uint32_t lx = lane % VRC_TILE_W, ly = lane / VRC_TILE_W;
 #else
     /* Morton lane order: every 4 consecutive lanes (the unit the texture addresser works on)
@@ -1067,7 +1064,6 @@ __global__ __launch_bounds__( 512, GROUP > 8 ? 2 : 4 ) void vrc_k_raycast_split(
         lut[tid] = lutGlobal[tid];
     if( tid < VRC_TFP_ENTRIES - 256u )
         lut[256u + tid] = lutGlobal[256u + tid];
-#if defined( VRC_ADDR_TABLES )
     if( tid < 256u )
     {
         const vrc_lay lay = vrc_make_lay( f.sbx, f.sby );
@@ -1075,7 +1071,6 @@ __global__ __launch_bounds__( 512, GROUP > 8 ? 2 : 4 ) void vrc_k_raycast_split(
         vrc_addr_tab[256u + tid] = vrc_lay_y( lay, tid );
         vrc_addr_tab[512u + tid] = vrc_lay_z( lay, tid );
     }
-#endif
     __syncthreads();
     const uint32_t tilesY = nTiles / tilesX;
     const uint32_t slotIndex = blockIdx.x * 4u + sub;
@@ -1180,7 +1175,6 @@ __global__ __launch_bounds__( VRC_WG_THREADS, 4 ) void vrc_k_raycast_part(
             lut[tid + i * VRC_WG_THREADS] = lutGlobal[tid + i * VRC_WG_THREADS];
     if( tid < VRC_TFP_ENTRIES - 256u )
         lut[256u + tid] = lutGlobal[256u + tid];
-#if defined( VRC_ADDR_TABLES )
     {
         const vrc_lay lay = vrc_make_lay( f.sbx, f.sby );
 #pragma unroll
@@ -1195,7 +1189,6 @@ __global__ __launch_bounds__( VRC_WG_THREADS, 4 ) void vrc_k_raycast_part(
             }
         }
     }
-#endif
     __syncthreads();
     /* from here on the waves of the workgroup are independent */
     uint32_t px = 0, py = 0;

@@ -7,12 +7,5 @@
 
 hipError_t vrc_launch_raycast_iso( const vrc_raycast_args& a, hipStream_t stream )
 {
-#if VRC_LAYOUT == 0
     return launch_mip_fold< VRC_FOLD_FIRST >( a, stream );
-#else
-    /* (the gradient reads a sample's voxel back from its address, which is written for the product's layout alone) */
-    (void)a;
-    (void)stream;
-    return hipErrorInvalidValue;
-#endif
 }

@@ -244,12 +244,8 @@ __device__ __forceinline__ void lds_stage( const uint8_t* __restrict__ slotPtr, 
                                            uint8_t* dst, uint32_t pz, F between )
 {
     lds_u32x4 v[N];
-#if defined( VRC_LDS_LOAD_ALL ) /* developer build: lanes that stage nothing load too (the caller clamps their piece) */
-    {
-#else
     if( on )
     {
-#endif
         uint32_t pl = partial;
 #pragma unroll
         for( int z = 0; z < N; ++z )
@@ -956,7 +952,6 @@ __global__ __launch_bounds__( 64 * VRC_LDS_WAVES, sizeof( V ) == 2 ? VRC_LDS_OCC
                 const uint32_t nm = wave_or( part ? 1u << nSteps : 0u );
                 nMin = (uint32_t)__builtin_ctz( nm );
                 nMax = 31u - (uint32_t)__builtin_clz( nm );
-#if !defined( VRC_LDS_NO_STEP_CAP )
                 /* a level tile (its lanes within a step of each other) takes whole fast groups and leaves the odd
                  * step to the next pass: the general batches that would take it cost a third of a fast group */
                 if( nMax - nMin <= 1u && nMin >= VRC_LDS_GF )
@@ -964,18 +959,12 @@ __global__ __launch_bounds__( 64 * VRC_LDS_WAVES, sizeof( V ) == 2 ? VRC_LDS_OCC
                     nMax = nMin - nMin % VRC_LDS_GF;
                     nSteps = nSteps < nMax ? nSteps : nMax;
                 }
-#endif
             };
             const uint32_t pz = VRC_LDS_PY * box.dy; /* slice pitch of this pass */
             VRC_LDS_PHASE( 2 )
             /* ---- stage the box: atlas (micro-blocked) -> LDS (linear) --------------------- */
             {
-#if defined( VRC_LDS_LOAD_ALL )
-                const uint32_t x = box.x0 + ( sxr * 8u < box.dx ? sxr * 8u : box.dx - 8u ),
-                               y = box.y0 + ( syp * 2u < box.dy ? syp * 2u : box.dy - 2u );
-#else
                 const uint32_t x = box.x0 + sxr * 8u, y = box.y0 + syp * 2u;
-#endif
                 const bool on = sxr * 8u < box.dx && syp * 2u < box.dy;
                 const uint32_t partial =
                     ( ( y >> VRC_MB_SHIFT ) * f.sbx + ( x >> VRC_MB_SHIFT ) ) * VRC_MB_VOXELS + vrc_mb_y( y );
@@ -1178,14 +1167,6 @@ __global__ __launch_bounds__( 64 * VRC_LDS_WAVES, sizeof( V ) == 2 ? VRC_LDS_OCC
 
         VRC_LDS_PHASE( 5 )
         /* C: lanes no box of this round served: the same steps by byte gathers from the atlas */
-#if defined( VRC_LDS_ABLATE_GATHER ) /* developer timing build: the left-over lanes skip their steps (wrong pixels) */
-        if( inTodo )
-        {
-            fx += 8u * fdx; fy += 8u * fdy; fz += 8u * fdz;
-            travel -= 8.0f * lstep;
-            inTodo = false;
-        }
-#endif
         const bool gathers = __builtin_amdgcn_ballot_w64( inTodo ) != 0ull;
         if( gathers )
         {

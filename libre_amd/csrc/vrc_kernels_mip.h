@@ -53,7 +53,6 @@ __global__ __launch_bounds__( VRC_MIP_WG_THREADS ) __attribute__( ( amdgpu_waves
     __shared__ uint16_t tileCand[DDA ? 1u : VRC_WAVES_PER_GROUP * VRC_TILE_CANDIDATES];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
-#if defined( VRC_ADDR_TABLES )
     if( FIXED )
     {
         const vrc_lay lay = vrc_make_lay( f.sbx, f.sby );
@@ -65,7 +64,6 @@ __global__ __launch_bounds__( VRC_MIP_WG_THREADS ) __attribute__( ( amdgpu_waves
         }
         __syncthreads();
     }
-#endif
     /* from here on the waves of the workgroup are independent */
     const uint32_t slotIndex = blockIdx.x * VRC_WAVES_PER_GROUP + ( tid >> 6 );
     const uint32_t tilesY = nTiles / tilesX;

@@ -58,7 +58,6 @@ __global__ __launch_bounds__( VRC_RL_THREADS, VRC_RL_MIN_BLOCKS ) void vrc_k_ray
     else
         for( uint32_t i = tid; i < lutEntries; i += VRC_RL_THREADS )
             lutLevels[i] = lutGlobal[i];
-#if defined( VRC_ADDR_TABLES )
     if( MODE == VRC_MODE_PACKED || MODE == VRC_MODE_PACKED_GREY )
     {
         for( uint32_t u = tid; u < 256u; u += VRC_RL_THREADS )
@@ -80,7 +79,6 @@ __global__ __launch_bounds__( VRC_RL_THREADS, VRC_RL_MIN_BLOCKS ) void vrc_k_ray
             vrc_addr_tab[512u + u] = 64u * u + czz * q - VRC_MB_FIX_Z( u );
         }
     }
-#endif
     __syncthreads();
     const uint32_t slotIndex = blockIdx.x * VRC_RL_WAVES + ( tid >> 6 );
     const uint32_t tilesY = nTiles / tilesX;

@@ -131,7 +131,6 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_p
         for( uint32_t i = tid; i < VRC_TFP_ENTRIES; i += VRC_WALK_THREADS )
             lut[i] = lutGlobal[i];
     }
-#if defined( VRC_ADDR_TABLES )
     {
         const vrc_lay lay = vrc_make_lay( f.sbx, f.sby );
         for( uint32_t u = tid; u < 256u; u += VRC_WALK_THREADS )
@@ -141,7 +140,6 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_p
             vrc_addr_tab[512u + u] = vrc_lay_z( lay, u );
         }
     }
-#endif
     __syncthreads();
     /* from here on the waves of the workgroup are independent */
     const uint32_t slotIndex = blockIdx.x * VRC_WALK_WAVES + ( tid >> 6 );

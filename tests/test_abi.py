@@ -87,11 +87,31 @@ def test_developer_switches_need_the_dev_build_guard(tmp_path):
                    % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     base = ["g++", "-std=c++17", "-fsyntax-only", "-Wno-unknown-pragmas", str(src)]
     assert subprocess.run(base, capture_output=True).returncode == 0
-    for sw in ("-DVRC_ABLATE_NO_FETCH", "-DVRC_ZRUN", "-DVRC_PIPELINE", "-DVRC_LAYOUT=5", "-DVRC_LANES_ROWMAJOR",
-               "-DVRC_GROUP=4", "-DVRC_LDS_STATS", "-DVRC_TEST_BIAS_ENTRY"):
+    for sw in ("-DVRC_ABLATE_NO_FETCH", "-DVRC_PACKED_ABLATE=1", "-DVRC_WG_TIMELINE", "-DVRC_UNIFORM_GROUP=8",
+               "-DVRC_LEAN_GROUP=16", "-DVRC_GROUP=4", "-DVRC_LDS_STATS", "-DVRC_TEST_BIAS_ENTRY"):
         r = subprocess.run(base + [sw], capture_output=True, text=True)
         assert r.returncode != 0 and "VRC_DEV_BUILD" in r.stderr, sw
         assert subprocess.run(base + [sw, "-DVRC_DEV_BUILD"], capture_output=True).returncode == 0, sw
+
+
+def test_retired_switches_are_gone_from_the_sources():
+    # the measured-and-rejected alternatives (profiles/README.md, "Retired compile-time switches") left the kernel
+    # sources for good: no file of the product names one, in code, in the guard or in a comment
+    retired = ("VRC_PIPELINE", "VRC_ZRUN", "VRC_INT_STEPS", "VRC_SETPRIO", "VRC_ABLATE_HALF_FETCH",
+               "VRC_ABLATE_QUARTER_FETCH", "VRC_TAIL_GROUP", "VRC_NO_SERIAL_STEPS", "VRC_NO_UNIFORM_INT_STEPS",
+               "VRC_DEV_KNOBS", "VRC_NO_ADDR_TABLES", "VRC_ADDR_TABLES", "VRC_LAYOUT", "VRC_LAYOUT_PADX",
+               "VRC_UNIFORM_SMALL_GROUP", "VRC_LEAN_REMAINDER", "VRC_LANES_ROWMAJOR", "VRC_LDS_LOAD_ALL",
+               "VRC_LDS_NO_STEP_CAP", "VRC_LDS_ABLATE_GATHER")
+    pattern = re.compile(r"\b(?:%s)\b|VRC_PACKED_ABLATE\s*==\s*3" % "|".join(retired))
+    seen = 0
+    for d in (os.path.join("libre_amd", "csrc"), "include"):
+        for root, _, files in os.walk(os.path.join(ROOT, d)):
+            for f in files:
+                path = os.path.join(root, f)
+                found = pattern.findall(open(path, errors="replace").read())
+                assert not found, (path, sorted(set(found)))
+                seen += 1
+    assert seen > 10  # (the walk found the sources)
 
 
 def test_option_numbers_match_the_header(built):

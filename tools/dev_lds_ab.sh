@@ -1,5 +1,5 @@
 #!/bin/bash
-# Developer A/B of trilinear kernel forms ON the GPU box: library variants (tools/build_variants.sh / dev_layouts.sh:
+# Developer A/B of trilinear kernel forms ON the GPU box: library variants (tools/build_variants.sh:
 # VRC_LDS_ROWS, VRC_LDS_OCC, VRC_LDS_STAGE_N, VRC_LDS_KMAX, VRC_PGROUP, ... are COMPILE-time switches, one library
 # each) x kernels x volumes x views.
 # usage: tools/dev_lds_ab.sh OUT "lib1 lib2 ..." "kernel1 kernel2 ..." [extra dev_bench args]     (kernels: 3 = LDS-staged, 5 = tap-packed)

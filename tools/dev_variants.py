@@ -1,4 +1,4 @@
-"""Developer A/B of libvrc_hip.so builds (tools/dev_layouts.sh) on one scene: every build renders the
+"""Developer A/B of libvrc_hip.so builds (tools/build_variants.sh) on one scene: every build renders the
 same frame (checked against the first build's frame), then the gather kernel is timed.
 usage: python tools/dev_variants.py [--volume mem|hash] [--steps 20] variants/a.so variants/b.so ..."""
 import argparse

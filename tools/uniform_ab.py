@@ -3,7 +3,7 @@ for bit), then the raycast kernel timed from the library's HIP events (vrc_get_s
 usage: python tools/uniform_ab.py [--volume mem|hash] [--steps 20] [--rounds 3] [--lib libvrc_hip.so]
 A library that does not know the option (an older build) is timed once, as "off".
 Forms of the uniform march against each other (the product carries no switch for them: they are builds,
-tools/build_variants.sh NAME "-DVRC_NO_UNIFORM_INT_STEPS" / "-DVRC_UNIFORM_GROUP=8", or an older commit's library):
+tools/build_variants.sh NAME "-DVRC_UNIFORM_GROUP=8", or an older commit's library):
        python tools/uniform_ab.py --libs parent=variants/libvrc_hip_parent.so new=libre_amd/lib/libvrc_hip.so ...
 renders the frame with every library, option on (compared bit for bit with the first one's, counts included), and
 times them in alternating rounds in this one process.
