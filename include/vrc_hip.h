@@ -261,6 +261,12 @@ typedef struct
                                     * the replay of a uniform brick neither fetches the node nor counts the steps again.
                                     * Same layout, same bytes, same frame and sample count; every other view records
                                     * and replays the lists as before */
+#define VRC_OPT_SHADING 29          /* 0 (default): the composite frame as it is; 1: every sample's colour is lit by the
+                                    * volume's gradient at the sample ("A shaded composite frame" below).  Any other
+                                    * value: VRC_EINVAL.  Read only when VRC_OPT_PROJECTION = VRC_PROJECTION_COMPOSITE:
+                                    * MIP and isosurface frames ignore it */
+#define VRC_OPT_SHADING_AMBIENT 30  /* the ambient share of that light in thousandths, 0 ... 1000, default 250; anything
+                                    * else: VRC_EINVAL.  ambient = (float)k / 1000.0f */
 /* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
  * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
  * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots
@@ -396,6 +402,36 @@ typedef struct
  * the option for an explicit VRC_KERNEL_LDS or _PACKED, vrc_set_ray_lod on and VRC_VARIANT_GLRAYCASTER;
  * VRC_OPT_DEPTH_SPLIT and VRC_OPT_ERT_COMPACTION are silently the plain kernel.  A depth cue, a "<=" surface, smooth
  * (trilinear) gradients and several isovalues are not part of it. */
+
+/* A shaded composite frame (VRC_OPT_PROJECTION = VRC_PROJECTION_COMPOSITE, VRC_OPT_SHADING = 1).  The composite frame
+ * with one change: the colour a sample adds is multiplied by a headlight term; its opacity is not.
+ *   Samples.  Ray set-up, intervals, node order and its quirks, the restart per brick and the sample positions
+ *     (VRC_OPT_STEPPING 0 and 1) are the composite frame's; so is the classification (the classified table for point
+ *     samples of 8-bit voxels, the transfer function and the opacity correction per sample otherwise), the 255/256 clamp,
+ *     the accumulation across passes and early ray termination at 0.999, which looks at alpha only.
+ *   Sample.  With e = (rgb * alpha', alpha') as the unshaded march has it, the shaded march composites (e.rgb * s,
+ *     e.alpha'), s = ambient + (1 - ambient) * |G.dir| / |G|: two-sided, dir the ray's unit direction, s = 1 where |G| is 0
+ *     or not finite; float32, the operations in the order of an isosurface pixel's s, nothing fused.
+ *   Gradient.  G is the isosurface frame's ("An isosurface frame", Gradient), taken at the voxel the POINT sampler
+ *     addresses at the sample's position, under both filters: central differences of the stored voxels around it, indices
+ *     clamped to the slot, integer atlases differenced in integers (offset binary cancels) and float atlases in float32,
+ *     times the node's voxels per world unit.  Interpolated gradients are not part of it.
+ *   What follows, bit for bit, against the same context, pool and options with VRC_OPT_SHADING = 0 marched by gathers
+ *     (VRC_KERNEL_REFERENCE_ORDER or _GRID_DDA; AUTO with point samples): the alpha channel and vrc_stats.samples are
+ *     equal; with VRC_OPT_SHADING_AMBIENT = 1000 the whole frame is; a brick all of whose voxels are equal (mem://)
+ *     contributes what it did, with VRC_OPT_UNIFORM_BRICKS 1 (its slot is marched from one table entry, no gathers)
+ *     and 0 (the gradients are gathered and are zero).  A sample whose alpha' is 0 adds nothing whatever s is: its six
+ *     neighbour voxels are not fetched.  With the option at 0 every frame launches the kernel instances it launched
+ *     before the option existed.
+ * Served: VRC_KERNEL_AUTO, _REFERENCE_ORDER and _GRID_DDA; both filters (trilinear by gathers: AUTO does not take the
+ * LDS-staged form and does not build the tap-packed atlas for a shaded frame); all seven voxel types; atlases of more than
+ * 2^32 voxels; the clamped sampler (overlap 0); row maps, caller-owned frame buffers, frames of several passes;
+ * VRC_OPT_COUNT_SAMPLES; VRC_OPT_RAY_CACHE as before.  Silently the plain shaded kernel: VRC_OPT_DEPTH_SPLIT,
+ * VRC_OPT_ERT_COMPACTION, VRC_OPT_GREY_TABLE (the four-float form, the same frame) and VRC_OPT_WALK_CACHE (a shaded frame
+ * is not replayed: VRC_OPT_WALK_CACHE_USED reads 0, nothing is allocated, and the lists an unshaded view recorded are
+ * forgotten, to be recorded again when that view returns).  VRC_EINVAL from vrc_render, naming the option: an explicit
+ * VRC_KERNEL_LDS or _PACKED, vrc_set_ray_lod on, VRC_VARIANT_GLRAYCASTER, and either shading option changed between
+ * vrc_pre_render and vrc_post_render.  Specular terms, movable lights and picking are not part of it. */
 
 #define VRC_VARIANT_CUDARAYCASTER 0 /* renderers/cudaRaycaster/cuda/Renderer.cu:95-230 */
 #define VRC_VARIANT_GLRAYCASTER 1   /* renderers/glRaycaster/shaders/fragRaycast.glsl:113-215: pixel centre

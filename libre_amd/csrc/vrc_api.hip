@@ -324,6 +324,12 @@ struct vrc_ctx
     float* dIsoGrad = nullptr;
     size_t dIsoGradPixels = 0;
     bool gradValid = false;
+    /* a shaded composite frame (include/vrc_hip.h, "A shaded composite frame"): the two options, and what the frame's
+     * first composite vrc_render read of them (-1 = none yet), as frameFold is its fold */
+    int64_t optShading = 0;          /* VRC_OPT_SHADING */
+    int64_t optShadingAmbient = 250; /* VRC_OPT_SHADING_AMBIENT, thousandths */
+    int64_t frameShading = -1;
+    int64_t frameShadingAmbient = -1;
     uint32_t* dRayList = nullptr; /* counts | two ray lists (vrc_internal.h) */
     size_t dRayListCap = 0;       /* pixels */
     int lastErtParts = 0;         /* of the last vrc_render */
@@ -575,6 +581,16 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_MIP_DEPTH_CUE is the cue strength in thousandths, 0 (off) to 1000" );
         c->optMipDepthCue = value;
         return VRC_OK;
+    case VRC_OPT_SHADING:
+        if( value != 0 && value != 1 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_SHADING is 0 (off) or 1 (light every sample of a composite frame by its gradient)" );
+        c->optShading = value;
+        return VRC_OK;
+    case VRC_OPT_SHADING_AMBIENT:
+        if( value < 0 || value > 1000 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_SHADING_AMBIENT is the ambient share in thousandths, 0 to 1000" );
+        c->optShadingAmbient = value;
+        return VRC_OK;
     case VRC_OPT_ERT_COMPACTION:
         if( value < 0 || value > VRC_MAX_ERT_PARTS )
             return fail( VRC_EINVAL, "VRC_OPT_ERT_COMPACTION: 0 (off) or 2.." + std::to_string( VRC_MAX_ERT_PARTS ) +
@@ -622,6 +638,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_MIP_DEPTH: *value = c->optMipDepth; return VRC_OK;
     case VRC_OPT_MIP_DEPTH_CUE: *value = c->optMipDepthCue; return VRC_OK;
     case VRC_OPT_VARIANT: *value = c->optVariant; return VRC_OK;
+    case VRC_OPT_SHADING: *value = c->optShading; return VRC_OK;
+    case VRC_OPT_SHADING_AMBIENT: *value = c->optShadingAmbient; return VRC_OK;
     case VRC_OPT_KERNEL_USED: *value = c->stats.kernel_variant; return VRC_OK;
     case VRC_OPT_GRID_WALK_USED: *value = c->gridWalkUsed; return VRC_OK;
     default: return fail( VRC_EINVAL, "vrc_get_option: unknown option" );
@@ -1526,6 +1544,7 @@ int vrc_pre_render( vrc_ctx* c, const vrc_view_data* view )
     c->depthValid = false;
     c->frameIso = false;
     c->gradValid = false;
+    c->frameShading = c->frameShadingAmbient = -1;
     c->projState.pixels = 0u; /* vrc_get_projection_values: nothing to read until a MIP pass of this frame */
     return VRC_OK;
 }
@@ -1706,6 +1725,29 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                                          : "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_PROJECTION = MIP is defined on the "
                                            "cudaRaycaster variant's sample set" );
     }
+    /* a shaded composite frame (include/vrc_hip.h, "A shaded composite frame"): read by composite frames only; served by
+     * the gather marches of vrc_kernels_shade.hip and refused where those have no form */
+    const bool shade = !mip && c->optShading != 0;
+    if( !mip )
+    {
+        if( c->frameShading >= 0 && c->frameShading != c->optShading )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_SHADING changed between vrc_pre_render and vrc_post_render; the "
+                                     "passes of one frame are all shaded or none is" );
+        if( c->frameShadingAmbient >= 0 && c->frameShadingAmbient != c->optShadingAmbient )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_SHADING_AMBIENT changed between vrc_pre_render and vrc_post_render; "
+                                     "the passes of one frame take one ambient share" );
+    }
+    if( shade )
+    {
+        if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no shaded form; VRC_OPT_SHADING = 1 is "
+                                     "marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
+        if( c->rayLod )
+            return fail( VRC_EINVAL, "vrc_render: vrc_set_ray_lod is on; VRC_OPT_SHADING = 1 renders a per-brick cut" );
+        if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_SHADING = 1 is defined on the "
+                                     "cudaRaycaster variant's sample set" );
+    }
     const bool linear = c->optFilter == VRC_FILTER_TRILINEAR;
     /* samples classified one by one (padded transfer function in the table buffer) whenever the
      * 257-entry classified table cannot be used: continuous or 16-bit densities */
@@ -1853,7 +1895,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * positions and its classifier need -- 8- or 16-bit bricks with overlap >= 1 in slots of at most 248 voxels a side,
      * VRC_OPT_TF_FRAC_BITS = 8, fixed-point stepping -- and 2.25 times the atlas in device memory; either brick
      * enumeration (grid walk where the node set is grid-aligned, else the reference-order loop) */
-    const bool packedEligible = linear && !glSuper && !mip && !c->cachedClamp && slotsFit8Bits &&
+    const bool packedEligible = linear && !glSuper && !mip && !shade && !c->cachedClamp && slotsFit8Bits &&
                                 pool_packed_possible( pool ) && c->optTfFracBits == 8 && c->optStepping != 0;
     bool usePacked = false;
     if( c->optKernel == VRC_KERNEL_PACKED )
@@ -1870,11 +1912,12 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
          * it the frame takes the staged form below */
         usePacked = pool_enable_packed( pool );
     const bool useLds = c->rayLod ? ( ldsLodEligible && c->optKernel != VRC_KERNEL_GRID_DDA && !usePacked )
-                                  : !glSuper && !usePacked && !mip && ( c->optKernel == VRC_KERNEL_LDS ||
+                                  : !glSuper && !usePacked && !mip && !shade && ( c->optKernel == VRC_KERNEL_LDS ||
                                                   ( c->optKernel == VRC_KERNEL_AUTO && linear && ldsEligible ) );
 
     vrc_raycast_args a;
     std::memset( &a, 0, sizeof( a ) );
+    a.shade = shade;
     vrc_frame& f = a.frame;
     {
         vrc_atlas_geom geom;
@@ -2058,6 +2101,12 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         c->projState.shift = pool->rangeShift;
     }
     c->frameProjection = c->optProjection;
+    if( !mip )
+    {
+        c->frameShading = c->optShading;
+        c->frameShadingAmbient = c->optShadingAmbient;
+    }
+    f.shadeAmbient = shade ? (float)c->optShadingAmbient / 1000.0f : 0.0f;
 
     a.nodes = c->dNodes;
     a.gridTable = ( useDda || c->rayLod ) ? c->dGrid : nullptr;
@@ -2081,7 +2130,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * restart sample per brick).  (ii) The frame starts from zero (first pass: the clear is folded in).
      * (iii) the table-driven point-sampling walk kernel. */
     a.depthSplit = false;
-    if( c->optDepthSplit && !mip && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 && !pool->bigAtlas &&
+    if( c->optDepthSplit && !mip && !shade && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 && !pool->bigAtlas &&
         !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && f.clearFirst )
     {
         const double nMax = 1.7320508 * (double)render->samplesPerRay +
@@ -2097,7 +2146,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     a.ertParts = 0;
     a.rayList = nullptr;
     /* (the same predicate as the launcher's, vrc_launch_raycast: what vrc_get_ray_counts reports is what ran) */
-    if( c->optErtParts > 1 && !mip && !a.depthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 &&
+    if( c->optErtParts > 1 && !mip && !shade && !a.depthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 &&
         !pool->bigAtlas && !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && c->fbW < 65536u && c->fbH < 65536u &&
         VRC_TILE_W == 8u )
     {
@@ -2345,6 +2394,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                    : mip       ? ( c->optMipFold == VRC_MIP_FOLD_MIN    ? vrc_launch_raycast_minip( a, c->stream )
                                    : c->optMipFold == VRC_MIP_FOLD_MEAN ? vrc_launch_raycast_meanip( a, c->stream )
                                                                         : vrc_launch_raycast_mip( a, c->stream ) )
+                   : shade     ? vrc_launch_raycast_shade( a, c->stream )
                    : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
                    : c->rayLod ? vrc_launch_raycast_raylod( a, c->stream )
                    : c->walkCacheUsed == 4 ? vrc_launch_raycast_replay( a, c->stream )

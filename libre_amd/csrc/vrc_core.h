@@ -248,6 +248,9 @@ struct vrc_frame
      * (vrc_render); a frame that leaves them 0 records and replays the other form */
     uint32_t walkLean;
     uint32_t walkSlots;
+    /* a shaded composite frame (VRC_OPT_SHADING, the vrc_k_raycast_shade instances; at the end: no field above moves):
+     * the ambient share of the headlight in [0, 1] (VRC_OPT_SHADING_AMBIENT / 1000).  No other kernel reads it */
+    float shadeAmbient;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -3008,6 +3011,27 @@ VRC_HD void vrc_slot_local_voxel( uint32_t e, uint32_t sbx, uint32_t sby, uint32
     z = ( bz << VRC_MB_SHIFT ) | ( ( in >> 5 ) & 3u ) | ( ( in >> 6 ) & 4u );
 }
 
+/* The addressing and the difference of a gradient, shared by the gradient of an isosurface hit (below) and the gradient of
+ * every sample of a shaded composite frame (vrc_shade_group): a voxel coordinate clamped to the slot, its two neighbours
+ * along an axis clamped the same way, and the difference of the two stored voxels.  Whatever coordinate goes into
+ * vrc_gradient_clamp, what comes out lies in [0, dim), and so do the two neighbours of such a coordinate: a gather at
+ * them stays inside the slot. */
+VRC_HD uint32_t vrc_gradient_clamp( uint32_t c, uint32_t dim ) { return c < dim ? c : dim - 1u; }
+VRC_HD void vrc_gradient_neighbours( uint32_t c, uint32_t dim, uint32_t& lo, uint32_t& hi )
+{
+    lo = c > 0u ? c - 1u : 0u;
+    hi = c + 1u < dim ? c + 1u : dim - 1u;
+}
+template < typename ATLAS_T >
+VRC_HD float vrc_gradient_diff( ATLAS_T vHi, ATLAS_T vLo )
+{
+    VRC_STRICT_FP
+    if constexpr( sizeof( ATLAS_T ) == 4 )
+        return (float)vHi - (float)vLo;
+    else
+        return (float)( (int32_t)vHi - (int32_t)vLo );
+}
+
 /* The gradient of a hit: central differences of stored voxels around slot-local element `where` of node n, indices
  * clamped to the slot, times the node's voxels per world unit -- six gathers, once per ray and pass.  Integer voxels
  * are differenced in integers (exact; an offset-binary shift cancels), float voxels in float. */
@@ -3028,21 +3052,15 @@ VRC_HD void vrc_iso_gradient( const vrc_frame& f, const vrc_dev_node& n, const A
     }
 #pragma unroll
     for( int a = 0; a < 3; ++a ) /* (a coordinate read back from a sample's own address lies inside the slot) */
-        c[a] = c[a] < f.slotDim[a] ? c[a] : f.slotDim[a] - 1u;
+        c[a] = vrc_gradient_clamp( c[a], f.slotDim[a] );
 #pragma unroll
     for( int a = 0; a < 3; ++a )
     {
         uint32_t lo[3] = { c[0], c[1], c[2] }, hi[3] = { c[0], c[1], c[2] };
-        lo[a] = c[a] > 0u ? c[a] - 1u : 0u;
-        hi[a] = c[a] + 1u < f.slotDim[a] ? c[a] + 1u : f.slotDim[a] - 1u;
+        vrc_gradient_neighbours( c[a], f.slotDim[a], lo[a], hi[a] );
         const ATLAS_T vHi = vrc_gather( slot, base + vrc_slot_local_index( hi[0], hi[1], hi[2], sbx, sby ) );
         const ATLAS_T vLo = vrc_gather( slot, base + vrc_slot_local_index( lo[0], lo[1], lo[2], sbx, sby ) );
-        float diff;
-        if constexpr( sizeof( ATLAS_T ) == 4 )
-            diff = (float)vHi - (float)vLo;
-        else
-            diff = (float)( (int32_t)vHi - (int32_t)vLo );
-        g[a] = diff * n.voxPerWorld[a];
+        g[a] = vrc_gradient_diff< ATLAS_T >( vHi, vLo ) * n.voxPerWorld[a];
     }
 }
 
@@ -3212,6 +3230,357 @@ VRC_HD vrc_f4 vrc_classify_mip( const vrc_f4* tfp, float d, const vrc_classifier
     e.z = VRC_LERP2( b, t0.z, a, t1.z ) * alpha;
     e.w = alpha;
     return e;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * EXTENSION: a shaded composite frame (VRC_OPT_SHADING = 1; include/vrc_hip.h, "A shaded composite frame").
+ *
+ * The composite frame with one change: the colour a sample adds is multiplied by the headlight term of the isosurface
+ * frame, s = ambient + (1 - ambient) |G.dir| / |G| (vrc_iso_shade), G the central differences of the stored voxels around
+ * the voxel the POINT sampler addresses at the sample's position (under both filters; vrc_gradient_* above: the
+ * isosurface gradient's clamping and differencing), times the node's voxels per world unit.  The opacity is not
+ * touched, so the samples, their order, early ray termination and the alpha channel are the unshaded frame's; with
+ * ambient = 1, and wherever G is 0, so is the whole pixel.
+ *
+ * Sample positions, addresses, gathers and classification are those of the unshaded march of the same sampler,
+ * expression for expression (vrc_group_indices_fixed, vrc_group_indices, vrc_march_segment_linear), in the control
+ * structure of vrc_march_segment_as: whole groups while more than a group of steps remains, the early-exit test once per
+ * group with the exact replay, a masked tail.  Per group: centre addresses and gathers, classification, a ballot of
+ * alpha' > 0, the six neighbour gathers of every sample that has one -- skipped by the lanes whose sample is transparent
+ * (its e is 0 whatever s is) and by the wave when no lane needs them --, the differences, s, the blends.  A neighbour's
+ * address is the centre's with one per-axis part swapped (the LDS tables under fixed-point stepping).
+ * Groups of VRC_SHADE_GROUP = 4: 24 neighbour voxels in flight beside four classified samples; 8 x 6 do not fit the
+ * registers of four waves per SIMD (DESIGN.md has the table of the instances).
+ * ---------------------------------------------------------------------------------------- */
+#define VRC_MODE_SHADE 10           /* point samples: the classified table for 8-bit voxels, vrc_classify otherwise */
+#define VRC_MODE_SHADE_TRILINEAR 11 /* trilinear samples by gathers */
+VRC_HD constexpr bool vrc_mode_is_shade( int mode ) { return mode == VRC_MODE_SHADE || mode == VRC_MODE_SHADE_TRILINEAR; }
+#define VRC_SHADE_GROUP 4
+#if defined( VRC_SHADE_SKIP_HOOK ) && !defined( __HIPCC__ )
+/* host test builds only (tests/cpu_harness/shade_harness.cpp): 0 = gather the gradient of transparent samples too; and
+ * how many samples were taken with / without their gradient */
+static int vrc_shade_skip_hook = 1;
+static unsigned long long vrc_shade_gradients[2];
+#endif
+
+/* per-axis parts of a slot-local element offset (vrc_voxel_address = x part + y part + z part + slotBase): the LDS
+ * tables where the kernel filled them (fixed-point stepping: coordinates below 256), the arithmetic form elsewhere */
+template < bool FIXED >
+VRC_HD uint32_t vrc_shade_part( const vrc_sampler& s, int axis, uint32_t u )
+{
+#if defined( __HIP_DEVICE_COMPILE__ )
+    if constexpr( FIXED )
+        return vrc_addr_tab[256u * (uint32_t)axis + ( u & 255u )];
+#endif
+    if( axis == 0 )
+        return vrc_mul24( u >> VRC_MB_SHIFT, 504u ) + u;
+    if( axis == 1 )
+        return vrc_mul24( u >> VRC_MB_SHIFT, s.cyy ) + ( u << 3 ) + VRC_MB_FIX_Y( u );
+    return vrc_mul24( u >> VRC_MB_SHIFT, s.czz ) + ( u << 6 ) - VRC_MB_FIX_Z( u );
+}
+
+/* N samples of a segment: e[k] = (rgb alpha' s, alpha') of sample k; MASKED: only the first cnt are the reference's, the
+ * others read element 0 and come out as zeros (an exact no-op in the blend) */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T, int N, bool MASKED >
+VRC_HD void vrc_shade_group( const vrc_frame& f, const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
+                             const ATLAS_T* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
+                             const vrc_f3& dir, uint32_t cnt, vrc_f4* e )
+{
+    typedef typename vrc_density< ATLAS_T >::type D;
+    static_assert( !( TRILINEAR && FIXED ), "the trilinear gather march steps in float" );
+    static_assert( !( CLAMP && FIXED ), "the clamped sampler steps in float" );
+    uint32_t ux[N], uy[N], uz[N]; /* the voxel the point sampler addresses */
+    /* 1. the sample itself: addresses, gathers, classification */
+    if constexpr( TRILINEAR )
+    {
+        vrc_taps t[N];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            VRC_FAST_FP
+            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
+            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
+            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
+            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
+            float qx = lx, qy = ly, qz = lz;
+            if( CLAMP )
+            {
+                qx = fminf( fmaxf( qx, 0.0f ), sm.hix );
+                qy = fminf( fmaxf( qy, 0.0f ), sm.hiy );
+                qz = fminf( fmaxf( qz, 0.0f ), sm.hiz );
+            }
+            ux[k] = (uint32_t)(int)qx;
+            uy[k] = (uint32_t)(int)qy;
+            uz[k] = (uint32_t)(int)qz;
+            pos.x += step.x;
+            pos.y += step.y;
+            pos.z += step.z;
+        }
+        float v[N][8];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+#pragma unroll
+            for( int c = 0; c < 8; ++c )
+            {
+                const uint32_t a = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
+                v[k][c] = (float)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? a : 0u );
+            }
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
+            const vrc_f4 c = vrc_classify( lut, vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz ), cls );
+            e[k] = ( !MASKED || (uint32_t)k < cnt ) ? c : z;
+        }
+    }
+    else
+    {
+        uint32_t idx[N];
+        if constexpr( FIXED )
+        {
+#pragma unroll
+            for( int k = 0; k < N; ++k )
+            {
+                ux[k] = fp.x >> 24;
+                uy[k] = fp.y >> 24;
+                uz[k] = fp.z >> 24;
+                fp.x += fp.dx;
+                fp.y += fp.dy;
+                fp.z += fp.dz;
+#if defined( __HIP_DEVICE_COMPILE__ )
+                asm( "" : "+v"( fp.x ), "+v"( fp.y ), "+v"( fp.z ) ); /* (vrc_group_indices_fixed: keep the three additions) */
+#endif
+            }
+#pragma unroll
+            for( int k = 0; k < N; ++k )
+            {
+#if defined( __HIP_DEVICE_COMPILE__ )
+                idx[k] = vrc_shade_part< true >( sm, 0, ux[k] ) + vrc_shade_part< true >( sm, 1, uy[k] ) +
+                         vrc_shade_part< true >( sm, 2, uz[k] ) + sm.slotBase;
+#else
+                idx[k] = vrc_voxel_address( sm, ux[k], uy[k], uz[k] );
+#endif
+            }
+        }
+        else
+        {
+            VRC_FAST_FP
+#pragma unroll
+            for( int k = 0; k < N; ++k )
+            {
+                float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
+                float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
+                float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
+                if( CLAMP )
+                {
+                    lx = fminf( fmaxf( lx, 0.0f ), sm.hix );
+                    ly = fminf( fmaxf( ly, 0.0f ), sm.hiy );
+                    lz = fminf( fmaxf( lz, 0.0f ), sm.hiz );
+                }
+                ux[k] = (uint32_t)(int)lx;
+                uy[k] = (uint32_t)(int)ly;
+                uz[k] = (uint32_t)(int)lz;
+                idx[k] = vrc_voxel_address( sm, ux[k], uy[k], uz[k] );
+                pos.x += step.x;
+                pos.y += step.y;
+                pos.z += step.z;
+            }
+        }
+        D d[N];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+            d[k] = (D)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? idx[k] : 0u );
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            if constexpr( PERSAMPLE )
+            {
+                const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
+                const vrc_f4 c = vrc_classify( lut, (float)d[k], cls );
+                e[k] = ( !MASKED || (uint32_t)k < cnt ) ? c : z;
+            }
+            else
+                e[k] = lut[( !MASKED || (uint32_t)k < cnt ) ? d[k] : 256u]; /* (entry 256: all zeros) */
+        }
+    }
+    /* 2. which samples need their gradient: a transparent one adds (0, 0) whatever s is */
+    bool need[N], any = false;
+#pragma unroll
+    for( int k = 0; k < N; ++k )
+    {
+        const bool taken = !MASKED || (uint32_t)k < cnt;
+        need[k] = taken && e[k].w > 0.0f;
+#if defined( VRC_SHADE_SKIP_HOOK ) && !defined( __HIPCC__ )
+        if( vrc_shade_skip_hook == 0 )
+            need[k] = taken;
+        if( taken )
+            ++vrc_shade_gradients[need[k] ? 1 : 0];
+#endif
+        any = any || need[k];
+    }
+#if defined( __HIP_DEVICE_COMPILE__ )
+    any = __builtin_amdgcn_ballot_w64( any ) != 0ull;
+#endif
+    if( !any )
+        return;
+    /* 3. the six neighbours, back to back.  Every coordinate goes through vrc_gradient_clamp and
+     * vrc_gradient_neighbours: all of them lie inside the slot, whatever the sampler made of the position */
+    ATLAS_T vLo[N][3], vHi[N][3];
+#pragma unroll
+    for( int k = 0; k < N; ++k )
+    {
+#pragma unroll
+        for( int a = 0; a < 3; ++a )
+            vLo[k][a] = vHi[k][a] = (ATLAS_T)0;
+        if( need[k] )
+        {
+            const uint32_t c[3] = { vrc_gradient_clamp( ux[k], f.slotDim[0] ), vrc_gradient_clamp( uy[k], f.slotDim[1] ),
+                                    vrc_gradient_clamp( uz[k], f.slotDim[2] ) };
+            const uint32_t part[3] = { vrc_shade_part< FIXED >( sm, 0, c[0] ), vrc_shade_part< FIXED >( sm, 1, c[1] ),
+                                       vrc_shade_part< FIXED >( sm, 2, c[2] ) };
+#pragma unroll
+            for( int a = 0; a < 3; ++a )
+            {
+                uint32_t lo, hi;
+                vrc_gradient_neighbours( c[a], f.slotDim[a], lo, hi );
+                const uint32_t rest = part[( a + 1 ) % 3] + part[( a + 2 ) % 3] + sm.slotBase;
+                vHi[k][a] = vrc_gather( atlas, vrc_shade_part< FIXED >( sm, a, hi ) + rest );
+                vLo[k][a] = vrc_gather( atlas, vrc_shade_part< FIXED >( sm, a, lo ) + rest );
+            }
+        }
+    }
+    /* 4. differences, s, the shaded colour */
+#pragma unroll
+    for( int k = 0; k < N; ++k )
+    {
+        VRC_STRICT_FP
+        if( need[k] )
+        {
+            const float g[3] = { vrc_gradient_diff< ATLAS_T >( vHi[k][0], vLo[k][0] ) * sm.kx,
+                                 vrc_gradient_diff< ATLAS_T >( vHi[k][1], vLo[k][1] ) * sm.ky,
+                                 vrc_gradient_diff< ATLAS_T >( vHi[k][2], vLo[k][2] ) * sm.kz };
+            const float sh = vrc_iso_shade( g, dir, f.shadeAmbient );
+            e[k].x = e[k].x * sh;
+            e[k].y = e[k].y * sh;
+            e[k].z = e[k].z * sh;
+        }
+    }
+}
+
+template < bool CLAMP, bool COUNT, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T, int GROUP >
+VRC_HD bool vrc_shade_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_segment s, const vrc_f3& dir,
+                               const ATLAS_T* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
+                               vrc_f4& color, uint32_t& nSamples )
+{
+    const float stepSize = f.stepSize;
+    const vrc_sampler sm = vrc_make_sampler( n, f );
+    float travel = s.dist;
+    vrc_f3 pos = s.pos;
+    bool done = false;
+    if( !( travel > 0.0f ) )
+        return false;
+    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
+    if( FIXED )
+        fp = vrc_fixpos_init( sm, pos, s.step );
+    /* whole groups: every sample is one the reference loop reaches (vrc_march_segment_as) */
+    const float guard = stepSize * (float)( GROUP + 1 );
+    while( travel > guard )
+    {
+        vrc_f4 e[GROUP];
+        vrc_shade_group< CLAMP, FIXED, TRILINEAR, PERSAMPLE, ATLAS_T, GROUP, false >( f, sm, pos, s.step, fp, atlas, lut, cls,
+                                                                                     dir, (uint32_t)GROUP, e );
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            travel -= stepSize; /* same sequential subtraction as the reference */
+        const vrc_f4 saved = color;
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            vrc_composite( color, e[k] );
+        if( COUNT )
+            nSamples += GROUP;
+        if( color.w > VRC_EARLY_EXIT )
+        {
+            /* crossed inside this group: replay it with the reference's per-sample exit */
+            color = saved;
+            if( COUNT )
+                nSamples -= GROUP;
+#pragma unroll
+            for( int k = 0; k < GROUP; ++k )
+            {
+                vrc_composite( color, e[k], done );
+                if( COUNT )
+                    nSamples += done ? 0u : 1u;
+                done = done || ( color.w > VRC_EARLY_EXIT );
+            }
+            return true;
+        }
+    }
+    constexpr int TAILG = GROUP >= 4 ? GROUP / 2 : 1;
+    while( travel > 0.0f && !done )
+    {
+        uint32_t cnt = 0;
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+        {
+            cnt += travel > 0.0f ? 1u : 0u;
+            travel -= stepSize;
+        }
+        vrc_f4 e[TAILG];
+        vrc_shade_group< CLAMP, FIXED, TRILINEAR, PERSAMPLE, ATLAS_T, TAILG, true >( f, sm, pos, s.step, fp, atlas, lut, cls, dir,
+                                                                                    cnt, e );
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+        {
+            const bool active = ( (uint32_t)k < cnt ) && !done;
+            vrc_composite( color, e[k], done );
+            if( COUNT )
+                nSamples += active ? 1u : 0u;
+            done = done || ( color.w > VRC_EARLY_EXIT );
+        }
+    }
+    return done;
+}
+
+/* One brick of one ray of a shaded frame: vrc_march_brick_from's decisions -- the slot's 64-bit base moved into the lane's
+ * pointer (BIG), the uniform march of a slot known to hold one value, taken by the whole wave or not at all (there G = 0
+ * and s = 1: the unshaded march itself) -- around the shaded segment.  dir: the ray's unit direction */
+template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, bool BIG, typename SRC >
+VRC_HD bool vrc_shade_brick( const vrc_frame& f, const vrc_dev_node& n, const SRC& src, const vrc_f3& dir,
+                             const ATLAS_T* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
+                             vrc_f4& color, uint32_t& nSamples )
+{
+    static_assert( vrc_mode_is_shade( MODE ), "a shaded mode" );
+    constexpr bool TRILINEAR = MODE == VRC_MODE_SHADE_TRILINEAR;
+    if constexpr( BIG )
+    {
+        vrc_dev_node local = n;
+        local.slotBase = 0u;
+        const ATLAS_T* slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
+        return vrc_shade_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, false, SRC >( f, local, src, dir, slot, lut, cls, color,
+                                                                                 nSamples );
+    }
+    else
+    {
+        if constexpr( !TRILINEAR && sizeof( ATLAS_T ) == 1 )
+        {
+            uint32_t word = 0u;
+            if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
+                word = f.slotInfo[n.slotInfoIndex - 1u];
+            bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
+#if defined( __HIP_DEVICE_COMPILE__ )
+            general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
+#endif
+            if( !general )
+            {
+                const vrc_segment& s = src.distOnly();
+                return vrc_march_segment_as< CLAMP, COUNT, FIXED, ATLAS_T, VRC_GROUP, vrc_f4, false, true >(
+                    f, n, s, atlas, lut, color, nSamples, 0.0f, nullptr, lut[word & 0xFFu] );
+            }
+        }
+        const vrc_segment& s = src.full();
+        return vrc_shade_segment< CLAMP, COUNT, FIXED, TRILINEAR, TRILINEAR || sizeof( ATLAS_T ) != 1, ATLAS_T, VRC_SHADE_GROUP >(
+            f, n, s, dir, atlas, lut, cls, color, nSamples );
+    }
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -3501,12 +3870,13 @@ VRC_HD void vrc_pixel_reference_order( const vrc_frame& f, const vrc_dev_node* _
                                        uint32_t& nSamples, const uint16_t* candidates = nullptr,
                                        uint32_t nCandidates = 0 )
 {
-    if( f.variant == VRC_VARIANT_GL && f.samplesPerPixel > 1u )
-    {
-        vrc_pixel_gl_supersampled< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, nodes, atlas, lut, cls, pixelBuffer,
-                                                                                   px, py, nSamples, candidates, nCandidates );
-        return;
-    }
+    if constexpr( !vrc_mode_is_shade( MODE ) ) /* (a shaded frame is defined on the cudaRaycaster variant's sample set) */
+        if( f.variant == VRC_VARIANT_GL && f.samplesPerPixel > 1u )
+        {
+            vrc_pixel_gl_supersampled< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, nodes, atlas, lut, cls, pixelBuffer,
+                                                                                       px, py, nSamples, candidates, nCandidates );
+            return;
+        }
     const vrc_ray r = vrc_setup_ray( f, px, f.rowMap ? f.rowMap[py] : py );
     const uint32_t pixelPos = py * f.width + px;
     const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
@@ -3533,7 +3903,14 @@ VRC_HD void vrc_pixel_reference_order( const vrc_frame& f, const vrc_dev_node* _
                 break;
             continue;
         }
-        if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, lut, cls, color,
+        if constexpr( vrc_mode_is_shade( MODE ) )
+        {
+            const vrc_segment_ready src = { s };
+            if( vrc_shade_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_ready >( f, n, src, r.dir, atlas, lut, cls,
+                                                                                              color, nSamples ) )
+                break;
+        }
+        else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, lut, cls, color,
                                                                      nSamples ) )
             break;
     }
@@ -3715,6 +4092,13 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                     vrc_segment_complete( r, iv, f.stepSize, &s );
                     if( vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, color, nSamples, (uint32_t)node ) ) /* (color: the ray's MIP state) */
                         finished = true; /* (an isosurface frame: every brick from here on lies behind the ray's hit) */
+                }
+                else if constexpr( vrc_mode_is_shade( MODE ) )
+                {
+                    const vrc_segment_from_interval src = { r, iv, f.stepSize };
+                    if( vrc_shade_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_from_interval >(
+                            f, n, src, r.dir, atlas, lut, cls, color, nSamples ) )
+                        finished = true;
                 }
                 else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, r, iv, atlas, lut, cls, color,
                                                                                        nSamples ) )

@@ -155,6 +155,7 @@ struct vrc_raycast_args
      * records the event behind the sequence */
     hipEvent_t stopEvent;
     bool* attached;
+    bool shade; /* a shaded composite frame (VRC_OPT_SHADING = 1; frame.shadeAmbient set): vrc_launch_raycast_shade marches it */
 };
 
 /* the one dispatch of a single-launch march: with a's stop event if it has one (the dispatch then carries its own
@@ -204,7 +205,7 @@ hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream );
 static inline bool vrc_walk_replay_eligible( const vrc_raycast_args& a )
 {
     return a.gridDda && a.gridTable && !a.packed && !a.linear && a.elemBytes == 1 && !a.bigAtlas && !a.clamp &&
-           a.fixedStepping && a.ertParts <= 1 && !a.depthSplit && VRC_TILE_W == 8u;
+           a.fixedStepping && a.ertParts <= 1 && !a.depthSplit && !a.shade && VRC_TILE_W == 8u;
 }
 static inline int vrc_walk_replay_group( const vrc_raycast_args& a )
 {
@@ -261,6 +262,11 @@ hipError_t vrc_launch_projection_depths( const vrc_frame& f, const float* depth,
 /* an isosurface frame (vrc_kernels_iso.hip; VRC_OPT_PROJECTION = VRC_PROJECTION_ISO): the first-crossing fold of the MIP
  * kernel; frame.mipMax, frame.mipDepth and frame.isoGrad set, frame.slotMax = NULL: every sample is taken */
 hipError_t vrc_launch_raycast_iso( const vrc_raycast_args& a, hipStream_t stream );
+
+/* a shaded composite frame (vrc_kernels_shade.hip; VRC_OPT_SHADING = 1): a.shade and frame.shadeAmbient set; the
+ * reference-order loop or the grid walk (a.gridDda), point or trilinear (a.linear) samples by gathers, every atlas type;
+ * lut = the classified table (8-bit point samples) or the padded transfer function, as vrc_launch_raycast takes it */
+hipError_t vrc_launch_raycast_shade( const vrc_raycast_args& a, hipStream_t stream );
 
 /* LDS-staged form (vrc_kernels_lds.hip): needs gridTable, !clamp, 8x8 tiles */
 hipError_t vrc_launch_raycast_lds( const vrc_raycast_args& a, hipStream_t stream );

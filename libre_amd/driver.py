@@ -8,6 +8,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LIVRE_HIP_HOST_LIB: another build of the same library (the sanitizer run of the host tests)
 LIB_PATH = os.environ.get("LIVRE_HIP_HOST_LIB") or os.path.join(_HERE, "lib", "libLivreHipRaycastPipeline.so")
+# include/vrc_hip.h, "A shaded composite frame": the two options App.set_shading sets (libre_amd/vrc.py has them all)
+OPT_SHADING, OPT_SHADING_AMBIENT = 29, 30
 
 
 class Params(C.Structure):  # lvh_params
@@ -161,6 +163,12 @@ class App:
         """The isosurface of frames rendered under VRC_OPT_PROJECTION = PROJECTION_ISO: the isovalue in the volume's own
         units and the ambient share of the shading in [0, 1]; reaches every renderer slot."""
         check(self.L, self.L.lvh_app_set_isosurface(self.h, float(iso_value), float(ambient)))
+
+    def set_shading(self, on, ambient=0.25):
+        """A shaded composite frame (VRC_OPT_SHADING, VRC_OPT_SHADING_AMBIENT): every sample's colour lit by the volume's
+        gradient, with the ambient share in [0, 1] (kept in thousandths); reaches every renderer slot."""
+        self.set_option(OPT_SHADING_AMBIENT, int(round(float(ambient) * 1000.0)))
+        self.set_option(OPT_SHADING, 1 if on else 0)
 
     def get_option(self, option):
         v = C.c_int64()
