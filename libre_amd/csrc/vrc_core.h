@@ -4437,8 +4437,13 @@ VRC_HD void vrc_pixel_walk_replay( const vrc_frame& f, const vrc_dev_node* __res
  * again.  The slot word's address comes from the list, so the node is not fetched in front of the ballot, and a
  * uniform visit marches the n of its word: no node, no dist, no vrc_exact_step_count, no second ballot (every visit of
  * a lean list counts exactly, so the wave would always have taken the counted form).  A visit that gathers fetches its
- * node, interval and ray as the other form does and runs the same march on the same segment.  In flight before the
- * march of visit k: the list word of visit k + 2 and the slot word of visit k + 1.  The index is clamped by walkSlots
+ * node, interval and ray inside its own branch (no prediction from the visit before) and runs the same march on the
+ * same segment.  In flight across the march of visit k: the list word of visit k + 2 and the slot word of visit k + 1.
+ * Neither load stands under a branch -- the list word comes from visit min(k + 2, walkK - 1) (vrc_lean_list_word), the
+ * slot word through a pointer that is always valid (vrc_lean_slot_load) -- because a load that a path may skip leaves
+ * the compiler one safe wait for the values of the visit before, vmcnt(0), right behind the loads just issued.  As
+ * compiled for gfx950 the loop waits at its top for the two loads of the visit before, issues the two new ones, and
+ * meets no vector-memory wait before its latch.  The index is clamped by walkSlots
  * as the node is by the table, so no list content reaches past slotInfo.  The colour stays in the march's own form
  * (two floats under a grey table) across the visits and is widened once, at the store: what every march of the
  * other form does on its way out */
@@ -4449,19 +4454,35 @@ VRC_HD vrc_f4 vrc_lean_narrow( const vrc_f4& c, const vrc_f4* ) { return c; }
 VRC_HD vrc_f4 vrc_lean_widen( const vrc_f2& c ) { return vrc_f4{ c.x, c.x, c.x, c.w }; }
 VRC_HD vrc_f4 vrc_lean_widen( const vrc_f4& c ) { return c; }
 /* the slot word of a list word, in two steps so that the load can be issued a visit ahead and nothing waits for it
- * before the visit that reads it: the load (always from a word of slotInfo: index clamped), and the rule */
+ * before the visit that reads it: the load and the rule.  The load is unconditional, so that no branch stands between
+ * it and the march it is to overlap: it reads through a pointer that is always valid -- a word of slotInfo (index
+ * clamped by walkSlots; a lean frame has walkSlots >= 1) or, for a frame without slotInfo (VRC_OPT_UNIFORM_BRICKS = 0
+ * over lean lists), word 0 of the lists themselves -- and the rule selects: 0 without slotInfo or without an index */
 VRC_HD uint32_t vrc_lean_slot_load( const vrc_frame& f, uint32_t packed )
 {
     const uint32_t idx = packed & ( ( 1u << VRC_WALK_LEAN_INDEX_BITS ) - 1u );
-    if( f.slotInfo == nullptr )
-        return 0u;
-    const uint32_t last = f.walkSlots - 1u; /* (a lean frame: walkSlots >= 1) */
+    const bool have = f.slotInfo != nullptr;
+    const uint32_t* const from = have ? f.slotInfo : f.walkCache;
+    const uint32_t last = have ? f.walkSlots - 1u : 0u;
     const uint32_t i = idx != 0u ? idx - 1u : 0u;
-    return f.slotInfo[i < last ? i : last];
+    return from[i < last ? i : last];
 }
-VRC_HD uint32_t vrc_lean_slot_word( uint32_t packed, uint32_t loaded )
+VRC_HD uint32_t vrc_lean_slot_word( const vrc_frame& f, uint32_t packed, uint32_t loaded )
 {
-    return ( packed & ( ( 1u << VRC_WALK_LEAN_INDEX_BITS ) - 1u ) ) != 0u ? loaded : 0u;
+    return ( f.slotInfo != nullptr && ( packed & ( ( 1u << VRC_WALK_LEAN_INDEX_BITS ) - 1u ) ) != 0u ) ? loaded : 0u;
+}
+/* The list word (second plane) of visit v of a ray, v clamped to the last visit the planes hold.  The invariant the
+ * unconditional reads rest on: the planes hold walkK >= 1 visits for EVERY ray of EVERY whole tile -- (1 + 4 walkK) x
+ * walkPlane words, walkPlane = tiles x 64, rayIndex < walkPlane (vrc_render sizes them so; vrc_k_walk_record writes
+ * plane 0 of every lane of a tile, those outside the frame included) -- so visit min(v, walkK - 1) of any ray index
+ * below walkPlane is an allocated word, whatever the ray's count says.  A word read past the ray's count may hold
+ * anything: it is never marched (the loop ends at count), and as a slot index it is clamped like any other.  v is the
+ * same in every lane of a wave, so the clamp is scalar work */
+VRC_HD uint32_t vrc_lean_list_word( const vrc_frame& f, uint32_t rayIndex, uint32_t v )
+{
+    const uint32_t lastVisit = f.walkK - 1u;
+    const size_t plane = 2u + 4u * (size_t)( v < lastVisit ? v : lastVisit );
+    return f.walkCache[(size_t)rayIndex + plane * f.walkPlane];
 }
 
 template < bool COUNT, int MODE, int GROUP >
@@ -4475,10 +4496,8 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
     const E* const tab = reinterpret_cast< const E* >( lut );
     const uint32_t pixelPos = py * f.width + px;
     const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
-    const size_t P = f.walkPlane;
-    const uint32_t* const wc = f.walkCache;
-    uint32_t count = wc[rayIndex];
-    count = count < f.walkK ? count : f.walkK;
+    const uint32_t listed = f.walkCache[rayIndex];
+    const uint32_t count = listed < f.walkK ? listed : f.walkK;
     if( count == 0u )
     {
         if( f.clearFirst )
@@ -4490,27 +4509,17 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
         return;
     E color = vrc_lean_narrow( start, (const E*)nullptr );
     const uint32_t lastNode = f.nodeCount - 1u;
-    /* pre: the word of visit k + 2 (its second plane); the visit's own first plane lies 9 planes in front of it */
-    size_t pre = (size_t)rayIndex + 2u * P;
-    uint32_t packed = wc[pre];
-    uint32_t packedNext = count > 1u ? wc[pre + 4u * P] : 0u;
-    pre += 8u * P;
+    /* the words of the first two visits: unconditional like the loop's (a list of one visit reads its word twice) */
+    uint32_t packed = vrc_lean_list_word( f, rayIndex, 0u );
+    uint32_t packedNext = vrc_lean_list_word( f, rayIndex, 1u );
     uint32_t loaded = vrc_lean_slot_load( f, packed );
-    bool gathered = false; /* did the visit before take the gather march?  (the whole wave takes it or none of it) */
     for( uint32_t k = 0u; k < count; ++k )
     {
-        /* (the slot word first: its address is a list word that arrived a visit ago) */
+        /* the two prefetches, neither under a branch (the slot word first: its address is a list word that arrived a
+         * visit ago) */
         const uint32_t loadedNext = vrc_lean_slot_load( f, packedNext );
-        uint32_t packedAfter = 0u;
-        if( k + 2u < count )
-            packedAfter = wc[pre];
-        const uint32_t* const at = wc + ( pre - 9u * P );
-        vrc_walk_early early; /* (only `have` is set where nothing was loaded: the rest is then not read) */
-        early.have = false;
-        if( gathered )
-            early = vrc_walk_load_early( f, rayIndex, at );
-        gathered = false;
-        const uint32_t word = vrc_lean_slot_word( packed, loaded );
+        const uint32_t packedAfter = vrc_lean_list_word( f, rayIndex, k + 2u );
+        const uint32_t word = vrc_lean_slot_word( f, packed, loaded );
         bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
 #if defined( __HIP_DEVICE_COMPILE__ )
         general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
@@ -4520,15 +4529,19 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
             done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], packed >> VRC_WALK_LEAN_INDEX_BITS, nSamples );
         else
         {
+            /* the gather visit's own loads, all inside its branch: the interval and the ray's direction are asked for
+             * in front of the node, so the five of them travel while the node index and the node arrive */
+            const uint32_t* const at = f.walkCache + ( (size_t)rayIndex + ( 1u + 4u * (size_t)k ) * f.walkPlane );
+            const vrc_walk_early early = vrc_walk_load_early( f, rayIndex, at );
             const uint32_t node = at[0];
             const vrc_dev_node n = nodes[node < lastNode ? node : lastNode];
+            bool gathered = false;
             const vrc_segment_from_walk src = { f, rayIndex, at, 0.0f, early, &gathered };
             done = vrc_march_segment_as< false, COUNT, true, uint8_t, GROUP, E >( f, n, src.full(), atlas, tab, color,
                                                                                   nSamples, 0.0f );
         }
         if( done )
             break;
-        pre += 4u * P;
         packed = packedNext;
         packedNext = packedAfter;
         loaded = loadedNext;

@@ -6,7 +6,8 @@ Forms of the uniform march against each other (the product carries no switch for
 tools/build_variants.sh NAME "-DVRC_UNIFORM_GROUP=8", or an older commit's library):
        python tools/uniform_ab.py --libs parent=variants/libvrc_hip_parent.so new=libre_amd/lib/libvrc_hip.so ...
 renders the frame with every library, option on (compared bit for bit with the first one's, counts included), and
-times them in alternating rounds in this one process.
+times them in alternating rounds in this one process; --walk-always sets VRC_OPT_WALK_CACHE = 2 in each of them, so
+that a hash:// view is replayed (the gather path of the replay) instead of walked.
 VRC_OPT_STREAM_MARKERS (what vrc_render puts on the stream besides the march) in one process:
        python tools/uniform_ab.py --markers [--steps 2000] [--rounds 3]
 renders the frame with the option at 1 and at 0 (compared bit for bit), then in alternating rounds runs --steps frames
@@ -72,6 +73,8 @@ def several(a):
         L = vrc.load_library(os.path.abspath(path))
         names.append(name)
         scenes[name] = GpuScene(s, lib=L)
+        if a.walk_always:  # replay whatever the bricks hold: the gather path of the replay on hash://
+            vrc.check(L, L.vrc_set_option(scenes[name].ctx, vrc.OPT_WALK_CACHE, vrc.WALK_CACHE_ALWAYS))
     first = None
     for name in names:
         fb, n = scenes[name].render(count=True)[:2]
@@ -172,6 +175,8 @@ def main():
     ap.add_argument("--spin", type=float, nargs=2, default=(0.0, 0.0))
     ap.add_argument("--spr", type=int, default=0, help="samples per ray (0 = the automatic value)")
     ap.add_argument("--libs", nargs="+", default=None, metavar="NAME=PATH")
+    ap.add_argument("--walk-always", action="store_true",
+                    help="with --libs: VRC_OPT_WALK_CACHE = 2 in every context (a view that gathers is replayed too)")
     ap.add_argument("--markers", action="store_true", help="A/B of VRC_OPT_STREAM_MARKERS instead (see above)")
     ap.add_argument("--ray-cache", action="store_true", help="A/B of VRC_OPT_RAY_CACHE instead (see above)")
     ap.add_argument("--walk-cache", action="store_true", help="A/B of VRC_OPT_WALK_CACHE instead (see above)")
