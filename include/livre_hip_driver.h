@@ -118,12 +118,14 @@ int lvh_app_frame_histogram( lvh_app* app, uint64_t* bins, uint32_t capacity, ui
                              float* area, uint64_t* frame_id );
 /* Pick in a MIP frame rendered with depth tracking (VRC_OPT_MIP_DEPTH = 1 or VRC_OPT_MIP_DEPTH_CUE > 0; maximum or
  * minimum) or in an isosurface frame (VRC_PROJECTION_ISO, which always tracks depth: *hit = 1 where the ray reached
- * the isovalue, *value = V of the first sample that did, *t = its D, xyz = the surface point):
+ * the isovalue, *value = V of the first sample that did, *t = its D, xyz = the surface point) or in a composite frame
+ * rendered with VRC_OPT_COMPOSITE_DEPTH above 0 (lvh_app_set_option; *hit = 1 where the ray's opacity reached the
+ * threshold, *value = V of the sample at which it did, *t = its D, xyz = that point):
  * what lies behind pixel (x, y) of the window in the selected slot's last frame.  *hit = 1 if the pixel's ray
  * took a sample, *value = the projected value M in the volume's own units, *t = the ray parameter D of the nearest sample
  * that equals M, xyz = its position origin + D * dir (vrc_get_projection_values / vrc_get_projection_depths of that
  * pixel; any of the four may be NULL; value, t and xyz are unspecified without a hit).  An error, with a message: no
- * frame yet; the frame was composite, a MIP frame without depth tracking, or the mean fold; (x, y) outside the window
+ * frame yet; the frame was composite without VRC_OPT_COMPOSITE_DEPTH, a MIP frame without depth tracking, or the mean fold; (x, y) outside the window
  * or the tile of this process; in band mode (lvh_app_set_bands), a row this process did not render.
  * Every call reads the whole frame's values, counts, depths and positions back (24 bytes a pixel, two small kernels, one
  * synchronisation) and returns one entry: meant for a click, not for a loop over the window -- a caller that wants many

@@ -267,6 +267,10 @@ typedef struct
                                     * MIP and isosurface frames ignore it */
 #define VRC_OPT_SHADING_AMBIENT 30  /* the ambient share of that light in thousandths, 0 ... 1000, default 250; anything
                                     * else: VRC_EINVAL.  ambient = (float)k / 1000.0f */
+#define VRC_OPT_COMPOSITE_DEPTH 31  /* 0 (default): a composite frame keeps no depth; 1 ... 999: the opacity threshold in
+                                    * thousandths at which every ray's depth is kept ("The depth of a composite frame"
+                                    * below).  Anything else: VRC_EINVAL.  Read only when VRC_OPT_PROJECTION =
+                                    * VRC_PROJECTION_COMPOSITE: MIP and isosurface frames ignore it */
 /* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
  * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
  * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots
@@ -432,6 +436,41 @@ typedef struct
  * forgotten, to be recorded again when that view returns).  VRC_EINVAL from vrc_render, naming the option: an explicit
  * VRC_KERNEL_LDS or _PACKED, vrc_set_ray_lod on, VRC_VARIANT_GLRAYCASTER, and either shading option changed between
  * vrc_pre_render and vrc_post_render.  Specular terms, movable lights and picking are not part of it. */
+
+/* The depth of a composite frame (VRC_OPT_PROJECTION = VRC_PROJECTION_COMPOSITE, VRC_OPT_COMPOSITE_DEPTH = k, 1 ... 999).
+ * The composite frame as it is, and beside it, per pixel, where the ray's accumulated opacity first reaches a threshold:
+ * what a click on the picture picks, and a depth image to combine the frame with.  tau = (float)k / 1000.0f, one rounded
+ * division; 999 gives exactly the early-exit threshold 0.999f, so a ray that terminates early has crossed.
+ *   Frame.  The frame and vrc_stats.samples are those of the same context, pool and options with the option at 0 marched
+ *     by gathers (VRC_KERNEL_REFERENCE_ORDER or _GRID_DDA; AUTO with point samples), bit for bit, all four channels.
+ *   Depth of a ray.  Take the samples in the order the march composites them (under the reference-order loop: list
+ *     order, which is no visibility order).  A_i is the float32 alpha the ray holds after compositing sample i.  The
+ *     crossing sample is the first with A_i >= tau.  D = t_j = tNear + (float)j * stepSize of that sample ("The depth of
+ *     a MIP frame", Depth of a sample, unchanged: the same formula for both steppings and both filters).  V is that
+ *     sample's value as vrc_get_projection_values reports a MIP sample: for a point sample the voxel in the volume's own
+ *     units, signed types un-shifted; for a trilinear sample the interpolated float.  A ray that never reaches tau has
+ *     D = +infinity and count 0; its pixel is what it would have been anyway.
+ *   Passes.  The context owns (D, V) per pixel of the pixel buffer, as it owns a MIP frame's running pair; vrc_pre_render
+ *     invalidates it and the frame's first pass does not read it.  A later pass sets the pair only of a pixel whose D is
+ *     still +infinity; its alpha comes in from the pixel buffer, as the composite's does.  After every pass of a frame
+ *     that started from a cleared buffer: isfinite(D) if and only if the pixel's alpha >= tau.  Changing the option
+ *     between vrc_pre_render and vrc_post_render: the next vrc_render returns VRC_EINVAL and names the option.
+ *   Read-backs, valid from the frame's first such pass until the next vrc_pre_render.  vrc_get_projection_values: V, and
+ *     count 1 where the ray crossed, 0 elsewhere.  vrc_get_projection_depths: D and origin + D * dir.  With the option at
+ *     0 both refuse a composite frame as they did.
+ *   VRC_OPT_UNIFORM_BRICKS.  A slot known to hold one value is marched from its table entry without fetching (point
+ *     samples of 8-bit voxels); D, V, the frame and the counts are bit-identical with the option on or off.
+ * Served: VRC_KERNEL_AUTO, _REFERENCE_ORDER and _GRID_DDA; all seven voxel types; both filters (trilinear by gathers: AUTO
+ * takes neither the LDS-staged form nor the tap-packed atlas); the clamped sampler; atlases of more than 2^32 voxels; row
+ * maps; caller-owned frame buffers; VRC_OPT_COUNT_SAMPLES; VRC_OPT_RAY_CACHE as before.  Silently the plain depth-tracking
+ * kernel: VRC_OPT_DEPTH_SPLIT, VRC_OPT_ERT_COMPACTION, VRC_OPT_GREY_TABLE (the four-float form, the same frame) and
+ * VRC_OPT_WALK_CACHE (exactly as a shaded frame: not replayed, VRC_OPT_WALK_CACHE_USED reads 0, nothing is allocated,
+ * recorded lists are forgotten).  VRC_EINVAL from vrc_render, naming the option: an explicit VRC_KERNEL_LDS or _PACKED,
+ * vrc_set_ray_lod on, VRC_VARIANT_GLRAYCASTER, and VRC_OPT_SHADING = 1 together with this option (alpha does not depend
+ * on shading: an application that picks in a shaded picture renders the unshaded frame once).  With the option at 0 every
+ * frame launches the kernel instances it launched before the option existed.  A depth cue on the composite, shading and
+ * depth in one frame, replay from the walk cache, the LDS, packed and per-ray-LOD forms, gradients at the crossing,
+ * several thresholds per frame and depth buffers coming in are not part of it. */
 
 #define VRC_VARIANT_CUDARAYCASTER 0 /* renderers/cudaRaycaster/cuda/Renderer.cu:95-230 */
 #define VRC_VARIANT_GLRAYCASTER 1   /* renderers/glRaycaster/shaders/fragRaycast.glsl:113-215: pixel centre

@@ -330,6 +330,10 @@ struct vrc_ctx
     int64_t optShadingAmbient = 250; /* VRC_OPT_SHADING_AMBIENT, thousandths */
     int64_t frameShading = -1;
     int64_t frameShadingAmbient = -1;
+    /* the depth of a composite frame (include/vrc_hip.h, "The depth of a composite frame"): the option, and what the
+     * frame's first composite vrc_render read of it (-1 = none yet).  The pair per pixel lives in dMipMax and dMipDepth */
+    int64_t optCompositeDepth = 0; /* VRC_OPT_COMPOSITE_DEPTH, thousandths */
+    int64_t frameCompositeDepth = -1;
     uint32_t* dRayList = nullptr; /* counts | two ray lists (vrc_internal.h) */
     size_t dRayListCap = 0;       /* pixels */
     int lastErtParts = 0;         /* of the last vrc_render */
@@ -591,6 +595,11 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_SHADING_AMBIENT is the ambient share in thousandths, 0 to 1000" );
         c->optShadingAmbient = value;
         return VRC_OK;
+    case VRC_OPT_COMPOSITE_DEPTH:
+        if( value < 0 || value > 999 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_COMPOSITE_DEPTH is 0 (off) or the opacity threshold in thousandths, 1 to 999" );
+        c->optCompositeDepth = value;
+        return VRC_OK;
     case VRC_OPT_ERT_COMPACTION:
         if( value < 0 || value > VRC_MAX_ERT_PARTS )
             return fail( VRC_EINVAL, "VRC_OPT_ERT_COMPACTION: 0 (off) or 2.." + std::to_string( VRC_MAX_ERT_PARTS ) +
@@ -640,6 +649,7 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_VARIANT: *value = c->optVariant; return VRC_OK;
     case VRC_OPT_SHADING: *value = c->optShading; return VRC_OK;
     case VRC_OPT_SHADING_AMBIENT: *value = c->optShadingAmbient; return VRC_OK;
+    case VRC_OPT_COMPOSITE_DEPTH: *value = c->optCompositeDepth; return VRC_OK;
     case VRC_OPT_KERNEL_USED: *value = c->stats.kernel_variant; return VRC_OK;
     case VRC_OPT_GRID_WALK_USED: *value = c->gridWalkUsed; return VRC_OK;
     default: return fail( VRC_EINVAL, "vrc_get_option: unknown option" );
@@ -1545,6 +1555,7 @@ int vrc_pre_render( vrc_ctx* c, const vrc_view_data* view )
     c->frameIso = false;
     c->gradValid = false;
     c->frameShading = c->frameShadingAmbient = -1;
+    c->frameCompositeDepth = -1;
     c->projState.pixels = 0u; /* vrc_get_projection_values: nothing to read until a MIP pass of this frame */
     return VRC_OK;
 }
@@ -1737,6 +1748,26 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             return fail( VRC_EINVAL, "vrc_render: VRC_OPT_SHADING_AMBIENT changed between vrc_pre_render and vrc_post_render; "
                                      "the passes of one frame take one ambient share" );
     }
+    /* the depth of a composite frame (include/vrc_hip.h, "The depth of a composite frame"): read by composite frames only;
+     * served by the gather marches of vrc_kernels_cdepth.hip and refused where those have no form */
+    const bool cdepth = !mip && c->optCompositeDepth != 0;
+    if( !mip && c->frameCompositeDepth >= 0 && c->frameCompositeDepth != c->optCompositeDepth )
+        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_COMPOSITE_DEPTH changed between vrc_pre_render and vrc_post_render; the "
+                                 "passes of one frame cross one threshold" );
+    if( cdepth )
+    {
+        if( shade )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_SHADING = 1 together with VRC_OPT_COMPOSITE_DEPTH; alpha does not "
+                                     "depend on shading: render the unshaded frame to pick in a shaded picture" );
+        if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no depth-tracking form; "
+                                     "VRC_OPT_COMPOSITE_DEPTH is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
+        if( c->rayLod )
+            return fail( VRC_EINVAL, "vrc_render: vrc_set_ray_lod is on; VRC_OPT_COMPOSITE_DEPTH tracks a per-brick cut" );
+        if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_COMPOSITE_DEPTH is defined on the "
+                                     "cudaRaycaster variant's sample set" );
+    }
     if( shade )
     {
         if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
@@ -1895,7 +1926,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * positions and its classifier need -- 8- or 16-bit bricks with overlap >= 1 in slots of at most 248 voxels a side,
      * VRC_OPT_TF_FRAC_BITS = 8, fixed-point stepping -- and 2.25 times the atlas in device memory; either brick
      * enumeration (grid walk where the node set is grid-aligned, else the reference-order loop) */
-    const bool packedEligible = linear && !glSuper && !mip && !shade && !c->cachedClamp && slotsFit8Bits &&
+    const bool packedEligible = linear && !glSuper && !mip && !shade && !cdepth && !c->cachedClamp && slotsFit8Bits &&
                                 pool_packed_possible( pool ) && c->optTfFracBits == 8 && c->optStepping != 0;
     bool usePacked = false;
     if( c->optKernel == VRC_KERNEL_PACKED )
@@ -1912,12 +1943,13 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
          * it the frame takes the staged form below */
         usePacked = pool_enable_packed( pool );
     const bool useLds = c->rayLod ? ( ldsLodEligible && c->optKernel != VRC_KERNEL_GRID_DDA && !usePacked )
-                                  : !glSuper && !usePacked && !mip && !shade && ( c->optKernel == VRC_KERNEL_LDS ||
+                                  : !glSuper && !usePacked && !mip && !shade && !cdepth && ( c->optKernel == VRC_KERNEL_LDS ||
                                                   ( c->optKernel == VRC_KERNEL_AUTO && linear && ldsEligible ) );
 
     vrc_raycast_args a;
     std::memset( &a, 0, sizeof( a ) );
     a.shade = shade;
+    a.cdepth = cdepth;
     vrc_frame& f = a.frame;
     {
         vrc_atlas_geom geom;
@@ -2100,7 +2132,54 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         c->projState.floatState = ( linear || pool->elemBytes == 4 ) ? 1u : 0u;
         c->projState.shift = pool->rangeShift;
     }
+    if( cdepth )
+    {
+        /* the pair per pixel of the pixel buffer in use, where a MIP frame's running maximum and depth are: grown,
+         * invalidated by vrc_pre_render (mipFirst) and not read by the frame's first pass as those are */
+        const size_t pixels = (size_t)c->fbW * c->fbH;
+        if( pixels > c->dMipMaxPixels )
+        {
+            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+            if( c->dMipMax ) VRC_HIP_CHECK( hipFree( c->dMipMax ) );
+            c->dMipMax = nullptr;
+            c->dMipMaxPixels = 0;
+            VRC_HIP_CHECK( hipMalloc( &c->dMipMax, pixels * sizeof( uint32_t ) ) );
+            c->dMipMaxPixels = pixels;
+            if( !c->mipFirst ) /* a later pass of a frame whose pixel buffer grew: no pixel has crossed as far as this knows */
+                VRC_HIP_CHECK( hipMemsetAsync( c->dMipMax, 0xFF, pixels * sizeof( uint32_t ), c->stream ) );
+        }
+        if( pixels > c->dMipDepthPixels )
+        {
+            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+            if( c->dMipDepth ) VRC_HIP_CHECK( hipFree( c->dMipDepth ) );
+            c->dMipDepth = nullptr;
+            c->dMipDepthPixels = 0;
+            VRC_HIP_CHECK( hipMalloc( &c->dMipDepth, pixels * sizeof( float ) ) );
+            c->dMipDepthPixels = pixels;
+            if( !c->mipFirst )
+                VRC_HIP_CHECK( hipMemsetD32Async( reinterpret_cast< hipDeviceptr_t >( c->dMipDepth ), 0x7F800000, pixels, c->stream ) );
+        }
+        f.mipMax = c->dMipMax;
+        f.mipDepth = c->dMipDepth;
+        f.mipFirst = c->mipFirst ? 1u : 0u;
+        c->mipFirst = false;
+        c->gradValid = false;
+        c->depthValid = true;
+        c->depthFrame = f;
+        c->depthRows = c->rowMap;
+        /* what this pass leaves for vrc_get_projection_values: V as a first-crossing frame leaves it */
+        c->projState.mipMax = c->dMipMax;
+        c->projState.meanSum = nullptr;
+        c->projState.meanCount = nullptr;
+        c->projState.pixels = (uint32_t)pixels;
+        c->projState.fold = (uint32_t)VRC_FOLD_FIRST;
+        c->projState.floatState = ( linear || pool->elemBytes == 4 ) ? 1u : 0u;
+        c->projState.shift = pool->rangeShift;
+    }
+    f.cdepthTau = cdepth ? (float)c->optCompositeDepth / 1000.0f : 0.0f;
     c->frameProjection = c->optProjection;
+    if( !mip )
+        c->frameCompositeDepth = c->optCompositeDepth;
     if( !mip )
     {
         c->frameShading = c->optShading;
@@ -2130,7 +2209,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * restart sample per brick).  (ii) The frame starts from zero (first pass: the clear is folded in).
      * (iii) the table-driven point-sampling walk kernel. */
     a.depthSplit = false;
-    if( c->optDepthSplit && !mip && !shade && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 && !pool->bigAtlas &&
+    if( c->optDepthSplit && !mip && !shade && !cdepth && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 && !pool->bigAtlas &&
         !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && f.clearFirst )
     {
         const double nMax = 1.7320508 * (double)render->samplesPerRay +
@@ -2146,7 +2225,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     a.ertParts = 0;
     a.rayList = nullptr;
     /* (the same predicate as the launcher's, vrc_launch_raycast: what vrc_get_ray_counts reports is what ran) */
-    if( c->optErtParts > 1 && !mip && !shade && !a.depthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 &&
+    if( c->optErtParts > 1 && !mip && !shade && !cdepth && !a.depthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 &&
         !pool->bigAtlas && !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && c->fbW < 65536u && c->fbH < 65536u &&
         VRC_TILE_W == 8u )
     {
@@ -2394,6 +2473,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                    : mip       ? ( c->optMipFold == VRC_MIP_FOLD_MIN    ? vrc_launch_raycast_minip( a, c->stream )
                                    : c->optMipFold == VRC_MIP_FOLD_MEAN ? vrc_launch_raycast_meanip( a, c->stream )
                                                                         : vrc_launch_raycast_mip( a, c->stream ) )
+                   : cdepth    ? vrc_launch_raycast_cdepth( a, c->stream )
                    : shade     ? vrc_launch_raycast_shade( a, c->stream )
                    : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
                    : c->rayLod ? vrc_launch_raycast_raylod( a, c->stream )

@@ -251,6 +251,11 @@ struct vrc_frame
     /* a shaded composite frame (VRC_OPT_SHADING, the vrc_k_raycast_shade instances; at the end: no field above moves):
      * the ambient share of the headlight in [0, 1] (VRC_OPT_SHADING_AMBIENT / 1000).  No other kernel reads it */
     float shadeAmbient;
+    /* the depth of a composite frame (VRC_OPT_COMPOSITE_DEPTH, the vrc_k_raycast_cdepth instances; at the end: no field
+     * above moves): the opacity threshold, (float)value / 1000.0f.  The passes of the frame meet in mipMax (the bits of V,
+     * VRC_MIP_EMPTY = not crossed) and mipDepth (D), owned, invalidated and not read by a first pass (mipFirst) as an
+     * isosurface frame's are.  No other kernel reads it */
+    float cdepthTau;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -3584,6 +3589,364 @@ VRC_HD bool vrc_shade_brick( const vrc_frame& f, const vrc_dev_node& n, const SR
 }
 
 /* ------------------------------------------------------------------------------------------
+ * EXTENSION: the depth of a composite frame (VRC_OPT_COMPOSITE_DEPTH; include/vrc_hip.h, "The depth of a composite
+ * frame").
+ *
+ * The composite frame, untouched, and beside it per ray the first sample -- in the order the march composites them --
+ * after which the ray's float32 alpha is >= tau: D = t_j = tNear + (float)j * stepSize of that sample
+ * (vrc_mip_sample_t), V its value as a MIP frame keeps a sample's (the stored voxel of an 8- or 16-bit atlas as an
+ * integer, the bits of the float voxel or of the interpolated float otherwise; vrc_projection_value reads it back).
+ *
+ * Sample positions, addresses, gathers and classification are those of the unshaded march of the same sampler,
+ * expression for expression (the first part of vrc_shade_group), in the control structure of vrc_shade_segment: whole
+ * groups, one test per group, the exact replay from the saved colour, a masked tail.  The test is the early exit's OR
+ * "alpha >= tau and the ray has not crossed": alpha never decreases, so a group after which alpha is below tau holds no
+ * crossing sample, and the group in which the test fires is replayed sample by sample -- once per ray for the crossing,
+ * once for the early exit, in one loop.  The replay of a group that did not end the ray composites the same samples in
+ * the same order with a weight that is never forced to 0: the colour it leaves is the group's, bit for bit, so frame
+ * and count are the unshaded frame's whatever tau is.  The densities of the group in flight are kept beside its
+ * classified samples (one register a sample) instead of fetching the crossing sample again.
+ * Groups of VRC_CDEPTH_GROUP = 8 point samples through the classified table, VRC_CDEPTH_GROUP_CLASSIFIED = 6 under the
+ * clamped sampler and for point samples classified one by one, and VRC_CDEPTH_GROUP_TRILINEAR = 4 trilinear ones: the largest at which no instance uses
+ * scratch (DESIGN.md has the table of the instances).
+ * ---------------------------------------------------------------------------------------- */
+#define VRC_MODE_CDEPTH 12           /* point samples: the classified table for 8-bit voxels, vrc_classify otherwise */
+#define VRC_MODE_CDEPTH_TRILINEAR 13 /* trilinear samples by gathers */
+VRC_HD constexpr bool vrc_mode_is_cdepth( int mode ) { return mode == VRC_MODE_CDEPTH || mode == VRC_MODE_CDEPTH_TRILINEAR; }
+#define VRC_CDEPTH_GROUP 8            /* point samples through the classified table (8-bit voxels) */
+#define VRC_CDEPTH_GROUP_CLASSIFIED 6 /* ... under the clamped sampler, and point samples classified one by one (16-bit
+                                       * and float voxels) */
+#define VRC_CDEPTH_GROUP_TRILINEAR 4
+
+/* what a ray keeps beside its colour: has it crossed (in this pass or, by the pixel's D, in one before), and the pair */
+struct vrc_cdepth_state
+{
+    float d;    /* +infinity until the ray crosses */
+    uint32_t v; /* VRC_MIP_EMPTY until then */
+    bool crossed;
+};
+VRC_HD uint32_t vrc_cdepth_bits( uint32_t v ) { return v; }
+VRC_HD uint32_t vrc_cdepth_bits( float v ) { return vrc_float_bits( v ); }
+
+/* after sample j of the segment was composited (not frozen): the crossing, once per ray */
+VRC_HD void vrc_cdepth_note( vrc_cdepth_state& z, const vrc_f4& color, float tau, float tNear, uint32_t j, float stepSize,
+                             uint32_t v )
+{
+    if( !z.crossed && color.w >= tau )
+    {
+        z.crossed = true;
+        z.d = vrc_mip_sample_t( tNear, j, stepSize );
+        z.v = v;
+    }
+}
+
+/* N samples of a segment: e[k] = (rgb alpha', alpha') of sample k and vb[k] its value; MASKED: only the first cnt are
+ * the reference's, the others read element 0 and come out as zeros (an exact no-op in the blend).  The first part of
+ * vrc_shade_group, and nothing of its gradient */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T, int N, bool MASKED >
+VRC_HD void vrc_cdepth_group( const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
+                              const ATLAS_T* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls, uint32_t cnt,
+                              vrc_f4* e, uint32_t* vb )
+{
+    typedef typename vrc_density< ATLAS_T >::type D;
+    static_assert( !( TRILINEAR && FIXED ), "the trilinear gather march steps in float" );
+    static_assert( !( CLAMP && FIXED ), "the clamped sampler steps in float" );
+    if constexpr( TRILINEAR )
+    {
+        vrc_taps t[N];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            VRC_FAST_FP
+            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
+            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
+            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
+            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
+            pos.x += step.x;
+            pos.y += step.y;
+            pos.z += step.z;
+        }
+        float v[N][8];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+#pragma unroll
+            for( int c = 0; c < 8; ++c )
+            {
+                const uint32_t a = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
+                v[k][c] = (float)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? a : 0u );
+            }
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
+            const float d = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
+            const vrc_f4 c = vrc_classify( lut, d, cls );
+            e[k] = ( !MASKED || (uint32_t)k < cnt ) ? c : z;
+            vb[k] = vrc_float_bits( d );
+        }
+    }
+    else
+    {
+        uint32_t idx[N];
+        if constexpr( FIXED )
+        {
+#pragma unroll
+            for( int k = 0; k < N; ++k )
+            {
+                const uint32_t ux = fp.x >> 24, uy = fp.y >> 24, uz = fp.z >> 24;
+                fp.x += fp.dx;
+                fp.y += fp.dy;
+                fp.z += fp.dz;
+#if defined( __HIP_DEVICE_COMPILE__ )
+                asm( "" : "+v"( fp.x ), "+v"( fp.y ), "+v"( fp.z ) ); /* (vrc_group_indices_fixed: keep the three additions) */
+                idx[k] = vrc_shade_part< true >( sm, 0, ux ) + vrc_shade_part< true >( sm, 1, uy ) +
+                         vrc_shade_part< true >( sm, 2, uz ) + sm.slotBase;
+#else
+                idx[k] = vrc_voxel_address( sm, ux, uy, uz );
+#endif
+            }
+        }
+        else
+        {
+            VRC_FAST_FP
+#pragma unroll
+            for( int k = 0; k < N; ++k )
+            {
+                float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
+                float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
+                float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
+                if( CLAMP )
+                {
+                    lx = fminf( fmaxf( lx, 0.0f ), sm.hix );
+                    ly = fminf( fmaxf( ly, 0.0f ), sm.hiy );
+                    lz = fminf( fmaxf( lz, 0.0f ), sm.hiz );
+                }
+                idx[k] = vrc_voxel_address( sm, (uint32_t)(int)lx, (uint32_t)(int)ly, (uint32_t)(int)lz );
+                pos.x += step.x;
+                pos.y += step.y;
+                pos.z += step.z;
+            }
+        }
+        D d[N];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+            d[k] = (D)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? idx[k] : 0u );
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            if constexpr( PERSAMPLE )
+            {
+                const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
+                const vrc_f4 c = vrc_classify( lut, (float)d[k], cls );
+                e[k] = ( !MASKED || (uint32_t)k < cnt ) ? c : z;
+            }
+            else
+                e[k] = lut[( !MASKED || (uint32_t)k < cnt ) ? d[k] : 256u]; /* (entry 256: all zeros) */
+            vb[k] = vrc_cdepth_bits( d[k] );
+        }
+    }
+}
+
+template < bool CLAMP, bool COUNT, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T, int GROUP >
+VRC_HD bool vrc_cdepth_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_segment s, const ATLAS_T* __restrict__ atlas,
+                                const vrc_f4* lut, const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples,
+                                vrc_cdepth_state& z )
+{
+    const float stepSize = f.stepSize;
+    const float tau = f.cdepthTau;
+    const vrc_sampler sm = vrc_make_sampler( n, f );
+    float travel = s.dist;
+    vrc_f3 pos = s.pos;
+    bool done = false;
+    if( !( travel > 0.0f ) )
+        return false;
+    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
+    if( FIXED )
+        fp = vrc_fixpos_init( sm, pos, s.step );
+    uint32_t first = 0u; /* the index, in its segment, of the first sample of the group in flight */
+    /* whole groups: every sample is one the reference loop reaches (vrc_march_segment_as) */
+    const float guard = stepSize * (float)( GROUP + 1 );
+    while( travel > guard )
+    {
+        vrc_f4 e[GROUP];
+        uint32_t vb[GROUP];
+        vrc_cdepth_group< CLAMP, FIXED, TRILINEAR, PERSAMPLE, ATLAS_T, GROUP, false >( sm, pos, s.step, fp, atlas, lut, cls,
+                                                                                      (uint32_t)GROUP, e, vb );
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            travel -= stepSize; /* same sequential subtraction as the reference */
+        const vrc_f4 saved = color;
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            vrc_composite( color, e[k] );
+        if( COUNT )
+            nSamples += GROUP;
+        const bool leave = color.w > VRC_EARLY_EXIT;
+        if( leave || ( !z.crossed && color.w >= tau ) )
+        {
+            /* the early exit or the crossing lies inside this group: replay it with the reference's per-sample exit.
+             * Where the ray goes on, no weight was forced to 0 and the colour is the group's again */
+            color = saved;
+            if( COUNT )
+                nSamples -= GROUP;
+#pragma unroll
+            for( int k = 0; k < GROUP; ++k )
+            {
+                vrc_composite( color, e[k], done );
+                if( COUNT )
+                    nSamples += done ? 0u : 1u;
+                if( !done )
+                    vrc_cdepth_note( z, color, tau, s.tNear, first + (uint32_t)k, stepSize, vb[k] );
+                done = done || ( color.w > VRC_EARLY_EXIT );
+            }
+            if( leave )
+                return true;
+        }
+        first += (uint32_t)GROUP;
+    }
+    constexpr int TAILG = GROUP >= 4 ? GROUP / 2 : 1;
+    while( travel > 0.0f && !done )
+    {
+        uint32_t cnt = 0;
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+        {
+            cnt += travel > 0.0f ? 1u : 0u;
+            travel -= stepSize;
+        }
+        vrc_f4 e[TAILG];
+        uint32_t vb[TAILG];
+        vrc_cdepth_group< CLAMP, FIXED, TRILINEAR, PERSAMPLE, ATLAS_T, TAILG, true >( sm, pos, s.step, fp, atlas, lut, cls, cnt, e,
+                                                                                     vb );
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+        {
+            const bool active = ( (uint32_t)k < cnt ) && !done;
+            vrc_composite( color, e[k], done );
+            if( COUNT )
+                nSamples += active ? 1u : 0u;
+            if( active )
+                vrc_cdepth_note( z, color, tau, s.tNear, first + (uint32_t)k, stepSize, vb[k] );
+            done = done || ( color.w > VRC_EARLY_EXIT );
+        }
+        first += (uint32_t)TAILG;
+    }
+    return done;
+}
+
+/* A slot known to hold one value (vrc_march_segment_as, UNIFORM): the same composites of its one table entry in the same
+ * order and the same count -- counted in integers where that is the float chain's count exactly, taken by the whole wave
+ * or not at all, else the float chain sample by sample -- with the crossing found as vrc_cdepth_segment finds it */
+template < bool COUNT >
+VRC_HD bool vrc_cdepth_uniform( const vrc_frame& f, const vrc_segment& s, const vrc_f4 ue, uint32_t value, vrc_f4& color,
+                                uint32_t& nSamples, vrc_cdepth_state& z )
+{
+    const float stepSize = f.stepSize;
+    const float tau = f.cdepthTau;
+    float travel = s.dist;
+    if( !( travel > 0.0f ) )
+        return false;
+    uint32_t first = 0u;
+    uint32_t nLeft;
+    bool counted = vrc_exact_step_count( travel, stepSize, &nLeft );
+#if defined( __HIP_DEVICE_COMPILE__ )
+    counted = __builtin_amdgcn_ballot_w64( !counted ) == 0ull;
+#endif
+    if( !counted )
+    {
+        for( ; travel > 0.0f; travel -= stepSize, ++first )
+        {
+            vrc_composite( color, ue );
+            if( COUNT )
+                nSamples += 1u;
+            vrc_cdepth_note( z, color, tau, s.tNear, first, stepSize, value );
+            if( color.w > VRC_EARLY_EXIT )
+                return true;
+        }
+        return false;
+    }
+    while( nLeft >= (uint32_t)VRC_UNIFORM_GROUP )
+    {
+        const vrc_f4 saved = color;
+#pragma unroll
+        for( int k = 0; k < VRC_UNIFORM_GROUP; ++k )
+            vrc_composite( color, ue );
+        if( color.w > VRC_EARLY_EXIT || ( !z.crossed && color.w >= tau ) )
+        {
+            color = saved;
+#pragma unroll 1 /* (unrolled with its sixteen exits this loop took over 300 registers of scratch) */
+            for( uint32_t k = 0; k < (uint32_t)VRC_UNIFORM_GROUP; ++k )
+            {
+                vrc_composite( color, ue );
+                if( COUNT )
+                    nSamples += 1u;
+                vrc_cdepth_note( z, color, tau, s.tNear, first + k, stepSize, value );
+                if( color.w > VRC_EARLY_EXIT )
+                    return true;
+            }
+        }
+        else if( COUNT )
+            nSamples += (uint32_t)VRC_UNIFORM_GROUP;
+        nLeft -= (uint32_t)VRC_UNIFORM_GROUP;
+        first += (uint32_t)VRC_UNIFORM_GROUP;
+    }
+    for( ; nLeft > 0u; --nLeft, ++first )
+    {
+        vrc_composite( color, ue );
+        if( COUNT )
+            nSamples += 1u;
+        vrc_cdepth_note( z, color, tau, s.tNear, first, stepSize, value );
+        if( color.w > VRC_EARLY_EXIT )
+            return true;
+    }
+    return false;
+}
+
+/* One brick of one ray of a depth-tracking composite frame: vrc_shade_brick's decisions -- the slot's 64-bit base moved
+ * into the lane's pointer (BIG), the uniform march of a slot known to hold one value, taken by the whole wave or not at
+ * all -- around the segment above */
+template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, bool BIG, typename SRC >
+VRC_HD bool vrc_cdepth_brick( const vrc_frame& f, const vrc_dev_node& n, const SRC& src, const ATLAS_T* __restrict__ atlas,
+                              const vrc_f4* lut, const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples,
+                              vrc_cdepth_state& z )
+{
+    static_assert( vrc_mode_is_cdepth( MODE ), "a depth-tracking composite mode" );
+    constexpr bool TRILINEAR = MODE == VRC_MODE_CDEPTH_TRILINEAR;
+    if constexpr( BIG )
+    {
+        vrc_dev_node local = n;
+        local.slotBase = 0u;
+        const ATLAS_T* slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
+        return vrc_cdepth_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, false, SRC >( f, local, src, slot, lut, cls, color, nSamples,
+                                                                                  z );
+    }
+    else
+    {
+        if constexpr( !TRILINEAR && sizeof( ATLAS_T ) == 1 )
+        {
+            uint32_t word = 0u;
+            if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
+                word = f.slotInfo[n.slotInfoIndex - 1u];
+            bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
+#if defined( __HIP_DEVICE_COMPILE__ )
+            general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
+#endif
+            if( !general )
+            {
+                const vrc_segment& s = src.distOnly();
+                return vrc_cdepth_uniform< COUNT >( f, s, lut[word & 0xFFu], word & 0xFFu, color, nSamples, z );
+            }
+        }
+        const vrc_segment& s = src.full();
+        return vrc_cdepth_segment< CLAMP, COUNT, FIXED, TRILINEAR, TRILINEAR || sizeof( ATLAS_T ) != 1, ATLAS_T,
+                                   TRILINEAR                 ? VRC_CDEPTH_GROUP_TRILINEAR
+                                   : ( sizeof( ATLAS_T ) == 1 && !CLAMP ) ? VRC_CDEPTH_GROUP
+                                                            : VRC_CDEPTH_GROUP_CLASSIFIED >( f, n, s, atlas, lut, cls, color,
+                                                                                             nSamples, z );
+    }
+}
+
+/* ------------------------------------------------------------------------------------------
  * Reference-order pixel: the O(nodeCount) loop of Renderer.cu:172-227, nodes in host order.
  * ---------------------------------------------------------------------------------------- */
 /* MODE: how a sample is fetched and classified.
@@ -3868,9 +4231,10 @@ VRC_HD void vrc_pixel_reference_order( const vrc_frame& f, const vrc_dev_node* _
                                        const vrc_classifier& cls,
                                        vrc_f4* __restrict__ pixelBuffer, uint32_t px, uint32_t py,
                                        uint32_t& nSamples, const uint16_t* candidates = nullptr,
-                                       uint32_t nCandidates = 0 )
+                                       uint32_t nCandidates = 0, vrc_cdepth_state* cdepth = nullptr )
 {
-    if constexpr( !vrc_mode_is_shade( MODE ) ) /* (a shaded frame is defined on the cudaRaycaster variant's sample set) */
+    /* (cdepth: the ray's crossing state, the depth-tracking composite modes only) */
+    if constexpr( !vrc_mode_is_shade( MODE ) && !vrc_mode_is_cdepth( MODE ) ) /* (a shaded frame is defined on the cudaRaycaster variant's sample set) */
         if( f.variant == VRC_VARIANT_GL && f.samplesPerPixel > 1u )
         {
             vrc_pixel_gl_supersampled< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, nodes, atlas, lut, cls, pixelBuffer,
@@ -3908,6 +4272,13 @@ VRC_HD void vrc_pixel_reference_order( const vrc_frame& f, const vrc_dev_node* _
             const vrc_segment_ready src = { s };
             if( vrc_shade_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_ready >( f, n, src, r.dir, atlas, lut, cls,
                                                                                               color, nSamples ) )
+                break;
+        }
+        else if constexpr( vrc_mode_is_cdepth( MODE ) )
+        {
+            const vrc_segment_ready src = { s };
+            if( vrc_cdepth_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_ready >( f, n, src, atlas, lut, cls, color,
+                                                                                               nSamples, *cdepth ) )
                 break;
         }
         else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, lut, cls, color,
@@ -3949,8 +4320,10 @@ template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, int G
 VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_dev_node* __restrict__ nodes,
                               const int32_t* __restrict__ gridTable, const ATLAS_T* __restrict__ atlas,
                               const vrc_f4* lut, const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples,
-                              int part = -1, int parts = 2, int partDir = 2, uint32_t* walkOut = nullptr )
+                              int part = -1, int parts = 2, int partDir = 2, uint32_t* walkOut = nullptr,
+                              vrc_cdepth_state* cdepth = nullptr )
 {
+    /* (cdepth: the ray's crossing state, the depth-tracking composite modes only) */
     /* (walkOut: VRC_MODE_WALK_RECORD only -- the ray's word of the walk cache's plane 0; nSamples then counts visits) */
     /* ray interval inside the brick grid */
     const vrc_f3 gmin = { f.gridMin[0], f.gridMin[1], f.gridMin[2] };
@@ -4100,6 +4473,13 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                             f, n, src, r.dir, atlas, lut, cls, color, nSamples ) )
                         finished = true;
                 }
+                else if constexpr( vrc_mode_is_cdepth( MODE ) )
+                {
+                    const vrc_segment_from_interval src = { r, iv, f.stepSize };
+                    if( vrc_cdepth_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_from_interval >(
+                            f, n, src, atlas, lut, cls, color, nSamples, *cdepth ) )
+                        finished = true;
+                }
                 else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, r, iv, atlas, lut, cls, color,
                                                                                        nSamples ) )
                     finished = true;
@@ -4189,7 +4569,7 @@ VRC_HD void vrc_pixel_grid_dda( const vrc_frame& f, const vrc_dev_node* __restri
                                 const ATLAS_T* __restrict__ atlas, const vrc_f4* lut,
                                 const vrc_classifier& cls,
                                 vrc_f4* __restrict__ pixelBuffer, uint32_t px, uint32_t py,
-                                uint32_t& nSamples, uint32_t rayIndex = 0u )
+                                uint32_t& nSamples, uint32_t rayIndex = 0u, vrc_cdepth_state* cdepth = nullptr )
 {
     /* rayIndex: tile * 64 + lane, the pixel's word in every plane of the ray cache (vrc_frame::rayCache; read only when
      * f.rayMode is not 0).  The mode is a frame constant, so the whole wave takes one side.  Both sides end in the same
@@ -4255,7 +4635,7 @@ VRC_HD void vrc_pixel_grid_dda( const vrc_frame& f, const vrc_dev_node* __restri
     if( color.w > VRC_EARLY_EXIT )
         return;
     vrc_ray_grid_dda< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, r, nodes, gridTable, atlas, lut, cls, color,
-                                                                   nSamples );
+                                                                   nSamples, -1, 2, 2, nullptr, cdepth );
     pixelBuffer[pixelPos] = color;
 }
 

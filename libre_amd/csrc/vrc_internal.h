@@ -156,6 +156,8 @@ struct vrc_raycast_args
     hipEvent_t stopEvent;
     bool* attached;
     bool shade; /* a shaded composite frame (VRC_OPT_SHADING = 1; frame.shadeAmbient set): vrc_launch_raycast_shade marches it */
+    bool cdepth; /* a composite frame that keeps the depth of its rays' crossings (VRC_OPT_COMPOSITE_DEPTH above 0; frame.cdepthTau,
+                  * frame.mipMax and frame.mipDepth set): vrc_launch_raycast_cdepth marches it */
 };
 
 /* the one dispatch of a single-launch march: with a's stop event if it has one (the dispatch then carries its own
@@ -205,7 +207,7 @@ hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream );
 static inline bool vrc_walk_replay_eligible( const vrc_raycast_args& a )
 {
     return a.gridDda && a.gridTable && !a.packed && !a.linear && a.elemBytes == 1 && !a.bigAtlas && !a.clamp &&
-           a.fixedStepping && a.ertParts <= 1 && !a.depthSplit && !a.shade && VRC_TILE_W == 8u;
+           a.fixedStepping && a.ertParts <= 1 && !a.depthSplit && !a.shade && !a.cdepth && VRC_TILE_W == 8u;
 }
 static inline int vrc_walk_replay_group( const vrc_raycast_args& a )
 {
@@ -267,6 +269,10 @@ hipError_t vrc_launch_raycast_iso( const vrc_raycast_args& a, hipStream_t stream
  * reference-order loop or the grid walk (a.gridDda), point or trilinear (a.linear) samples by gathers, every atlas type;
  * lut = the classified table (8-bit point samples) or the padded transfer function, as vrc_launch_raycast takes it */
 hipError_t vrc_launch_raycast_shade( const vrc_raycast_args& a, hipStream_t stream );
+
+/* the depth of a composite frame (vrc_kernels_cdepth.hip; VRC_OPT_COMPOSITE_DEPTH above 0): a.cdepth, frame.cdepthTau,
+ * frame.mipMax and frame.mipDepth set; the forms, atlas types and lut of vrc_launch_raycast_shade */
+hipError_t vrc_launch_raycast_cdepth( const vrc_raycast_args& a, hipStream_t stream );
 
 /* LDS-staged form (vrc_kernels_lds.hip): needs gridTable, !clamp, 8x8 tiles */
 hipError_t vrc_launch_raycast_lds( const vrc_raycast_args& a, hipStream_t stream );

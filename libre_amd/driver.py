@@ -10,6 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LIVRE_HIP_HOST_LIB") or os.path.join(_HERE, "lib", "libLivreHipRaycastPipeline.so")
 # include/vrc_hip.h, "A shaded composite frame": the two options App.set_shading sets (libre_amd/vrc.py has them all)
 OPT_SHADING, OPT_SHADING_AMBIENT = 29, 30
+# "The depth of a composite frame": the option App.set_composite_depth sets
+OPT_COMPOSITE_DEPTH = 31
 
 
 class Params(C.Structure):  # lvh_params
@@ -169,6 +171,11 @@ class App:
         gradient, with the ambient share in [0, 1] (kept in thousandths); reaches every renderer slot."""
         self.set_option(OPT_SHADING_AMBIENT, int(round(float(ambient) * 1000.0)))
         self.set_option(OPT_SHADING, 1 if on else 0)
+
+    def set_composite_depth(self, threshold):
+        """The depth of a composite frame (VRC_OPT_COMPOSITE_DEPTH): 0 turns it off; 1 ... 999 is the opacity threshold in
+        thousandths at which every ray's depth is kept, which App.pick then answers from; reaches every renderer slot."""
+        self.set_option(OPT_COMPOSITE_DEPTH, int(threshold))
 
     def get_option(self, option):
         v = C.c_int64()

@@ -19,6 +19,7 @@ OPT_WALK_CACHE, OPT_WALK_CACHE_USED, OPT_WALK_CACHE_BUDGET, OPT_WALK_CACHE_BYTES
 WALK_CACHE_ALWAYS = 2  # VRC_OPT_WALK_CACHE: replay also where most visits gather
 OPT_WALK_LEAN_USED = 28  # read-only: 1 = the last render replayed lean lists
 OPT_SHADING, OPT_SHADING_AMBIENT = 29, 30  # a shaded composite frame: 0 / 1, and the ambient share in thousandths (default 250)
+OPT_COMPOSITE_DEPTH = 31  # the depth of a composite frame: 0 (off), or the opacity threshold in thousandths, 1 ... 999
 PROJECTION_COMPOSITE, PROJECTION_MIP, PROJECTION_ISO = 0, 1, 2
 MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2
 VARIANT_CUDARAYCASTER, VARIANT_GLRAYCASTER = 0, 1
