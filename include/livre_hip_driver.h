@@ -66,7 +66,9 @@ int lvh_app_set_bands( lvh_app* app, const uint32_t* y0, const uint32_t* h, uint
 /* vrc_set_option on the renderer of the selected slot.  VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP, VRC_OPT_MIP_FOLD,
  * VRC_OPT_MIP_DEPTH and VRC_OPT_MIP_DEPTH_CUE say how
  * the app forms its pixels: they reach every renderer of the app, those of extra slots and those made later included;
- * so do VRC_OPT_RAY_CACHE, VRC_OPT_WALK_CACHE and VRC_OPT_WALK_CACHE_BUDGET (every renderer has caches of its own).
+ * so do VRC_OPT_RAY_CACHE, VRC_OPT_WALK_CACHE and VRC_OPT_WALK_CACHE_BUDGET (every renderer has caches of its own),
+ * and VRC_OPT_SHADING, VRC_OPT_SHADING_AMBIENT, VRC_OPT_COMPOSITE_DEPTH and VRC_OPT_PREINTEGRATION (a pre-integrated
+ * composite frame: every renderer builds and keeps a table of its own).
  * With VRC_PROJECTION_MIP, whichever fold (maximum, minimum, mean), a frame that asks for per-ray LOD
  * (lvh_app_set_ray_lod) renders its per-brick cut. */
 int lvh_app_set_option( lvh_app* app, int vrc_option, int64_t value );

@@ -271,6 +271,12 @@ typedef struct
                                     * thousandths at which every ray's depth is kept ("The depth of a composite frame"
                                     * below).  Anything else: VRC_EINVAL.  Read only when VRC_OPT_PROJECTION =
                                     * VRC_PROJECTION_COMPOSITE: MIP and isosurface frames ignore it */
+#define VRC_OPT_PREINTEGRATION 32   /* 0 (default): every sample of a composite frame is classified on its own; 1: every
+                                    * step is, from a table pre-integrated over the values at its two ends ("A
+                                    * pre-integrated composite frame" below).  Any other value: VRC_EINVAL.  Read only
+                                    * when VRC_OPT_PROJECTION = VRC_PROJECTION_COMPOSITE: MIP and isosurface frames
+                                    * ignore it */
+#define VRC_OPT_PREINT_BUILDS 33    /* read-only: how many times this context has built a pre-integrated table */
 /* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
  * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
  * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots
@@ -471,6 +477,59 @@ typedef struct
  * frame launches the kernel instances it launched before the option existed.  A depth cue on the composite, shading and
  * depth in one frame, replay from the walk cache, the LDS, packed and per-ray-LOD forms, gradients at the crossing,
  * several thresholds per frame and depth buffers coming in are not part of it. */
+
+/* A pre-integrated composite frame (VRC_OPT_PROJECTION = VRC_PROJECTION_COMPOSITE, VRC_OPT_PREINTEGRATION = 1).
+ * The composite frame classifies every sample on its own and so steps over whatever the transfer function does between
+ * the values of two consecutive samples; this frame classifies the step: what sample j adds is looked up by the values at
+ * both ends of the step that ends in it.
+ *   Samples.  Ray set-up, intervals, node order with its quirks, the restart per brick, the sample positions under both
+ *     VRC_OPT_STEPPING values, accumulation across passes and early termination at 0.999 on alpha are the composite
+ *     frame's, unchanged.  Only what a sample contributes changes.
+ *   Pairing.  A brick visit takes samples j = 0 ... n-1 with values d_0 ... d_{n-1}: for a point sample the stored voxel,
+ *     for a trilinear sample the interpolated float.  Sample j >= 1 composites E(d_{j-1}, d_j); sample 0 of every visit
+ *     composites E(d_0, d_0).  The previous value is NOT carried from one brick visit to the next: every visit stays a
+ *     function of its own brick and interval, so that frames split into passes, the reference-order loop, row maps and
+ *     a later replay stay consistent with one another; a visit of one sample falls back to the plain classification.
+ *   The step's entry.  TF(x) is the 256-texel transfer function read at clamp(x, 0, 255) by exact linear interpolation
+ *     between texels floor and floor + 1 (the weight quantisation of VRC_OPT_TF_FRAC_BITS is not applied).
+ *     a(x) = min(TF_alpha(x), 255/256), tau(x) = -ln(1 - a(x)), k = maxSamplesPerRay / samplesPerRay, and
+ *     x(d) = (d - r0) / (r1 - r0) * 256 - 0.5 the coordinate the plain classification uses (the range moved for signed
+ *     pools as there).  For xf != xb, over [xf, xb]:
+ *       taubar = int tau dx / (xb - xf),  alpha = 1 - exp(-k taubar),  cbar = int tau TF_rgb dx / int tau dx,
+ *       E = (cbar alpha, alpha), and E = 0 where int tau dx = 0.
+ *     E is symmetric in its two arguments.  Its opacity is exact for a value that changes linearly across the step; its
+ *     colour is the extinction-weighted mean, self-attenuation inside the step ignored.  For xf = xb, E is the plain
+ *     classification of that value.
+ *   Two tables, 256 x 256 vrc_f4 (1 MiB) in float32, built on the GPU in float64 by one builder; every entry but a
+ *     copied diagonal is within 1e-6 of the mathematical value per channel.
+ *     Value-indexed (kind 0), for point samples of 8-bit voxels: P[u][v] = E(x(u), x(v)) for stored bytes u, v, indexed
+ *       exactly; the diagonal P[v][v] is a copy of the classified table's entry for v, bit for bit, VRC_OPT_TF_FRAC_BITS
+ *       included.
+ *     Texel-indexed (kind 1), for 16-bit, 32-bit and float voxels and the trilinear filter: T[i][j] = E(i, j) for texel
+ *       centres i, j; T[i][i] is the plain classification at x = i with exact float weights.  A sample reads it
+ *       bilinearly at (xf, xb) = (clamp(x(d_{j-1}), 0, 255), clamp(x(d_j), 0, 255)), x in float32 (a NaN reads 0): with
+ *       i0 = floor(xf), i1 = min(i0 + 1, 255), wf = xf - i0 and j0, j1, wb the same of xb, in float32 (each sum of two
+ *       products may be one product and one fused multiply-add),
+ *         E = (1 - wb) * ((1 - wf) * T[i0][j0] + wf * T[i1][j0]) + wb * ((1 - wf) * T[i0][j1] + wf * T[i1][j1]).
+ *       (Sample 0 of a visit reads it at (x, x): the plain classification at a texel centre, its bilinear blend between.)
+ *     A table is rebuilt only when the transfer function, the range, k, VRC_OPT_TF_FRAC_BITS or the kind the frame needs
+ *     changed; it is allocated by the first frame that needs it and freed with the context.  VRC_OPT_PREINT_BUILDS
+ *     counts the builds.  vrc_get_preintegrated_table reads the last frame's table back.
+ *   VRC_OPT_UNIFORM_BRICKS.  A slot known to hold one value v is marched from the classified table's entry for v as it
+ *     is in the plain frame; the diagonal being a copy, frame and counts are bit-identical with the option on or off
+ *     (point samples of 8-bit voxels).
+ * Served: VRC_KERNEL_AUTO, _REFERENCE_ORDER and _GRID_DDA; all seven voxel types; both filters (trilinear by gathers: AUTO
+ * takes neither the LDS-staged form nor the tap-packed atlas); the clamped sampler; atlases of more than 2^32 voxels; row
+ * maps; caller-owned frame buffers; frames of several passes; VRC_OPT_COUNT_SAMPLES; VRC_OPT_RAY_CACHE as before.
+ * Silently the plain pre-integrated kernel: VRC_OPT_DEPTH_SPLIT, VRC_OPT_ERT_COMPACTION, VRC_OPT_GREY_TABLE (the
+ * four-float form) and VRC_OPT_WALK_CACHE (exactly as a shaded frame: not replayed, VRC_OPT_WALK_CACHE_USED reads 0,
+ * nothing is allocated, recorded lists are forgotten).  VRC_EINVAL from vrc_render, naming the option: an explicit
+ * VRC_KERNEL_LDS or _PACKED, vrc_set_ray_lod on, VRC_VARIANT_GLRAYCASTER, VRC_OPT_SHADING = 1 or VRC_OPT_COMPOSITE_DEPTH
+ * above 0 together with this option, and the option changed between vrc_pre_render and vrc_post_render.  With the option
+ * at 0 every frame launches the kernel instances it launched before the option existed, and no table memory is
+ * allocated.  Carrying the value across visits, self-attenuated colour, a grey two-float table, combination with
+ * shading or depth, replay from the walk cache, the LDS, packed and per-ray-LOD forms and a table finer than 256 x 256
+ * are not part of it. */
 
 #define VRC_VARIANT_CUDARAYCASTER 0 /* renderers/cudaRaycaster/cuda/Renderer.cu:95-230 */
 #define VRC_VARIANT_GLRAYCASTER 1   /* renderers/glRaycaster/shaders/fragRaycast.glsl:113-215: pixel centre
@@ -698,6 +757,11 @@ int vrc_set_isosurface( vrc_ctx* ctx, float iso_value, float ambient );
  * projection. */
 int vrc_get_projection_gradients( vrc_ctx* ctx, float* host_g /* W x H x 3 */ );
 
+/* The table the last pre-integrated vrc_render of this context used ("A pre-integrated composite frame" above):
+ * host_rgba[(row * 256 + col) * 4 + channel]; *kind (may be NULL) = 0 for the value-indexed table, 1 for the
+ * texel-indexed one.  Synchronous on the context's stream.  VRC_EINVAL before any such render. */
+int vrc_get_preintegrated_table( vrc_ctx* ctx, float* host_rgba /* 256 x 256 x 4 */, int* kind );
+
 /* ---- sort-first tile exchange (multi-GPU) ------------------------------------------------------- */
 /* One process per GPU renders row bands of the frame (vrc_set_row_map); the display rank receives
  * them over RCCL (xGMI inside a node) directly at their rows of the full frame.  This is the step
@@ -747,7 +811,8 @@ int vrc_last_kernel_occupancy( int* workgroups_per_cu, int* threads_per_workgrou
 #define VRC_ABI_VERSION 4 /* 3: vrc_gather_tiles takes the frame height; 4: VRC_KERNEL_PACKED, VRC_OPT_PACKED_ATLAS, vrc_last_kernel_occupancy
                            * (added since without a new number, as symbols a caller may bind weakly: the frame histogram,
                            * vrc_pool_create_typed / vrc_pool_voxel_type, vrc_get_projection_values,
-                           * vrc_get_projection_depths, vrc_set_isosurface, vrc_get_projection_gradients; as option
+                           * vrc_get_projection_depths, vrc_set_isosurface, vrc_get_projection_gradients,
+                           * vrc_get_preintegrated_table; as option
                            * values only: VRC_PROJECTION_ISO, VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP,
                            * VRC_OPT_MIP_FOLD, VRC_OPT_MIP_DEPTH, VRC_OPT_MIP_DEPTH_CUE) */
 /* = VRC_ABI_VERSION for the product build; -VRC_ABI_VERSION for a developer build of the library (compiled with

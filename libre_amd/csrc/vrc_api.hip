@@ -334,6 +334,16 @@ struct vrc_ctx
      * frame's first composite vrc_render read of it (-1 = none yet).  The pair per pixel lives in dMipMax and dMipDepth */
     int64_t optCompositeDepth = 0; /* VRC_OPT_COMPOSITE_DEPTH, thousandths */
     int64_t frameCompositeDepth = -1;
+    /* a pre-integrated composite frame (include/vrc_hip.h, "A pre-integrated composite frame"): the option, what the
+     * frame's first composite vrc_render read of it (-1 = none yet), and the one table: allocated by the first frame
+     * that needs it, rebuilt when the kind or one of the classified table's inputs changed */
+    int64_t optPreint = 0; /* VRC_OPT_PREINTEGRATION */
+    int64_t framePreint = -1;
+    vrc_f4* dPreint = nullptr;
+    int preintKind = -1; /* of the table in dPreint; -1: none built yet */
+    uint64_t preintTfVersion = 0;
+    vrc_lut_params preintParams;
+    int64_t preintBuilds = 0; /* VRC_OPT_PREINT_BUILDS */
     uint32_t* dRayList = nullptr; /* counts | two ray lists (vrc_internal.h) */
     size_t dRayListCap = 0;       /* pixels */
     int lastErtParts = 0;         /* of the last vrc_render */
@@ -463,6 +473,7 @@ void vrc_ctx_destroy( vrc_ctx* c )
     if( c->stream ) (void)hipStreamSynchronize( c->stream );
     if( c->dTf ) (void)hipFree( c->dTf );
     if( c->dLut ) (void)hipFree( c->dLut );
+    if( c->dPreint ) (void)hipFree( c->dPreint );
     if( c->hTf ) (void)hipHostFree( c->hTf );
     if( c->fbOwn ) (void)hipFree( c->fbOwn );
     if( c->dNodes ) (void)hipFree( c->dNodes );
@@ -600,6 +611,13 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_COMPOSITE_DEPTH is 0 (off) or the opacity threshold in thousandths, 1 to 999" );
         c->optCompositeDepth = value;
         return VRC_OK;
+    case VRC_OPT_PREINTEGRATION:
+        if( value != 0 && value != 1 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PREINTEGRATION is 0 (off) or 1 (classify every step of a composite frame from the pre-integrated table)" );
+        c->optPreint = value;
+        return VRC_OK;
+    case VRC_OPT_PREINT_BUILDS:
+        return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PREINT_BUILDS is read-only" );
     case VRC_OPT_ERT_COMPACTION:
         if( value < 0 || value > VRC_MAX_ERT_PARTS )
             return fail( VRC_EINVAL, "VRC_OPT_ERT_COMPACTION: 0 (off) or 2.." + std::to_string( VRC_MAX_ERT_PARTS ) +
@@ -650,6 +668,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_SHADING: *value = c->optShading; return VRC_OK;
     case VRC_OPT_SHADING_AMBIENT: *value = c->optShadingAmbient; return VRC_OK;
     case VRC_OPT_COMPOSITE_DEPTH: *value = c->optCompositeDepth; return VRC_OK;
+    case VRC_OPT_PREINTEGRATION: *value = c->optPreint; return VRC_OK;
+    case VRC_OPT_PREINT_BUILDS: *value = c->preintBuilds; return VRC_OK;
     case VRC_OPT_KERNEL_USED: *value = c->stats.kernel_variant; return VRC_OK;
     case VRC_OPT_GRID_WALK_USED: *value = c->gridWalkUsed; return VRC_OK;
     default: return fail( VRC_EINVAL, "vrc_get_option: unknown option" );
@@ -1556,6 +1576,7 @@ int vrc_pre_render( vrc_ctx* c, const vrc_view_data* view )
     c->gradValid = false;
     c->frameShading = c->frameShadingAmbient = -1;
     c->frameCompositeDepth = -1;
+    c->framePreint = -1;
     c->projState.pixels = 0u; /* vrc_get_projection_values: nothing to read until a MIP pass of this frame */
     return VRC_OK;
 }
@@ -1768,6 +1789,29 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             return fail( VRC_EINVAL, "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_COMPOSITE_DEPTH is defined on the "
                                      "cudaRaycaster variant's sample set" );
     }
+    /* a pre-integrated composite frame (include/vrc_hip.h, "A pre-integrated composite frame"): read by composite frames
+     * only; served by the gather marches of vrc_kernels_preint.hip and refused where those have no form */
+    const bool preint = !mip && c->optPreint != 0;
+    if( !mip && c->framePreint >= 0 && c->framePreint != c->optPreint )
+        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_PREINTEGRATION changed between vrc_pre_render and vrc_post_render; the "
+                                 "passes of one frame are all pre-integrated or none is" );
+    if( preint )
+    {
+        if( shade )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_SHADING = 1 together with VRC_OPT_PREINTEGRATION; a step has no one "
+                                     "gradient: the two are not combined" );
+        if( cdepth )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_COMPOSITE_DEPTH together with VRC_OPT_PREINTEGRATION; the depth is "
+                                     "defined on the plain frame's alpha: the two are not combined" );
+        if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no pre-integrated form; "
+                                     "VRC_OPT_PREINTEGRATION = 1 is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
+        if( c->rayLod )
+            return fail( VRC_EINVAL, "vrc_render: vrc_set_ray_lod is on; VRC_OPT_PREINTEGRATION = 1 renders a per-brick cut" );
+        if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
+            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_PREINTEGRATION = 1 is defined on the "
+                                     "cudaRaycaster variant's sample set" );
+    }
     if( shade )
     {
         if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
@@ -1811,6 +1855,23 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             for( uint32_t d = 0; d < 256u; ++d )
                 m = std::max( m, vrc_lut_entry( c->hTf, d, lp ).w );
             c->lutMaxAlpha = m;
+        }
+    }
+    /* the pre-integrated table, behind the classified table on the stream (its value-indexed diagonal copies that one):
+     * value-indexed where the frame marches stored bytes through the classified table, texel-indexed otherwise */
+    if( preint )
+    {
+        const int kind = classify ? VRC_PREINT_TEXEL : VRC_PREINT_VALUE;
+        if( !c->dPreint )
+            VRC_HIP_CHECK( hipMalloc( &c->dPreint, (size_t)VRC_PREINT_ENTRIES * sizeof( vrc_f4 ) ) );
+        if( c->preintKind != kind || c->preintTfVersion != c->tfVersion ||
+            std::memcmp( &lp, &c->preintParams, sizeof( lp ) ) != 0 )
+        {
+            VRC_HIP_CHECK( vrc_launch_build_preint( c->dTf, c->dLut, c->dPreint, lp, kind, c->stream ) );
+            c->preintKind = kind;
+            c->preintTfVersion = c->tfVersion;
+            c->preintParams = lp;
+            ++c->preintBuilds;
         }
     }
 
@@ -1926,7 +1987,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * positions and its classifier need -- 8- or 16-bit bricks with overlap >= 1 in slots of at most 248 voxels a side,
      * VRC_OPT_TF_FRAC_BITS = 8, fixed-point stepping -- and 2.25 times the atlas in device memory; either brick
      * enumeration (grid walk where the node set is grid-aligned, else the reference-order loop) */
-    const bool packedEligible = linear && !glSuper && !mip && !shade && !cdepth && !c->cachedClamp && slotsFit8Bits &&
+    const bool packedEligible = linear && !glSuper && !mip && !shade && !cdepth && !preint && !c->cachedClamp && slotsFit8Bits &&
                                 pool_packed_possible( pool ) && c->optTfFracBits == 8 && c->optStepping != 0;
     bool usePacked = false;
     if( c->optKernel == VRC_KERNEL_PACKED )
@@ -1943,13 +2004,14 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
          * it the frame takes the staged form below */
         usePacked = pool_enable_packed( pool );
     const bool useLds = c->rayLod ? ( ldsLodEligible && c->optKernel != VRC_KERNEL_GRID_DDA && !usePacked )
-                                  : !glSuper && !usePacked && !mip && !shade && !cdepth && ( c->optKernel == VRC_KERNEL_LDS ||
+                                  : !glSuper && !usePacked && !mip && !shade && !cdepth && !preint && ( c->optKernel == VRC_KERNEL_LDS ||
                                                   ( c->optKernel == VRC_KERNEL_AUTO && linear && ldsEligible ) );
 
     vrc_raycast_args a;
     std::memset( &a, 0, sizeof( a ) );
     a.shade = shade;
     a.cdepth = cdepth;
+    a.preint = preint;
     vrc_frame& f = a.frame;
     {
         vrc_atlas_geom geom;
@@ -2177,6 +2239,9 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         c->projState.shift = pool->rangeShift;
     }
     f.cdepthTau = cdepth ? (float)c->optCompositeDepth / 1000.0f : 0.0f;
+    f.preintTable = preint ? c->dPreint : nullptr;
+    if( !mip )
+        c->framePreint = c->optPreint;
     c->frameProjection = c->optProjection;
     if( !mip )
         c->frameCompositeDepth = c->optCompositeDepth;
@@ -2209,7 +2274,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * restart sample per brick).  (ii) The frame starts from zero (first pass: the clear is folded in).
      * (iii) the table-driven point-sampling walk kernel. */
     a.depthSplit = false;
-    if( c->optDepthSplit && !mip && !shade && !cdepth && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 && !pool->bigAtlas &&
+    if( c->optDepthSplit && !mip && !shade && !cdepth && !preint && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 && !pool->bigAtlas &&
         !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && f.clearFirst )
     {
         const double nMax = 1.7320508 * (double)render->samplesPerRay +
@@ -2225,7 +2290,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     a.ertParts = 0;
     a.rayList = nullptr;
     /* (the same predicate as the launcher's, vrc_launch_raycast: what vrc_get_ray_counts reports is what ran) */
-    if( c->optErtParts > 1 && !mip && !shade && !cdepth && !a.depthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 &&
+    if( c->optErtParts > 1 && !mip && !shade && !cdepth && !preint && !a.depthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 &&
         !pool->bigAtlas && !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && c->fbW < 65536u && c->fbH < 65536u &&
         VRC_TILE_W == 8u )
     {
@@ -2474,6 +2539,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                                    : c->optMipFold == VRC_MIP_FOLD_MEAN ? vrc_launch_raycast_meanip( a, c->stream )
                                                                         : vrc_launch_raycast_mip( a, c->stream ) )
                    : cdepth    ? vrc_launch_raycast_cdepth( a, c->stream )
+                   : preint    ? vrc_launch_raycast_preint( a, c->stream )
                    : shade     ? vrc_launch_raycast_shade( a, c->stream )
                    : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
                    : c->rayLod ? vrc_launch_raycast_raylod( a, c->stream )
@@ -2627,6 +2693,22 @@ int vrc_get_projection_gradients( vrc_ctx* c, float* hostG )
     VRC_HIP_CHECK( hipMemcpyAsync( hostG, c->dIsoGrad, (size_t)c->projState.pixels * 3u * sizeof( float ),
                                    hipMemcpyDeviceToHost, c->stream ) );
     VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+    return VRC_OK;
+}
+
+int vrc_get_preintegrated_table( vrc_ctx* c, float* hostRgba, int* kind )
+{
+    if( !c || !hostRgba )
+        return fail( VRC_EINVAL, "vrc_get_preintegrated_table: NULL argument" );
+    if( !c->dPreint || c->preintKind < 0 )
+        return fail( VRC_EINVAL, "vrc_get_preintegrated_table: no vrc_render with VRC_OPT_PREINTEGRATION = 1 yet; the table "
+                                 "is built by the first frame that needs it" );
+    VRC_HIP_CHECK( hipSetDevice( c->device ) );
+    VRC_HIP_CHECK( hipMemcpyAsync( hostRgba, c->dPreint, (size_t)VRC_PREINT_ENTRIES * sizeof( vrc_f4 ), hipMemcpyDeviceToHost,
+                                   c->stream ) );
+    VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+    if( kind )
+        *kind = c->preintKind;
     return VRC_OK;
 }
 

@@ -256,6 +256,10 @@ struct vrc_frame
      * VRC_MIP_EMPTY = not crossed) and mipDepth (D), owned, invalidated and not read by a first pass (mipFirst) as an
      * isosurface frame's are.  No other kernel reads it */
     float cdepthTau;
+    /* a pre-integrated composite frame (VRC_OPT_PREINTEGRATION, the vrc_k_raycast_preint instances; at the end: no field
+     * above moves): the 256 x 256 table of the frame, value-indexed (point samples of 8-bit voxels) or texel-indexed
+     * (vrc_preint_entry).  No other kernel reads it */
+    const vrc_f4* preintTable;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -3947,6 +3951,465 @@ VRC_HD bool vrc_cdepth_brick( const vrc_frame& f, const vrc_dev_node& n, const S
 }
 
 /* ------------------------------------------------------------------------------------------
+ * EXTENSION: a pre-integrated composite frame (VRC_OPT_PREINTEGRATION = 1; include/vrc_hip.h, "A pre-integrated
+ * composite frame").
+ *
+ * The composite frame with one change: what a sample contributes is looked up by the values at both ends of its step,
+ * E(d_{j-1}, d_j), in a 256 x 256 table pre-integrated from the transfer function; sample 0 of every brick visit is paired
+ * with itself.  Positions, addresses, gathers, the order of the blends and early ray termination are the plain march's.
+ *
+ * 1. The table (vrc_preint_*; float64, the same body on the host and in vrc_k_build_preint).  TF(x) is the 256 texels read
+ *    by exact linear interpolation at clamp(x, 0, 255); u(x) = 1 - min(TF_a(x), 255/256); tau = -ln u.  Between two texel
+ *    centres u is linear but for the point where TF_a crosses 255/256, behind which it is 1/256: vrc_preint_span splits
+ *    there.  On a piece with u and the colour linear, int tau and int tau c have closed forms (vrc_preint_piece); where u
+ *    moves by less than a fifth of its smaller end these cancel, and an 8-point Gauss rule, there exact to rounding (the
+ *    logarithm's singularity is more than ten half-lengths away), takes their place.  An entry is the partial span at
+ *    either end plus a difference of per-texel prefix sums (256 x 4 doubles, built once per launch and block), or one
+ *    partial span where both ends share a texel interval: nothing small is ever the difference of two large numbers
+ *    but the prefix difference, whose error of 255 ln 256 x 2^-52 is far inside the 1e-6 the contract allows.
+ * 2. The march (vrc_preint_group, vrc_preint_segment): vrc_shade_segment's structure -- whole groups while more than a
+ *    group of steps remains, the early-exit test once per group with the exact replay from the saved colour, a masked
+ *    tail -- with, per group, the gathers, then the table reads, then the blends, and one carried value per lane: the last
+ *    value of the group before (the visit's first sample: its own).  A no-op slot of the tail reads entry (0, 0) of the
+ *    table, comes out as zeros and leaves the carried value alone.
+ * ---------------------------------------------------------------------------------------- */
+#define VRC_MODE_PREINT 14           /* point samples */
+#define VRC_MODE_PREINT_TRILINEAR 15 /* trilinear samples by gathers */
+VRC_HD constexpr bool vrc_mode_is_preint( int mode ) { return mode == VRC_MODE_PREINT || mode == VRC_MODE_PREINT_TRILINEAR; }
+#define VRC_PREINT_GROUP 8       /* the value-indexed table: 8 voxels, then 8 table entries in flight */
+#define VRC_PREINT_GROUP_TEXEL 4 /* the texel-indexed table: 4 voxels or 32 taps, then 16 table entries in flight (8 x 4
+                                  * entries beside the walk's state do not fit the registers of four waves per SIMD) */
+#define VRC_PREINT_DIM 256u
+#define VRC_PREINT_ENTRIES ( VRC_PREINT_DIM * VRC_PREINT_DIM )
+#define VRC_PREINT_VALUE 0 /* kinds of table: indexed by two stored bytes ... */
+#define VRC_PREINT_TEXEL 1 /* ... or read bilinearly at two texel coordinates */
+
+struct vrc_preint_sum
+{
+    double i, r, g, b; /* int tau, int tau red, int tau green, int tau blue */
+};
+
+/* one piece of length len on which u runs linearly from ua to ub and the colour from ca to cb */
+VRC_HD void vrc_preint_piece( double len, double ua, double ub, const double* ca, const double* cb, vrc_preint_sum& acc )
+{
+    if( !( len > 0.0 ) )
+        return;
+    const double m = ub - ua;
+    const double lo = ua < ub ? ua : ub;
+    double i0, i1; /* int_0^1 -ln u dw and int_0^1 -ln u w dw, u = ua + m w */
+    if( fabs( m ) >= 0.2 * lo )
+    {
+        const double la = log( ua ), lb = log( ub );
+        const double h0 = ( ub * lb - ub ) - ( ua * la - ua );
+        const double h1 = ( 0.5 * ub * ub * lb - 0.25 * ub * ub ) - ( 0.5 * ua * ua * la - 0.25 * ua * ua );
+        i0 = -h0 / m;
+        i1 = -( h1 - ua * h0 ) / ( m * m );
+    }
+    else
+    {
+        const double gx[4] = { 0.019855071751231912, 0.10166676129318664, 0.2372337950418355, 0.4082826787521751 };
+        const double gw[4] = { 0.050614268145188344, 0.11119051722668717, 0.15685332293894352, 0.18134189168918088 };
+        i0 = i1 = 0.0;
+        for( int q = 0; q < 4; ++q )
+        {
+            const double w0 = gx[q], w1 = 1.0 - gx[q];
+            const double t0 = -log( ua + m * w0 ), t1 = -log( ua + m * w1 );
+            i0 += gw[q] * ( t0 + t1 );
+            i1 += gw[q] * ( t0 * w0 + t1 * w1 );
+        }
+    }
+    acc.i += len * i0;
+    acc.r += len * ( ca[0] * i0 + ( cb[0] - ca[0] ) * i1 );
+    acc.g += len * ( ca[1] * i0 + ( cb[1] - ca[1] ) * i1 );
+    acc.b += len * ( ca[2] * i0 + ( cb[2] - ca[2] ) * i1 );
+}
+
+/* [s, e] of the interval between texel centres i and i + 1 (0 <= s <= e <= 1), split where TF_a crosses 255/256 */
+VRC_HD void vrc_preint_span( const float* tf, uint32_t i, double s, double e, vrc_preint_sum& acc )
+{
+    if( !( e > s ) )
+        return;
+    const double top = 255.0 / 256.0;
+    const double a0 = (double)tf[i * 4u + 3u], a1 = (double)tf[i * 4u + 7u];
+    const double c0[3] = { (double)tf[i * 4u], (double)tf[i * 4u + 1u], (double)tf[i * 4u + 2u] };
+    const double c1[3] = { (double)tf[i * 4u + 4u], (double)tf[i * 4u + 5u], (double)tf[i * 4u + 6u] };
+    double cut[3] = { s, e, e };
+    int pieces = 1;
+    if( ( a0 < top ) != ( a1 < top ) )
+    {
+        const double t = ( top - a0 ) / ( a1 - a0 );
+        if( t > s && t < e )
+        {
+            cut[1] = t;
+            pieces = 2;
+        }
+    }
+    for( int p = 0; p < pieces; ++p )
+    {
+        const double p0 = cut[p], p1 = cut[p + 1];
+        const double mid = a0 + ( a1 - a0 ) * ( 0.5 * ( p0 + p1 ) );
+        double ua = 1.0 / 256.0, ub = 1.0 / 256.0;
+        if( mid < top ) /* the piece lies on the unclamped side: its ends may touch the crossing */
+        {
+            const double q0 = a0 + ( a1 - a0 ) * p0, q1 = a0 + ( a1 - a0 ) * p1;
+            ua = 1.0 - ( q0 < top ? q0 : top );
+            ub = 1.0 - ( q1 < top ? q1 : top );
+        }
+        const double ca[3] = { c0[0] + ( c1[0] - c0[0] ) * p0, c0[1] + ( c1[1] - c0[1] ) * p0, c0[2] + ( c1[2] - c0[2] ) * p0 };
+        const double cb[3] = { c0[0] + ( c1[0] - c0[0] ) * p1, c0[1] + ( c1[1] - c0[1] ) * p1, c0[2] + ( c1[2] - c0[2] ) * p1 };
+        vrc_preint_piece( p1 - p0, ua, ub, ca, cb, acc );
+    }
+}
+
+/* beyond the first or last texel centre the transfer function is that texel */
+VRC_HD void vrc_preint_outside( const float* tf, uint32_t i, double len, vrc_preint_sum& acc )
+{
+    if( !( len > 0.0 ) )
+        return;
+    const double top = 255.0 / 256.0;
+    const double a = (double)tf[i * 4u + 3u];
+    const double tau = -log( 1.0 - ( a < top ? a : top ) );
+    acc.i += len * tau;
+    acc.r += len * tau * (double)tf[i * 4u];
+    acc.g += len * tau * (double)tf[i * 4u + 1u];
+    acc.b += len * tau * (double)tf[i * 4u + 2u];
+}
+
+/* the plain classification at texel coordinate x, in float64 with exact weights: E(x, x) */
+VRC_HD vrc_f4 vrc_preint_plain( const float* tf, double x, double k )
+{
+    const double top = 255.0 / 256.0;
+    const double xc = x < 0.0 ? 0.0 : ( x > 255.0 ? 255.0 : x );
+    const uint32_t i0 = xc < 255.0 ? (uint32_t)xc : 254u;
+    const double w = xc - (double)i0;
+    const double a = (double)tf[i0 * 4u + 3u] + ( (double)tf[i0 * 4u + 7u] - (double)tf[i0 * 4u + 3u] ) * w;
+    const double alpha = 1.0 - pow( 1.0 - ( a < top ? a : top ), k );
+    vrc_f4 e;
+    e.x = (float)( ( (double)tf[i0 * 4u] + ( (double)tf[i0 * 4u + 4u] - (double)tf[i0 * 4u] ) * w ) * alpha );
+    e.y = (float)( ( (double)tf[i0 * 4u + 1u] + ( (double)tf[i0 * 4u + 5u] - (double)tf[i0 * 4u + 1u] ) * w ) * alpha );
+    e.z = (float)( ( (double)tf[i0 * 4u + 2u] + ( (double)tf[i0 * 4u + 6u] - (double)tf[i0 * 4u + 2u] ) * w ) * alpha );
+    e.w = (float)alpha;
+    return e;
+}
+
+/* prefix[i] = the integrals over [0, i], i = 0 ... 255, summed in texel order */
+VRC_HD void vrc_preint_prefix( const float* tf, vrc_preint_sum* prefix )
+{
+    vrc_preint_sum run = { 0.0, 0.0, 0.0, 0.0 };
+    prefix[0] = run;
+    for( uint32_t i = 0; i + 1u < VRC_PREINT_DIM; ++i )
+    {
+        vrc_preint_sum one = { 0.0, 0.0, 0.0, 0.0 };
+        vrc_preint_span( tf, i, 0.0, 1.0, one );
+        run.i += one.i;
+        run.r += one.r;
+        run.g += one.g;
+        run.b += one.b;
+        prefix[i + 1u] = run;
+    }
+}
+
+/* E(xf, xb), xf != xb as texel coordinates (unclamped); the smaller one is always integrated from, so that the entry is
+ * symmetric bit for bit */
+VRC_HD vrc_f4 vrc_preint_entry( const float* tf, const vrc_preint_sum* prefix, double xf, double xb, double k )
+{
+    const double lo = xf < xb ? xf : xb, hi = xf < xb ? xb : xf;
+    vrc_preint_sum acc = { 0.0, 0.0, 0.0, 0.0 };
+    vrc_preint_outside( tf, 0u, ( hi < 0.0 ? hi : 0.0 ) - lo, acc );
+    vrc_preint_outside( tf, 255u, hi - ( lo > 255.0 ? lo : 255.0 ), acc );
+    const double cl = lo < 0.0 ? 0.0 : ( lo > 255.0 ? 255.0 : lo ), ch = hi < 0.0 ? 0.0 : ( hi > 255.0 ? 255.0 : hi );
+    if( ch > cl )
+    {
+        const uint32_t il = cl < 255.0 ? (uint32_t)cl : 254u, ih = ch < 255.0 ? (uint32_t)ch : 254u;
+        if( il == ih )
+            vrc_preint_span( tf, il, cl - (double)il, ch - (double)il, acc );
+        else
+        {
+            vrc_preint_span( tf, il, cl - (double)il, 1.0, acc );
+            acc.i += prefix[ih].i - prefix[il + 1u].i;
+            acc.r += prefix[ih].r - prefix[il + 1u].r;
+            acc.g += prefix[ih].g - prefix[il + 1u].g;
+            acc.b += prefix[ih].b - prefix[il + 1u].b;
+            vrc_preint_span( tf, ih, 0.0, ch - (double)ih, acc );
+        }
+    }
+    vrc_f4 e = { 0.f, 0.f, 0.f, 0.f };
+    if( !( acc.i > 0.0 ) )
+        return e;
+    const double alpha = -expm1( -k * ( acc.i / ( hi - lo ) ) );
+    e.x = (float)( acc.r / acc.i * alpha );
+    e.y = (float)( acc.g / acc.i * alpha );
+    e.z = (float)( acc.b / acc.i * alpha );
+    e.w = (float)alpha;
+    return e;
+}
+
+/* the texel coordinate of stored value d as vrc_classify forms it, in float64 (the value-indexed table) */
+VRC_HD double vrc_preint_value_coord( uint32_t d, const vrc_lut_params& p )
+{
+    return ( (double)d - (double)p.rangeMin ) / ( (double)p.rangeMax - (double)p.rangeMin ) * 256.0 - 0.5;
+}
+
+/* entry (row, col) of the table of `kind`; lut: the classified table, whose entries the diagonal of the value-indexed
+ * table copies */
+VRC_HD vrc_f4 vrc_preint_table_entry( const float* tf, const vrc_f4* lut, const vrc_preint_sum* prefix, vrc_lut_params p,
+                                      int kind, uint32_t row, uint32_t col )
+{
+    const double k = (double)p.alphaCorrection;
+    if( kind == VRC_PREINT_VALUE )
+    {
+        if( row == col )
+            return lut[row];
+        return vrc_preint_entry( tf, prefix, vrc_preint_value_coord( row, p ), vrc_preint_value_coord( col, p ), k );
+    }
+    if( row == col )
+        return vrc_preint_plain( tf, (double)row, k );
+    return vrc_preint_entry( tf, prefix, (double)row, (double)col, k );
+}
+
+/* the texel coordinate of a sample of the texel-indexed table: vrc_classify's, clamped to the texel centres (NaN: 0) */
+VRC_HD float vrc_preint_coord( float d, const vrc_classifier& k )
+{
+    VRC_FAST_FP
+    return fminf( fmaxf( d * k.mult + k.add, 0.0f ), 255.0f );
+}
+
+/* the texel-indexed table read bilinearly at (xf, xb), both in [0, 255]: exact float32 weights, taps clamped to 255,
+ *   E = (1 - wb) ((1 - wf) T[i0][j0] + wf T[i1][j0]) + wb ((1 - wf) T[i0][j1] + wf T[i1][j1]) */
+VRC_HD vrc_f4 vrc_preint_read( const vrc_f4* table, float xf, float xb )
+{
+    const float ff = floorf( xf ), fb = floorf( xb );
+    const float wf = xf - ff, wb = xb - fb;
+    const float vf = 1.0f - wf, vb = 1.0f - wb;
+    const uint32_t i0 = (uint32_t)ff, j0 = (uint32_t)fb;
+    const uint32_t i1 = i0 < 255u ? i0 + 1u : 255u, j1 = j0 < 255u ? j0 + 1u : 255u;
+    const vrc_f4 t00 = table[i0 * VRC_PREINT_DIM + j0], t10 = table[i1 * VRC_PREINT_DIM + j0];
+    const vrc_f4 t01 = table[i0 * VRC_PREINT_DIM + j1], t11 = table[i1 * VRC_PREINT_DIM + j1];
+    vrc_f4 e;
+    e.x = VRC_LERP2( vb, VRC_LERP2( vf, t00.x, wf, t10.x ), wb, VRC_LERP2( vf, t01.x, wf, t11.x ) );
+    e.y = VRC_LERP2( vb, VRC_LERP2( vf, t00.y, wf, t10.y ), wb, VRC_LERP2( vf, t01.y, wf, t11.y ) );
+    e.z = VRC_LERP2( vb, VRC_LERP2( vf, t00.z, wf, t10.z ), wb, VRC_LERP2( vf, t01.z, wf, t11.z ) );
+    e.w = VRC_LERP2( vb, VRC_LERP2( vf, t00.w, wf, t10.w ), wb, VRC_LERP2( vf, t01.w, wf, t11.w ) );
+    return e;
+}
+
+/* N samples of a segment: e[k] = the table's entry for the step that ends in sample k.  carry: the value (VALUE: the
+ * stored byte; otherwise the texel coordinate) of the sample before the group; first: the group opens a visit, whose
+ * sample 0 is paired with itself.  MASKED: only the first cnt >= 1 are the reference's; the others read entry (0, 0),
+ * come out as zeros (an exact no-op in the blend) and do not move carry */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, bool VALUE, typename ATLAS_T, int N, bool MASKED >
+VRC_HD void vrc_preint_group( const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
+                              const ATLAS_T* __restrict__ atlas, const vrc_f4* __restrict__ table, const vrc_classifier& cls,
+                              uint32_t cnt, float& carry, bool& first, vrc_f4* e )
+{
+    typedef typename vrc_density< ATLAS_T >::type D;
+    static_assert( !( TRILINEAR && FIXED ), "the trilinear gather march steps in float" );
+    static_assert( !( CLAMP && FIXED ), "the clamped sampler steps in float" );
+    static_assert( !VALUE || ( !TRILINEAR && sizeof( ATLAS_T ) == 1 ), "the value-indexed table takes stored bytes" );
+    [[maybe_unused]] float x[N];     /* the texel coordinates of the samples, or (VALUE) ... */
+    [[maybe_unused]] uint32_t dv[N]; /* ... their stored bytes */
+    if constexpr( TRILINEAR )
+    {
+        vrc_taps t[N];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            VRC_FAST_FP
+            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
+            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
+            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
+            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
+            pos.x += step.x;
+            pos.y += step.y;
+            pos.z += step.z;
+        }
+        float v[N][8];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+#pragma unroll
+            for( int c = 0; c < 8; ++c )
+            {
+                const uint32_t a = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
+                v[k][c] = (float)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? a : 0u );
+            }
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+            x[k] = vrc_preint_coord( vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz ), cls );
+    }
+    else
+    {
+        uint32_t idx[N];
+        if constexpr( FIXED )
+            vrc_group_indices_fixed< N >( sm, fp, idx );
+        else
+            vrc_group_indices< CLAMP, N >( sm, pos, step, idx );
+        D d[N];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+            d[k] = (D)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? idx[k] : 0u );
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            if constexpr( VALUE )
+                dv[k] = (uint32_t)d[k];
+            else
+                x[k] = vrc_preint_coord( (float)d[k], cls );
+        }
+    }
+    /* the table: entry k by the value before it and its own */
+    const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
+    if constexpr( VALUE )
+    {
+        uint32_t before = first ? dv[0] : (uint32_t)carry;
+        vrc_f4 t[N];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            const bool taken = !MASKED || (uint32_t)k < cnt;
+            t[k] = table[taken ? before * VRC_PREINT_DIM + dv[k] : 0u];
+            before = taken ? dv[k] : before;
+        }
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+            e[k] = ( !MASKED || (uint32_t)k < cnt ) ? t[k] : z;
+        carry = (float)before;
+    }
+    else
+    {
+        float before = first ? x[0] : carry;
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            const bool taken = !MASKED || (uint32_t)k < cnt;
+            const vrc_f4 t = vrc_preint_read( table, taken ? before : 0.0f, taken ? x[k] : 0.0f );
+            e[k] = taken ? t : z;
+            before = taken ? x[k] : before;
+        }
+        carry = before;
+    }
+    first = false;
+}
+
+template < bool CLAMP, bool COUNT, bool FIXED, bool TRILINEAR, bool VALUE, typename ATLAS_T, int GROUP >
+VRC_HD bool vrc_preint_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_segment s, const ATLAS_T* __restrict__ atlas,
+                                const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples )
+{
+    const float stepSize = f.stepSize;
+    const vrc_sampler sm = vrc_make_sampler( n, f );
+    const vrc_f4* __restrict__ table = f.preintTable;
+    float travel = s.dist;
+    vrc_f3 pos = s.pos;
+    bool done = false;
+    if( !( travel > 0.0f ) )
+        return false;
+    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
+    if( FIXED )
+        fp = vrc_fixpos_init( sm, pos, s.step );
+    float carry = 0.0f;
+    bool first = true; /* the previous value is not carried from one brick visit to the next */
+    /* whole groups: every sample is one the reference loop reaches (vrc_march_segment_as) */
+    const float guard = stepSize * (float)( GROUP + 1 );
+    while( travel > guard )
+    {
+        vrc_f4 e[GROUP];
+        vrc_preint_group< CLAMP, FIXED, TRILINEAR, VALUE, ATLAS_T, GROUP, false >( sm, pos, s.step, fp, atlas, table, cls,
+                                                                                  (uint32_t)GROUP, carry, first, e );
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            travel -= stepSize; /* same sequential subtraction as the reference */
+        const vrc_f4 saved = color;
+#pragma unroll
+        for( int k = 0; k < GROUP; ++k )
+            vrc_composite( color, e[k] );
+        if( COUNT )
+            nSamples += GROUP;
+        if( color.w > VRC_EARLY_EXIT )
+        {
+            /* crossed inside this group: replay it with the reference's per-sample exit */
+            color = saved;
+            if( COUNT )
+                nSamples -= GROUP;
+#pragma unroll
+            for( int k = 0; k < GROUP; ++k )
+            {
+                vrc_composite( color, e[k], done );
+                if( COUNT )
+                    nSamples += done ? 0u : 1u;
+                done = done || ( color.w > VRC_EARLY_EXIT );
+            }
+            return true;
+        }
+    }
+    constexpr int TAILG = GROUP >= 4 ? GROUP / 2 : 1;
+    while( travel > 0.0f && !done )
+    {
+        uint32_t cnt = 0;
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+        {
+            cnt += travel > 0.0f ? 1u : 0u;
+            travel -= stepSize;
+        }
+        vrc_f4 e[TAILG];
+        vrc_preint_group< CLAMP, FIXED, TRILINEAR, VALUE, ATLAS_T, TAILG, true >( sm, pos, s.step, fp, atlas, table, cls, cnt,
+                                                                                 carry, first, e );
+#pragma unroll
+        for( int k = 0; k < TAILG; ++k )
+        {
+            const bool active = ( (uint32_t)k < cnt ) && !done;
+            vrc_composite( color, e[k], done );
+            if( COUNT )
+                nSamples += active ? 1u : 0u;
+            done = done || ( color.w > VRC_EARLY_EXIT );
+        }
+    }
+    return done;
+}
+
+/* One brick of one ray of a pre-integrated frame: vrc_shade_brick's decisions -- the slot's 64-bit base moved into the
+ * lane's pointer (BIG), the uniform march of a slot known to hold one value v, taken by the whole wave or not at all,
+ * from lut[v] (the diagonal of the value-indexed table is a copy of that table: E(v, v) for every sample of the visit)
+ * -- around the segment above.  lut is read by that march alone */
+template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, bool BIG, typename SRC >
+VRC_HD bool vrc_preint_brick( const vrc_frame& f, const vrc_dev_node& n, const SRC& src, const ATLAS_T* __restrict__ atlas,
+                              const vrc_f4* lut, const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples )
+{
+    static_assert( vrc_mode_is_preint( MODE ), "a pre-integrated mode" );
+    constexpr bool TRILINEAR = MODE == VRC_MODE_PREINT_TRILINEAR;
+    constexpr bool VALUE = !TRILINEAR && sizeof( ATLAS_T ) == 1;
+    if constexpr( BIG )
+    {
+        vrc_dev_node local = n;
+        local.slotBase = 0u;
+        const ATLAS_T* slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
+        return vrc_preint_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, false, SRC >( f, local, src, slot, lut, cls, color, nSamples );
+    }
+    else
+    {
+        if constexpr( VALUE )
+        {
+            uint32_t word = 0u;
+            if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
+                word = f.slotInfo[n.slotInfoIndex - 1u];
+            bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
+#if defined( __HIP_DEVICE_COMPILE__ )
+            general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
+#endif
+            if( !general )
+            {
+                const vrc_segment& s = src.distOnly();
+                return vrc_march_segment_as< CLAMP, COUNT, FIXED, ATLAS_T, VRC_GROUP, vrc_f4, false, true >(
+                    f, n, s, atlas, lut, color, nSamples, 0.0f, nullptr, lut[word & 0xFFu] );
+            }
+        }
+        const vrc_segment& s = src.full();
+        return vrc_preint_segment< CLAMP, COUNT, FIXED, TRILINEAR, VALUE, ATLAS_T,
+                                   VALUE ? VRC_PREINT_GROUP : VRC_PREINT_GROUP_TEXEL >( f, n, s, atlas, cls, color,
+                                                                                                nSamples );
+    }
+}
+
+/* ------------------------------------------------------------------------------------------
  * Reference-order pixel: the O(nodeCount) loop of Renderer.cu:172-227, nodes in host order.
  * ---------------------------------------------------------------------------------------- */
 /* MODE: how a sample is fetched and classified.
@@ -4234,7 +4697,7 @@ VRC_HD void vrc_pixel_reference_order( const vrc_frame& f, const vrc_dev_node* _
                                        uint32_t nCandidates = 0, vrc_cdepth_state* cdepth = nullptr )
 {
     /* (cdepth: the ray's crossing state, the depth-tracking composite modes only) */
-    if constexpr( !vrc_mode_is_shade( MODE ) && !vrc_mode_is_cdepth( MODE ) ) /* (a shaded frame is defined on the cudaRaycaster variant's sample set) */
+    if constexpr( !vrc_mode_is_shade( MODE ) && !vrc_mode_is_cdepth( MODE ) && !vrc_mode_is_preint( MODE ) ) /* (a shaded frame is defined on the cudaRaycaster variant's sample set) */
         if( f.variant == VRC_VARIANT_GL && f.samplesPerPixel > 1u )
         {
             vrc_pixel_gl_supersampled< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, nodes, atlas, lut, cls, pixelBuffer,
@@ -4279,6 +4742,13 @@ VRC_HD void vrc_pixel_reference_order( const vrc_frame& f, const vrc_dev_node* _
             const vrc_segment_ready src = { s };
             if( vrc_cdepth_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_ready >( f, n, src, atlas, lut, cls, color,
                                                                                                nSamples, *cdepth ) )
+                break;
+        }
+        else if constexpr( vrc_mode_is_preint( MODE ) )
+        {
+            const vrc_segment_ready src = { s };
+            if( vrc_preint_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_ready >( f, n, src, atlas, lut, cls, color,
+                                                                                               nSamples ) )
                 break;
         }
         else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, lut, cls, color,
@@ -4478,6 +4948,13 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                     const vrc_segment_from_interval src = { r, iv, f.stepSize };
                     if( vrc_cdepth_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_from_interval >(
                             f, n, src, atlas, lut, cls, color, nSamples, *cdepth ) )
+                        finished = true;
+                }
+                else if constexpr( vrc_mode_is_preint( MODE ) )
+                {
+                    const vrc_segment_from_interval src = { r, iv, f.stepSize };
+                    if( vrc_preint_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_from_interval >(
+                            f, n, src, atlas, lut, cls, color, nSamples ) )
                         finished = true;
                 }
                 else if( vrc_march_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, r, iv, atlas, lut, cls, color,

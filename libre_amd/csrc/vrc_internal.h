@@ -158,6 +158,8 @@ struct vrc_raycast_args
     bool shade; /* a shaded composite frame (VRC_OPT_SHADING = 1; frame.shadeAmbient set): vrc_launch_raycast_shade marches it */
     bool cdepth; /* a composite frame that keeps the depth of its rays' crossings (VRC_OPT_COMPOSITE_DEPTH above 0; frame.cdepthTau,
                   * frame.mipMax and frame.mipDepth set): vrc_launch_raycast_cdepth marches it */
+    bool preint; /* a pre-integrated composite frame (VRC_OPT_PREINTEGRATION = 1; frame.preintTable set):
+                  * vrc_launch_raycast_preint marches it */
 };
 
 /* the one dispatch of a single-launch march: with a's stop event if it has one (the dispatch then carries its own
@@ -207,7 +209,7 @@ hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream );
 static inline bool vrc_walk_replay_eligible( const vrc_raycast_args& a )
 {
     return a.gridDda && a.gridTable && !a.packed && !a.linear && a.elemBytes == 1 && !a.bigAtlas && !a.clamp &&
-           a.fixedStepping && a.ertParts <= 1 && !a.depthSplit && !a.shade && !a.cdepth && VRC_TILE_W == 8u;
+           a.fixedStepping && a.ertParts <= 1 && !a.depthSplit && !a.shade && !a.cdepth && !a.preint && VRC_TILE_W == 8u;
 }
 static inline int vrc_walk_replay_group( const vrc_raycast_args& a )
 {
@@ -273,6 +275,15 @@ hipError_t vrc_launch_raycast_shade( const vrc_raycast_args& a, hipStream_t stre
 /* the depth of a composite frame (vrc_kernels_cdepth.hip; VRC_OPT_COMPOSITE_DEPTH above 0): a.cdepth, frame.cdepthTau,
  * frame.mipMax and frame.mipDepth set; the forms, atlas types and lut of vrc_launch_raycast_shade */
 hipError_t vrc_launch_raycast_cdepth( const vrc_raycast_args& a, hipStream_t stream );
+
+/* a pre-integrated composite frame (vrc_kernels_preint.hip; VRC_OPT_PREINTEGRATION = 1): a.preint and frame.preintTable
+ * set; the forms, atlas types and lut of vrc_launch_raycast_shade (lut is what a uniform brick is marched from) */
+hipError_t vrc_launch_raycast_preint( const vrc_raycast_args& a, hipStream_t stream );
+/* its table (vrc_core.h: vrc_preint_table_entry): 256 x 256 entries of `kind` (VRC_PREINT_VALUE, VRC_PREINT_TEXEL) from
+ * the 256-texel transfer function tf; lut: the classified table the value-indexed diagonal copies (may be NULL for
+ * VRC_PREINT_TEXEL).  One launch, float64 */
+hipError_t vrc_launch_build_preint( const float* tf, const vrc_f4* lut, vrc_f4* table, vrc_lut_params p, int kind,
+                                    hipStream_t stream );
 
 /* LDS-staged form (vrc_kernels_lds.hip): needs gridTable, !clamp, 8x8 tiles */
 hipError_t vrc_launch_raycast_lds( const vrc_raycast_args& a, hipStream_t stream );

@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("LIVRE_HIP_HOST_LIB") or os.path.join(_HERE, "lib", "l
 OPT_SHADING, OPT_SHADING_AMBIENT = 29, 30
 # "The depth of a composite frame": the option App.set_composite_depth sets
 OPT_COMPOSITE_DEPTH = 31
+# "A pre-integrated composite frame": the option App.set_preintegration sets
+OPT_PREINTEGRATION = 32
 
 
 class Params(C.Structure):  # lvh_params
@@ -176,6 +178,12 @@ class App:
         """The depth of a composite frame (VRC_OPT_COMPOSITE_DEPTH): 0 turns it off; 1 ... 999 is the opacity threshold in
         thousandths at which every ray's depth is kept, which App.pick then answers from; reaches every renderer slot."""
         self.set_option(OPT_COMPOSITE_DEPTH, int(threshold))
+
+    def set_preintegration(self, on):
+        """A pre-integrated composite frame (VRC_OPT_PREINTEGRATION): every step of a composite frame is classified from a
+        table pre-integrated over the values at its two ends, instead of every sample on its own; reaches every renderer
+        slot."""
+        self.set_option(OPT_PREINTEGRATION, 1 if on else 0)
 
     def get_option(self, option):
         v = C.c_int64()

@@ -335,7 +335,8 @@ int lvh_app_set_option( lvh_app* app, int option, int64_t value )
     if( option == VRC_OPT_PROJECTION || option == VRC_OPT_MIP_SKIP || option == VRC_OPT_MIP_FOLD ||
         option == VRC_OPT_MIP_DEPTH || option == VRC_OPT_MIP_DEPTH_CUE || option == VRC_OPT_RAY_CACHE ||
         option == VRC_OPT_WALK_CACHE || option == VRC_OPT_WALK_CACHE_BUDGET || option == VRC_OPT_SHADING ||
-        option == VRC_OPT_SHADING_AMBIENT || option == VRC_OPT_COMPOSITE_DEPTH )
+        option == VRC_OPT_SHADING_AMBIENT || option == VRC_OPT_COMPOSITE_DEPTH ||
+        option == VRC_OPT_PREINTEGRATION )
     {
         /* how the app forms its pixels: every renderer it has, and every one it makes later (lvh_app_set_frames_in_flight) */
         try

@@ -20,6 +20,9 @@ WALK_CACHE_ALWAYS = 2  # VRC_OPT_WALK_CACHE: replay also where most visits gathe
 OPT_WALK_LEAN_USED = 28  # read-only: 1 = the last render replayed lean lists
 OPT_SHADING, OPT_SHADING_AMBIENT = 29, 30  # a shaded composite frame: 0 / 1, and the ambient share in thousandths (default 250)
 OPT_COMPOSITE_DEPTH = 31  # the depth of a composite frame: 0 (off), or the opacity threshold in thousandths, 1 ... 999
+OPT_PREINTEGRATION = 32  # a pre-integrated composite frame: 0 / 1
+OPT_PREINT_BUILDS = 33  # read-only: how many pre-integrated tables the context has built
+PREINT_VALUE, PREINT_TEXEL = 0, 1  # kinds of table vrc_get_preintegrated_table reports
 PROJECTION_COMPOSITE, PROJECTION_MIP, PROJECTION_ISO = 0, 1, 2
 MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2
 VARIANT_CUDARAYCASTER, VARIANT_GLRAYCASTER = 0, 1
@@ -72,7 +75,7 @@ EXPORTS = [
     "vrc_pool_histogram", "vrc_pool_enable_histograms", "vrc_frame_histogram", "vrc_get_frame_histogram",
     "vrc_update", "vrc_pre_render", "vrc_set_row_map", "vrc_set_framebuffer", "vrc_get_framebuffer", "vrc_render",
     "vrc_post_render", "vrc_synchronize", "vrc_get_stats", "vrc_get_ray_counts", "vrc_get_projection_values", "vrc_get_projection_depths",
-    "vrc_set_isosurface", "vrc_get_projection_gradients", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
+    "vrc_set_isosurface", "vrc_get_projection_gradients", "vrc_get_preintegrated_table", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
     "vrc_comm_unique_id", "vrc_comm_create", "vrc_comm_destroy", "vrc_comm_info", "vrc_gather_tiles",
 ]
 COMM_ID_BYTES = 128
@@ -148,6 +151,8 @@ def load_library(path=None):
     if hasattr(L, "vrc_set_isosurface"):
         L.vrc_set_isosurface.argtypes = [vp, C.c_float, C.c_float]
         L.vrc_get_projection_gradients.argtypes = [vp, vp]
+    if hasattr(L, "vrc_get_preintegrated_table"):
+        L.vrc_get_preintegrated_table.argtypes = [vp, vp, C.POINTER(C.c_int)]
     L.vrc_comm_unique_id.argtypes = [C.c_char_p]
     L.vrc_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     L.vrc_comm_destroy.argtypes = [vp]
@@ -195,3 +200,15 @@ def projection_gradients(L, ctx, width, height):
     g = np.empty((height, width, 3), dtype=np.float32)
     check(L, L.vrc_get_projection_gradients(ctx, g.ctypes.data))
     return g
+
+
+def preintegrated_table(L, ctx):
+    """vrc_get_preintegrated_table: the table the last pre-integrated vrc_render of ctx used, as a float32 array of
+    256 x 256 x 4 (row, column, rgba), and its kind (PREINT_VALUE or PREINT_TEXEL)."""
+    import numpy as np
+    if not hasattr(L, "vrc_get_preintegrated_table"):
+        raise VrcError(VRC_EUNSUPPORTED, "this libvrc_hip.so has no vrc_get_preintegrated_table")
+    t = np.empty((256, 256, 4), dtype=np.float32)
+    kind = C.c_int(-1)
+    check(L, L.vrc_get_preintegrated_table(ctx, t.ctypes.data, C.byref(kind)))
+    return t, kind.value
