@@ -115,8 +115,16 @@ def _values(brick, c, k, vpw, filter_mode):
     return lo, others
 
 
-def render(s, filter_mode=0, prev=None, _mutate=None):
-    """One pass over s.nodes[:s.n_nodes]; prev: the Result of the passes before it (the running maximum)."""
+def render(s, filter_mode=0, prev=None, _mutate=None, trace=None):
+    """One pass over s.nodes[:s.n_nodes]; prev: the Result of the passes before it (the running maximum).
+
+    trace: a list that receives, per brick of the list that some ray meets and in list order, what every such ray takes
+    from it (tests/skip_window.py predicts the sample count with skipping from that): a dict of `node` (the index in
+    the list), `rays` (flat pixel indices) and, per ray, `tn` (the entry distance), `c_lo` / `c_hi` (the samples it
+    surely takes / takes with every doubtful one) and the largest and smallest value among them as intervals --
+    `max_lo` (over the certain samples at their smallest reading, -inf without one) <= `max_hi` (over every possible
+    sample at its largest reading), `min_lo` <= `min_hi` likewise; `samples`: (smallest reading, largest reading, certain?, possible?), each rays x
+    samples in march order (absent for a grazed brick's one doubtful sample).  Nothing else changes."""
     assert _mutate is None or _mutate in MUTATIONS, _mutate
     view, rd = s.view, s.render
     step = 1.0 / float(rd.samplesPerRay)
@@ -194,6 +202,13 @@ def render(s, filter_mode=0, prev=None, _mutate=None):
                 doubt(g[mask], there[mask])
             maybe[g] = True
             c_hi[g] += np.where(hit[g], 0, 1)
+            if trace is not None and (~hit[g]).any():  # one sample or none, of any of its readings
+                ghi, only = vlo.copy(), ~hit[g]
+                for mask, there in others:
+                    ghi = np.where(mask, np.maximum(ghi, there), ghi)
+                zero = np.zeros(int(only.sum()), dtype=np.int64)
+                trace.append(dict(node=i, rays=g[only], tn=tn[g][only], c_lo=zero, c_hi=zero + 1,
+                                  max_lo=zero - np.inf, max_hi=ghi[only], min_lo=vlo[only], min_hi=zero + np.inf))
         p = np.nonzero(hit)[0]
         if p.size == 0:
             continue
@@ -228,6 +243,15 @@ def render(s, filter_mode=0, prev=None, _mutate=None):
         counts[p] += count
         c_lo[p] += n_sure
         c_hi[p] += count + next_tie
+        if trace is not None:
+            vhi = vlo.copy()
+            for mask, there in others:
+                vhi = np.where(mask, np.maximum(vhi, there), vhi)
+            poss = kidx < (count + next_tie)[:, None]
+            trace.append(dict(node=i, rays=p, tn=tn[p], c_lo=n_sure, c_hi=count + next_tie,
+                              max_lo=np.where(sure, vlo, -np.inf).max(axis=1), max_hi=np.where(poss, vhi, -np.inf).max(axis=1),
+                              min_lo=np.where(poss, vlo, np.inf).min(axis=1), min_hi=np.where(sure, vhi, np.inf).min(axis=1),
+                              samples=(vlo, vhi, sure, poss)))
         # doubtful: the larger readings of samples near faces, the barely-taken last and barely-not-taken next sample
         for mask, there in others:
             sel = np.nonzero(mask & (kidx < count[:, None]))

@@ -13,6 +13,7 @@ import mip_scenes
 import nongrid
 import orc
 import scenes
+import skip_window
 import voxel_types
 from fold_ref import FOLD_MAX, FOLD_MEAN, FOLD_MIN
 from gpu_run import GpuScene
@@ -224,6 +225,18 @@ def test_minimum_skipping_and_uniform_bricks_change_no_pixel(name, filter_mode):
         assert frames[0, 1][1] == n, "uniform bricks: the same count"
         print("%s filter %d: samples %d, with skipping %d / %d" % (name, filter_mode, n, frames[1, 0][1], frames[1, 1][1]))
         assert frames[1, 0][1] < n and frames[1, 1][1] < n
+        if not filter_mode:
+            # how many, not only fewer (tests/skip_window.py: the window predicted from mip_ref and the smallest voxel
+            # NumPy finds in every uploaded brick), for the grid walk and for the loop in list order
+            w = skip_window.of(name, skip_window.MIN, skip_window.DDA)
+            for uniform in (0, 1):
+                skip_window.check(w, frames[1, uniform][1], "%s minimum, grid walk, uniform bricks %d" % (name, uniform))
+            for uniform in (0, 1):
+                _fold(g, FOLD_MIN, skip=1, uniform=uniform)
+                fb1, n1, st = g.render(kernel=vrc.KERNEL_REFERENCE_ORDER)
+                assert st.kernel_variant == vrc.KERNEL_REFERENCE_ORDER and np.array_equal(fb1, fb)
+                skip_window.check(skip_window.of(name, skip_window.MIN, skip_window.REFORDER), n1,
+                                  "%s minimum, reference order, uniform bricks %d" % (name, uniform))
 
 
 @pytest.mark.parametrize("kernel", [vrc.KERNEL_REFERENCE_ORDER, vrc.KERNEL_GRID_DDA], ids=["reforder", "dda"])

@@ -13,6 +13,7 @@ import mip_ref
 import mip_scenes
 import nonfinite
 import scenes
+import skip_window
 import voxel_types
 from gpu_run import GpuScene
 from iso_ref import ISO
@@ -197,6 +198,17 @@ def test_skipping_and_uniform_bricks_change_no_bit(name, filter_mode):
         print("%s filter %d: samples %d, with skipping %d / %d" % (name, filter_mode, n, out[1, 0][1], out[1, 1][1]))
         assert out[0, 1][1] == n and out[1, 1][1] == out[1, 0][1], "uniform bricks: the same count"
         assert out[1, 0][1] < n
+        if not filter_mode:
+            # how many, not only fewer (tests/skip_window.py: the window predicted from mip_ref, the largest voxel NumPy
+            # finds in every uploaded brick and the header's rule), for the grid walk and for the loop in list order
+            skip_window.check(skip_window.iso_of(name, skip_window.DDA), out[1, 0][1], "%s isosurface, grid walk" % name)
+            for uniform in (0, 1):
+                _iso(g, ISO[name], skip=1, uniform=uniform)
+                o = _frame(g, kernel=vrc.KERNEL_REFERENCE_ORDER)
+                assert iso_ref.check(r, o[2], o[3], o[4], o[5], iso_ref.tolerance(s, filter_mode))[0] == 0
+                skip_window.check(skip_window.iso_of(name, skip_window.REFORDER), o[1],
+                                  "%s isosurface, reference order, uniform bricks %d" % (name, uniform))
+            _iso(g, ISO[name], skip=0, uniform=0)
         # without skipping the count is the MIP frame's without skipping
         _opt(g, vrc.OPT_PROJECTION, vrc.PROJECTION_MIP)
         _opt(g, vrc.OPT_MIP_FOLD, 0)

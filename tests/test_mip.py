@@ -9,6 +9,7 @@ import mip_ref
 import mip_scenes
 import nongrid
 import orc
+import skip_window
 import voxel_types
 from gpu_run import GpuScene
 from libre_amd import vrc
@@ -121,6 +122,18 @@ def test_skipping_and_uniform_bricks_change_no_pixel(name, filter_mode):
         _count_ok(r, n, name)
         if name in ("skip", "skip16"):
             assert frames[1, 0][1] < n and frames[1, 1][1] < n
+        if name in ("skip", "skip16") and not filter_mode:
+            # how many, not only fewer: the window tests/skip_window.py predicts from mip_ref and the words NumPy finds
+            # in the uploaded bricks (tests/test_slot_words_cpu.py: it is narrow and lies below the count without skipping)
+            w = skip_window.of(name, skip_window.MAX, skip_window.DDA)
+            for uniform in (0, 1):
+                skip_window.check(w, frames[1, uniform][1], "%s grid walk, uniform bricks %d" % (name, uniform))
+            for uniform in (0, 1):  # ... and the loop in list order
+                _mip(g, skip=1, uniform=uniform)
+                fb1, n1, st = g.render(kernel=vrc.KERNEL_REFERENCE_ORDER)
+                assert st.kernel_variant == vrc.KERNEL_REFERENCE_ORDER and np.array_equal(fb1, fb)
+                skip_window.check(skip_window.of(name, skip_window.MAX, skip_window.REFORDER), n1,
+                                  "%s reference order, uniform bricks %d" % (name, uniform))
 
 
 @pytest.mark.parametrize("kernel", [vrc.KERNEL_REFERENCE_ORDER, vrc.KERNEL_GRID_DDA], ids=["reforder", "dda"])
