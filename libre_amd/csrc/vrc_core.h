@@ -52,7 +52,6 @@
 #error "developer switches of the raycast kernels need -DVRC_DEV_BUILD (the product is built without any of them)"
 #endif
 
-
 #include <stdint.h>
 #include <type_traits>
 
@@ -126,6 +125,7 @@ struct vrc_dev_node
 #define VRC_SLOT_VALUE_MASK 0xFFFFu
 #define VRC_SLOT_KNOWN 0x10000u
 #define VRC_SLOT_MIXED 0x20000u
+VRC_HD bool vrc_slot_holds_one_value( uint32_t word ) { return ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) == VRC_SLOT_KNOWN; }
 
 /* Frame constants, derived on the host exactly as Renderer.cu:159-170 does per thread. */
 struct vrc_frame
@@ -1850,7 +1850,6 @@ VRC_HD void vrc_packed_offsets( const vrc_sampler& s, vrc_fixpos& p, uint32_t bi
 #define VRC_PGROUP16 12 /* 16-bit voxels: four registers of taps per sample in flight (6 / 8 / 12 measured: 2.03 / 1.92 / 1.80 ms on C2) */
 #endif
 
-
 /* March one brick segment through the packed atlas (Renderer.cu:206-223 with the trilinear fetch).  Organised as
  * vrc_march_segment_as: whole groups without per-sample tests while more than GROUP steps remain, the early-exit
  * test once per group with an exact replay, a general tail.  tab: vrc_cls8_entry table.  E: vrc_f4, or vrc_f2
@@ -2624,7 +2623,7 @@ VRC_HD void vrc_mean_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc
         if( march && n.slotInfoIndex != 0u && f.slotInfo != nullptr )
         {
             const uint32_t word = f.slotInfo[n.slotInfoIndex - 1u];
-            if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) == VRC_SLOT_KNOWN )
+            if( vrc_slot_holds_one_value( word ) )
             {
                 const uint32_t steps = vrc_step_count( s.dist, f.stepSize );
                 sum += (ACC)( word & VRC_SLOT_VALUE_MASK ) * (ACC)steps;
@@ -2964,7 +2963,7 @@ VRC_HD bool vrc_iso_brick( const vrc_frame& f, const vrc_dev_node& n, uint32_t n
         if( march && n.slotInfoIndex != 0u && f.slotInfo != nullptr )
         {
             const uint32_t word = f.slotInfo[n.slotInfoIndex - 1u];
-            if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) == VRC_SLOT_KNOWN )
+            if( vrc_slot_holds_one_value( word ) )
             {
                 const D value = (D)( word & VRC_SLOT_VALUE_MASK );
                 if( value >= thr && ( s.tNear < z.d || ( s.tNear == z.d && value > z.v ) ) )
@@ -3021,7 +3020,7 @@ VRC_HD void vrc_slot_local_voxel( uint32_t e, uint32_t sbx, uint32_t sby, uint32
 }
 
 /* The addressing and the difference of a gradient, shared by the gradient of an isosurface hit (below) and the gradient of
- * every sample of a shaded composite frame (vrc_shade_group): a voxel coordinate clamped to the slot, its two neighbours
+ * every sample of a shaded composite frame (vrc_shade_policy): a voxel coordinate clamped to the slot, its two neighbours
  * along an axis clamped the same way, and the difference of the two stored voxels.  Whatever coordinate goes into
  * vrc_gradient_clamp, what comes out lies in [0, dim), and so do the two neighbours of such a coordinate: a gather at
  * them stays inside the slot. */
@@ -3161,7 +3160,7 @@ VRC_HD bool vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
             if( march && f.slotInfo != nullptr )
             {
                 const uint32_t word = f.slotInfo[n.slotInfoIndex - 1u];
-                if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) == VRC_SLOT_KNOWN )
+                if( vrc_slot_holds_one_value( word ) )
                 {
                     if constexpr( DEPTH )
                     {
@@ -3242,36 +3241,15 @@ VRC_HD vrc_f4 vrc_classify_mip( const vrc_f4* tfp, float d, const vrc_classifier
 }
 
 /* ------------------------------------------------------------------------------------------
- * EXTENSION: a shaded composite frame (VRC_OPT_SHADING = 1; include/vrc_hip.h, "A shaded composite frame").
+ * The grouped march of the composite EXTENSIONS below (shaded, depth-tracking, pre-integrated): one front that takes a
+ * group's samples, one segment loop around it, one wrapper around a brick visit.  What a mode makes of the values is its
+ * policy (vrc_shade_policy, vrc_cdepth_policy, vrc_preint_policy).
  *
- * The composite frame with one change: the colour a sample adds is multiplied by the headlight term of the isosurface
- * frame, s = ambient + (1 - ambient) |G.dir| / |G| (vrc_iso_shade), G the central differences of the stored voxels around
- * the voxel the POINT sampler addresses at the sample's position (under both filters; vrc_gradient_* above: the
- * isosurface gradient's clamping and differencing), times the node's voxels per world unit.  The opacity is not
- * touched, so the samples, their order, early ray termination and the alpha channel are the unshaded frame's; with
- * ambient = 1, and wherever G is 0, so is the whole pixel.
- *
- * Sample positions, addresses, gathers and classification are those of the unshaded march of the same sampler,
- * expression for expression (vrc_group_indices_fixed, vrc_group_indices, vrc_march_segment_linear), in the control
- * structure of vrc_march_segment_as: whole groups while more than a group of steps remains, the early-exit test once per
- * group with the exact replay, a masked tail.  Per group: centre addresses and gathers, classification, a ballot of
- * alpha' > 0, the six neighbour gathers of every sample that has one -- skipped by the lanes whose sample is transparent
- * (its e is 0 whatever s is) and by the wave when no lane needs them --, the differences, s, the blends.  A neighbour's
- * address is the centre's with one per-axis part swapped (the LDS tables under fixed-point stepping).
- * Groups of VRC_SHADE_GROUP = 4: 24 neighbour voxels in flight beside four classified samples; 8 x 6 do not fit the
- * registers of four waves per SIMD (DESIGN.md has the table of the instances).
+ * Sample positions, addresses and gathers are those of the unshaded march of the same sampler, expression for expression
+ * (vrc_group_indices_fixed, vrc_group_indices, vrc_march_segment_linear), in the control structure of
+ * vrc_march_segment_as: whole groups while more than a group of steps remains, one test per group with the exact replay
+ * from the saved colour, a masked tail.
  * ---------------------------------------------------------------------------------------- */
-#define VRC_MODE_SHADE 10           /* point samples: the classified table for 8-bit voxels, vrc_classify otherwise */
-#define VRC_MODE_SHADE_TRILINEAR 11 /* trilinear samples by gathers */
-VRC_HD constexpr bool vrc_mode_is_shade( int mode ) { return mode == VRC_MODE_SHADE || mode == VRC_MODE_SHADE_TRILINEAR; }
-#define VRC_SHADE_GROUP 4
-#if defined( VRC_SHADE_SKIP_HOOK ) && !defined( __HIPCC__ )
-/* host test builds only (tests/cpu_harness/shade_harness.cpp): 0 = gather the gradient of transparent samples too; and
- * how many samples were taken with / without their gradient */
-static int vrc_shade_skip_hook = 1;
-static unsigned long long vrc_shade_gradients[2];
-#endif
-
 /* per-axis parts of a slot-local element offset (vrc_voxel_address = x part + y part + z part + slotBase): the LDS
  * tables where the kernel filled them (fixed-point stepping: coordinates below 256), the arithmetic form elsewhere */
 template < bool FIXED >
@@ -3288,18 +3266,31 @@ VRC_HD uint32_t vrc_shade_part( const vrc_sampler& s, int axis, uint32_t u )
     return vrc_mul24( u >> VRC_MB_SHIFT, s.czz ) + ( u << 6 ) - VRC_MB_FIX_Z( u );
 }
 
-/* N samples of a segment: e[k] = (rgb alpha' s, alpha') of sample k; MASKED: only the first cnt are the reference's, the
- * others read element 0 and come out as zeros (an exact no-op in the blend) */
-template < bool CLAMP, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T, int N, bool MASKED >
-VRC_HD void vrc_shade_group( const vrc_frame& f, const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
-                             const ATLAS_T* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
-                             const vrc_f3& dir, uint32_t cnt, vrc_f4* e )
+/* the value of a sample: the stored voxel of a point sample, the interpolated float of a trilinear one */
+template < bool TRILINEAR, typename ATLAS_T >
+struct vrc_group_value
 {
-    typedef typename vrc_density< ATLAS_T >::type D;
+    typedef typename vrc_density< ATLAS_T >::type type;
+};
+template < typename ATLAS_T >
+struct vrc_group_value< true, ATLAS_T >
+{
+    typedef float type;
+};
+
+/* The front of a group: the next N samples of a segment, pos / fp advanced past them: every address, then every gather,
+ * then use( k, value of sample k ) for k = 0 ... N - 1 (the value: vrc_group_value< TRILINEAR, ATLAS_T >::type; handed
+ * over one by one, the interpolation of a trilinear sample right before what the mode does with it, as the unshaded
+ * marches order the two).  VOXEL: ux/uy/uz[k] is the voxel the POINT sampler addresses at sample k, under both filters.
+ * MASKED: only the first cnt are the reference's; the others read element 0 */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, typename ATLAS_T, int N, bool MASKED, bool VOXEL, typename USE >
+VRC_HD void vrc_group_values( const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
+                              const ATLAS_T* __restrict__ atlas, uint32_t cnt, const USE& use,
+                              [[maybe_unused]] uint32_t* ux = nullptr, [[maybe_unused]] uint32_t* uy = nullptr,
+                              [[maybe_unused]] uint32_t* uz = nullptr )
+{
     static_assert( !( TRILINEAR && FIXED ), "the trilinear gather march steps in float" );
     static_assert( !( CLAMP && FIXED ), "the clamped sampler steps in float" );
-    uint32_t ux[N], uy[N], uz[N]; /* the voxel the point sampler addresses */
-    /* 1. the sample itself: addresses, gathers, classification */
     if constexpr( TRILINEAR )
     {
         vrc_taps t[N];
@@ -3311,16 +3302,19 @@ VRC_HD void vrc_shade_group( const vrc_frame& f, const vrc_sampler& sm, vrc_f3& 
             const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
             const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
             t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
-            float qx = lx, qy = ly, qz = lz;
-            if( CLAMP )
+            if constexpr( VOXEL )
             {
-                qx = fminf( fmaxf( qx, 0.0f ), sm.hix );
-                qy = fminf( fmaxf( qy, 0.0f ), sm.hiy );
-                qz = fminf( fmaxf( qz, 0.0f ), sm.hiz );
+                float qx = lx, qy = ly, qz = lz;
+                if( CLAMP )
+                {
+                    qx = fminf( fmaxf( qx, 0.0f ), sm.hix );
+                    qy = fminf( fmaxf( qy, 0.0f ), sm.hiy );
+                    qz = fminf( fmaxf( qz, 0.0f ), sm.hiz );
+                }
+                ux[k] = (uint32_t)(int)qx;
+                uy[k] = (uint32_t)(int)qy;
+                uz[k] = (uint32_t)(int)qz;
             }
-            ux[k] = (uint32_t)(int)qx;
-            uy[k] = (uint32_t)(int)qy;
-            uz[k] = (uint32_t)(int)qz;
             pos.x += step.x;
             pos.y += step.y;
             pos.z += step.z;
@@ -3336,17 +3330,18 @@ VRC_HD void vrc_shade_group( const vrc_frame& f, const vrc_sampler& sm, vrc_f3& 
             }
 #pragma unroll
         for( int k = 0; k < N; ++k )
-        {
-            const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
-            const vrc_f4 c = vrc_classify( lut, vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz ), cls );
-            e[k] = ( !MASKED || (uint32_t)k < cnt ) ? c : z;
-        }
+            use( k, vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz ) );
     }
     else
     {
         uint32_t idx[N];
-        if constexpr( FIXED )
+        if constexpr( !VOXEL && FIXED )
+            vrc_group_indices_fixed< N >( sm, fp, idx );
+        else if constexpr( !VOXEL )
+            vrc_group_indices< CLAMP, N >( sm, pos, step, idx );
+        else if constexpr( FIXED )
         {
+            /* (vrc_group_indices_fixed with the voxel kept) */
 #pragma unroll
             for( int k = 0; k < N; ++k )
             {
@@ -3362,17 +3357,12 @@ VRC_HD void vrc_shade_group( const vrc_frame& f, const vrc_sampler& sm, vrc_f3& 
             }
 #pragma unroll
             for( int k = 0; k < N; ++k )
-            {
-#if defined( __HIP_DEVICE_COMPILE__ )
                 idx[k] = vrc_shade_part< true >( sm, 0, ux[k] ) + vrc_shade_part< true >( sm, 1, uy[k] ) +
                          vrc_shade_part< true >( sm, 2, uz[k] ) + sm.slotBase;
-#else
-                idx[k] = vrc_voxel_address( sm, ux[k], uy[k], uz[k] );
-#endif
-            }
         }
         else
         {
+            /* (vrc_group_indices with the voxel kept) */
             VRC_FAST_FP
 #pragma unroll
             for( int k = 0; k < N; ++k )
@@ -3395,91 +3385,43 @@ VRC_HD void vrc_shade_group( const vrc_frame& f, const vrc_sampler& sm, vrc_f3& 
                 pos.z += step.z;
             }
         }
-        D d[N];
+        typename vrc_density< ATLAS_T >::type d[N];
 #pragma unroll
         for( int k = 0; k < N; ++k )
-            d[k] = (D)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? idx[k] : 0u );
+            d[k] = (typename vrc_density< ATLAS_T >::type)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? idx[k] : 0u );
 #pragma unroll
         for( int k = 0; k < N; ++k )
-        {
-            if constexpr( PERSAMPLE )
-            {
-                const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
-                const vrc_f4 c = vrc_classify( lut, (float)d[k], cls );
-                e[k] = ( !MASKED || (uint32_t)k < cnt ) ? c : z;
-            }
-            else
-                e[k] = lut[( !MASKED || (uint32_t)k < cnt ) ? d[k] : 256u]; /* (entry 256: all zeros) */
-        }
-    }
-    /* 2. which samples need their gradient: a transparent one adds (0, 0) whatever s is */
-    bool need[N], any = false;
-#pragma unroll
-    for( int k = 0; k < N; ++k )
-    {
-        const bool taken = !MASKED || (uint32_t)k < cnt;
-        need[k] = taken && e[k].w > 0.0f;
-#if defined( VRC_SHADE_SKIP_HOOK ) && !defined( __HIPCC__ )
-        if( vrc_shade_skip_hook == 0 )
-            need[k] = taken;
-        if( taken )
-            ++vrc_shade_gradients[need[k] ? 1 : 0];
-#endif
-        any = any || need[k];
-    }
-#if defined( __HIP_DEVICE_COMPILE__ )
-    any = __builtin_amdgcn_ballot_w64( any ) != 0ull;
-#endif
-    if( !any )
-        return;
-    /* 3. the six neighbours, back to back.  Every coordinate goes through vrc_gradient_clamp and
-     * vrc_gradient_neighbours: all of them lie inside the slot, whatever the sampler made of the position */
-    ATLAS_T vLo[N][3], vHi[N][3];
-#pragma unroll
-    for( int k = 0; k < N; ++k )
-    {
-#pragma unroll
-        for( int a = 0; a < 3; ++a )
-            vLo[k][a] = vHi[k][a] = (ATLAS_T)0;
-        if( need[k] )
-        {
-            const uint32_t c[3] = { vrc_gradient_clamp( ux[k], f.slotDim[0] ), vrc_gradient_clamp( uy[k], f.slotDim[1] ),
-                                    vrc_gradient_clamp( uz[k], f.slotDim[2] ) };
-            const uint32_t part[3] = { vrc_shade_part< FIXED >( sm, 0, c[0] ), vrc_shade_part< FIXED >( sm, 1, c[1] ),
-                                       vrc_shade_part< FIXED >( sm, 2, c[2] ) };
-#pragma unroll
-            for( int a = 0; a < 3; ++a )
-            {
-                uint32_t lo, hi;
-                vrc_gradient_neighbours( c[a], f.slotDim[a], lo, hi );
-                const uint32_t rest = part[( a + 1 ) % 3] + part[( a + 2 ) % 3] + sm.slotBase;
-                vHi[k][a] = vrc_gather( atlas, vrc_shade_part< FIXED >( sm, a, hi ) + rest );
-                vLo[k][a] = vrc_gather( atlas, vrc_shade_part< FIXED >( sm, a, lo ) + rest );
-            }
-        }
-    }
-    /* 4. differences, s, the shaded colour */
-#pragma unroll
-    for( int k = 0; k < N; ++k )
-    {
-        VRC_STRICT_FP
-        if( need[k] )
-        {
-            const float g[3] = { vrc_gradient_diff< ATLAS_T >( vHi[k][0], vLo[k][0] ) * sm.kx,
-                                 vrc_gradient_diff< ATLAS_T >( vHi[k][1], vLo[k][1] ) * sm.ky,
-                                 vrc_gradient_diff< ATLAS_T >( vHi[k][2], vLo[k][2] ) * sm.kz };
-            const float sh = vrc_iso_shade( g, dir, f.shadeAmbient );
-            e[k].x = e[k].x * sh;
-            e[k].y = e[k].y * sh;
-            e[k].z = e[k].z * sh;
-        }
+            use( k, d[k] );
     }
 }
 
-template < bool CLAMP, bool COUNT, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T, int GROUP >
-VRC_HD bool vrc_shade_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_segment s, const vrc_f3& dir,
-                               const ATLAS_T* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
-                               vrc_f4& color, uint32_t& nSamples )
+/* what value d adds as the plain composite classifies it: vrc_classify (PERSAMPLE), else the classified table.  A
+ * sample that is not taken (a no-op slot of a masked group) comes out as zeros, an exact no-op in the blend */
+template < bool PERSAMPLE, typename V >
+VRC_HD vrc_f4 vrc_group_classify( const vrc_f4* lut, const vrc_classifier& cls, bool taken, V d )
+{
+    if constexpr( PERSAMPLE )
+    {
+        const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
+        const vrc_f4 c = vrc_classify( lut, (float)d, cls );
+        return taken ? c : z;
+    }
+    else
+        return lut[taken ? d : 256u]; /* (entry 256: all zeros) */
+}
+
+/* One segment, marched in groups of GROUP.  POLICY p is the mode:
+ *   p.template group< N, MASKED >( sm, pos, step, fp, atlas, cnt, e )   e[k] = what sample k adds (the front, then its own)
+ *   POLICY::NOTES    false: nothing more.  true: the mode keeps something per ray beside the colour, and
+ *   p.wants( color )            is its term of the per-group test: the group just blended has to be replayed
+ *   p.note( color, j, k )       follows the blend of sample k of the group, sample j of the segment, where that sample
+ *                               was composited (not frozen)
+ * Every whole group holds only samples the reference loop reaches (vrc_march_segment_as); the group in which the test
+ * fires is replayed from the saved colour with the reference's per-sample exit.  Where the ray goes on after a replay
+ * (NOTES only), no weight was forced to 0 and the colour is the group's again, bit for bit */
+template < bool COUNT, bool FIXED, int GROUP, typename ATLAS_T, typename POLICY >
+VRC_HD bool vrc_group_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_segment s, const ATLAS_T* __restrict__ atlas,
+                               POLICY& p, vrc_f4& color, uint32_t& nSamples )
 {
     const float stepSize = f.stepSize;
     const vrc_sampler sm = vrc_make_sampler( n, f );
@@ -3491,13 +3433,12 @@ VRC_HD bool vrc_shade_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_se
     vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
     if( FIXED )
         fp = vrc_fixpos_init( sm, pos, s.step );
-    /* whole groups: every sample is one the reference loop reaches (vrc_march_segment_as) */
+    [[maybe_unused]] uint32_t first = 0u; /* the index, in its segment, of the first sample of the group in flight */
     const float guard = stepSize * (float)( GROUP + 1 );
     while( travel > guard )
     {
         vrc_f4 e[GROUP];
-        vrc_shade_group< CLAMP, FIXED, TRILINEAR, PERSAMPLE, ATLAS_T, GROUP, false >( f, sm, pos, s.step, fp, atlas, lut, cls,
-                                                                                     dir, (uint32_t)GROUP, e );
+        p.template group< GROUP, false >( sm, pos, s.step, fp, atlas, (uint32_t)GROUP, e );
 #pragma unroll
         for( int k = 0; k < GROUP; ++k )
             travel -= stepSize; /* same sequential subtraction as the reference */
@@ -3507,9 +3448,12 @@ VRC_HD bool vrc_shade_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_se
             vrc_composite( color, e[k] );
         if( COUNT )
             nSamples += GROUP;
-        if( color.w > VRC_EARLY_EXIT )
+        const bool leave = color.w > VRC_EARLY_EXIT;
+        bool replay = leave;
+        if constexpr( POLICY::NOTES )
+            replay = leave || p.wants( color );
+        if( replay )
         {
-            /* crossed inside this group: replay it with the reference's per-sample exit */
             color = saved;
             if( COUNT )
                 nSamples -= GROUP;
@@ -3519,10 +3463,18 @@ VRC_HD bool vrc_shade_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_se
                 vrc_composite( color, e[k], done );
                 if( COUNT )
                     nSamples += done ? 0u : 1u;
+                if constexpr( POLICY::NOTES )
+                    if( !done )
+                        p.note( color, first + (uint32_t)k, k );
                 done = done || ( color.w > VRC_EARLY_EXIT );
             }
-            return true;
+            if constexpr( !POLICY::NOTES )
+                return true;
+            else if( leave )
+                return true;
         }
+        if constexpr( POLICY::NOTES )
+            first += (uint32_t)GROUP;
     }
     constexpr int TAILG = GROUP >= 4 ? GROUP / 2 : 1;
     while( travel > 0.0f && !done )
@@ -3535,8 +3487,7 @@ VRC_HD bool vrc_shade_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_se
             travel -= stepSize;
         }
         vrc_f4 e[TAILG];
-        vrc_shade_group< CLAMP, FIXED, TRILINEAR, PERSAMPLE, ATLAS_T, TAILG, true >( f, sm, pos, s.step, fp, atlas, lut, cls, dir,
-                                                                                    cnt, e );
+        p.template group< TAILG, true >( sm, pos, s.step, fp, atlas, cnt, e );
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
         {
@@ -3544,53 +3495,179 @@ VRC_HD bool vrc_shade_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_se
             vrc_composite( color, e[k], done );
             if( COUNT )
                 nSamples += active ? 1u : 0u;
+            if constexpr( POLICY::NOTES )
+                if( active )
+                    p.note( color, first + (uint32_t)k, k );
             done = done || ( color.w > VRC_EARLY_EXIT );
         }
+        if constexpr( POLICY::NOTES )
+            first += (uint32_t)TAILG;
     }
     return done;
 }
 
-/* One brick of one ray of a shaded frame: vrc_march_brick_from's decisions -- the slot's 64-bit base moved into the lane's
- * pointer (BIG), the uniform march of a slot known to hold one value, taken by the whole wave or not at all (there G = 0
- * and s = 1: the unshaded march itself) -- around the shaded segment.  dir: the ray's unit direction */
-template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, bool BIG, typename SRC >
-VRC_HD bool vrc_shade_brick( const vrc_frame& f, const vrc_dev_node& n, const SRC& src, const vrc_f3& dir,
-                             const ATLAS_T* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
-                             vrc_f4& color, uint32_t& nSamples )
+/* Is the brick one whose upload found one value in every voxel (the slot's word, written by the repack kernel on the
+ * stream and under the fences of the voxels themselves; 0 where the frame has no words) -- for every lane of the wave?
+ * Taken by the whole wave or not at all: a lane in a uniform brick of a wave that also holds other bricks gathers its
+ * constant voxels like the rest, the same samples either way */
+VRC_HD bool vrc_slot_uniform_wave( const vrc_frame& f, const vrc_dev_node& n, uint32_t& word )
 {
-    static_assert( vrc_mode_is_shade( MODE ), "a shaded mode" );
-    constexpr bool TRILINEAR = MODE == VRC_MODE_SHADE_TRILINEAR;
+    word = 0u;
+    if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
+        word = f.slotInfo[n.slotInfoIndex - 1u];
+    bool general = !vrc_slot_holds_one_value( word );
+#if defined( __HIP_DEVICE_COMPILE__ )
+    general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
+#endif
+    return !general;
+}
+
+/* One brick of one ray, around a mode's marches.  BIG: the atlas holds more than 2^32 voxels; offsets inside a slot stay
+ * 32-bit and the slot's 64-bit base moves into the lane's pointer.  UNIFORM: the mode has a march for a slot known to
+ * hold one value, uniform( n, s, atlas, value ) on the distance-only segment; otherwise, and for every other slot,
+ * general( n, s, atlas ) on the full one */
+template < bool BIG, bool UNIFORM, typename ATLAS_T, typename SRC, typename MARCH_UNIFORM, typename MARCH >
+VRC_HD bool vrc_brick_visit( const vrc_frame& f, const vrc_dev_node& n, const SRC& src, const ATLAS_T* __restrict__ atlas,
+                             const MARCH_UNIFORM& uniform, const MARCH& general )
+{
     if constexpr( BIG )
     {
         vrc_dev_node local = n;
         local.slotBase = 0u;
         const ATLAS_T* slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
-        return vrc_shade_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, false, SRC >( f, local, src, dir, slot, lut, cls, color,
-                                                                                 nSamples );
+        return vrc_brick_visit< false, UNIFORM >( f, local, src, slot, uniform, general );
     }
     else
     {
-        if constexpr( !TRILINEAR && sizeof( ATLAS_T ) == 1 )
+        if constexpr( UNIFORM )
         {
-            uint32_t word = 0u;
-            if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
-                word = f.slotInfo[n.slotInfoIndex - 1u];
-            bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
-#if defined( __HIP_DEVICE_COMPILE__ )
-            general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
-#endif
-            if( !general )
+            uint32_t word;
+            if( vrc_slot_uniform_wave( f, n, word ) )
             {
                 const vrc_segment& s = src.distOnly();
-                return vrc_march_segment_as< CLAMP, COUNT, FIXED, ATLAS_T, VRC_GROUP, vrc_f4, false, true >(
-                    f, n, s, atlas, lut, color, nSamples, 0.0f, nullptr, lut[word & 0xFFu] );
+                return uniform( n, s, atlas, word & 0xFFu );
             }
         }
         const vrc_segment& s = src.full();
-        return vrc_shade_segment< CLAMP, COUNT, FIXED, TRILINEAR, TRILINEAR || sizeof( ATLAS_T ) != 1, ATLAS_T, VRC_SHADE_GROUP >(
-            f, n, s, dir, atlas, lut, cls, color, nSamples );
+        return general( n, s, atlas );
     }
 }
+
+/* ------------------------------------------------------------------------------------------
+ * EXTENSION: a shaded composite frame (VRC_OPT_SHADING = 1; include/vrc_hip.h, "A shaded composite frame").
+ *
+ * The composite frame with one change: the colour a sample adds is multiplied by the headlight term of the isosurface
+ * frame, s = ambient + (1 - ambient) |G.dir| / |G| (vrc_iso_shade), G the central differences of the stored voxels around
+ * the voxel the POINT sampler addresses at the sample's position (under both filters; vrc_gradient_* above: the
+ * isosurface gradient's clamping and differencing), times the node's voxels per world unit.  The opacity is not
+ * touched, so the samples, their order, early ray termination and the alpha channel are the unshaded frame's; with
+ * ambient = 1, and wherever G is 0, so is the whole pixel.
+ *
+ * Sample positions, addresses, gathers and classification are those of the unshaded march of the same sampler
+ * (vrc_group_values, vrc_group_classify), in the shared segment loop (vrc_group_segment) with the early-exit test alone.
+ * Per group: centre addresses and gathers, classification, a ballot of
+ * alpha' > 0, the six neighbour gathers of every sample that has one -- skipped by the lanes whose sample is transparent
+ * (its e is 0 whatever s is) and by the wave when no lane needs them --, the differences, s, the blends.  A neighbour's
+ * address is the centre's with one per-axis part swapped (the LDS tables under fixed-point stepping).
+ * Groups of VRC_SHADE_GROUP = 4: 24 neighbour voxels in flight beside four classified samples; 8 x 6 do not fit the
+ * registers of four waves per SIMD (DESIGN.md has the table of the instances).
+ * ---------------------------------------------------------------------------------------- */
+#define VRC_MODE_SHADE 10           /* point samples: the classified table for 8-bit voxels, vrc_classify otherwise */
+#define VRC_MODE_SHADE_TRILINEAR 11 /* trilinear samples by gathers */
+VRC_HD constexpr bool vrc_mode_is_shade( int mode ) { return mode == VRC_MODE_SHADE || mode == VRC_MODE_SHADE_TRILINEAR; }
+#define VRC_SHADE_GROUP 4
+#if defined( VRC_SHADE_SKIP_HOOK ) && !defined( __HIPCC__ )
+/* host test builds only (tests/cpu_harness/shade_harness.cpp): 0 = gather the gradient of transparent samples too; and
+ * how many samples were taken with / without their gradient */
+static int vrc_shade_skip_hook = 1;
+static unsigned long long vrc_shade_gradients[2];
+#endif
+
+/* the shaded mode of vrc_group_segment.  dir: the ray's unit direction */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T >
+struct vrc_shade_policy
+{
+    static constexpr bool NOTES = false;
+    const vrc_frame& f;
+    const vrc_f4* lut;
+    const vrc_classifier& cls;
+    const vrc_f3& dir;
+
+    /* e[k] = (rgb alpha' s, alpha') of sample k */
+    template < int N, bool MASKED >
+    VRC_HD void group( const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
+                       const ATLAS_T* __restrict__ atlas, uint32_t cnt, vrc_f4* e ) const
+    {
+        /* 1. the sample itself: addresses, gathers, classification */
+        uint32_t ux[N], uy[N], uz[N];
+        typedef typename vrc_group_value< TRILINEAR, ATLAS_T >::type V;
+        vrc_group_values< CLAMP, FIXED, TRILINEAR, ATLAS_T, N, MASKED, true >(
+            sm, pos, step, fp, atlas, cnt,
+            [&]( int k, V d ) { e[k] = vrc_group_classify< PERSAMPLE >( lut, cls, !MASKED || (uint32_t)k < cnt, d ); }, ux, uy, uz );
+        /* 2. which samples need their gradient: a transparent one adds (0, 0) whatever s is */
+        bool need[N], any = false;
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            const bool taken = !MASKED || (uint32_t)k < cnt;
+            need[k] = taken && e[k].w > 0.0f;
+#if defined( VRC_SHADE_SKIP_HOOK ) && !defined( __HIPCC__ )
+            if( vrc_shade_skip_hook == 0 )
+                need[k] = taken;
+            if( taken )
+                ++vrc_shade_gradients[need[k] ? 1 : 0];
+#endif
+            any = any || need[k];
+        }
+#if defined( __HIP_DEVICE_COMPILE__ )
+        any = __builtin_amdgcn_ballot_w64( any ) != 0ull;
+#endif
+        if( !any )
+            return;
+        /* 3. the six neighbours, back to back.  Every coordinate goes through vrc_gradient_clamp and
+         * vrc_gradient_neighbours: all of them lie inside the slot, whatever the sampler made of the position */
+        ATLAS_T vLo[N][3], vHi[N][3];
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+#pragma unroll
+            for( int a = 0; a < 3; ++a )
+                vLo[k][a] = vHi[k][a] = (ATLAS_T)0;
+            if( need[k] )
+            {
+                const uint32_t c[3] = { vrc_gradient_clamp( ux[k], f.slotDim[0] ), vrc_gradient_clamp( uy[k], f.slotDim[1] ),
+                                        vrc_gradient_clamp( uz[k], f.slotDim[2] ) };
+                const uint32_t part[3] = { vrc_shade_part< FIXED >( sm, 0, c[0] ), vrc_shade_part< FIXED >( sm, 1, c[1] ),
+                                           vrc_shade_part< FIXED >( sm, 2, c[2] ) };
+#pragma unroll
+                for( int a = 0; a < 3; ++a )
+                {
+                    uint32_t lo, hi;
+                    vrc_gradient_neighbours( c[a], f.slotDim[a], lo, hi );
+                    const uint32_t rest = part[( a + 1 ) % 3] + part[( a + 2 ) % 3] + sm.slotBase;
+                    vHi[k][a] = vrc_gather( atlas, vrc_shade_part< FIXED >( sm, a, hi ) + rest );
+                    vLo[k][a] = vrc_gather( atlas, vrc_shade_part< FIXED >( sm, a, lo ) + rest );
+                }
+            }
+        }
+        /* 4. differences, s, the shaded colour */
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+        {
+            VRC_STRICT_FP
+            if( need[k] )
+            {
+                const float g[3] = { vrc_gradient_diff< ATLAS_T >( vHi[k][0], vLo[k][0] ) * sm.kx,
+                                     vrc_gradient_diff< ATLAS_T >( vHi[k][1], vLo[k][1] ) * sm.ky,
+                                     vrc_gradient_diff< ATLAS_T >( vHi[k][2], vLo[k][2] ) * sm.kz };
+                const float sh = vrc_iso_shade( g, dir, f.shadeAmbient );
+                e[k].x = e[k].x * sh;
+                e[k].y = e[k].y * sh;
+                e[k].z = e[k].z * sh;
+            }
+        }
+    }
+};
 
 /* ------------------------------------------------------------------------------------------
  * EXTENSION: the depth of a composite frame (VRC_OPT_COMPOSITE_DEPTH; include/vrc_hip.h, "The depth of a composite
@@ -3601,9 +3678,9 @@ VRC_HD bool vrc_shade_brick( const vrc_frame& f, const vrc_dev_node& n, const SR
  * (vrc_mip_sample_t), V its value as a MIP frame keeps a sample's (the stored voxel of an 8- or 16-bit atlas as an
  * integer, the bits of the float voxel or of the interpolated float otherwise; vrc_projection_value reads it back).
  *
- * Sample positions, addresses, gathers and classification are those of the unshaded march of the same sampler,
- * expression for expression (the first part of vrc_shade_group), in the control structure of vrc_shade_segment: whole
- * groups, one test per group, the exact replay from the saved colour, a masked tail.  The test is the early exit's OR
+ * Sample positions, addresses, gathers and classification are those of the unshaded march of the same sampler
+ * (vrc_group_values, vrc_group_classify), in the shared segment loop (vrc_group_segment) with a term of its own in the
+ * per-group test and a note per replayed sample (vrc_cdepth_policy).  The test is the early exit's OR
  * "alpha >= tau and the ray has not crossed": alpha never decreases, so a group after which alpha is below tau holds no
  * crossing sample, and the group in which the test fires is replayed sample by sample -- once per ray for the crossing,
  * once for the early exit, in one loop.  The replay of a group that did not end the ray composites the same samples in
@@ -3644,203 +3721,37 @@ VRC_HD void vrc_cdepth_note( vrc_cdepth_state& z, const vrc_f4& color, float tau
     }
 }
 
-/* N samples of a segment: e[k] = (rgb alpha', alpha') of sample k and vb[k] its value; MASKED: only the first cnt are
- * the reference's, the others read element 0 and come out as zeros (an exact no-op in the blend).  The first part of
- * vrc_shade_group, and nothing of its gradient */
-template < bool CLAMP, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T, int N, bool MASKED >
-VRC_HD void vrc_cdepth_group( const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
-                              const ATLAS_T* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls, uint32_t cnt,
-                              vrc_f4* e, uint32_t* vb )
+/* the depth-tracking mode of vrc_group_segment, for one segment (tNear: its first sample's t).  GROUP: the largest group
+ * it is asked for */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T, int GROUP >
+struct vrc_cdepth_policy
 {
-    typedef typename vrc_density< ATLAS_T >::type D;
-    static_assert( !( TRILINEAR && FIXED ), "the trilinear gather march steps in float" );
-    static_assert( !( CLAMP && FIXED ), "the clamped sampler steps in float" );
-    if constexpr( TRILINEAR )
-    {
-        vrc_taps t[N];
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-        {
-            VRC_FAST_FP
-            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
-            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
-            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
-            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
-            pos.x += step.x;
-            pos.y += step.y;
-            pos.z += step.z;
-        }
-        float v[N][8];
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-#pragma unroll
-            for( int c = 0; c < 8; ++c )
-            {
-                const uint32_t a = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
-                v[k][c] = (float)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? a : 0u );
-            }
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-        {
-            const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
-            const float d = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
-            const vrc_f4 c = vrc_classify( lut, d, cls );
-            e[k] = ( !MASKED || (uint32_t)k < cnt ) ? c : z;
-            vb[k] = vrc_float_bits( d );
-        }
-    }
-    else
-    {
-        uint32_t idx[N];
-        if constexpr( FIXED )
-        {
-#pragma unroll
-            for( int k = 0; k < N; ++k )
-            {
-                const uint32_t ux = fp.x >> 24, uy = fp.y >> 24, uz = fp.z >> 24;
-                fp.x += fp.dx;
-                fp.y += fp.dy;
-                fp.z += fp.dz;
-#if defined( __HIP_DEVICE_COMPILE__ )
-                asm( "" : "+v"( fp.x ), "+v"( fp.y ), "+v"( fp.z ) ); /* (vrc_group_indices_fixed: keep the three additions) */
-                idx[k] = vrc_shade_part< true >( sm, 0, ux ) + vrc_shade_part< true >( sm, 1, uy ) +
-                         vrc_shade_part< true >( sm, 2, uz ) + sm.slotBase;
-#else
-                idx[k] = vrc_voxel_address( sm, ux, uy, uz );
-#endif
-            }
-        }
-        else
-        {
-            VRC_FAST_FP
-#pragma unroll
-            for( int k = 0; k < N; ++k )
-            {
-                float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
-                float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
-                float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
-                if( CLAMP )
-                {
-                    lx = fminf( fmaxf( lx, 0.0f ), sm.hix );
-                    ly = fminf( fmaxf( ly, 0.0f ), sm.hiy );
-                    lz = fminf( fmaxf( lz, 0.0f ), sm.hiz );
-                }
-                idx[k] = vrc_voxel_address( sm, (uint32_t)(int)lx, (uint32_t)(int)ly, (uint32_t)(int)lz );
-                pos.x += step.x;
-                pos.y += step.y;
-                pos.z += step.z;
-            }
-        }
-        D d[N];
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-            d[k] = (D)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? idx[k] : 0u );
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-        {
-            if constexpr( PERSAMPLE )
-            {
-                const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
-                const vrc_f4 c = vrc_classify( lut, (float)d[k], cls );
-                e[k] = ( !MASKED || (uint32_t)k < cnt ) ? c : z;
-            }
-            else
-                e[k] = lut[( !MASKED || (uint32_t)k < cnt ) ? d[k] : 256u]; /* (entry 256: all zeros) */
-            vb[k] = vrc_cdepth_bits( d[k] );
-        }
-    }
-}
+    static constexpr bool NOTES = true;
+    const vrc_f4* lut;
+    const vrc_classifier& cls;
+    vrc_cdepth_state& z;
+    float tau, tNear, stepSize;
+    uint32_t vb[GROUP]; /* the values of the group in flight */
 
-template < bool CLAMP, bool COUNT, bool FIXED, bool TRILINEAR, bool PERSAMPLE, typename ATLAS_T, int GROUP >
-VRC_HD bool vrc_cdepth_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_segment s, const ATLAS_T* __restrict__ atlas,
-                                const vrc_f4* lut, const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples,
-                                vrc_cdepth_state& z )
-{
-    const float stepSize = f.stepSize;
-    const float tau = f.cdepthTau;
-    const vrc_sampler sm = vrc_make_sampler( n, f );
-    float travel = s.dist;
-    vrc_f3 pos = s.pos;
-    bool done = false;
-    if( !( travel > 0.0f ) )
-        return false;
-    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
-    if( FIXED )
-        fp = vrc_fixpos_init( sm, pos, s.step );
-    uint32_t first = 0u; /* the index, in its segment, of the first sample of the group in flight */
-    /* whole groups: every sample is one the reference loop reaches (vrc_march_segment_as) */
-    const float guard = stepSize * (float)( GROUP + 1 );
-    while( travel > guard )
+    /* e[k] = (rgb alpha', alpha') of sample k */
+    template < int N, bool MASKED >
+    VRC_HD void group( const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
+                       const ATLAS_T* __restrict__ atlas, uint32_t cnt, vrc_f4* e )
     {
-        vrc_f4 e[GROUP];
-        uint32_t vb[GROUP];
-        vrc_cdepth_group< CLAMP, FIXED, TRILINEAR, PERSAMPLE, ATLAS_T, GROUP, false >( sm, pos, s.step, fp, atlas, lut, cls,
-                                                                                      (uint32_t)GROUP, e, vb );
-#pragma unroll
-        for( int k = 0; k < GROUP; ++k )
-            travel -= stepSize; /* same sequential subtraction as the reference */
-        const vrc_f4 saved = color;
-#pragma unroll
-        for( int k = 0; k < GROUP; ++k )
-            vrc_composite( color, e[k] );
-        if( COUNT )
-            nSamples += GROUP;
-        const bool leave = color.w > VRC_EARLY_EXIT;
-        if( leave || ( !z.crossed && color.w >= tau ) )
-        {
-            /* the early exit or the crossing lies inside this group: replay it with the reference's per-sample exit.
-             * Where the ray goes on, no weight was forced to 0 and the colour is the group's again */
-            color = saved;
-            if( COUNT )
-                nSamples -= GROUP;
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-            {
-                vrc_composite( color, e[k], done );
-                if( COUNT )
-                    nSamples += done ? 0u : 1u;
-                if( !done )
-                    vrc_cdepth_note( z, color, tau, s.tNear, first + (uint32_t)k, stepSize, vb[k] );
-                done = done || ( color.w > VRC_EARLY_EXIT );
-            }
-            if( leave )
-                return true;
-        }
-        first += (uint32_t)GROUP;
+        static_assert( N <= GROUP, "vb holds the group" );
+        typedef typename vrc_group_value< TRILINEAR, ATLAS_T >::type V;
+        vrc_group_values< CLAMP, FIXED, TRILINEAR, ATLAS_T, N, MASKED, false >( sm, pos, step, fp, atlas, cnt, [&]( int k, V d ) {
+            e[k] = vrc_group_classify< PERSAMPLE >( lut, cls, !MASKED || (uint32_t)k < cnt, d );
+            vb[k] = vrc_cdepth_bits( d );
+        } );
     }
-    constexpr int TAILG = GROUP >= 4 ? GROUP / 2 : 1;
-    while( travel > 0.0f && !done )
-    {
-        uint32_t cnt = 0;
-#pragma unroll
-        for( int k = 0; k < TAILG; ++k )
-        {
-            cnt += travel > 0.0f ? 1u : 0u;
-            travel -= stepSize;
-        }
-        vrc_f4 e[TAILG];
-        uint32_t vb[TAILG];
-        vrc_cdepth_group< CLAMP, FIXED, TRILINEAR, PERSAMPLE, ATLAS_T, TAILG, true >( sm, pos, s.step, fp, atlas, lut, cls, cnt, e,
-                                                                                     vb );
-#pragma unroll
-        for( int k = 0; k < TAILG; ++k )
-        {
-            const bool active = ( (uint32_t)k < cnt ) && !done;
-            vrc_composite( color, e[k], done );
-            if( COUNT )
-                nSamples += active ? 1u : 0u;
-            if( active )
-                vrc_cdepth_note( z, color, tau, s.tNear, first + (uint32_t)k, stepSize, vb[k] );
-            done = done || ( color.w > VRC_EARLY_EXIT );
-        }
-        first += (uint32_t)TAILG;
-    }
-    return done;
-}
+    VRC_HD bool wants( const vrc_f4& color ) const { return !z.crossed && color.w >= tau; }
+    VRC_HD void note( const vrc_f4& color, uint32_t j, int k ) { vrc_cdepth_note( z, color, tau, tNear, j, stepSize, vb[k] ); }
+};
 
 /* A slot known to hold one value (vrc_march_segment_as, UNIFORM): the same composites of its one table entry in the same
  * order and the same count -- counted in integers where that is the float chain's count exactly, taken by the whole wave
- * or not at all, else the float chain sample by sample -- with the crossing found as vrc_cdepth_segment finds it */
+ * or not at all, else the float chain sample by sample -- with the crossing found as vrc_group_segment finds it */
 template < bool COUNT >
 VRC_HD bool vrc_cdepth_uniform( const vrc_frame& f, const vrc_segment& s, const vrc_f4 ue, uint32_t value, vrc_f4& color,
                                 uint32_t& nSamples, vrc_cdepth_state& z )
@@ -3906,50 +3817,6 @@ VRC_HD bool vrc_cdepth_uniform( const vrc_frame& f, const vrc_segment& s, const 
     return false;
 }
 
-/* One brick of one ray of a depth-tracking composite frame: vrc_shade_brick's decisions -- the slot's 64-bit base moved
- * into the lane's pointer (BIG), the uniform march of a slot known to hold one value, taken by the whole wave or not at
- * all -- around the segment above */
-template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, bool BIG, typename SRC >
-VRC_HD bool vrc_cdepth_brick( const vrc_frame& f, const vrc_dev_node& n, const SRC& src, const ATLAS_T* __restrict__ atlas,
-                              const vrc_f4* lut, const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples,
-                              vrc_cdepth_state& z )
-{
-    static_assert( vrc_mode_is_cdepth( MODE ), "a depth-tracking composite mode" );
-    constexpr bool TRILINEAR = MODE == VRC_MODE_CDEPTH_TRILINEAR;
-    if constexpr( BIG )
-    {
-        vrc_dev_node local = n;
-        local.slotBase = 0u;
-        const ATLAS_T* slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
-        return vrc_cdepth_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, false, SRC >( f, local, src, slot, lut, cls, color, nSamples,
-                                                                                  z );
-    }
-    else
-    {
-        if constexpr( !TRILINEAR && sizeof( ATLAS_T ) == 1 )
-        {
-            uint32_t word = 0u;
-            if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
-                word = f.slotInfo[n.slotInfoIndex - 1u];
-            bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
-#if defined( __HIP_DEVICE_COMPILE__ )
-            general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
-#endif
-            if( !general )
-            {
-                const vrc_segment& s = src.distOnly();
-                return vrc_cdepth_uniform< COUNT >( f, s, lut[word & 0xFFu], word & 0xFFu, color, nSamples, z );
-            }
-        }
-        const vrc_segment& s = src.full();
-        return vrc_cdepth_segment< CLAMP, COUNT, FIXED, TRILINEAR, TRILINEAR || sizeof( ATLAS_T ) != 1, ATLAS_T,
-                                   TRILINEAR                 ? VRC_CDEPTH_GROUP_TRILINEAR
-                                   : ( sizeof( ATLAS_T ) == 1 && !CLAMP ) ? VRC_CDEPTH_GROUP
-                                                            : VRC_CDEPTH_GROUP_CLASSIFIED >( f, n, s, atlas, lut, cls, color,
-                                                                                             nSamples, z );
-    }
-}
-
 /* ------------------------------------------------------------------------------------------
  * EXTENSION: a pre-integrated composite frame (VRC_OPT_PREINTEGRATION = 1; include/vrc_hip.h, "A pre-integrated
  * composite frame").
@@ -3967,9 +3834,8 @@ VRC_HD bool vrc_cdepth_brick( const vrc_frame& f, const vrc_dev_node& n, const S
  *    either end plus a difference of per-texel prefix sums (256 x 4 doubles, built once per launch and block), or one
  *    partial span where both ends share a texel interval: nothing small is ever the difference of two large numbers
  *    but the prefix difference, whose error of 255 ln 256 x 2^-52 is far inside the 1e-6 the contract allows.
- * 2. The march (vrc_preint_group, vrc_preint_segment): vrc_shade_segment's structure -- whole groups while more than a
- *    group of steps remains, the early-exit test once per group with the exact replay from the saved colour, a masked
- *    tail -- with, per group, the gathers, then the table reads, then the blends, and one carried value per lane: the last
+ * 2. The march (vrc_preint_policy): the shared front and segment loop (vrc_group_values, vrc_group_segment) with the
+ *    early-exit test alone; per group the gathers, then the table reads, then the blends, and one carried value per lane: the last
  *    value of the group before (the visit's first sample: its own).  A no-op slot of the tail reads entry (0, 0) of the
  *    table, comes out as zeros and leaves the carried value alone.
  * ---------------------------------------------------------------------------------------- */
@@ -4193,70 +4059,14 @@ VRC_HD vrc_f4 vrc_preint_read( const vrc_f4* table, float xf, float xb )
     return e;
 }
 
-/* N samples of a segment: e[k] = the table's entry for the step that ends in sample k.  carry: the value (VALUE: the
- * stored byte; otherwise the texel coordinate) of the sample before the group; first: the group opens a visit, whose
- * sample 0 is paired with itself.  MASKED: only the first cnt >= 1 are the reference's; the others read entry (0, 0),
- * come out as zeros (an exact no-op in the blend) and do not move carry */
-template < bool CLAMP, bool FIXED, bool TRILINEAR, bool VALUE, typename ATLAS_T, int N, bool MASKED >
-VRC_HD void vrc_preint_group( const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
-                              const ATLAS_T* __restrict__ atlas, const vrc_f4* __restrict__ table, const vrc_classifier& cls,
-                              uint32_t cnt, float& carry, bool& first, vrc_f4* e )
+/* The table reads of a group: e[k] = the table's entry for the step that ends in sample k, by the value before it and its
+ * own (VALUE: the stored bytes dv[]; otherwise the texel coordinates x[]).  carry: the value of the sample before the
+ * group; first: the group opens a visit, whose sample 0 is paired with itself.  MASKED: only the first cnt >= 1 are the
+ * reference's; the others read entry (0, 0), come out as zeros (an exact no-op in the blend) and do not move carry */
+template < bool VALUE, int N, bool MASKED >
+VRC_HD void vrc_preint_entries( const vrc_f4* __restrict__ table, uint32_t cnt, [[maybe_unused]] const float* x,
+                                [[maybe_unused]] const uint32_t* dv, float& carry, bool& first, vrc_f4* e )
 {
-    typedef typename vrc_density< ATLAS_T >::type D;
-    static_assert( !( TRILINEAR && FIXED ), "the trilinear gather march steps in float" );
-    static_assert( !( CLAMP && FIXED ), "the clamped sampler steps in float" );
-    static_assert( !VALUE || ( !TRILINEAR && sizeof( ATLAS_T ) == 1 ), "the value-indexed table takes stored bytes" );
-    [[maybe_unused]] float x[N];     /* the texel coordinates of the samples, or (VALUE) ... */
-    [[maybe_unused]] uint32_t dv[N]; /* ... their stored bytes */
-    if constexpr( TRILINEAR )
-    {
-        vrc_taps t[N];
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-        {
-            VRC_FAST_FP
-            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
-            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
-            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
-            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
-            pos.x += step.x;
-            pos.y += step.y;
-            pos.z += step.z;
-        }
-        float v[N][8];
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-#pragma unroll
-            for( int c = 0; c < 8; ++c )
-            {
-                const uint32_t a = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
-                v[k][c] = (float)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? a : 0u );
-            }
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-            x[k] = vrc_preint_coord( vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz ), cls );
-    }
-    else
-    {
-        uint32_t idx[N];
-        if constexpr( FIXED )
-            vrc_group_indices_fixed< N >( sm, fp, idx );
-        else
-            vrc_group_indices< CLAMP, N >( sm, pos, step, idx );
-        D d[N];
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-            d[k] = (D)vrc_gather( atlas, ( !MASKED || (uint32_t)k < cnt ) ? idx[k] : 0u );
-#pragma unroll
-        for( int k = 0; k < N; ++k )
-        {
-            if constexpr( VALUE )
-                dv[k] = (uint32_t)d[k];
-            else
-                x[k] = vrc_preint_coord( (float)d[k], cls );
-        }
-    }
-    /* the table: entry k by the value before it and its own */
     const vrc_f4 z = { 0.f, 0.f, 0.f, 0.f };
     if constexpr( VALUE )
     {
@@ -4290,86 +4100,38 @@ VRC_HD void vrc_preint_group( const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& 
     first = false;
 }
 
-template < bool CLAMP, bool COUNT, bool FIXED, bool TRILINEAR, bool VALUE, typename ATLAS_T, int GROUP >
-VRC_HD bool vrc_preint_segment( const vrc_frame& f, const vrc_dev_node& n, vrc_segment s, const ATLAS_T* __restrict__ atlas,
-                                const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples )
+/* the pre-integrated mode of vrc_group_segment, for one brick visit: the front, then the table reads.  The previous value
+ * is not carried from one brick visit to the next */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, bool VALUE, typename ATLAS_T >
+struct vrc_preint_policy
 {
-    const float stepSize = f.stepSize;
-    const vrc_sampler sm = vrc_make_sampler( n, f );
-    const vrc_f4* __restrict__ table = f.preintTable;
-    float travel = s.dist;
-    vrc_f3 pos = s.pos;
-    bool done = false;
-    if( !( travel > 0.0f ) )
-        return false;
-    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
-    if( FIXED )
-        fp = vrc_fixpos_init( sm, pos, s.step );
-    float carry = 0.0f;
-    bool first = true; /* the previous value is not carried from one brick visit to the next */
-    /* whole groups: every sample is one the reference loop reaches (vrc_march_segment_as) */
-    const float guard = stepSize * (float)( GROUP + 1 );
-    while( travel > guard )
-    {
-        vrc_f4 e[GROUP];
-        vrc_preint_group< CLAMP, FIXED, TRILINEAR, VALUE, ATLAS_T, GROUP, false >( sm, pos, s.step, fp, atlas, table, cls,
-                                                                                  (uint32_t)GROUP, carry, first, e );
-#pragma unroll
-        for( int k = 0; k < GROUP; ++k )
-            travel -= stepSize; /* same sequential subtraction as the reference */
-        const vrc_f4 saved = color;
-#pragma unroll
-        for( int k = 0; k < GROUP; ++k )
-            vrc_composite( color, e[k] );
-        if( COUNT )
-            nSamples += GROUP;
-        if( color.w > VRC_EARLY_EXIT )
-        {
-            /* crossed inside this group: replay it with the reference's per-sample exit */
-            color = saved;
-            if( COUNT )
-                nSamples -= GROUP;
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-            {
-                vrc_composite( color, e[k], done );
-                if( COUNT )
-                    nSamples += done ? 0u : 1u;
-                done = done || ( color.w > VRC_EARLY_EXIT );
-            }
-            return true;
-        }
-    }
-    constexpr int TAILG = GROUP >= 4 ? GROUP / 2 : 1;
-    while( travel > 0.0f && !done )
-    {
-        uint32_t cnt = 0;
-#pragma unroll
-        for( int k = 0; k < TAILG; ++k )
-        {
-            cnt += travel > 0.0f ? 1u : 0u;
-            travel -= stepSize;
-        }
-        vrc_f4 e[TAILG];
-        vrc_preint_group< CLAMP, FIXED, TRILINEAR, VALUE, ATLAS_T, TAILG, true >( sm, pos, s.step, fp, atlas, table, cls, cnt,
-                                                                                 carry, first, e );
-#pragma unroll
-        for( int k = 0; k < TAILG; ++k )
-        {
-            const bool active = ( (uint32_t)k < cnt ) && !done;
-            vrc_composite( color, e[k], done );
-            if( COUNT )
-                nSamples += active ? 1u : 0u;
-            done = done || ( color.w > VRC_EARLY_EXIT );
-        }
-    }
-    return done;
-}
+    static_assert( !VALUE || ( !TRILINEAR && sizeof( ATLAS_T ) == 1 ), "the value-indexed table takes stored bytes" );
+    static constexpr bool NOTES = false;
+    const vrc_f4* __restrict__ table;
+    const vrc_classifier& cls;
+    float carry;
+    bool first;
 
-/* One brick of one ray of a pre-integrated frame: vrc_shade_brick's decisions -- the slot's 64-bit base moved into the
- * lane's pointer (BIG), the uniform march of a slot known to hold one value v, taken by the whole wave or not at all,
- * from lut[v] (the diagonal of the value-indexed table is a copy of that table: E(v, v) for every sample of the visit)
- * -- around the segment above.  lut is read by that march alone */
+    template < int N, bool MASKED >
+    VRC_HD void group( const vrc_sampler& sm, vrc_f3& pos, const vrc_f3& step, vrc_fixpos& fp,
+                       const ATLAS_T* __restrict__ atlas, uint32_t cnt, vrc_f4* e )
+    {
+        typedef typename vrc_group_value< TRILINEAR, ATLAS_T >::type V;
+        [[maybe_unused]] float x[N];     /* the texel coordinates of the samples, or (VALUE) ... */
+        [[maybe_unused]] uint32_t dv[N]; /* ... their stored bytes */
+        vrc_group_values< CLAMP, FIXED, TRILINEAR, ATLAS_T, N, MASKED, false >( sm, pos, step, fp, atlas, cnt, [&]( int k, V d ) {
+            if constexpr( VALUE )
+                dv[k] = (uint32_t)d;
+            else
+                x[k] = vrc_preint_coord( (float)d, cls );
+        } );
+        vrc_preint_entries< VALUE, N, MASKED >( table, cnt, x, dv, carry, first, e );
+    }
+};
+
+/* One brick of one ray of a pre-integrated frame: vrc_brick_visit around its marches.  A slot of bytes known to hold one
+ * value v is marched by the plain uniform march from lut[v] (the diagonal of the value-indexed table is a copy of that
+ * table: E(v, v) for every sample of the visit); lut is read by that march alone */
 template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, bool BIG, typename SRC >
 VRC_HD bool vrc_preint_brick( const vrc_frame& f, const vrc_dev_node& n, const SRC& src, const ATLAS_T* __restrict__ atlas,
                               const vrc_f4* lut, const vrc_classifier& cls, vrc_f4& color, uint32_t& nSamples )
@@ -4377,35 +4139,59 @@ VRC_HD bool vrc_preint_brick( const vrc_frame& f, const vrc_dev_node& n, const S
     static_assert( vrc_mode_is_preint( MODE ), "a pre-integrated mode" );
     constexpr bool TRILINEAR = MODE == VRC_MODE_PREINT_TRILINEAR;
     constexpr bool VALUE = !TRILINEAR && sizeof( ATLAS_T ) == 1;
-    if constexpr( BIG )
-    {
-        vrc_dev_node local = n;
-        local.slotBase = 0u;
-        const ATLAS_T* slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
-        return vrc_preint_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, false, SRC >( f, local, src, slot, lut, cls, color, nSamples );
-    }
+    return vrc_brick_visit< BIG, VALUE >(
+        f, n, src, atlas,
+        [&]( const vrc_dev_node& m, const vrc_segment& s, const ATLAS_T* __restrict__ a, uint32_t v ) {
+            return vrc_march_segment_as< CLAMP, COUNT, FIXED, ATLAS_T, VRC_GROUP, vrc_f4, false, true >(
+                f, m, s, a, lut, color, nSamples, 0.0f, nullptr, lut[v] );
+        },
+        [&]( const vrc_dev_node& m, const vrc_segment& s, const ATLAS_T* __restrict__ a ) {
+            vrc_preint_policy< CLAMP, FIXED, TRILINEAR, VALUE, ATLAS_T > p = { f.preintTable, cls, 0.0f, true };
+            return vrc_group_segment< COUNT, FIXED, VALUE ? VRC_PREINT_GROUP : VRC_PREINT_GROUP_TEXEL >( f, m, s, a, p, color,
+                                                                                                         nSamples );
+        } );
+}
+
+/* ------------------------------------------------------------------------------------------
+ * One brick of one ray of a shaded or a depth-tracking frame: vrc_brick_visit around the mode's marches.  dir: the ray's unit
+ * direction (the shaded modes); cdepth: the ray's crossing state (the depth-tracking modes).
+ * A slot of bytes known to hold one value v is marched from lut[v] by the plain uniform march: there a shaded frame has
+ * G = 0 and s = 1; the depth-tracking modes find the crossing in it as well (vrc_cdepth_uniform).
+ * ---------------------------------------------------------------------------------------- */
+template < bool CLAMP, bool COUNT, bool FIXED, int MODE, typename ATLAS_T, bool BIG, typename SRC >
+VRC_HD bool vrc_extension_brick( const vrc_frame& f, const vrc_dev_node& n, const SRC& src, [[maybe_unused]] const vrc_f3& dir,
+                                 const ATLAS_T* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
+                                 vrc_f4& color, uint32_t& nSamples, [[maybe_unused]] vrc_cdepth_state* cdepth )
+{
+    static_assert( vrc_mode_is_shade( MODE ) || vrc_mode_is_cdepth( MODE ), "a shaded or a depth-tracking mode" );
+    constexpr bool TRILINEAR = MODE == VRC_MODE_SHADE_TRILINEAR || MODE == VRC_MODE_CDEPTH_TRILINEAR;
+    constexpr bool BYTES = !TRILINEAR && sizeof( ATLAS_T ) == 1; /* the forms that look at the slot's word */
+    [[maybe_unused]] const auto plain = [&]( const vrc_dev_node& m, const vrc_segment& s, const ATLAS_T* __restrict__ a,
+                                             uint32_t v ) {
+        return vrc_march_segment_as< CLAMP, COUNT, FIXED, ATLAS_T, VRC_GROUP, vrc_f4, false, true >(
+            f, m, s, a, lut, color, nSamples, 0.0f, nullptr, lut[v] );
+    };
+    if constexpr( vrc_mode_is_shade( MODE ) )
+        return vrc_brick_visit< BIG, BYTES >(
+            f, n, src, atlas, plain, [&]( const vrc_dev_node& m, const vrc_segment& s, const ATLAS_T* __restrict__ a ) {
+                vrc_shade_policy< CLAMP, FIXED, TRILINEAR, !BYTES, ATLAS_T > p = { f, lut, cls, dir };
+                return vrc_group_segment< COUNT, FIXED, VRC_SHADE_GROUP >( f, m, s, a, p, color, nSamples );
+            } );
     else
     {
-        if constexpr( VALUE )
-        {
-            uint32_t word = 0u;
-            if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
-                word = f.slotInfo[n.slotInfoIndex - 1u];
-            bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
-#if defined( __HIP_DEVICE_COMPILE__ )
-            general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
-#endif
-            if( !general )
-            {
-                const vrc_segment& s = src.distOnly();
-                return vrc_march_segment_as< CLAMP, COUNT, FIXED, ATLAS_T, VRC_GROUP, vrc_f4, false, true >(
-                    f, n, s, atlas, lut, color, nSamples, 0.0f, nullptr, lut[word & 0xFFu] );
-            }
-        }
-        const vrc_segment& s = src.full();
-        return vrc_preint_segment< CLAMP, COUNT, FIXED, TRILINEAR, VALUE, ATLAS_T,
-                                   VALUE ? VRC_PREINT_GROUP : VRC_PREINT_GROUP_TEXEL >( f, n, s, atlas, cls, color,
-                                                                                                nSamples );
+        constexpr int GROUP = TRILINEAR          ? VRC_CDEPTH_GROUP_TRILINEAR
+                              : BYTES && !CLAMP ? VRC_CDEPTH_GROUP
+                                                : VRC_CDEPTH_GROUP_CLASSIFIED;
+        return vrc_brick_visit< BIG, BYTES >(
+            f, n, src, atlas,
+            [&]( const vrc_dev_node&, const vrc_segment& s, const ATLAS_T*, uint32_t v ) {
+                return vrc_cdepth_uniform< COUNT >( f, s, lut[v], v, color, nSamples, *cdepth );
+            },
+            [&]( const vrc_dev_node& m, const vrc_segment& s, const ATLAS_T* __restrict__ a ) {
+                vrc_cdepth_policy< CLAMP, FIXED, TRILINEAR, !BYTES, ATLAS_T, GROUP > p = { lut,     cls,        *cdepth, f.cdepthTau,
+                                                                                         s.tNear, f.stepSize, {} };
+                return vrc_group_segment< COUNT, FIXED, GROUP >( f, m, s, a, p, color, nSamples );
+            } );
     }
 }
 
@@ -4476,7 +4262,7 @@ VRC_HD bool vrc_march_brick_from( const vrc_frame& f, const vrc_dev_node& n, con
         uint32_t word = 0u;
         if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
             word = f.slotInfo[n.slotInfoIndex - 1u];
-        bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
+        bool general = !vrc_slot_holds_one_value( word );
 #if defined( __HIP_DEVICE_COMPILE__ )
         general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
 #endif
@@ -4730,18 +4516,11 @@ VRC_HD void vrc_pixel_reference_order( const vrc_frame& f, const vrc_dev_node* _
                 break;
             continue;
         }
-        if constexpr( vrc_mode_is_shade( MODE ) )
+        if constexpr( vrc_mode_is_shade( MODE ) || vrc_mode_is_cdepth( MODE ) )
         {
             const vrc_segment_ready src = { s };
-            if( vrc_shade_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_ready >( f, n, src, r.dir, atlas, lut, cls,
-                                                                                              color, nSamples ) )
-                break;
-        }
-        else if constexpr( vrc_mode_is_cdepth( MODE ) )
-        {
-            const vrc_segment_ready src = { s };
-            if( vrc_cdepth_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_ready >( f, n, src, atlas, lut, cls, color,
-                                                                                               nSamples, *cdepth ) )
+            if( vrc_extension_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_ready >( f, n, src, r.dir, atlas, lut,
+                                                                                                  cls, color, nSamples, cdepth ) )
                 break;
         }
         else if constexpr( vrc_mode_is_preint( MODE ) )
@@ -4919,7 +4698,7 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                         uint32_t word = 0u;
                         if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
                             word = f.slotInfo[n.slotInfoIndex - 1u];
-                        if( ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN )
+                        if( !vrc_slot_holds_one_value( word ) )
                             color.x += 1.0f; /* (exact: a ray visits far fewer than 2^24 bricks) */
                         /* ... and, asked by walkLean, whether a visit fails to pack (color.y != 0) */
                         uint32_t packed;
@@ -4936,18 +4715,11 @@ VRC_HD bool vrc_ray_grid_dda( const vrc_frame& f, const vrc_ray& r, const vrc_de
                     if( vrc_mip_brick< CLAMP, FIXED, MODE, ATLAS_T, GROUP, BIG >( f, n, s, atlas, color, nSamples, (uint32_t)node ) ) /* (color: the ray's MIP state) */
                         finished = true; /* (an isosurface frame: every brick from here on lies behind the ray's hit) */
                 }
-                else if constexpr( vrc_mode_is_shade( MODE ) )
+                else if constexpr( vrc_mode_is_shade( MODE ) || vrc_mode_is_cdepth( MODE ) )
                 {
                     const vrc_segment_from_interval src = { r, iv, f.stepSize };
-                    if( vrc_shade_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_from_interval >(
-                            f, n, src, r.dir, atlas, lut, cls, color, nSamples ) )
-                        finished = true;
-                }
-                else if constexpr( vrc_mode_is_cdepth( MODE ) )
-                {
-                    const vrc_segment_from_interval src = { r, iv, f.stepSize };
-                    if( vrc_cdepth_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_from_interval >(
-                            f, n, src, atlas, lut, cls, color, nSamples, *cdepth ) )
+                    if( vrc_extension_brick< CLAMP, COUNT, FIXED, MODE, ATLAS_T, BIG, vrc_segment_from_interval >(
+                            f, n, src, r.dir, atlas, lut, cls, color, nSamples, cdepth ) )
                         finished = true;
                 }
                 else if constexpr( vrc_mode_is_preint( MODE ) )
@@ -5377,7 +5149,7 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
         const uint32_t loadedNext = vrc_lean_slot_load( f, packedNext );
         const uint32_t packedAfter = vrc_lean_list_word( f, rayIndex, k + 2u );
         const uint32_t word = vrc_lean_slot_word( f, packed, loaded );
-        bool general = ( word & ( VRC_SLOT_KNOWN | VRC_SLOT_MIXED ) ) != VRC_SLOT_KNOWN;
+        bool general = !vrc_slot_holds_one_value( word );
 #if defined( __HIP_DEVICE_COMPILE__ )
         general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
 #endif

@@ -1,19 +1,13 @@
 /*
  * vrc_kernels_cdepth.hip -- gfx950 kernels of a composite frame that keeps the depth at which every ray's opacity crosses
- * a threshold (VRC_OPT_COMPOSITE_DEPTH above 0; vrc_core.h: vrc_cdepth_brick), and nothing else.  A frame with the option
- * at 0, a shaded frame, a MIP frame and an isosurface frame launch nothing from this file.
+ * a threshold (VRC_OPT_COMPOSITE_DEPTH above 0; vrc_core.h: vrc_cdepth_policy under vrc_extension_brick), and nothing
+ * else.  A frame with the option at 0, a shaded frame, a MIP frame and an isosurface frame launch nothing from this file.
  *
- * The kernel frame of the shaded composite (vrc_kernels_shade.hip: vrc_k_raycast_shade) around the depth-tracking march:
- * one wave64 = one 8x8 pixel tile in Morton lane order, four tiles of a schedule unit per workgroup, the tile schedule,
- * the tile culling of the reference-order loop, the classified table (or the padded transfer function) in LDS, the
- * per-axis address tables of the fixed-point stepping, the ray cache of the grid walk, samples always counted in a
- * register.  Behind the march the pixel's (D, V) is stored where this pass crossed and no pass before it had.
+ * The kernel frame (vrc_kernel_frame.h) around the depth-tracking march, with the classified table (or the padded
+ * transfer function) in LDS and the ray cache of the grid walk, samples always counted in a register.  Behind the march
+ * the pixel's (D, V) is stored where this pass crossed and no pass before it had.
  */
-#include "vrc_internal.h"
-
-#include <type_traits>
-
-#define VRC_CDEPTH_WG_THREADS ( 64u * VRC_WAVES_PER_GROUP )
+#include "vrc_kernel_frame.h"
 
 /* Waves per SIMD the compiler plans registers for (a register budget, not a residency limit; DESIGN.md has the table of
  * what every instance came out at).  LDS is 4 KiB of table, 3 KiB of address tables and, in the reference-order form,
@@ -25,89 +19,32 @@
 #define VRC_CDEPTH_MIN_WAVES ( MODE == VRC_MODE_CDEPTH_TRILINEAR ? 3 : 4 )
 
 template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
-__global__ __launch_bounds__( VRC_CDEPTH_WG_THREADS ) __attribute__( ( amdgpu_waves_per_eu( VRC_CDEPTH_MIN_WAVES, 8 ) ) ) void vrc_k_raycast_cdepth(
+__global__ __launch_bounds__( VRC_FRAME_WG_THREADS ) __attribute__( ( amdgpu_waves_per_eu( VRC_CDEPTH_MIN_WAVES, 8 ) ) ) void vrc_k_raycast_cdepth(
     const vrc_frame f, const vrc_dev_node* __restrict__ nodes, const int32_t* __restrict__ gridTable,
     const ATLAS_T* __restrict__ atlas, const vrc_f4* __restrict__ lutGlobal, const vrc_classifier cls,
     vrc_f4* __restrict__ pixelBuffer, unsigned long long* __restrict__ sampleCounter,
     const uint32_t* __restrict__ tileOrder, const uint32_t tilesX, const uint32_t nTiles )
 {
-    /* classified table (257 entries) or, where samples are classified one by one, the padded transfer function (258) */
     __shared__ vrc_f4 lut[VRC_TFP_ENTRIES];
     __shared__ uint16_t tileCand[DDA ? 1u : VRC_WAVES_PER_GROUP * VRC_TILE_CANDIDATES];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
-    for( uint32_t i = tid; i < VRC_TFP_ENTRIES; i += VRC_CDEPTH_WG_THREADS )
-        lut[i] = lutGlobal[i];
+    vrc_frame_fill_table( lut, lutGlobal, tid );
     if( FIXED )
-    {
-        const vrc_lay lay = vrc_make_lay( f.sbx, f.sby );
-        for( uint32_t u = tid; u < 256u; u += VRC_CDEPTH_WG_THREADS )
-        {
-            vrc_addr_tab[u] = vrc_lay_x( lay, u );
-            vrc_addr_tab[256u + u] = vrc_lay_y( lay, u );
-            vrc_addr_tab[512u + u] = vrc_lay_z( lay, u );
-        }
-    }
+        vrc_frame_fill_address_tables( f, tid );
     __syncthreads();
     /* from here on the waves of the workgroup are independent */
-    const uint32_t slotIndex = blockIdx.x * VRC_WAVES_PER_GROUP + ( tid >> 6 );
-    const uint32_t tilesY = nTiles / tilesX;
-    if( slotIndex >= vrc_schedule_slots( tilesX, tilesY ) )
+    vrc_frame_tile t;
+    if( !vrc_frame_find_tile( tileOrder, tilesX, nTiles, tid, lane, t ) )
         return;
-    const uint32_t tile = vrc_slot_tile( tileOrder, slotIndex, tilesX, tilesY );
-    if( tile == VRC_NO_TILE )
-        return;
-    const uint32_t tx = tile % tilesX, ty = tile / tilesX;
-    /* Morton lane order: four consecutive lanes are a 2x2 pixel quad (vrc_k_raycast) */
-    const uint32_t lx = ( lane & 1u ) | ( ( lane >> 1 ) & 2u ) | ( ( lane >> 2 ) & 4u );
-    const uint32_t ly = ( ( lane >> 1 ) & 1u ) | ( ( lane >> 2 ) & 2u ) | ( ( lane >> 3 ) & 4u );
-    const uint32_t px = tx * VRC_TILE_W + lx;
-    const uint32_t py = ty * VRC_TILE_H + ly;
-
     uint32_t nSamples = 0;
-    /* reference-order loop: the bricks this tile's rays can hit at all, found once per wave (vrc_core.h, "tile
-     * culling"; a brick that is not hit is a `continue`, so leaving it out changes no sample) */
-    const uint16_t* cand = nullptr;
-    uint32_t nCand = 0;
-    if( !DDA && f.nodeCount > 8u && f.nodeCount <= 65535u )
-    {
-        uint16_t* const mine = tileCand + ( tid >> 6 ) * VRC_TILE_CANDIDATES;
-        float r0 = 1e30f, r1 = -1e30f;
-        for( uint32_t j = 0; j < VRC_TILE_H; ++j )
-        {
-            const uint32_t row = ty * VRC_TILE_H + j;
-            if( row < f.height )
-            {
-                const float fr = (float)( f.rowMap ? f.rowMap[row] : row );
-                r0 = fminf( r0, fr );
-                r1 = fmaxf( r1, fr );
-            }
-        }
-        const vrc_tile_pyramid pyr = vrc_make_tile_pyramid( f, (float)( tx * VRC_TILE_W ) - 1.0f, r0 - 1.0f,
-                                                           (float)( tx * VRC_TILE_W + VRC_TILE_W ), r1 + 1.0f );
-        for( uint32_t base = 0; base < f.nodeCount; base += 64u )
-        {
-            const uint32_t i = base + lane;
-            bool in = false;
-            if( i < f.nodeCount )
-                in = vrc_pyramid_may_hit( pyr, nodes[i].aabbMin, nodes[i].aabbSize );
-            const uint64_t m = __builtin_amdgcn_ballot_w64( in );
-            const uint32_t at = nCand + __builtin_amdgcn_mbcnt_hi( (uint32_t)( m >> 32 ),
-                                                                   __builtin_amdgcn_mbcnt_lo( (uint32_t)m, 0u ) );
-            if( in && at < VRC_TILE_CANDIDATES )
-                mine[at] = (uint16_t)i;
-            nCand += (uint32_t)__builtin_popcountll( m );
-        }
-        __builtin_amdgcn_fence( __ATOMIC_RELEASE, "wavefront" );
-        __builtin_amdgcn_wave_barrier();
-        if( nCand <= VRC_TILE_CANDIDATES )
-            cand = mine;
-    }
-    if( px < f.width && py < f.height )
+    uint32_t nCand;
+    const uint16_t* const cand = vrc_frame_cull_tile< DDA >( f, nodes, tileCand, tid, lane, t.tx, t.ty, nCand );
+    if( t.px < f.width && t.py < f.height )
     {
         /* the pixel's pair: a first pass does not read it and leaves every pixel's; a later pass leaves the pair of a
          * pixel that had crossed alone, in the march (crossed from the start) and here */
-        const uint32_t pixelPos = py * f.width + px;
+        const uint32_t pixelPos = t.py * f.width + t.px;
         vrc_cdepth_state z = { vrc_bits_float( 0x7F800000u ), VRC_MIP_EMPTY, false };
         bool had = false;
         if( !f.mipFirst )
@@ -115,10 +52,10 @@ __global__ __launch_bounds__( VRC_CDEPTH_WG_THREADS ) __attribute__( ( amdgpu_wa
         z.crossed = had;
         if( DDA )
             vrc_pixel_grid_dda< CLAMP, true, FIXED, MODE, ATLAS_T, VRC_CDEPTH_GROUP, BIG >(
-                f, nodes, gridTable, atlas, lut, cls, pixelBuffer, px, py, nSamples, tile * 64u + lane, &z );
+                f, nodes, gridTable, atlas, lut, cls, pixelBuffer, t.px, t.py, nSamples, t.tile * 64u + lane, &z );
         else
             vrc_pixel_reference_order< CLAMP, true, FIXED, MODE, ATLAS_T, VRC_CDEPTH_GROUP, BIG >(
-                f, nodes, atlas, lut, cls, pixelBuffer, px, py, nSamples, cand, nCand, &z );
+                f, nodes, atlas, lut, cls, pixelBuffer, t.px, t.py, nSamples, cand, nCand, &z );
         if( f.mipFirst || ( z.crossed && !had ) )
         {
             f.mipDepth[pixelPos] = z.d;
@@ -126,79 +63,24 @@ __global__ __launch_bounds__( VRC_CDEPTH_WG_THREADS ) __attribute__( ( amdgpu_wa
         }
     }
     if( sampleCounter != nullptr )
+        vrc_frame_add_samples( sampleCounter, nSamples, lane );
+}
+
+struct vrc_cdepth_kernels
+{
+    static constexpr int POINT = VRC_MODE_CDEPTH, TRILINEAR = VRC_MODE_CDEPTH_TRILINEAR;
+    template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
+    static hipError_t launch( const vrc_raycast_args& a, hipStream_t stream )
     {
-        /* wave64 reduction, one atomic per wave */
-        unsigned long long s = nSamples;
-#pragma unroll
-        for( int off = 32; off > 0; off >>= 1 )
-            s += __shfl_down( s, off, 64 );
-        if( lane == 0 && s != 0 )
-            atomicAdd( sampleCounter, s );
+        return vrc_frame_launch< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >(
+            "vrc_k_raycast_cdepth", &vrc_k_raycast_cdepth< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >, a, stream );
     }
-}
-
-template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
-static hipError_t launch_cdepth( const vrc_raycast_args& a, hipStream_t stream )
-{
-    const uint32_t tilesX = ( a.frame.width + VRC_TILE_W - 1 ) / VRC_TILE_W;
-    const uint32_t tilesY = ( a.frame.height + VRC_TILE_H - 1 ) / VRC_TILE_H;
-    const uint32_t nTiles = tilesX * tilesY;
-    if( nTiles == 0 )
-        return hipSuccess;
-    vrc_internal_note_kernel( "vrc_k_raycast_cdepth<%s,%s,%s,%d,%s,%s>", DDA ? "true" : "false", CLAMP ? "true" : "false",
-                              FIXED ? "true" : "false", (int)MODE,
-                              std::is_same< ATLAS_T, float >::value ? "float" : sizeof( ATLAS_T ) == 1 ? "unsigned char" : "unsigned short",
-                              BIG ? "true" : "false" );
-    vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_cdepth< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >,
-                                 (int)VRC_CDEPTH_WG_THREADS, 0 );
-    vrc_launch_march( a, &vrc_k_raycast_cdepth< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >,
-                      dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WAVES_PER_GROUP - 1u ) / VRC_WAVES_PER_GROUP ),
-                      dim3( VRC_CDEPTH_WG_THREADS ), 0, stream, a.frame, a.nodes, a.gridTable, (const ATLAS_T*)a.atlas,
-                      a.lut, a.classifier, a.pixelBuffer, a.sampleCounter, a.tileOrder, tilesX, nTiles );
-    return hipGetLastError();
-}
-
-/* the sampler of the plain composite forms (vrc_launch_raycast): fixed-point stepping where the caller asked for it
- * and the slot has an overlap (point samples), the float chain with or without clamped addressing otherwise; the
- * trilinear gather form always steps in float */
-template < int MODE, typename ATLAS_T, bool BIG >
-static hipError_t launch_cdepth_sampler( const vrc_raycast_args& a, hipStream_t stream )
-{
-    /* (8-bit point samples of an atlas of more than 2^32 voxels step in float, as vrc_launch_raycast's BIG instances do:
-     * the depth frame takes the plain frame's sample positions) */
-    if constexpr( MODE == VRC_MODE_CDEPTH && ( !BIG || sizeof( ATLAS_T ) >= 2 ) )
-        if( a.fixedStepping && !a.clamp )
-            return a.gridDda ? launch_cdepth< true, false, true, MODE, ATLAS_T, BIG >( a, stream )
-                             : launch_cdepth< false, false, true, MODE, ATLAS_T, BIG >( a, stream );
-    if( a.clamp )
-        return a.gridDda ? launch_cdepth< true, true, false, MODE, ATLAS_T, BIG >( a, stream )
-                         : launch_cdepth< false, true, false, MODE, ATLAS_T, BIG >( a, stream );
-    return a.gridDda ? launch_cdepth< true, false, false, MODE, ATLAS_T, BIG >( a, stream )
-                     : launch_cdepth< false, false, false, MODE, ATLAS_T, BIG >( a, stream );
-}
-
-template < typename ATLAS_T >
-static hipError_t launch_cdepth_atlas( const vrc_raycast_args& a, hipStream_t stream )
-{
-    if( a.linear )
-        return a.bigAtlas ? launch_cdepth_sampler< VRC_MODE_CDEPTH_TRILINEAR, ATLAS_T, true >( a, stream )
-                          : launch_cdepth_sampler< VRC_MODE_CDEPTH_TRILINEAR, ATLAS_T, false >( a, stream );
-    return a.bigAtlas ? launch_cdepth_sampler< VRC_MODE_CDEPTH, ATLAS_T, true >( a, stream )
-                      : launch_cdepth_sampler< VRC_MODE_CDEPTH, ATLAS_T, false >( a, stream );
-}
+};
 
 hipError_t vrc_launch_raycast_cdepth( const vrc_raycast_args& a, hipStream_t stream )
 {
     if( VRC_TILE_W != 8u || a.lut == nullptr || !a.cdepth || a.shade || a.packed || a.frame.mipMax == nullptr ||
         a.frame.mipDepth == nullptr )
         return hipErrorInvalidValue;
-    if( a.gridDda && a.gridTable == nullptr )
-        return hipErrorInvalidValue;
-    switch( a.elemBytes )
-    {
-    case 1: return launch_cdepth_atlas< uint8_t >( a, stream );
-    case 2: return launch_cdepth_atlas< uint16_t >( a, stream );
-    case 4: return launch_cdepth_atlas< float >( a, stream );
-    default: return hipErrorInvalidValue;
-    }
+    return vrc_frame_launch_extension< vrc_cdepth_kernels >( a, stream );
 }

@@ -4,9 +4,7 @@
  * of which instantiates its own fold's instances and nothing else -- the instances of one fold take about half a minute
  * to compile, and a change to one fold's code does not rebuild the others'.
  *
- * The frame of the composite kernel (vrc_kernels.hip: vrc_k_raycast) around another march body: one wave64 = one
- * 8x8 pixel tile in Morton lane order, four tiles of a schedule unit per workgroup, the tile schedule, the tile
- * culling of the reference-order loop, the per-axis address tables of the fixed-point stepping.  What it does not
+ * The kernel frame (vrc_kernel_frame.h) around another march body.  What it does not
  * have: a table in LDS (the pixel is classified once per ray, from the padded transfer function in global memory),
  * a transmittance, an early-exit test.  Per sample: the address, the gather and half a v_max3 (minimum: v_min3; mean:
  * half a v_add3, or one v_add_f64).
@@ -17,11 +15,7 @@
 #ifndef VRC_KERNELS_MIP_H
 #define VRC_KERNELS_MIP_H
 
-#include "vrc_internal.h"
-
-#include <type_traits>
-
-#define VRC_MIP_WG_THREADS ( 64u * VRC_WAVES_PER_GROUP )
+#include "vrc_kernel_frame.h"
 
 /* Waves per SIMD the compiler plans registers for (amdgpu_waves_per_eu is a register budget, not a residency limit).
  * Without the classified table the LDS need is 3 KiB of address tables (plus 8 KiB of tile candidates in the
@@ -44,7 +38,7 @@
 #define VRC_MIP_MAX_WAVES ( ( vrc_mode_base( MODE ) == VRC_MODE_MIP && FIXED && !CLAMP && !BIG ) ? 5 : 8 )
 
 template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
-__global__ __launch_bounds__( VRC_MIP_WG_THREADS ) __attribute__( ( amdgpu_waves_per_eu( VRC_MIP_MIN_WAVES, VRC_MIP_MAX_WAVES ) ) ) void vrc_k_raycast_mip(
+__global__ __launch_bounds__( VRC_FRAME_WG_THREADS ) __attribute__( ( amdgpu_waves_per_eu( VRC_MIP_MIN_WAVES, VRC_MIP_MAX_WAVES ) ) ) void vrc_k_raycast_mip(
     const vrc_frame f, const vrc_dev_node* __restrict__ nodes, const int32_t* __restrict__ gridTable,
     const ATLAS_T* __restrict__ atlas, const vrc_f4* __restrict__ tfp, const vrc_classifier cls,
     vrc_f4* __restrict__ pixelBuffer, unsigned long long* __restrict__ sampleCounter,
@@ -55,103 +49,28 @@ __global__ __launch_bounds__( VRC_MIP_WG_THREADS ) __attribute__( ( amdgpu_waves
     const uint32_t lane = tid & 63u;
     if( FIXED )
     {
-        const vrc_lay lay = vrc_make_lay( f.sbx, f.sby );
-        for( uint32_t u = tid; u < 256u; u += VRC_MIP_WG_THREADS )
-        {
-            vrc_addr_tab[u] = vrc_lay_x( lay, u );
-            vrc_addr_tab[256u + u] = vrc_lay_y( lay, u );
-            vrc_addr_tab[512u + u] = vrc_lay_z( lay, u );
-        }
+        vrc_frame_fill_address_tables( f, tid );
         __syncthreads();
     }
     /* from here on the waves of the workgroup are independent */
-    const uint32_t slotIndex = blockIdx.x * VRC_WAVES_PER_GROUP + ( tid >> 6 );
-    const uint32_t tilesY = nTiles / tilesX;
-    if( slotIndex >= vrc_schedule_slots( tilesX, tilesY ) )
+    vrc_frame_tile t;
+    if( !vrc_frame_find_tile( tileOrder, tilesX, nTiles, tid, lane, t ) )
         return;
-    const uint32_t tile = vrc_slot_tile( tileOrder, slotIndex, tilesX, tilesY );
-    if( tile == VRC_NO_TILE )
-        return;
-    const uint32_t tx = tile % tilesX, ty = tile / tilesX;
-    /* Morton lane order: four consecutive lanes are a 2x2 pixel quad (vrc_k_raycast) */
-    const uint32_t lx = ( lane & 1u ) | ( ( lane >> 1 ) & 2u ) | ( ( lane >> 2 ) & 4u );
-    const uint32_t ly = ( ( lane >> 1 ) & 1u ) | ( ( lane >> 2 ) & 2u ) | ( ( lane >> 3 ) & 4u );
-    const uint32_t px = tx * VRC_TILE_W + lx;
-    const uint32_t py = ty * VRC_TILE_H + ly;
-
     uint32_t nSamples = 0;
-    /* reference-order loop: the bricks this tile's rays can hit at all, found once per wave (vrc_core.h, "tile
-     * culling"; a brick that is not hit is a `continue`, so leaving it out changes no sample) */
-    const uint16_t* cand = nullptr;
-    uint32_t nCand = 0;
-    if( !DDA && f.nodeCount > 8u && f.nodeCount <= 65535u )
-    {
-        uint16_t* const mine = tileCand + ( tid >> 6 ) * VRC_TILE_CANDIDATES;
-        float r0 = 1e30f, r1 = -1e30f;
-        for( uint32_t j = 0; j < VRC_TILE_H; ++j )
-        {
-            const uint32_t row = ty * VRC_TILE_H + j;
-            if( row < f.height )
-            {
-                const float fr = (float)( f.rowMap ? f.rowMap[row] : row );
-                r0 = fminf( r0, fr );
-                r1 = fmaxf( r1, fr );
-            }
-        }
-        const vrc_tile_pyramid pyr = vrc_make_tile_pyramid( f, (float)( tx * VRC_TILE_W ) - 1.0f, r0 - 1.0f,
-                                                           (float)( tx * VRC_TILE_W + VRC_TILE_W ), r1 + 1.0f );
-        for( uint32_t base = 0; base < f.nodeCount; base += 64u )
-        {
-            const uint32_t i = base + lane;
-            bool in = false;
-            if( i < f.nodeCount )
-                in = vrc_pyramid_may_hit( pyr, nodes[i].aabbMin, nodes[i].aabbSize );
-            const uint64_t m = __builtin_amdgcn_ballot_w64( in );
-            const uint32_t at = nCand + __builtin_amdgcn_mbcnt_hi( (uint32_t)( m >> 32 ),
-                                                                   __builtin_amdgcn_mbcnt_lo( (uint32_t)m, 0u ) );
-            if( in && at < VRC_TILE_CANDIDATES )
-                mine[at] = (uint16_t)i;
-            nCand += (uint32_t)__builtin_popcountll( m );
-        }
-        __builtin_amdgcn_fence( __ATOMIC_RELEASE, "wavefront" );
-        __builtin_amdgcn_wave_barrier();
-        if( nCand <= VRC_TILE_CANDIDATES )
-            cand = mine;
-    }
-    if( px < f.width && py < f.height )
+    uint32_t nCand;
+    const uint16_t* const cand = vrc_frame_cull_tile< DDA >( f, nodes, tileCand, tid, lane, t.tx, t.ty, nCand );
+    if( t.px < f.width && t.py < f.height )
         vrc_pixel_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, VRC_GROUP, BIG >( f, nodes, gridTable, atlas, tfp, cls, pixelBuffer,
-                                                                         px, py, nSamples, cand, nCand );
+                                                                         t.px, t.py, nSamples, cand, nCand );
     if( sampleCounter != nullptr )
-    {
-        /* wave64 reduction, one atomic per wave */
-        unsigned long long s = nSamples;
-#pragma unroll
-        for( int off = 32; off > 0; off >>= 1 )
-            s += __shfl_down( s, off, 64 );
-        if( lane == 0 && s != 0 )
-            atomicAdd( sampleCounter, s );
-    }
+        vrc_frame_add_samples( sampleCounter, nSamples, lane );
 }
 
 template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
 static hipError_t launch_mip( const vrc_raycast_args& a, hipStream_t stream )
 {
-    const uint32_t tilesX = ( a.frame.width + VRC_TILE_W - 1 ) / VRC_TILE_W;
-    const uint32_t tilesY = ( a.frame.height + VRC_TILE_H - 1 ) / VRC_TILE_H;
-    const uint32_t nTiles = tilesX * tilesY;
-    if( nTiles == 0 )
-        return hipSuccess;
-    vrc_internal_note_kernel( "vrc_k_raycast_mip<%s,%s,%s,%d,%s,%s>", DDA ? "true" : "false", CLAMP ? "true" : "false",
-                              FIXED ? "true" : "false", (int)MODE,
-                              std::is_same< ATLAS_T, float >::value ? "float" : sizeof( ATLAS_T ) == 1 ? "unsigned char" : "unsigned short",
-                              BIG ? "true" : "false" );
-    vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >,
-                                 (int)VRC_MIP_WG_THREADS, 0 );
-    vrc_launch_march( a, &vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >,
-                      dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WAVES_PER_GROUP - 1u ) / VRC_WAVES_PER_GROUP ),
-                      dim3( VRC_MIP_WG_THREADS ), 0, stream, a.frame, a.nodes, a.gridTable, (const ATLAS_T*)a.atlas,
-                      a.lut, a.classifier, a.pixelBuffer, a.sampleCounter, a.tileOrder, tilesX, nTiles );
-    return hipGetLastError();
+    return vrc_frame_launch< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >(
+        "vrc_k_raycast_mip", &vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >, a, stream );
 }
 
 /* the sampler of the composite forms: fixed-point stepping where the slot has an overlap and fits eight bits a side

@@ -1,6 +1,6 @@
 /*
  * cdepth_harness.cpp -- host build (g++) of the per-ray code of a composite frame that keeps the depth of its rays'
- * crossings (libre_amd/csrc/vrc_core.h: vrc_cdepth_brick under vrc_pixel_reference_order / vrc_pixel_grid_dda), for
+ * crossings (libre_amd/csrc/vrc_core.h: vrc_extension_brick under vrc_pixel_reference_order / vrc_pixel_grid_dda), for
  * tests/test_cdepth_cpu.py.  TEST INFRASTRUCTURE ONLY.  The same call renders the plain frame through the instances
  * vrc_launch_raycast picks (tau1000 = 0), so that the two can be compared bit for bit.
  *
@@ -321,14 +321,14 @@ uint64_t march( const tiny< T >& sc, const vrc_ray& r, const vrc_f4* lut, const 
             bool done;
             const vrc_f4* const table = sizeof( T ) == 1 ? lut : tfp;
             if( form == 1 )
-                done = vrc_cdepth_brick< CLAMP, true, false, VRC_MODE_CDEPTH_TRILINEAR, T, false, vrc_segment_ready >(
-                    sc.f, sc.t.nodes[i], src, sc.atlas.data(), tfp, cls, color, n, z );
+                done = vrc_extension_brick< CLAMP, true, false, VRC_MODE_CDEPTH_TRILINEAR, T, false, vrc_segment_ready >(
+                    sc.f, sc.t.nodes[i], src, r.dir, sc.atlas.data(), tfp, cls, color, n, &z );
             else if( form == 2 )
-                done = vrc_cdepth_brick< false, true, !CLAMP, VRC_MODE_CDEPTH, T, false, vrc_segment_ready >(
-                    sc.f, sc.t.nodes[i], src, sc.atlas.data(), table, cls, color, n, z );
+                done = vrc_extension_brick< false, true, !CLAMP, VRC_MODE_CDEPTH, T, false, vrc_segment_ready >(
+                    sc.f, sc.t.nodes[i], src, r.dir, sc.atlas.data(), table, cls, color, n, &z );
             else
-                done = vrc_cdepth_brick< CLAMP, true, false, VRC_MODE_CDEPTH, T, false, vrc_segment_ready >(
-                    sc.f, sc.t.nodes[i], src, sc.atlas.data(), table, cls, color, n, z );
+                done = vrc_extension_brick< CLAMP, true, false, VRC_MODE_CDEPTH, T, false, vrc_segment_ready >(
+                    sc.f, sc.t.nodes[i], src, r.dir, sc.atlas.data(), table, cls, color, n, &z );
             if( done )
                 break;
         }

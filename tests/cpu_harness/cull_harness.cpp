@@ -3,12 +3,14 @@
  * (libre_amd/csrc/vrc_core.h, "tile culling": vrc_make_tile_pyramid, vrc_pyramid_may_hit), for
  * tests/test_tile_cull_cpu.py and tests/test_tile_cull.py.  TEST INFRASTRUCTURE ONLY.
  *
- * The five kernels that carry the block (vrc_k_raycast, _mip, _shade, _cdepth, _preint) run it per wave: the wave's
+ * The five kernels that carry the block (vrc_k_raycast and _preint their own copies in libre_amd/csrc/vrc_kernels.hip and
+ * vrc_kernels_preint.hip; _mip, _shade and _cdepth the shared one, libre_amd/csrc/vrc_kernel_frame.h:
+ * vrc_frame_cull_tile) run it per wave: the wave's
  * 8x8 tile, a pyramid through its corner pixels with one pixel of margin, the list tested 64 bricks at a time, the
  * survivors compacted by ballot into 16-bit indices.  cull_tile() below restates that loop in plain C++ -- lanes
  * become an inner loop, the ballot a running count -- and calls the product's own pyramid functions.  The rule that
  * picks one of the four regimes is restated with it; tests/test_tile_cull_cpu.py reads the kernel sources to check
- * that the constants here are the ones the kernels carry.
+ * that the constants here are the ones all three copies carry, and that every other kernel calls the shared one.
  *
  * tests/host_san/cull_selftest.cpp includes this file and adds a main(): the stand-alone program for the address and
  * undefined-behaviour sanitizers.
@@ -74,7 +76,7 @@ int prepare( cull_setup& c, const uint32_t atlasDim[3], const uint32_t slotDim[3
     return 0;
 }
 
-/* The wave's block, statement for statement (vrc_kernels.hip, "reference-order loop"): the pyramid of tile (tx, ty),
+/* The wave's block, statement for statement (vrc_kernel_frame.h: vrc_frame_cull_tile): the pyramid of tile (tx, ty),
  * the list against it in steps of 64, the survivors into mine[0 .. VRC_TILE_CANDIDATES).  kept (nodeCount bytes, or
  * null): 1 where the pyramid keeps the brick.  Returns the survivor count.  The test itself does not depend on the
  * regime; which loop the lanes then run is cull_regime(). */

@@ -1,6 +1,6 @@
 /*
  * shade_harness.cpp -- host build (g++) of the per-ray code of a shaded composite frame (libre_amd/csrc/vrc_core.h:
- * vrc_shade_brick under vrc_pixel_reference_order / vrc_pixel_grid_dda), for tests/test_shade_cpu.py.  TEST
+ * vrc_extension_brick under vrc_pixel_reference_order / vrc_pixel_grid_dda), for tests/test_shade_cpu.py.  TEST
  * INFRASTRUCTURE ONLY.  The same call renders the unshaded frame through the instances vrc_launch_raycast picks
  * (shading = 0), so that the two can be compared bit for bit.
  *
@@ -310,14 +310,14 @@ uint64_t march( const tiny< T >& sc, const vrc_ray& r, const vrc_f4* lut, const 
             bool done;
             const vrc_f4* const table = sizeof( T ) == 1 ? lut : tfp;
             if( form == 1 )
-                done = vrc_shade_brick< CLAMP, true, false, VRC_MODE_SHADE_TRILINEAR, T, false, vrc_segment_ready >(
-                    sc.f, sc.t.nodes[i], src, r.dir, sc.atlas.data(), tfp, cls, color, n );
+                done = vrc_extension_brick< CLAMP, true, false, VRC_MODE_SHADE_TRILINEAR, T, false, vrc_segment_ready >(
+                    sc.f, sc.t.nodes[i], src, r.dir, sc.atlas.data(), tfp, cls, color, n, nullptr );
             else if( form == 2 )
-                done = vrc_shade_brick< false, true, !CLAMP, VRC_MODE_SHADE, T, false, vrc_segment_ready >(
-                    sc.f, sc.t.nodes[i], src, r.dir, sc.atlas.data(), table, cls, color, n );
+                done = vrc_extension_brick< false, true, !CLAMP, VRC_MODE_SHADE, T, false, vrc_segment_ready >(
+                    sc.f, sc.t.nodes[i], src, r.dir, sc.atlas.data(), table, cls, color, n, nullptr );
             else
-                done = vrc_shade_brick< CLAMP, true, false, VRC_MODE_SHADE, T, false, vrc_segment_ready >(
-                    sc.f, sc.t.nodes[i], src, r.dir, sc.atlas.data(), table, cls, color, n );
+                done = vrc_extension_brick< CLAMP, true, false, VRC_MODE_SHADE, T, false, vrc_segment_ready >(
+                    sc.f, sc.t.nodes[i], src, r.dir, sc.atlas.data(), table, cls, color, n, nullptr );
             if( done )
                 break;
         }

@@ -298,18 +298,31 @@ def test_a_frame_of_two_passes(name):
 
 # ---- the four regimes, by construction ---------------------------------------------------------------------------------------
 def test_the_thresholds_are_the_kernels():
-    """cull_limits() against the sources: the five kernels carry one and the same condition around the block, the tile is
-    the wave's, and the candidates' array is the macro of vrc_core.h."""
+    """cull_limits() against the sources: the condition around the block, the two comparisons with the candidates' array
+    and the margins stand in the shared block of vrc_kernel_frame.h, which the kernels of vrc_kernels_mip.h,
+    vrc_kernels_shade.hip and vrc_kernels_cdepth.hip each call once, carrying none of them themselves -- and once each in
+    vrc_kernels.hip, whose code object is held to the last byte and did not stay so with the call, and in
+    vrc_kernels_preint.hip, whose 8-bit point-sampled instance ran 6-7 % slower over the shared pieces; nowhere else.
+    The tile is the wave's, and the candidates' array is the macro of vrc_core.h."""
     lim = cull.limits()
-    found = 0
-    for f in ("vrc_kernels.hip", "vrc_kernels_mip.h", "vrc_kernels_shade.hip", "vrc_kernels_cdepth.hip", "vrc_kernels_preint.hip"):
+    block, own = "vrc_kernel_frame.h", ("vrc_kernels.hip", "vrc_kernels_preint.hip")
+    callers = ("vrc_kernels_mip.h", "vrc_kernels_shade.hip", "vrc_kernels_cdepth.hip")
+    pieces = (r"f\.nodeCount > (\d+)u && f\.nodeCount <= (\d+)u", r"at < VRC_TILE_CANDIDATES", r"nCand <= VRC_TILE_CANDIDATES",
+              r"- 1\.0f, r0 - 1\.0f", r"r1 \+ 1\.0f")
+    sources = sorted(n for n in os.listdir(CSRC) if n.endswith((".h", ".hip")))
+    assert block in sources and all(k in sources for k in own + callers)
+    for f in sources:
         text = open(os.path.join(CSRC, f)).read()
-        m = re.findall(r"f\.nodeCount > (\d+)u && f\.nodeCount <= (\d+)u", text)
-        assert len(m) == 1 and (int(m[0][0]), int(m[0][1])) == (lim.lower, lim.upper), (f, m)
-        assert len(re.findall(r"at < VRC_TILE_CANDIDATES", text)) == 1 and len(re.findall(r"nCand <= VRC_TILE_CANDIDATES", text)) == 1
-        assert "- 1.0f, r0 - 1.0f" in text and "r1 + 1.0f" in text, f
-        found += 1
-    assert found == 5
+        counts = [len(re.findall(p, text)) for p in pieces]
+        assert counts == ([1] * len(pieces) if f == block or f in own else [0] * len(pieces)), (f, counts)
+        calls = len(re.findall(r"vrc_frame_cull_tile< DDA >\(", text))
+        assert calls == (1 if f in callers else 0), (f, calls)
+        if f in callers:
+            assert '#include "%s"' % block in text, f
+        if f == block or f in own:
+            m = re.findall(pieces[0], text)
+            assert (int(m[0][0]), int(m[0][1])) == (lim.lower, lim.upper), (f, m)
+    assert len(re.findall(r"vrc_frame_cull_tile\(", open(os.path.join(CSRC, block)).read())) == 1, "one definition"
     core = open(os.path.join(CSRC, "vrc_core.h")).read()
     assert int(re.search(r"#define VRC_TILE_CANDIDATES (\d+)u", core).group(1)) == lim.candidates
     internal = open(os.path.join(CSRC, "vrc_internal.h")).read()
