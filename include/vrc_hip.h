@@ -277,6 +277,17 @@ typedef struct
                                     * when VRC_OPT_PROJECTION = VRC_PROJECTION_COMPOSITE: MIP and isosurface frames
                                     * ignore it */
 #define VRC_OPT_PREINT_BUILDS 33    /* read-only: how many times this context has built a pre-integrated table */
+#define VRC_OPT_WALK_UNIFORM_ONLY 34 /* 1 (default) | 0.  A view that replays lean lists (VRC_OPT_WALK_LEAN_USED = 1) and
+                                    * none of whose visits meets a brick that is not known to be uniform -- by the count
+                                    * pass of those lists, and while the pool has taken no upload and VRC_OPT_UNIFORM_BRICKS
+                                    * has not changed since that pass, under VRC_WALK_CACHE_ALWAYS too -- is replayed by
+                                    * an instance that holds no gather march (vrc_last_kernel:
+                                    * vrc_k_raycast_replay<...,uniform,lean>): fewer registers, more waves in flight.  The
+                                    * same lists, the same frame and sample count, bit for bit.  Any other view, and
+                                    * every view at 0, replays as before; changing the option starts nothing over.  Any
+                                    * other value: VRC_EINVAL */
+#define VRC_OPT_WALK_UNIFORM_ONLY_USED 35 /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render
+                                    * replayed its lists with that instance, 0 if it did anything else */
 /* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
  * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
  * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots

@@ -246,6 +246,13 @@ struct vrc_ctx
      * VRC_OPT_WALK_LEAN_USED */
     bool walkLeanAsked = false, walkLean = false;
     int64_t walkLeanUsed = 0;
+    /* the uniform-only replay (VRC_OPT_WALK_UNIFORM_ONLY).  walkGathers: what the count pass of the lists in the planes
+     * said of the slot words it read, those of walkGen and walkSlotInfo -- compared for this whatever VRC_OPT_WALK_CACHE
+     * says, because at VRC_WALK_CACHE_ALWAYS the lists outlive an upload and that answer does not.  walkUniformUsed:
+     * VRC_OPT_WALK_UNIFORM_ONLY_USED */
+    unsigned long long walkGathers = 0;
+    int64_t optWalkUniformOnly = 1;
+    int64_t walkUniformUsed = 0;
     int64_t optStepping = 1;
     int64_t optVariant = VRC_VARIANT_CUDARAYCASTER;
     bool rayLod = false; /* vrc_set_ray_lod */
@@ -571,6 +578,13 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
             c->walkState = vrc_ctx::WALK_IDLE;
         c->optWalkBudget = value;
         return VRC_OK;
+    case VRC_OPT_WALK_UNIFORM_ONLY:
+        if( value != 0 && value != 1 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_UNIFORM_ONLY is 0 (off) or 1 (on)" );
+        c->optWalkUniformOnly = value; /* (which instance replays the lists: nothing starts over) */
+        return VRC_OK;
+    case VRC_OPT_WALK_UNIFORM_ONLY_USED:
+        return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_UNIFORM_ONLY_USED is read-only" );
     case VRC_OPT_PROJECTION:
         if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP && value != VRC_PROJECTION_ISO )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite), 1 (maximum intensity) or 2 (isosurface)" );
@@ -659,6 +673,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_WALK_CACHE_BUDGET: *value = c->optWalkBudget; return VRC_OK;
     case VRC_OPT_WALK_CACHE_BYTES: *value = (int64_t)( c->dWalkWords * sizeof( uint32_t ) ); return VRC_OK;
     case VRC_OPT_WALK_LEAN_USED: *value = c->walkLeanUsed; return VRC_OK;
+    case VRC_OPT_WALK_UNIFORM_ONLY: *value = c->optWalkUniformOnly; return VRC_OK;
+    case VRC_OPT_WALK_UNIFORM_ONLY_USED: *value = c->walkUniformUsed; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->optProjection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->optMipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->optMipFold; return VRC_OK;
@@ -2364,6 +2380,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold */
     c->walkCacheUsed = 0;
     c->walkLeanUsed = 0;
+    c->walkUniformUsed = 0;
     f.walkCache = nullptr;
     f.walkPlane = f.walkK = 0u;
     f.walkLean = f.walkSlots = 0u;
@@ -2444,6 +2461,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
                         }
                         c->walkK = k;
                         c->walkLean = c->walkLeanAsked && c->hWalkMax->notLean == 0u;
+                        c->walkGathers = c->hWalkMax->gathers;
                         walkRecord = true;
                         c->walkCacheUsed = 3;
                     }
@@ -2460,6 +2478,16 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             f.walkLean = c->walkLean ? 1u : 0u;
             f.walkSlots = (uint32_t)nSlots;
             c->walkLeanUsed = ( c->walkLean && c->walkCacheUsed == 4 ) ? 1 : 0;
+            /* the uniform-only instance (vrc_kernels_walk.hip): a replayed lean frame none of whose visits gathers --
+             * by the count pass of these lists, which is still the answer while the pool has taken no upload and the
+             * words are the ones it read.  Where the lists outlive that (VRC_WALK_CACHE_ALWAYS) the frame goes back to
+             * the lean instance and keeps them */
+            if( c->walkLeanUsed && c->optWalkUniformOnly && c->walkGathers == 0ull && c->walkGen == gen &&
+                c->walkSlotInfo == f.slotInfo )
+            {
+                f.walkLean = VRC_WALK_LEAN_UNIFORM;
+                c->walkUniformUsed = 1;
+            }
         }
         else if( walkCount )
             f.walkLean = leanAsked ? 1u : 0u; /* (the count pass: check every visit) */

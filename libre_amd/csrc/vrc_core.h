@@ -39,6 +39,7 @@
     defined( VRC_GROUP ) || \
     defined( VRC_GREY_GROUP ) || \
     defined( VRC_GREY_MAX_WAVES ) || defined( VRC_REPLAY_GREY_MAX_WAVES ) || \
+    defined( VRC_REPLAY_UNIFORM_MAX_WAVES ) || defined( VRC_REPLAY_UNIFORM_WG_WAVES ) || \
     defined( VRC_LGROUP ) || \
     defined( VRC_PGROUP ) || defined( VRC_PGROUP16 ) || defined( VRC_PACKED_WAVES ) || defined( VRC_PACKED_ABLATE ) || \
     defined( VRC_SPLIT_GROUP ) || \
@@ -245,7 +246,10 @@ struct vrc_frame
      * node's slotInfoIndex, what the uniform march would otherwise fetch and compute again in every frame -- and the
      * replay is vrc_pixel_walk_replay_lean.  In the count pass (walkK = 0) it asks whether every visit can be packed.
      * walkSlots: the words of slotInfo, what an index read from a list is clamped by.  The host sets both
-     * (vrc_render); a frame that leaves them 0 records and replays the other form */
+     * (vrc_render); a frame that leaves them 0 records and replays the other form.  VRC_WALK_LEAN_UNIFORM (a replayed
+     * frame only): the same lists, and the host knows that none of their visits gathers -- the replay is the uniform-only
+     * instance (vrc_pixel_walk_replay_lean< ..., true >) */
+#define VRC_WALK_LEAN_UNIFORM 2u
     uint32_t walkLean;
     uint32_t walkSlots;
     /* a shaded composite frame (VRC_OPT_SHADING, the vrc_k_raycast_shade instances; at the end: no field above moves):
@@ -5114,7 +5118,13 @@ VRC_HD uint32_t vrc_lean_list_word( const vrc_frame& f, uint32_t rayIndex, uint3
     return f.walkCache[(size_t)rayIndex + plane * f.walkPlane];
 }
 
-template < bool COUNT, int MODE, int GROUP >
+/* UNIFORM_ONLY: the same replay for a frame none of whose visits gathers (vrc_frame::walkLean = VRC_WALK_LEAN_UNIFORM:
+ * the count pass of these lists found no such visit, and the host has seen no upload and no other slotInfo since).  The
+ * wave then never asks whether one of its lanes gathers -- no ballot -- and the gather march is not in the function:
+ * what is left is the loads, the rule and vrc_march_uniform_lean, in 20 registers where the other form holds the gather
+ * march's 79 across the loop.  A word that does not hold one value after all (the host's rule is what keeps it from
+ * happening) is clamped like any other and ends the ray's list at that visit: nothing is read through it */
+template < bool COUNT, int MODE, int GROUP, bool UNIFORM_ONLY = false >
 VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* __restrict__ nodes,
                                         const uint8_t* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
                                         vrc_f4* __restrict__ pixelBuffer, uint32_t px, uint32_t py, uint32_t& nSamples,
@@ -5149,25 +5159,36 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
         const uint32_t loadedNext = vrc_lean_slot_load( f, packedNext );
         const uint32_t packedAfter = vrc_lean_list_word( f, rayIndex, k + 2u );
         const uint32_t word = vrc_lean_slot_word( f, packed, loaded );
+        const uint32_t n = packed >> VRC_WALK_LEAN_INDEX_BITS;
         bool general = !vrc_slot_holds_one_value( word );
-#if defined( __HIP_DEVICE_COMPILE__ )
-        general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
-#endif
         bool done;
-        if( !general )
-            done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], packed >> VRC_WALK_LEAN_INDEX_BITS, nSamples );
+        if constexpr( UNIFORM_ONLY )
+        {
+            /* no ballot, and no gather march in the function: such a word ends the list */
+            if( general )
+                break;
+            done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], n, nSamples );
+        }
         else
         {
-            /* the gather visit's own loads, all inside its branch: the interval and the ray's direction are asked for
-             * in front of the node, so the five of them travel while the node index and the node arrive */
-            const uint32_t* const at = f.walkCache + ( (size_t)rayIndex + ( 1u + 4u * (size_t)k ) * f.walkPlane );
-            const vrc_walk_early early = vrc_walk_load_early( f, rayIndex, at );
-            const uint32_t node = at[0];
-            const vrc_dev_node n = nodes[node < lastNode ? node : lastNode];
-            bool gathered = false;
-            const vrc_segment_from_walk src = { f, rayIndex, at, 0.0f, early, &gathered };
-            done = vrc_march_segment_as< false, COUNT, true, uint8_t, GROUP, E >( f, n, src.full(), atlas, tab, color,
-                                                                                  nSamples, 0.0f );
+#if defined( __HIP_DEVICE_COMPILE__ )
+            general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
+#endif
+            if( !general )
+                done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], n, nSamples );
+            else
+            {
+                /* the gather visit's own loads, all inside its branch: the interval and the ray's direction are asked
+                 * for in front of the node, so the five of them travel while the node index and the node arrive */
+                const uint32_t* const at = f.walkCache + ( (size_t)rayIndex + ( 1u + 4u * (size_t)k ) * f.walkPlane );
+                const vrc_walk_early early = vrc_walk_load_early( f, rayIndex, at );
+                const uint32_t node = at[0];
+                const vrc_dev_node nd = nodes[node < lastNode ? node : lastNode];
+                bool gathered = false;
+                const vrc_segment_from_walk src = { f, rayIndex, at, 0.0f, early, &gathered };
+                done = vrc_march_segment_as< false, COUNT, true, uint8_t, GROUP, E >( f, nd, src.full(), atlas, tab,
+                                                                                      color, nSamples, 0.0f );
+            }
         }
         if( done )
             break;

@@ -100,18 +100,33 @@ hipError_t vrc_launch_walk_record( const vrc_raycast_args& a, vrc_walk_count* re
 #ifndef VRC_REPLAY_GREY_MAX_WAVES
 #define VRC_REPLAY_GREY_MAX_WAVES 6
 #endif
+/* The uniform-only instances (UNIFORM: vrc_pixel_walk_replay_lean< ..., true >, a lean frame none of whose visits
+ * gathers) hold no gather march and need 20 to 24 registers (50 to 54 counted), so the registers allow eight waves per SIMD and the
+ * attribute asks for them; they stage the classified table alone -- nothing in them steps through a brick, so no
+ * vrc_addr_tab.  Waves per SIMD and waves per workgroup as measured on C2 (profiles/r15_uniform_only.txt) */
+#ifndef VRC_REPLAY_UNIFORM_MAX_WAVES
+#define VRC_REPLAY_UNIFORM_MAX_WAVES 8
+#endif
+#ifndef VRC_REPLAY_UNIFORM_WG_WAVES
+#define VRC_REPLAY_UNIFORM_WG_WAVES VRC_WALK_WAVES /* (1: every wave stages a table of its own and meets no barrier) */
+#endif
 /* GROUP: samples a lane of the gather march keeps in flight -- what vrc_launch_raycast picks for the walking instance */
-#define VRC_REPLAY_K_MIN_WAVES ( GROUP > VRC_GREY_GROUP ? 2 : 5 )
-#define VRC_REPLAY_K_MAX_WAVES ( GROUP > VRC_GREY_GROUP ? 8 : ( MODE == VRC_MODE_GREY ? VRC_REPLAY_GREY_MAX_WAVES : 5 ) )
+#define VRC_REPLAY_K_MIN_WAVES ( UNIFORM ? VRC_REPLAY_UNIFORM_MAX_WAVES : ( GROUP > VRC_GREY_GROUP ? 2 : 5 ) )
+#define VRC_REPLAY_K_MAX_WAVES \
+    ( UNIFORM ? VRC_REPLAY_UNIFORM_MAX_WAVES \
+              : ( GROUP > VRC_GREY_GROUP ? 8 : ( MODE == VRC_MODE_GREY ? VRC_REPLAY_GREY_MAX_WAVES : 5 ) ) )
+#define VRC_REPLAY_K_WAVES ( UNIFORM ? VRC_REPLAY_UNIFORM_WG_WAVES : VRC_WALK_WAVES )
 /* LEAN: the replay of a lean list (vrc_frame::walkLean, vrc_pixel_walk_replay_lean); everything around the pixel is
- * the same kernel */
-template < bool COUNT, int MODE, int GROUP, bool LEAN = false >
-__global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_per_eu( VRC_REPLAY_K_MIN_WAVES, VRC_REPLAY_K_MAX_WAVES ) ) ) void vrc_k_raycast_replay(
+ * the same kernel.  UNIFORM (with LEAN): its uniform-only form */
+template < bool COUNT, int MODE, int GROUP, bool LEAN = false, bool UNIFORM = false >
+__global__ __launch_bounds__( 64u * VRC_REPLAY_K_WAVES ) __attribute__( ( amdgpu_waves_per_eu( VRC_REPLAY_K_MIN_WAVES, VRC_REPLAY_K_MAX_WAVES ) ) ) void vrc_k_raycast_replay(
     const vrc_frame f, const vrc_dev_node* __restrict__ nodes, const uint8_t* __restrict__ atlas,
     const vrc_f4* __restrict__ lutGlobal, const vrc_classifier cls, vrc_f4* __restrict__ pixelBuffer,
     unsigned long long* __restrict__ sampleCounter, const uint32_t* __restrict__ tileOrder, const uint32_t tilesX,
     const uint32_t nTiles )
 {
+    static_assert( LEAN || !UNIFORM, "the uniform-only form replays lean lists" );
+    constexpr uint32_t WAVES = VRC_REPLAY_K_WAVES, THREADS = 64u * WAVES;
     static_assert( MODE == VRC_MODE_TABLE || MODE == VRC_MODE_GREY, "the instances of the uniform-brick march" );
     /* the classified table (257 entries), as vrc_k_raycast stages it */
     __shared__ vrc_f4 lut[VRC_CLS8_ENTRIES];
@@ -120,7 +135,7 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_p
     if( MODE == VRC_MODE_GREY )
     {
         vrc_f2* const lut2 = reinterpret_cast< vrc_f2* >( lut );
-        for( uint32_t i = tid; i < VRC_LUT_ENTRIES; i += VRC_WALK_THREADS )
+        for( uint32_t i = tid; i < VRC_LUT_ENTRIES; i += THREADS )
         {
             const vrc_f4 e = lutGlobal[i];
             lut2[i] = vrc_f2{ e.x, e.w };
@@ -128,12 +143,13 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_p
     }
     else
     {
-        for( uint32_t i = tid; i < VRC_TFP_ENTRIES; i += VRC_WALK_THREADS )
+        for( uint32_t i = tid; i < VRC_TFP_ENTRIES; i += THREADS )
             lut[i] = lutGlobal[i];
     }
+    if constexpr( !UNIFORM )
     {
         const vrc_lay lay = vrc_make_lay( f.sbx, f.sby );
-        for( uint32_t u = tid; u < 256u; u += VRC_WALK_THREADS )
+        for( uint32_t u = tid; u < 256u; u += THREADS )
         {
             vrc_addr_tab[u] = vrc_lay_x( lay, u );
             vrc_addr_tab[256u + u] = vrc_lay_y( lay, u );
@@ -142,7 +158,7 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_p
     }
     __syncthreads();
     /* from here on the waves of the workgroup are independent */
-    const uint32_t slotIndex = blockIdx.x * VRC_WALK_WAVES + ( tid >> 6 );
+    const uint32_t slotIndex = blockIdx.x * WAVES + ( tid >> 6 );
     const uint32_t tilesY = nTiles / tilesX;
     if( slotIndex >= vrc_schedule_slots( tilesX, tilesY ) )
         return;
@@ -156,8 +172,8 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_p
     if( px < f.width && py < f.height )
     {
         if constexpr( LEAN )
-            vrc_pixel_walk_replay_lean< COUNT, MODE, GROUP >( f, nodes, atlas, lut, cls, pixelBuffer, px, py, nSamples,
-                                                              tile * 64u + lane );
+            vrc_pixel_walk_replay_lean< COUNT, MODE, GROUP, UNIFORM >( f, nodes, atlas, lut, cls, pixelBuffer, px, py,
+                                                                       nSamples, tile * 64u + lane );
         else
             vrc_pixel_walk_replay< COUNT, MODE, GROUP >( f, nodes, atlas, lut, cls, pixelBuffer, px, py, nSamples,
                                                          tile * 64u + lane );
@@ -174,20 +190,22 @@ __global__ __launch_bounds__( VRC_WALK_THREADS ) __attribute__( ( amdgpu_waves_p
     }
 }
 
-template < bool COUNT, int MODE, int GROUP, bool LEAN >
+template < bool COUNT, int MODE, int GROUP, bool LEAN, bool UNIFORM = false >
 static hipError_t launch_replay( const vrc_raycast_args& a, hipStream_t stream )
 {
     const uint32_t tilesX = ( a.frame.width + 7u ) / 8u, tilesY = ( a.frame.height + 7u ) / 8u;
     const uint32_t nTiles = tilesX * tilesY;
     if( nTiles == 0 )
         return hipSuccess;
-    vrc_internal_note_kernel( "vrc_k_raycast_replay<%s,%d,unsigned char,%d%s>", COUNT ? "true" : "false", (int)MODE, (int)GROUP,
-                              LEAN ? ",lean" : "" );
-    vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_replay< COUNT, MODE, GROUP, LEAN >, (int)VRC_WALK_THREADS, 0 );
-    vrc_launch_march( a, &vrc_k_raycast_replay< COUNT, MODE, GROUP, LEAN >,
-                      dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WALK_WAVES - 1u ) / VRC_WALK_WAVES ),
-                      dim3( VRC_WALK_THREADS ), 0, stream, a.frame, a.nodes, (const uint8_t*)a.atlas, a.lut, a.classifier,
-                      a.pixelBuffer, a.sampleCounter, a.tileOrder, tilesX, nTiles );
+    constexpr uint32_t WAVES = VRC_REPLAY_K_WAVES;
+    /* (the uniform-only form is a lean form: its name ends as theirs does) */
+    vrc_internal_note_kernel( "vrc_k_raycast_replay<%s,%d,unsigned char,%d%s%s>", COUNT ? "true" : "false", (int)MODE, (int)GROUP,
+                              UNIFORM ? ",uniform" : "", LEAN ? ",lean" : "" );
+    vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_replay< COUNT, MODE, GROUP, LEAN, UNIFORM >, (int)( 64u * WAVES ), 0 );
+    vrc_launch_march( a, &vrc_k_raycast_replay< COUNT, MODE, GROUP, LEAN, UNIFORM >,
+                      dim3( ( vrc_schedule_slots( tilesX, tilesY ) + WAVES - 1u ) / WAVES ), dim3( 64u * WAVES ), 0, stream,
+                      a.frame, a.nodes, (const uint8_t*)a.atlas, a.lut, a.classifier, a.pixelBuffer, a.sampleCounter,
+                      a.tileOrder, tilesX, nTiles );
     return hipGetLastError();
 }
 
@@ -195,6 +213,9 @@ static hipError_t launch_replay( const vrc_raycast_args& a, hipStream_t stream )
 template < int MODE, int GROUP >
 static hipError_t launch_replay( const vrc_raycast_args& a, hipStream_t stream )
 {
+    if( a.frame.walkLean == VRC_WALK_LEAN_UNIFORM )
+        return a.sampleCounter ? launch_replay< true, MODE, GROUP, true, true >( a, stream )
+                               : launch_replay< false, MODE, GROUP, true, true >( a, stream );
     if( a.frame.walkLean != 0u )
         return a.sampleCounter ? launch_replay< true, MODE, GROUP, true >( a, stream )
                                : launch_replay< false, MODE, GROUP, true >( a, stream );

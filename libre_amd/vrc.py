@@ -22,6 +22,7 @@ OPT_SHADING, OPT_SHADING_AMBIENT = 29, 30  # a shaded composite frame: 0 / 1, an
 OPT_COMPOSITE_DEPTH = 31  # the depth of a composite frame: 0 (off), or the opacity threshold in thousandths, 1 ... 999
 OPT_PREINTEGRATION = 32  # a pre-integrated composite frame: 0 / 1
 OPT_PREINT_BUILDS = 33  # read-only: how many pre-integrated tables the context has built
+OPT_WALK_UNIFORM_ONLY, OPT_WALK_UNIFORM_ONLY_USED = 34, 35  # replay a view without gathers by the uniform-only instance: 0 / 1 (default); read-only: 1 = the last render did
 PREINT_VALUE, PREINT_TEXEL = 0, 1  # kinds of table vrc_get_preintegrated_table reports
 PROJECTION_COMPOSITE, PROJECTION_MIP, PROJECTION_ISO = 0, 1, 2
 MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2

@@ -19,7 +19,11 @@ VRC_OPT_WALK_CACHE (the brick grid walked every frame against the march replayed
        python tools/uniform_ab.py --walk-cache [--steps 2000] [--rounds 3]
 Frames and sample counts at 0 and 1 are compared bit for bit, and the option at 1 must have reached the replay
 (VRC_OPT_WALK_CACHE_USED = 4), before anything is timed; the kernel instance of either side is reported.
-With --steps of 200 or more, --libs reports the wall time per frame and the mean kernel time of such a loop as well."""
+With --steps of 200 or more, --libs reports the wall time per frame and the mean kernel time of such a loop as well.
+VRC_OPT_WALK_UNIFORM_ONLY (the lean replay against its uniform-only instance) beside builds, in one process:
+       python tools/uniform_ab.py --uniform-only --libs parent=variants/libvrc_hip_parent.so new=libre_amd/lib/libvrc_hip.so
+times `new` with the option at 0 and at 1 (new@0, new@1) and `parent`, which does not know it, once; the frames
+compared bit for bit are replayed ones, and on mem:// the option's read-back must say what was asked."""
 import argparse
 import ctypes as C
 import json
@@ -75,19 +79,41 @@ def several(a):
         scenes[name] = GpuScene(s, lib=L)
         if a.walk_always:  # replay whatever the bricks hold: the gather path of the replay on hash://
             vrc.check(L, L.vrc_set_option(scenes[name].ctx, vrc.OPT_WALK_CACHE, vrc.WALK_CACHE_ALWAYS))
-    first = None
+    # --uniform-only: a library that knows VRC_OPT_WALK_UNIFORM_ONLY is timed at 0 and at 1 (NAME@0, NAME@1: one context,
+    # the same lists, the option set in front of every timed loop); one that does not is timed once, as NAME
+    sides = []  # (label, library's name, value of the option or None)
     for name in names:
-        fb, n = scenes[name].render(count=True)[:2]
+        g = scenes[name]
+        if a.uniform_only and g.L.vrc_set_option(g.ctx, vrc.OPT_WALK_UNIFORM_ONLY, 1) == 0:
+            sides += [(name + "@0", name, 0), (name + "@1", name, 1)]
+        else:
+            sides.append((name, name, None))
+
+    def select(side):
+        g = scenes[side[1]]
+        if side[2] is not None:
+            vrc.check(g.L, g.L.vrc_set_option(g.ctx, vrc.OPT_WALK_UNIFORM_ONLY, side[2]))
+        return g
+    first = None
+    for side in sides:
+        g = select(side)
+        for _ in range(7 if a.uniform_only else 1):  # (--uniform-only: the frame compared is a replayed one)
+            fb, n = g.render(count=True)[:2]
         if first is None:
             first = (fb, n)
-        assert (fb == first[0]).all() and n == first[1], "%s: frame or count differs from %s" % (name, names[0])
-    ms = {name: [] for name in names}
-    wall = {name: [] for name in names}
-    mean = {name: [] for name in names}
+        assert (fb == first[0]).all() and n == first[1], "%s: frame or count differs from %s" % (side[0], sides[0][0])
+        if side[2] is not None:
+            used = C.c_int64(-1)
+            vrc.check(g.L, g.L.vrc_get_option(g.ctx, vrc.OPT_WALK_UNIFORM_ONLY_USED, C.byref(used)))
+            assert used.value == side[2] or a.volume != "mem", "%s: VRC_OPT_WALK_UNIFORM_ONLY_USED reads %d" % (side[0], used.value)
+    ms = {side[0]: [] for side in sides}
+    wall = {side[0]: [] for side in sides}
+    mean = {side[0]: [] for side in sides}
     kernels = {}
     for _ in range(a.rounds):
-        for name in names:
-            g = scenes[name]
+        for side in sides:
+            name = side[0]
+            g = select(side)
             if a.steps >= 200:  # a loop long enough for a wall time
                 for _ in range(6):  # synchronised frames: the tile schedule, the ray cache and the walk cache settle
                     g.render(count=False)
@@ -177,6 +203,8 @@ def main():
     ap.add_argument("--libs", nargs="+", default=None, metavar="NAME=PATH")
     ap.add_argument("--walk-always", action="store_true",
                     help="with --libs: VRC_OPT_WALK_CACHE = 2 in every context (a view that gathers is replayed too)")
+    ap.add_argument("--uniform-only", action="store_true",
+                    help="with --libs: time every library that knows VRC_OPT_WALK_UNIFORM_ONLY at 0 and at 1 (NAME@0, NAME@1)")
     ap.add_argument("--markers", action="store_true", help="A/B of VRC_OPT_STREAM_MARKERS instead (see above)")
     ap.add_argument("--ray-cache", action="store_true", help="A/B of VRC_OPT_RAY_CACHE instead (see above)")
     ap.add_argument("--walk-cache", action="store_true", help="A/B of VRC_OPT_WALK_CACHE instead (see above)")
