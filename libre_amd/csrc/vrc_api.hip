@@ -8,12 +8,12 @@
  */
 #include "../../include/vrc_hip.h"
 #include "vrc_internal.h"
+#include "vrc_plan.h"
 #include "vrc_tables.h"
 
 #include <algorithm>
 #include <array>
 #include <cmath>
-#include <cstdio>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -139,11 +139,49 @@ struct vrc_pool
     std::vector< std::array< uint32_t, 3 > > slotSize;
 };
 
+/* walk cache (VRC_OPT_WALK_CACHE; vrc_core.h: vrc_frame::walkCache).  state: IDLE nothing known; COUNTING the count pass
+ * is on the stream, its result on the way to hMax behind ev; VALID the planes hold the lists of frame's constants over
+ * the node table as it is.  Nothing here exists before the first count pass: a camera that moves every frame allocates
+ * nothing.  The count pass runs only for a frame whose constants, node list and (option at 1) pool uploads are those of
+ * the vrc_render before, prev*: what changes every call -- passes over different node subsets, bricks streaming in --
+ * launches nothing extra.  gen, slotInfo: the uploads and uniformity words the count pass read (render_walk_cache) */
+struct vrc_walk_cache
+{
+    enum { IDLE = 0, COUNTING = 1, VALID = 2 };
+    int state = IDLE;
+    uint32_t* dLists = nullptr;
+    size_t words = 0;               /* allocated */
+    uint32_t k = 0;                 /* visits per ray the planes hold */
+    vrc_walk_count* dMax = nullptr; /* the count pass's result, and its pinned copy */
+    vrc_walk_count* hMax = nullptr;
+    hipEvent_t ev = nullptr;
+    vrc_frame frame;
+    vrc_frame prevFrame;
+    bool prevSet = false;
+    uint64_t prevGen = 0, gen = 0;
+    const uint32_t* slotInfo = nullptr;
+    int64_t used = 0; /* VRC_OPT_WALK_CACHE_USED */
+    /* the form of the lists (vrc_core.h: vrc_frame::walkLean).  leanAsked: what the host saw when the count pass went
+     * out -- a step that vrc_exact_step_count counts, a pool whose slot indices fit the word -- and so what that pass was
+     * asked to check; part of what the lists are valid for.  lean: the form the record pass wrote.  leanUsed:
+     * VRC_OPT_WALK_LEAN_USED */
+    bool leanAsked = false, lean = false;
+    int64_t leanUsed = 0;
+    /* the uniform-only replay (VRC_OPT_WALK_UNIFORM_ONLY).  gathers: what the count pass of the lists in the planes
+     * said of the slot words it read, those of gen and slotInfo -- compared for this whatever VRC_OPT_WALK_CACHE
+     * says, because at VRC_WALK_CACHE_ALWAYS the lists outlive an upload and that answer does not.  uniformUsed:
+     * VRC_OPT_WALK_UNIFORM_ONLY_USED */
+    unsigned long long gathers = 0;
+    int64_t uniformUsed = 0;
+};
+
 struct vrc_ctx
 {
     int device = 0;
     hipStream_t ownStream = nullptr;
     hipStream_t stream = nullptr;
+    vrc_options opt;   /* vrc_plan.h: every VRC_OPT_* that can be set */
+    vrc_latches latch; /* ... and what the frame's first pass read of those its later passes must not change */
 
     /* cuda::ColorMap + cuda::ClipPlanes state */
     float* dTf = nullptr;
@@ -159,7 +197,6 @@ struct vrc_ctx
     vrc_lut_params lutParams = { 0, 0, 0, 0 };
     float lutMaxAlpha = 1.0f; /* largest opacity in the classified table (1: unknown) */
     bool tfGrey = false;      /* red == green == blue in every entry of the transfer function (bitwise) */
-    int64_t optGreyTable = 1; /* VRC_OPT_GREY_TABLE */
     bool lutLinear = false;
     uint32_t lutLevels = 1;
 
@@ -205,7 +242,6 @@ struct vrc_ctx
     bool tileOrderValid = false;
     uint32_t tileOrderReused = 0; /* frames in a row that kept the schedule of a nearby view */
     vrc_frame tileOrderFrame;
-    int64_t optTileOrder = 1;
     /* ray cache (VRC_OPT_RAY_CACHE; vrc_core.h: vrc_frame::rayCache): the planes, regrown like dTileOrder; the frame
      * constants of the vrc_render before (rayPrevSet: there was one that could have used the cache) and whether the
      * planes hold the rays of exactly those constants; the mode the last vrc_render used (VRC_OPT_RAY_CACHE_USED) */
@@ -214,47 +250,8 @@ struct vrc_ctx
     bool rayCacheValid = false;
     bool rayPrevSet = false;
     vrc_frame rayPrevFrame;
-    int64_t optRayCache = 1;
     int64_t rayCacheUsed = 0;
-    /* walk cache (VRC_OPT_WALK_CACHE; vrc_core.h: vrc_frame::walkCache).  walkState: WALK_IDLE nothing known; WALK_COUNTING
-     * the count pass is on the stream, its result on the way to hWalkMax behind evWalk; WALK_VALID the planes hold the
-     * lists of walkFrame's constants over the node table as it is.  Nothing here exists before the first count pass: a
-     * camera that moves every frame allocates nothing.  The count pass runs only for a frame whose constants, node list
-     * and (option at 1) pool uploads are those of the vrc_render before, walkPrev*: what changes every call -- passes over
-     * different node subsets, bricks streaming in -- launches nothing extra.  Option at 1: a view whose visits mostly
-     * gather stays on the walk (walkGen, walkSlotInfo: the uploads and uniformity words that was decided under; when they
-     * change the view is counted again) */
-    enum { WALK_IDLE = 0, WALK_COUNTING = 1, WALK_VALID = 2 };
-    int walkState = WALK_IDLE;
-    uint32_t* dWalk = nullptr;
-    size_t dWalkWords = 0;        /* allocated */
-    uint32_t walkK = 0;           /* visits per ray the planes hold */
-    vrc_walk_count* dWalkMax = nullptr; /* the count pass's result, and its pinned copy */
-    vrc_walk_count* hWalkMax = nullptr;
-    hipEvent_t evWalk = nullptr;
-    vrc_frame walkFrame;
-    vrc_frame walkPrevFrame;
-    bool walkPrevSet = false;
-    uint64_t walkPrevGen = 0, walkGen = 0;
-    const uint32_t* walkSlotInfo = nullptr;
-    int64_t optWalkCache = 1;
-    int64_t optWalkBudget = VRC_WALK_CACHE_DEFAULT_BUDGET;
-    int64_t walkCacheUsed = 0;
-    /* the form of the lists (vrc_core.h: vrc_frame::walkLean).  walkLeanAsked: what the host saw when the count pass went
-     * out -- a step that vrc_exact_step_count counts, a pool whose slot indices fit the word -- and so what that pass was
-     * asked to check; part of what the lists are valid for.  walkLean: the form the record pass wrote.  walkLeanUsed:
-     * VRC_OPT_WALK_LEAN_USED */
-    bool walkLeanAsked = false, walkLean = false;
-    int64_t walkLeanUsed = 0;
-    /* the uniform-only replay (VRC_OPT_WALK_UNIFORM_ONLY).  walkGathers: what the count pass of the lists in the planes
-     * said of the slot words it read, those of walkGen and walkSlotInfo -- compared for this whatever VRC_OPT_WALK_CACHE
-     * says, because at VRC_WALK_CACHE_ALWAYS the lists outlive an upload and that answer does not.  walkUniformUsed:
-     * VRC_OPT_WALK_UNIFORM_ONLY_USED */
-    unsigned long long walkGathers = 0;
-    int64_t optWalkUniformOnly = 1;
-    int64_t walkUniformUsed = 0;
-    int64_t optStepping = 1;
-    int64_t optVariant = VRC_VARIANT_CUDARAYCASTER;
+    vrc_walk_cache walk;
     bool rayLod = false; /* vrc_set_ray_lod */
     float rayLodSse = 1.0f, rayLodWorldPerPixel = 0.0f;
 
@@ -270,47 +267,27 @@ struct vrc_ctx
     uint32_t evFoldedLaunches = 0;
     bool timed = false;
 
-    int64_t optKernel = VRC_KERNEL_AUTO;
-    int64_t optFilter = 0;
-    int64_t optTfFracBits = 8;
-    int64_t optCount = 0;
-    int64_t optTiming = 1;
-    int64_t optDepthSplit = 0;
-    int64_t optErtParts = 0;     /* VRC_OPT_ERT_COMPACTION */
-    int64_t optPackedAtlas = 1;  /* VRC_OPT_PACKED_ATLAS */
-    int64_t optUniformBricks = 1; /* VRC_OPT_UNIFORM_BRICKS */
-    int64_t optStreamMarkers = 0; /* VRC_OPT_STREAM_MARKERS */
-    int64_t optProjection = VRC_PROJECTION_COMPOSITE; /* VRC_OPT_PROJECTION */
-    int64_t optMipSkip = 1;                           /* VRC_OPT_MIP_SKIP */
-    int64_t optMipFold = VRC_MIP_FOLD_MAX;            /* VRC_OPT_MIP_FOLD */
     /* MIP: one running maximum per pixel of the pixel buffer (vrc_core.h: vrc_frame::mipMax), whichever buffer that
-     * is; vrc_pre_render invalidates it (mipFirst: the next MIP pass does not read it) and forgets the projection of
-     * the frame before (frameProjection: that of the frame's first vrc_render, -1 = none yet) */
+     * is; vrc_pre_render invalidates it (mipFirst: the next MIP pass does not read it) and forgets the latches of
+     * the frame before */
     uint32_t* dMipMax = nullptr;
     size_t dMipMaxPixels = 0;
     bool mipFirst = true;
-    int64_t frameProjection = -1;
     /* the mean fold's running (sum, count) per pixel (vrc_frame::meanSum, meanCount): allocated, invalidated and grown
-     * where dMipMax is; frameFold: the fold of the frame's first MIP vrc_render, as frameProjection is its projection */
+     * where dMipMax is */
     unsigned long long* dMeanSum = nullptr;
     uint32_t* dMeanCount = nullptr;
     size_t dMeanPixels = 0;
-    int64_t frameFold = -1;
     /* what vrc_get_projection_values reads: the state the frame's last MIP pass left (pixels = 0: none -- no MIP pass
      * since vrc_pre_render), and the device buffer its kernel writes (values | counts) */
     vrc_projection_state projState = { nullptr, nullptr, nullptr, 0u, 0u, 0u, 0.0f };
     float* dProjOut = nullptr;
     size_t dProjOutPixels = 0;
-    /* the depth of the projected sample (include/vrc_hip.h, "The depth of a MIP frame") */
-    int64_t optMipDepth = 0;    /* VRC_OPT_MIP_DEPTH */
-    int64_t optMipDepthCue = 0; /* VRC_OPT_MIP_DEPTH_CUE, thousandths */
-    /* one running D per pixel beside dMipMax (vrc_frame::mipDepth): allocated by the first frame that tracks depth, grown
-     * and invalidated where dMipMax is; frameDepth / frameCue: what the frame's first MIP vrc_render read of the two
-     * options (-1 = none yet), as frameFold is its fold */
+    /* the depth of the projected sample (include/vrc_hip.h, "The depth of a MIP frame"): one running D per pixel beside
+     * dMipMax (vrc_frame::mipDepth): allocated by the first frame that tracks depth, grown and invalidated where dMipMax
+     * is.  A composite frame's depth (VRC_OPT_COMPOSITE_DEPTH) keeps its pair per pixel in the same two buffers */
     float* dMipDepth = nullptr;
     size_t dMipDepthPixels = 0;
-    int64_t frameDepth = -1;
-    int64_t frameCue = -1;
     /* what vrc_get_projection_depths reads: did the frame's last MIP pass track depth, the frame it marched (camera,
      * pixel buffer geometry) with the row map it had, and the device buffer of the read-back (t | xyz | rows) */
     bool depthValid = false;
@@ -319,33 +296,16 @@ struct vrc_ctx
     float* dDepthOut = nullptr;
     size_t dDepthOutWords = 0;
     /* an isosurface frame (include/vrc_hip.h, "An isosurface frame"): vrc_set_isosurface's two values (isoSet: called at
-     * all), what the frame's first ISO vrc_render read of them (frameIso: did one), the running G per pixel beside
-     * dMipMax and dMipDepth (vrc_frame::isoGrad, three floats a pixel: grown and invalidated where they are), and whether
-     * the frame's last pass left one (vrc_get_projection_gradients) */
+     * all), the running G per pixel beside dMipMax and dMipDepth (vrc_frame::isoGrad, three floats a pixel: grown and
+     * invalidated where they are), and whether the frame's last pass left one (vrc_get_projection_gradients) */
     bool isoSet = false;
     float isoValue = 0.0f;
     float isoAmbient = 0.0f;
-    bool frameIso = false;
-    float frameIsoValue = 0.0f;
-    float frameIsoAmbient = 0.0f;
     float* dIsoGrad = nullptr;
     size_t dIsoGradPixels = 0;
     bool gradValid = false;
-    /* a shaded composite frame (include/vrc_hip.h, "A shaded composite frame"): the two options, and what the frame's
-     * first composite vrc_render read of them (-1 = none yet), as frameFold is its fold */
-    int64_t optShading = 0;          /* VRC_OPT_SHADING */
-    int64_t optShadingAmbient = 250; /* VRC_OPT_SHADING_AMBIENT, thousandths */
-    int64_t frameShading = -1;
-    int64_t frameShadingAmbient = -1;
-    /* the depth of a composite frame (include/vrc_hip.h, "The depth of a composite frame"): the option, and what the
-     * frame's first composite vrc_render read of it (-1 = none yet).  The pair per pixel lives in dMipMax and dMipDepth */
-    int64_t optCompositeDepth = 0; /* VRC_OPT_COMPOSITE_DEPTH, thousandths */
-    int64_t frameCompositeDepth = -1;
-    /* a pre-integrated composite frame (include/vrc_hip.h, "A pre-integrated composite frame"): the option, what the
-     * frame's first composite vrc_render read of it (-1 = none yet), and the one table: allocated by the first frame
-     * that needs it, rebuilt when the kind or one of the classified table's inputs changed */
-    int64_t optPreint = 0; /* VRC_OPT_PREINTEGRATION */
-    int64_t framePreint = -1;
+    /* a pre-integrated composite frame (include/vrc_hip.h, "A pre-integrated composite frame"): the one table, allocated
+     * by the first frame that needs it, rebuilt when the kind or one of the classified table's inputs changed */
     vrc_f4* dPreint = nullptr;
     int preintKind = -1; /* of the table in dPreint; -1: none built yet */
     uint64_t preintTfVersion = 0;
@@ -362,7 +322,8 @@ struct vrc_ctx
      * pinned ring (an area is rewritten only after the copy that read it has run) */
     unsigned long long* dFrameHist = nullptr;
     unsigned long long* hFrameHist = nullptr; /* pinned */
-    uint32_t frameHistCap = 0, frameHistBins = 0;
+    size_t frameHistCap = 0;
+    uint32_t frameHistBins = 0;
     vrc_hist_ref* dHistRefs = nullptr;
     vrc_hist_ref* hHistRefs = nullptr; /* pinned, kNodeStages areas of histRefsCap */
     size_t histRefsCap = 0;
@@ -370,6 +331,47 @@ struct vrc_ctx
     bool histRefsUsed[kNodeStages] = { false, false, false, false };
     uint32_t histRefsNext = 0;
 };
+
+#define VRC_TRY( call ) /* a step that has already said why it failed */ \
+    do { const int _rc = ( call ); if( _rc != VRC_OK ) return _rc; } while( 0 )
+
+/* one allocation of a growth group: where its pointer lives, its bytes per element of the group's capacity plus a fixed
+ * tail, device or pinned memory */
+struct vrc_grown
+{
+    enum { DEVICE = 0, PINNED = 1 };
+    void** p;
+    size_t elemBytes, tailBytes;
+    int where;
+    template< class T > vrc_grown( T*& q, size_t elem = sizeof( T ), size_t tail = 0, int w = DEVICE )
+        : p( reinterpret_cast< void** >( &q ) ), elemBytes( elem ), tailBytes( tail ), where( w ) {}
+};
+
+/* Where the capacity `cap` the allocations share is below n elements, make it `want` (>= n): behind a synchronisation of
+ * the context's stream -- whatever reads the old ones has run -- all are freed, then all allocated anew; nothing is
+ * carried over.  After a failed allocation what was not reallocated is NULL and the capacity is 0.  grew: it happened,
+ * and the contents are the caller's to fill */
+static int ctx_grow( vrc_ctx* c, size_t& cap, size_t n, size_t want, std::initializer_list< vrc_grown > bufs, bool* grew = nullptr )
+{
+    if( grew )
+        *grew = n > cap;
+    if( n <= cap )
+        return VRC_OK;
+    VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
+    for( const vrc_grown& b : bufs )
+        if( *b.p )
+            VRC_HIP_CHECK( b.where == vrc_grown::PINNED ? hipHostFree( *b.p ) : hipFree( *b.p ) );
+    for( const vrc_grown& b : bufs )
+        *b.p = nullptr;
+    cap = 0;
+    for( const vrc_grown& b : bufs )
+    {
+        const size_t bytes = want * b.elemBytes + b.tailBytes;
+        VRC_HIP_CHECK( b.where == vrc_grown::PINNED ? hipHostMalloc( b.p, bytes ) : hipMalloc( b.p, bytes ) );
+    }
+    cap = want;
+    return VRC_OK;
+}
 
 int vrc_internal_fail( int code, const std::string& msg ) { return fail( code, msg ); }
 static thread_local char tlsKernel[160] = "";
@@ -436,12 +438,19 @@ int vrc_ctx_create( int device, vrc_ctx** out )
     vrc_ctx* c = new vrc_ctx();
     c->device = device;
     std::memset( c->planes, 0, sizeof( c->planes ) );
+    /* default transfer function: linear grey ramp (the reference uploads lexis' default
+     * colour map in cuda::ColorMap::ColorMap, cuda/ColorMap.cu:32; that map lives in the
+     * un-vendored Lexis library, so the default here is documented and explicit) */
+    float tf[256 * 4];
+    for( int i = 0; i < 256; ++i )
+        tf[i * 4 + 0] = tf[i * 4 + 1] = tf[i * 4 + 2] = tf[i * 4 + 3] = (float)i / 255.0f;
     hipError_t e = hipStreamCreateWithFlags( &c->ownStream, hipStreamNonBlocking );
     if( e == hipSuccess ) e = hipMalloc( &c->dTf, 256 * 4 * sizeof( float ) );
     if( e == hipSuccess ) e = hipMalloc( &c->dLut, ( VRC_MAX_LOD_LEVELS * VRC_LUT_ENTRIES + 1u ) * sizeof( vrc_f4 ) );
     if( e == hipSuccess ) e = hipHostMalloc( &c->hTf, 256 * 4 * sizeof( float ) );
     if( e == hipSuccess ) e = hipMalloc( &c->dCounter, sizeof( unsigned long long ) );
     if( e == hipSuccess ) e = hipHostMalloc( &c->hCounter, sizeof( unsigned long long ) );
+    if( e == hipSuccess ) e = hipMemcpy( c->dTf, tf, sizeof( tf ), hipMemcpyHostToDevice );
     if( e != hipSuccess )
     {
         const std::string msg = std::string( "vrc_ctx_create: " ) + hipGetErrorString( e );
@@ -450,23 +459,10 @@ int vrc_ctx_create( int device, vrc_ctx** out )
     }
     c->stream = c->ownStream;
     *c->hCounter = 0;
-    /* default transfer function: linear grey ramp (the reference uploads lexis' default
-     * colour map in cuda::ColorMap::ColorMap, cuda/ColorMap.cu:32; that map lives in the
-     * un-vendored Lexis library, so the default here is documented and explicit) */
-    float tf[256 * 4];
-    for( int i = 0; i < 256; ++i )
-        tf[i * 4 + 0] = tf[i * 4 + 1] = tf[i * 4 + 2] = tf[i * 4 + 3] = (float)i / 255.0f;
     std::memcpy( c->hTf, tf, sizeof( tf ) );
     c->tfGrey = true;
     if( const char* g = std::getenv( "VRC_GREY_TABLE" ) ) /* default of VRC_OPT_GREY_TABLE for this process */
-        c->optGreyTable = g[0] != '0';
-    e = hipMemcpy( c->dTf, tf, sizeof( tf ), hipMemcpyHostToDevice );
-    if( e != hipSuccess )
-    {
-        const std::string msg = std::string( "vrc_ctx_create: " ) + hipGetErrorString( e );
-        vrc_ctx_destroy( c );
-        return fail( VRC_EHIP, msg );
-    }
+        c->opt.greyTable = g[0] != '0';
     c->tfVersion = 1;
     *out = c;
     return VRC_OK;
@@ -478,39 +474,20 @@ void vrc_ctx_destroy( vrc_ctx* c )
         return;
     (void)hipSetDevice( c->device );
     if( c->stream ) (void)hipStreamSynchronize( c->stream );
-    if( c->dTf ) (void)hipFree( c->dTf );
-    if( c->dLut ) (void)hipFree( c->dLut );
-    if( c->dPreint ) (void)hipFree( c->dPreint );
-    if( c->hTf ) (void)hipHostFree( c->hTf );
-    if( c->fbOwn ) (void)hipFree( c->fbOwn );
-    if( c->dNodes ) (void)hipFree( c->dNodes );
-    if( c->dGrid ) (void)hipFree( c->dGrid );
-    if( c->hStage ) (void)hipHostFree( c->hStage );
+    const std::initializer_list< void* > device = {
+        c->dTf,      c->dLut,     c->dPreint,  c->fbOwn,     c->dNodes,    c->dGrid,    c->dTileOrder, c->dRayCache,
+        c->walk.dLists, c->walk.dMax, c->dRayList, c->dMipMax, c->dMeanSum, c->dMeanCount, c->dProjOut, c->dMipDepth,
+        c->dIsoGrad, c->dDepthOut, c->dRowMap, c->dCounter,  c->dFrameHist, c->dHistRefs };
+    const std::initializer_list< void* > pinned = { c->hTf, c->hStage, c->walk.hMax, c->hCounter, c->hFrameHist, c->hHistRefs };
+    for( void* d : device )
+        if( d ) (void)hipFree( d );
+    for( void* h : pinned )
+        if( h ) (void)hipHostFree( h );
     for( hipEvent_t e : c->stageEvent )
         if( e ) (void)hipEventDestroy( e );
-    if( c->dTileOrder ) (void)hipFree( c->dTileOrder );
-    if( c->dRayCache ) (void)hipFree( c->dRayCache );
-    if( c->dWalk ) (void)hipFree( c->dWalk );
-    if( c->dWalkMax ) (void)hipFree( c->dWalkMax );
-    if( c->hWalkMax ) (void)hipHostFree( c->hWalkMax );
-    if( c->evWalk ) (void)hipEventDestroy( c->evWalk );
-    if( c->dRayList ) (void)hipFree( c->dRayList );
-    if( c->dMipMax ) (void)hipFree( c->dMipMax );
-    if( c->dMeanSum ) (void)hipFree( c->dMeanSum );
-    if( c->dMeanCount ) (void)hipFree( c->dMeanCount );
-    if( c->dProjOut ) (void)hipFree( c->dProjOut );
-    if( c->dMipDepth ) (void)hipFree( c->dMipDepth );
-    if( c->dIsoGrad ) (void)hipFree( c->dIsoGrad );
-    if( c->dDepthOut ) (void)hipFree( c->dDepthOut );
-    if( c->dRowMap ) (void)hipFree( c->dRowMap );
-    if( c->dCounter ) (void)hipFree( c->dCounter );
-    if( c->hCounter ) (void)hipHostFree( c->hCounter );
-    if( c->dFrameHist ) (void)hipFree( c->dFrameHist );
-    if( c->hFrameHist ) (void)hipHostFree( c->hFrameHist );
-    if( c->dHistRefs ) (void)hipFree( c->dHistRefs );
-    if( c->hHistRefs ) (void)hipHostFree( c->hHistRefs );
     for( hipEvent_t e : c->histRefsEvent )
         if( e ) (void)hipEventDestroy( e );
+    if( c->walk.ev ) (void)hipEventDestroy( c->walk.ev );
     c->evRing.reset(); /* (the events live on while a pool's render fence names one) */
     if( c->ownStream ) (void)hipStreamDestroy( c->ownStream );
     delete c;
@@ -525,7 +502,7 @@ int vrc_ctx_set_stream( vrc_ctx* c, void* s )
     c->stream = s ? (hipStream_t)s : c->ownStream;
     c->waitedPoolUid = c->waitedGen = 0; /* the new stream has waited for no upload */
     c->rayCacheValid = c->rayPrevSet = false; /* (the planes were written on the stream before) */
-    c->walkState = vrc_ctx::WALK_IDLE;        /* (and so were the lists; a count pass in flight has ended above) */
+    c->walk.state = vrc_walk_cache::IDLE;        /* (and so were the lists; a count pass in flight has ended above) */
     return VRC_OK;
 }
 
@@ -538,50 +515,50 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
     case VRC_OPT_KERNEL:
         if( value < VRC_KERNEL_AUTO || ( value > VRC_KERNEL_LDS && value != VRC_KERNEL_PACKED ) )
             return fail( VRC_EINVAL, "vrc_set_option: bad kernel variant" );
-        c->optKernel = value;
+        c->opt.kernel = value;
         return VRC_OK;
     case VRC_OPT_FILTER:
         if( value != VRC_FILTER_NEAREST && value != VRC_FILTER_TRILINEAR )
             return fail( VRC_EINVAL, "vrc_set_option: filter is 0 (nearest) or 1 (trilinear)" );
-        c->optFilter = value;
+        c->opt.filter = value;
         return VRC_OK;
     case VRC_OPT_TF_FRAC_BITS:
         if( value < 0 || value > 16 )
             return fail( VRC_EINVAL, "vrc_set_option: tf frac bits out of range" );
-        c->optTfFracBits = value;
+        c->opt.tfFracBits = value;
         return VRC_OK;
-    case VRC_OPT_COUNT_SAMPLES: c->optCount = value ? 1 : 0; return VRC_OK;
-    case VRC_OPT_TILE_ORDER: c->optTileOrder = value ? 1 : 0; return VRC_OK;
-    case VRC_OPT_STEPPING: c->optStepping = value ? 1 : 0; return VRC_OK;
-    case VRC_OPT_KERNEL_TIMING: c->optTiming = value ? 1 : 0; return VRC_OK;
-    case VRC_OPT_DEPTH_SPLIT: c->optDepthSplit = value ? 1 : 0; return VRC_OK;
-    case VRC_OPT_GREY_TABLE: c->optGreyTable = value ? 1 : 0; return VRC_OK;
-    case VRC_OPT_PACKED_ATLAS: c->optPackedAtlas = value ? 1 : 0; return VRC_OK;
-    case VRC_OPT_UNIFORM_BRICKS: c->optUniformBricks = value ? 1 : 0; return VRC_OK;
-    case VRC_OPT_STREAM_MARKERS: c->optStreamMarkers = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_COUNT_SAMPLES: c->opt.count = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_TILE_ORDER: c->opt.tileOrder = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_STEPPING: c->opt.stepping = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_KERNEL_TIMING: c->opt.timing = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_DEPTH_SPLIT: c->opt.depthSplit = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_GREY_TABLE: c->opt.greyTable = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_PACKED_ATLAS: c->opt.packedAtlas = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_UNIFORM_BRICKS: c->opt.uniformBricks = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_STREAM_MARKERS: c->opt.streamMarkers = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_RAY_CACHE:
-        if( c->optRayCache != ( value ? 1 : 0 ) )
+        if( c->opt.rayCache != ( value ? 1 : 0 ) )
             c->rayCacheValid = c->rayPrevSet = false;
-        c->optRayCache = value ? 1 : 0;
+        c->opt.rayCache = value ? 1 : 0;
         return VRC_OK;
     case VRC_OPT_WALK_CACHE:
         if( value < 0 || value > VRC_WALK_CACHE_ALWAYS )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_CACHE is 0 (off), 1 (on) or 2 (on for every view)" );
-        if( c->optWalkCache != value )
-            c->walkState = vrc_ctx::WALK_IDLE;
-        c->optWalkCache = value;
+        if( c->opt.walkCache != value )
+            c->walk.state = vrc_walk_cache::IDLE;
+        c->opt.walkCache = value;
         return VRC_OK;
     case VRC_OPT_WALK_CACHE_BUDGET:
         if( value < 0 )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_CACHE_BUDGET is a number of bytes" );
-        if( c->optWalkBudget != value )
-            c->walkState = vrc_ctx::WALK_IDLE;
-        c->optWalkBudget = value;
+        if( c->opt.walkBudget != value )
+            c->walk.state = vrc_walk_cache::IDLE;
+        c->opt.walkBudget = value;
         return VRC_OK;
     case VRC_OPT_WALK_UNIFORM_ONLY:
         if( value != 0 && value != 1 )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_UNIFORM_ONLY is 0 (off) or 1 (on)" );
-        c->optWalkUniformOnly = value; /* (which instance replays the lists: nothing starts over) */
+        c->opt.walkUniformOnly = value; /* (which instance replays the lists: nothing starts over) */
         return VRC_OK;
     case VRC_OPT_WALK_UNIFORM_ONLY_USED:
         return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_UNIFORM_ONLY_USED is read-only" );
@@ -592,43 +569,43 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
          * value is refused, here and not only by the render it could not serve */
         if( value == VRC_PROJECTION_ISO && !c->isoSet )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION = VRC_PROJECTION_ISO needs vrc_set_isosurface first" );
-        c->optProjection = value;
+        c->opt.projection = value;
         return VRC_OK;
-    case VRC_OPT_MIP_SKIP: c->optMipSkip = value ? 1 : 0; return VRC_OK;
+    case VRC_OPT_MIP_SKIP: c->opt.mipSkip = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_MIP_FOLD:
         if( value != VRC_MIP_FOLD_MAX && value != VRC_MIP_FOLD_MIN && value != VRC_MIP_FOLD_MEAN )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_MIP_FOLD is 0 (maximum), 1 (minimum) or 2 (mean)" );
-        c->optMipFold = value;
+        c->opt.mipFold = value;
         return VRC_OK;
     case VRC_OPT_MIP_DEPTH:
         if( value != 0 && value != 1 )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_MIP_DEPTH is 0 (off) or 1 (keep the depth of the projected sample)" );
-        c->optMipDepth = value;
+        c->opt.mipDepth = value;
         return VRC_OK;
     case VRC_OPT_MIP_DEPTH_CUE:
         if( value < 0 || value > 1000 )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_MIP_DEPTH_CUE is the cue strength in thousandths, 0 (off) to 1000" );
-        c->optMipDepthCue = value;
+        c->opt.mipDepthCue = value;
         return VRC_OK;
     case VRC_OPT_SHADING:
         if( value != 0 && value != 1 )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_SHADING is 0 (off) or 1 (light every sample of a composite frame by its gradient)" );
-        c->optShading = value;
+        c->opt.shading = value;
         return VRC_OK;
     case VRC_OPT_SHADING_AMBIENT:
         if( value < 0 || value > 1000 )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_SHADING_AMBIENT is the ambient share in thousandths, 0 to 1000" );
-        c->optShadingAmbient = value;
+        c->opt.shadingAmbient = value;
         return VRC_OK;
     case VRC_OPT_COMPOSITE_DEPTH:
         if( value < 0 || value > 999 )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_COMPOSITE_DEPTH is 0 (off) or the opacity threshold in thousandths, 1 to 999" );
-        c->optCompositeDepth = value;
+        c->opt.compositeDepth = value;
         return VRC_OK;
     case VRC_OPT_PREINTEGRATION:
         if( value != 0 && value != 1 )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PREINTEGRATION is 0 (off) or 1 (classify every step of a composite frame from the pre-integrated table)" );
-        c->optPreint = value;
+        c->opt.preint = value;
         return VRC_OK;
     case VRC_OPT_PREINT_BUILDS:
         return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PREINT_BUILDS is read-only" );
@@ -636,12 +613,12 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
         if( value < 0 || value > VRC_MAX_ERT_PARTS )
             return fail( VRC_EINVAL, "VRC_OPT_ERT_COMPACTION: 0 (off) or 2.." + std::to_string( VRC_MAX_ERT_PARTS ) +
                                          " launches per frame" );
-        c->optErtParts = value < 2 ? 0 : value;
+        c->opt.ertParts = value < 2 ? 0 : value;
         return VRC_OK;
     case VRC_OPT_VARIANT:
         if( value != VRC_VARIANT_CUDARAYCASTER && value != VRC_VARIANT_GLRAYCASTER )
             return fail( VRC_EINVAL, "vrc_set_option: variant is 0 (cudaRaycaster) or 1 (glRaycaster)" );
-        c->optVariant = value;
+        c->opt.variant = value;
         return VRC_OK;
     default: return fail( VRC_EINVAL, "vrc_set_option: unknown option" );
     }
@@ -653,38 +630,38 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
         return fail( VRC_EINVAL, "vrc_get_option: NULL argument" );
     switch( option )
     {
-    case VRC_OPT_KERNEL: *value = c->optKernel; return VRC_OK;
-    case VRC_OPT_FILTER: *value = c->optFilter; return VRC_OK;
-    case VRC_OPT_TF_FRAC_BITS: *value = c->optTfFracBits; return VRC_OK;
-    case VRC_OPT_COUNT_SAMPLES: *value = c->optCount; return VRC_OK;
-    case VRC_OPT_TILE_ORDER: *value = c->optTileOrder; return VRC_OK;
-    case VRC_OPT_STEPPING: *value = c->optStepping; return VRC_OK;
-    case VRC_OPT_KERNEL_TIMING: *value = c->optTiming; return VRC_OK;
-    case VRC_OPT_DEPTH_SPLIT: *value = c->optDepthSplit; return VRC_OK;
-    case VRC_OPT_ERT_COMPACTION: *value = c->optErtParts; return VRC_OK;
-    case VRC_OPT_GREY_TABLE: *value = c->optGreyTable; return VRC_OK;
-    case VRC_OPT_PACKED_ATLAS: *value = c->optPackedAtlas; return VRC_OK;
-    case VRC_OPT_UNIFORM_BRICKS: *value = c->optUniformBricks; return VRC_OK;
-    case VRC_OPT_STREAM_MARKERS: *value = c->optStreamMarkers; return VRC_OK;
-    case VRC_OPT_RAY_CACHE: *value = c->optRayCache; return VRC_OK;
+    case VRC_OPT_KERNEL: *value = c->opt.kernel; return VRC_OK;
+    case VRC_OPT_FILTER: *value = c->opt.filter; return VRC_OK;
+    case VRC_OPT_TF_FRAC_BITS: *value = c->opt.tfFracBits; return VRC_OK;
+    case VRC_OPT_COUNT_SAMPLES: *value = c->opt.count; return VRC_OK;
+    case VRC_OPT_TILE_ORDER: *value = c->opt.tileOrder; return VRC_OK;
+    case VRC_OPT_STEPPING: *value = c->opt.stepping; return VRC_OK;
+    case VRC_OPT_KERNEL_TIMING: *value = c->opt.timing; return VRC_OK;
+    case VRC_OPT_DEPTH_SPLIT: *value = c->opt.depthSplit; return VRC_OK;
+    case VRC_OPT_ERT_COMPACTION: *value = c->opt.ertParts; return VRC_OK;
+    case VRC_OPT_GREY_TABLE: *value = c->opt.greyTable; return VRC_OK;
+    case VRC_OPT_PACKED_ATLAS: *value = c->opt.packedAtlas; return VRC_OK;
+    case VRC_OPT_UNIFORM_BRICKS: *value = c->opt.uniformBricks; return VRC_OK;
+    case VRC_OPT_STREAM_MARKERS: *value = c->opt.streamMarkers; return VRC_OK;
+    case VRC_OPT_RAY_CACHE: *value = c->opt.rayCache; return VRC_OK;
     case VRC_OPT_RAY_CACHE_USED: *value = c->rayCacheUsed; return VRC_OK;
-    case VRC_OPT_WALK_CACHE: *value = c->optWalkCache; return VRC_OK;
-    case VRC_OPT_WALK_CACHE_USED: *value = c->walkCacheUsed; return VRC_OK;
-    case VRC_OPT_WALK_CACHE_BUDGET: *value = c->optWalkBudget; return VRC_OK;
-    case VRC_OPT_WALK_CACHE_BYTES: *value = (int64_t)( c->dWalkWords * sizeof( uint32_t ) ); return VRC_OK;
-    case VRC_OPT_WALK_LEAN_USED: *value = c->walkLeanUsed; return VRC_OK;
-    case VRC_OPT_WALK_UNIFORM_ONLY: *value = c->optWalkUniformOnly; return VRC_OK;
-    case VRC_OPT_WALK_UNIFORM_ONLY_USED: *value = c->walkUniformUsed; return VRC_OK;
-    case VRC_OPT_PROJECTION: *value = c->optProjection; return VRC_OK;
-    case VRC_OPT_MIP_SKIP: *value = c->optMipSkip; return VRC_OK;
-    case VRC_OPT_MIP_FOLD: *value = c->optMipFold; return VRC_OK;
-    case VRC_OPT_MIP_DEPTH: *value = c->optMipDepth; return VRC_OK;
-    case VRC_OPT_MIP_DEPTH_CUE: *value = c->optMipDepthCue; return VRC_OK;
-    case VRC_OPT_VARIANT: *value = c->optVariant; return VRC_OK;
-    case VRC_OPT_SHADING: *value = c->optShading; return VRC_OK;
-    case VRC_OPT_SHADING_AMBIENT: *value = c->optShadingAmbient; return VRC_OK;
-    case VRC_OPT_COMPOSITE_DEPTH: *value = c->optCompositeDepth; return VRC_OK;
-    case VRC_OPT_PREINTEGRATION: *value = c->optPreint; return VRC_OK;
+    case VRC_OPT_WALK_CACHE: *value = c->opt.walkCache; return VRC_OK;
+    case VRC_OPT_WALK_CACHE_USED: *value = c->walk.used; return VRC_OK;
+    case VRC_OPT_WALK_CACHE_BUDGET: *value = c->opt.walkBudget; return VRC_OK;
+    case VRC_OPT_WALK_CACHE_BYTES: *value = (int64_t)( c->walk.words * sizeof( uint32_t ) ); return VRC_OK;
+    case VRC_OPT_WALK_LEAN_USED: *value = c->walk.leanUsed; return VRC_OK;
+    case VRC_OPT_WALK_UNIFORM_ONLY: *value = c->opt.walkUniformOnly; return VRC_OK;
+    case VRC_OPT_WALK_UNIFORM_ONLY_USED: *value = c->walk.uniformUsed; return VRC_OK;
+    case VRC_OPT_PROJECTION: *value = c->opt.projection; return VRC_OK;
+    case VRC_OPT_MIP_SKIP: *value = c->opt.mipSkip; return VRC_OK;
+    case VRC_OPT_MIP_FOLD: *value = c->opt.mipFold; return VRC_OK;
+    case VRC_OPT_MIP_DEPTH: *value = c->opt.mipDepth; return VRC_OK;
+    case VRC_OPT_MIP_DEPTH_CUE: *value = c->opt.mipDepthCue; return VRC_OK;
+    case VRC_OPT_VARIANT: *value = c->opt.variant; return VRC_OK;
+    case VRC_OPT_SHADING: *value = c->opt.shading; return VRC_OK;
+    case VRC_OPT_SHADING_AMBIENT: *value = c->opt.shadingAmbient; return VRC_OK;
+    case VRC_OPT_COMPOSITE_DEPTH: *value = c->opt.compositeDepth; return VRC_OK;
+    case VRC_OPT_PREINTEGRATION: *value = c->opt.preint; return VRC_OK;
     case VRC_OPT_PREINT_BUILDS: *value = c->preintBuilds; return VRC_OK;
     case VRC_OPT_KERNEL_USED: *value = c->stats.kernel_variant; return VRC_OK;
     case VRC_OPT_GRID_WALK_USED: *value = c->gridWalkUsed; return VRC_OK;
@@ -946,7 +923,7 @@ static int ctx_wait_uploads( vrc_ctx* c, vrc_pool* p )
     std::lock_guard< std::mutex > lock( p->mutex );
     if( !p->hasUpload )
         return VRC_OK;
-    if( !c->optStreamMarkers && c->waitedPoolUid == p->uid && c->waitedGen == p->uploadGen )
+    if( !c->opt.streamMarkers && c->waitedPoolUid == p->uid && c->waitedGen == p->uploadGen )
         return VRC_OK;
     VRC_HIP_CHECK( hipStreamWaitEvent( c->stream, p->lastUpload, 0 ) );
     c->waitedPoolUid = p->uid;
@@ -1525,20 +1502,13 @@ int vrc_set_row_map( vrc_ctx* c, const uint32_t* rows, uint32_t n )
     if( n == c->rowMap.size() && ( n == 0 || std::memcmp( rows, c->rowMap.data(), n * sizeof( uint32_t ) ) == 0 ) )
         return VRC_OK;
     VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-    if( n > c->dRowMapCap )
-    {
-        if( c->dRowMap ) VRC_HIP_CHECK( hipFree( c->dRowMap ) );
-        c->dRowMap = nullptr;
-        c->dRowMapCap = 0;
-        VRC_HIP_CHECK( hipMalloc( &c->dRowMap, n * sizeof( uint32_t ) ) );
-        c->dRowMapCap = n;
-    }
+    VRC_TRY( ctx_grow( c, c->dRowMapCap, n, n, { c->dRowMap } ) );
     if( n )
         VRC_HIP_CHECK( hipMemcpy( c->dRowMap, rows, n * sizeof( uint32_t ), hipMemcpyHostToDevice ) );
     c->rowMap.assign( rows, rows + n );
     c->tileOrderValid = false;
     c->rayCacheValid = c->rayPrevSet = false;
-    c->walkState = vrc_ctx::WALK_IDLE; /* (the stream was synchronised above) */
+    c->walk.state = vrc_walk_cache::IDLE; /* (the stream was synchronised above) */
     return VRC_OK;
 }
 
@@ -1565,15 +1535,7 @@ int vrc_pre_render( vrc_ctx* c, const vrc_view_data* view )
     else
     {
         const size_t pixels = (size_t)w * h;
-        if( pixels > c->fbOwnPixels )
-        {
-            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-            if( c->fbOwn ) VRC_HIP_CHECK( hipFree( c->fbOwn ) );
-            c->fbOwn = nullptr;
-            c->fbOwnPixels = 0;
-            VRC_HIP_CHECK( hipMalloc( &c->fbOwn, pixels * sizeof( vrc_f4 ) ) );
-            c->fbOwnPixels = pixels;
-        }
+        VRC_TRY( ctx_grow( c, c->fbOwnPixels, pixels, pixels, { c->fbOwn } ) );
         c->fbW = w;
         c->fbH = h;
     }
@@ -1583,16 +1545,9 @@ int vrc_pre_render( vrc_ctx* c, const vrc_view_data* view )
     c->clearPending = true;
     /* a new frame: its MIP passes start over, and it may take either projection */
     c->mipFirst = true;
-    c->frameProjection = -1;
-    c->frameFold = -1;
-    c->frameDepth = -1;
-    c->frameCue = -1;
+    c->latch = vrc_latches();
     c->depthValid = false;
-    c->frameIso = false;
     c->gradValid = false;
-    c->frameShading = c->frameShadingAmbient = -1;
-    c->frameCompositeDepth = -1;
-    c->framePreint = -1;
     c->projState.pixels = 0u; /* vrc_get_projection_values: nothing to read until a MIP pass of this frame */
     return VRC_OK;
 }
@@ -1617,11 +1572,7 @@ int vrc_set_framebuffer( vrc_ctx* c, void* deviceRgba, uint32_t width, uint32_t 
         return fail( VRC_EINVAL, "vrc_set_framebuffer: empty framebuffer" );
     if( deviceRgba && ( (uintptr_t)deviceRgba % 16u ) != 0 )
         return fail( VRC_EINVAL, "vrc_set_framebuffer: pointer must be 16-byte aligned" );
-    {
-        const int rc = resolve_clear( c );
-        if( rc != VRC_OK )
-            return rc;
-    }
+    VRC_TRY( resolve_clear( c ) );
     c->fbExt = (vrc_f4*)deviceRgba;
     if( deviceRgba )
     {
@@ -1647,58 +1598,37 @@ int vrc_get_framebuffer( vrc_ctx* c, void** deviceRgba, uint32_t* width, uint32_
 {
     if( !c )
         return fail( VRC_EINVAL, "vrc_get_framebuffer: ctx is NULL" );
-    {
-        const int rc = resolve_clear( c );
-        if( rc != VRC_OK )
-            return rc;
-    }
+    VRC_TRY( resolve_clear( c ) );
     if( deviceRgba ) *deviceRgba = ctx_fb( c );
     if( width ) *width = c->fbW;
     if( height ) *height = c->fbH;
     return VRC_OK;
 }
 
-/* node table + brick grid: vrc_tables.h */
-static int ensure_capacity( vrc_ctx* c, size_t nNodes, size_t nGrid )
+/* ---------------------------------------------------------------------------------------- */
+/* vrc_render is a sequence of phases (the render_* functions below, in the order they run); this is what they hand on.
+ * The ORDER is part of the contract: the refusals of render_mode come before anything is launched or latched, those of
+ * render_form after the tables are up to date; and every cached copy of the frame constants (tileOrderFrame,
+ * depthFrame, rayPrevFrame, walk.prevFrame, walk.frame) is compared and taken with exactly the fields set that the
+ * phases before it set -- a field set earlier makes an unchanged view compare unequal */
+struct render_pass
 {
-    if( nNodes > c->dNodesCap )
-    {
-        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-        if( c->dNodes ) VRC_HIP_CHECK( hipFree( c->dNodes ) );
-        c->dNodes = nullptr;
-        c->dNodesCap = 0;
-        const size_t cap = std::max< size_t >( nNodes, 1024 ); /* sized to n (fixes Q8) */
-        VRC_HIP_CHECK( hipMalloc( &c->dNodes, cap * sizeof( vrc_dev_node ) ) );
-        c->dNodesCap = cap;
-    }
-    if( nGrid > c->dGridCap )
-    {
-        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-        if( c->dGrid ) VRC_HIP_CHECK( hipFree( c->dGrid ) );
-        c->dGrid = nullptr;
-        c->dGridCap = 0;
-        const size_t cap = std::max< size_t >( nGrid, 4096 );
-        VRC_HIP_CHECK( hipMalloc( &c->dGrid, cap * sizeof( int32_t ) ) );
-        c->dGridCap = cap;
-    }
-    const size_t stageBytes = nNodes * sizeof( vrc_dev_node ) + nGrid * sizeof( int32_t );
-    if( stageBytes > c->hStageCap )
-    {
-        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-        if( c->hStage ) VRC_HIP_CHECK( hipHostFree( c->hStage ) );
-        c->hStage = nullptr;
-        c->hStageCap = 0;
-        const size_t cap = ( std::max< size_t >( stageBytes, 1 << 18 ) + 255 ) / 256 * 256;
-        VRC_HIP_CHECK( hipHostMalloc( &c->hStage, cap * kNodeStages ) );
-        c->hStageCap = cap;
-        for( int i = 0; i < kNodeStages; ++i )
-            c->stageUsed[i] = false;
-    }
-    return VRC_OK;
-}
+    const vrc_view_data* view;
+    const vrc_node_data* nodes;
+    uint32_t nNodes;
+    const vrc_render_data* render;
+    vrc_pool* pool;
+    vrc_lut_params lp;
+    vrc_mode mode;        /* vrc_plan.h */
+    vrc_form form;
+    bool sameNodes, tableWalk; /* the node list of the vrc_render before, on the same pool; vrc_plan_table_walk */
+    size_t pixels, plane; /* of the pixel buffer in use; of a plane of the ray and walk caches: its whole tiles */
+    bool walkCount, walkRecord; /* render_walk_cache: run the count / the record pass in front of this march */
+    vrc_raycast_args a;
+};
 
-int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* nodes, uint32_t nNodes,
-                const vrc_render_data* render, vrc_pool* pool )
+static int render_check_args( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* nodes, uint32_t nNodes,
+                              const vrc_render_data* render, vrc_pool* pool )
 {
     if( !c || !view || !render || !pool )
         return fail( VRC_EINVAL, "vrc_render: NULL argument" );
@@ -1715,135 +1645,27 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         return fail( VRC_EINVAL, "vrc_render: samplesPerRay is 0" );
     if( render->dataSourceRange[1] == render->dataSourceRange[0] )
         return fail( VRC_EINVAL, "vrc_render: empty data source range" );
-    if( nNodes == 0 ) /* CudaRaycastRenderer.cpp:157-158 */
-        return VRC_OK;
-    VRC_HIP_CHECK( hipSetDevice( c->device ) );
+    return VRC_OK;
+}
 
-    /* classified table, rebuilt only when one of its inputs changed */
-    vrc_lut_params lp;
+/* which frame this pass renders, or why not: nothing has been launched or latched when it refuses */
+static int render_mode( vrc_ctx* c, render_pass& p )
+{
     /* signed 8/16-bit voxels are in the atlas offset-binary (v + 128 / + 32768): the range moves with them, and every
      * kernel form serves the pool as the unsigned one it then is (the trilinear filter commutes with the offset) */
-    lp.rangeMin = render->dataSourceRange[0] + pool->rangeShift;
-    lp.rangeMax = render->dataSourceRange[1] + pool->rangeShift;
-    lp.alphaCorrection = (float)render->maxSamplesPerRay / (float)render->samplesPerRay;
-    lp.fracBits = (int)c->optTfFracBits;
-    if( pool->elemBytes == 4 && ( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED ) )
-        return fail( VRC_EINVAL, "vrc_render: 32-bit and float voxels are marched by gathers; the LDS-staged and tap-packed "
-                                 "forms take 8- and 16-bit voxels (VRC_OPT_KERNEL = AUTO, REFERENCE_ORDER or GRID_DDA)" );
-    /* an isosurface frame is a MIP frame with the first-crossing fold: it reads none of the MIP frame's options but
-     * VRC_OPT_MIP_SKIP, and is served and refused as one */
-    const bool iso = c->optProjection == VRC_PROJECTION_ISO;
-    const bool mip = c->optProjection == VRC_PROJECTION_MIP || iso;
-    if( c->frameProjection >= 0 && c->frameProjection != c->optProjection )
-        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_PROJECTION changed between vrc_pre_render and vrc_post_render; the "
-                                 "passes of one frame take one projection" );
-    if( iso && !c->isoSet )
-        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_PROJECTION = ISO needs vrc_set_isosurface first" );
-    if( iso && c->frameIso && ( c->frameIsoValue != c->isoValue || c->frameIsoAmbient != c->isoAmbient ) )
-        return fail( VRC_EINVAL, "vrc_render: vrc_set_isosurface changed iso_value or ambient between vrc_pre_render and "
-                                 "vrc_post_render; the passes of one frame take one isosurface" );
-    if( mip && !iso && c->frameFold >= 0 && c->frameFold != c->optMipFold )
-        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_MIP_FOLD changed between vrc_pre_render and vrc_post_render; the "
-                                 "passes of one frame take one fold" );
-    /* depth tracking: the maximum and the minimum only; the mean reads neither option */
-    const bool mipDepth = iso || ( mip && c->optMipFold != VRC_MIP_FOLD_MEAN && ( c->optMipDepth != 0 || c->optMipDepthCue > 0 ) );
-    if( mip && !iso && c->optMipFold != VRC_MIP_FOLD_MEAN )
-    {
-        if( c->frameDepth >= 0 && c->frameDepth != c->optMipDepth )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_MIP_DEPTH changed between vrc_pre_render and vrc_post_render; the "
-                                     "passes of one frame all keep the depth or none does" );
-        if( c->frameCue >= 0 && c->frameCue != c->optMipDepthCue )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_MIP_DEPTH_CUE changed between vrc_pre_render and vrc_post_render; "
-                                     "the passes of one frame take one cue strength" );
-    }
-    if( mip )
-    {
-        /* what the maximum-intensity projection is not defined for (include/vrc_hip.h) */
-        if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
-            return fail( VRC_EINVAL, iso ? "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no isosurface form; "
-                                           "VRC_OPT_PROJECTION = ISO is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)"
-                                         : "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no maximum-intensity form; "
-                                           "VRC_OPT_PROJECTION = MIP is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
-        if( c->rayLod )
-            return fail( VRC_EINVAL, iso ? "vrc_render: vrc_set_ray_lod is on; VRC_OPT_PROJECTION = ISO renders a per-brick cut"
-                                         : "vrc_render: vrc_set_ray_lod is on; VRC_OPT_PROJECTION = MIP renders a per-brick cut" );
-        if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
-            return fail( VRC_EINVAL, iso ? "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_PROJECTION = ISO is defined on the "
-                                           "cudaRaycaster variant's sample set"
-                                         : "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_PROJECTION = MIP is defined on the "
-                                           "cudaRaycaster variant's sample set" );
-    }
-    /* a shaded composite frame (include/vrc_hip.h, "A shaded composite frame"): read by composite frames only; served by
-     * the gather marches of vrc_kernels_shade.hip and refused where those have no form */
-    const bool shade = !mip && c->optShading != 0;
-    if( !mip )
-    {
-        if( c->frameShading >= 0 && c->frameShading != c->optShading )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_SHADING changed between vrc_pre_render and vrc_post_render; the "
-                                     "passes of one frame are all shaded or none is" );
-        if( c->frameShadingAmbient >= 0 && c->frameShadingAmbient != c->optShadingAmbient )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_SHADING_AMBIENT changed between vrc_pre_render and vrc_post_render; "
-                                     "the passes of one frame take one ambient share" );
-    }
-    /* the depth of a composite frame (include/vrc_hip.h, "The depth of a composite frame"): read by composite frames only;
-     * served by the gather marches of vrc_kernels_cdepth.hip and refused where those have no form */
-    const bool cdepth = !mip && c->optCompositeDepth != 0;
-    if( !mip && c->frameCompositeDepth >= 0 && c->frameCompositeDepth != c->optCompositeDepth )
-        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_COMPOSITE_DEPTH changed between vrc_pre_render and vrc_post_render; the "
-                                 "passes of one frame cross one threshold" );
-    if( cdepth )
-    {
-        if( shade )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_SHADING = 1 together with VRC_OPT_COMPOSITE_DEPTH; alpha does not "
-                                     "depend on shading: render the unshaded frame to pick in a shaded picture" );
-        if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no depth-tracking form; "
-                                     "VRC_OPT_COMPOSITE_DEPTH is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
-        if( c->rayLod )
-            return fail( VRC_EINVAL, "vrc_render: vrc_set_ray_lod is on; VRC_OPT_COMPOSITE_DEPTH tracks a per-brick cut" );
-        if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_COMPOSITE_DEPTH is defined on the "
-                                     "cudaRaycaster variant's sample set" );
-    }
-    /* a pre-integrated composite frame (include/vrc_hip.h, "A pre-integrated composite frame"): read by composite frames
-     * only; served by the gather marches of vrc_kernels_preint.hip and refused where those have no form */
-    const bool preint = !mip && c->optPreint != 0;
-    if( !mip && c->framePreint >= 0 && c->framePreint != c->optPreint )
-        return fail( VRC_EINVAL, "vrc_render: VRC_OPT_PREINTEGRATION changed between vrc_pre_render and vrc_post_render; the "
-                                 "passes of one frame are all pre-integrated or none is" );
-    if( preint )
-    {
-        if( shade )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_SHADING = 1 together with VRC_OPT_PREINTEGRATION; a step has no one "
-                                     "gradient: the two are not combined" );
-        if( cdepth )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_COMPOSITE_DEPTH together with VRC_OPT_PREINTEGRATION; the depth is "
-                                     "defined on the plain frame's alpha: the two are not combined" );
-        if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no pre-integrated form; "
-                                     "VRC_OPT_PREINTEGRATION = 1 is marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
-        if( c->rayLod )
-            return fail( VRC_EINVAL, "vrc_render: vrc_set_ray_lod is on; VRC_OPT_PREINTEGRATION = 1 renders a per-brick cut" );
-        if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_PREINTEGRATION = 1 is defined on the "
-                                     "cudaRaycaster variant's sample set" );
-    }
-    if( shade )
-    {
-        if( c->optKernel == VRC_KERNEL_LDS || c->optKernel == VRC_KERNEL_PACKED )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_KERNEL = LDS / PACKED has no shaded form; VRC_OPT_SHADING = 1 is "
-                                     "marched by gathers (AUTO, REFERENCE_ORDER or GRID_DDA)" );
-        if( c->rayLod )
-            return fail( VRC_EINVAL, "vrc_render: vrc_set_ray_lod is on; VRC_OPT_SHADING = 1 renders a per-brick cut" );
-        if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
-            return fail( VRC_EINVAL, "vrc_render: VRC_OPT_VARIANT = GLRAYCASTER; VRC_OPT_SHADING = 1 is defined on the "
-                                     "cudaRaycaster variant's sample set" );
-    }
-    const bool linear = c->optFilter == VRC_FILTER_TRILINEAR;
-    /* samples classified one by one (padded transfer function in the table buffer) whenever the
-     * 257-entry classified table cannot be used: continuous or 16-bit densities */
-    /* (MIP: the one classification per ray reads the padded transfer function too) */
-    const bool classify = linear || pool->elemBytes != 1 || mip;
+    p.lp.rangeMin = p.render->dataSourceRange[0] + p.pool->rangeShift;
+    p.lp.rangeMax = p.render->dataSourceRange[1] + p.pool->rangeShift;
+    p.lp.alphaCorrection = (float)p.render->maxSamplesPerRay / (float)p.render->samplesPerRay;
+    p.lp.fracBits = (int)c->opt.tfFracBits;
+    const vrc_refusal r = vrc_plan_mode( c->opt, c->latch, c->rayLod, c->isoSet, c->isoValue, c->isoAmbient, p.pool->elemBytes, p.mode );
+    return r.code == VRC_OK ? VRC_OK : fail( r.code, r.msg );
+}
+
+/* classified table, rebuilt only when one of its inputs changed; behind it the pre-integrated one */
+static int render_tables( vrc_ctx* c, render_pass& p )
+{
+    const vrc_lut_params& lp = p.lp;
+    const bool classify = p.mode.classify;
     /* per-ray LOD: one classified table per level, opacity exponent doubled per level (a level-j
      * brick is sampled with step * 2^j); always all levels, so the table does not depend on the list */
     const uint32_t lutLevels = ( c->rayLod && !classify ) ? (uint32_t)VRC_MAX_LOD_LEVELS : 1u;
@@ -1875,7 +1697,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     }
     /* the pre-integrated table, behind the classified table on the stream (its value-indexed diagonal copies that one):
      * value-indexed where the frame marches stored bytes through the classified table, texel-indexed otherwise */
-    if( preint )
+    if( p.mode.preint )
     {
         const int kind = classify ? VRC_PREINT_TEXEL : VRC_PREINT_VALUE;
         if( !c->dPreint )
@@ -1890,255 +1712,235 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
             ++c->preintBuilds;
         }
     }
+    return VRC_OK;
+}
 
-    /* node table + grid, re-derived and re-uploaded only when the node list changed
-     * (the reference re-uploads synchronously every pass, Renderer.cu:259-267) */
-    const bool sameNodes = c->cachedPoolUid == pool->uid && c->cachedNodes.size() == nNodes &&
-                           c->cachedRayLod == c->rayLod &&
-                           std::memcmp( c->cachedNodes.data(), nodes,
-                                        nNodes * sizeof( vrc_node_data ) ) == 0;
-    if( !sameNodes )
+static vrc_atlas_geom pool_geom( const vrc_pool* pool )
+{
+    vrc_atlas_geom geom;
+    for( int a = 0; a < 3; ++a )
     {
-        c->walkState = vrc_ctx::WALK_IDLE; /* the walk cache's lists index the node table that is replaced here */
-        vrc_host_tables t;
-        vrc_atlas_geom geom;
-        for( int a = 0; a < 3; ++a )
-        {
-            geom.atlasDim[a] = pool->atlasDim[a];
-            geom.slotDim[a] = pool->slotDim[a];
-        }
-        for( int a = 0; a < 3; ++a )
-            geom.slots[a] = pool->slots[a];
-        vrc_build_tables( geom, nodes, nNodes, t );
-        if( c->rayLod )
-            vrc_build_lod_tables( geom, nodes, nNodes, t );
-        const int rc = ensure_capacity( c, t.nodes.size(), t.grid.size() );
-        if( rc != VRC_OK )
-            return rc;
-        const uint32_t stage = c->stageNext++ % kNodeStages;
-        if( c->stageUsed[stage] ) /* the copies issued from this area four node lists ago */
-            VRC_HIP_CHECK( hipEventSynchronize( c->stageEvent[stage] ) );
-        if( !c->stageEvent[stage] )
-            VRC_HIP_CHECK( hipEventCreateWithFlags( &c->stageEvent[stage], hipEventDisableTiming ) );
-        uint8_t* h = (uint8_t*)c->hStage + (size_t)stage * c->hStageCap;
-        const size_t nb = t.nodes.size() * sizeof( vrc_dev_node );
-        const size_t gb = t.grid.size() * sizeof( int32_t );
-        std::memcpy( h, t.nodes.data(), nb );
-        VRC_HIP_CHECK( hipMemcpyAsync( c->dNodes, h, nb, hipMemcpyHostToDevice, c->stream ) );
-        if( gb )
-        {
-            std::memcpy( h + nb, t.grid.data(), gb );
-            VRC_HIP_CHECK(
-                hipMemcpyAsync( c->dGrid, h + nb, gb, hipMemcpyHostToDevice, c->stream ) );
-        }
-        VRC_HIP_CHECK( hipEventRecord( c->stageEvent[stage], c->stream ) );
-        c->stageUsed[stage] = true;
-        c->cachedNodes.assign( nodes, nodes + nNodes );
-        c->cachedPoolUid = pool->uid;
-        c->cachedGridOk = t.gridOk && !c->rayLod; /* the grid buffer holds the per-level tables */
-        c->cachedOneCell = t.oneCellPerBrick;
-        c->cachedRayLod = c->rayLod;
-        c->cachedLodOk = t.lodOk;
-        c->cachedLodLevels = t.lodLevels;
-        c->cachedFinestVoxel = t.finestVoxelWorld;
-        c->cachedClamp = t.clamp;
-        c->cachedGridFrame = t.g;
+        geom.atlasDim[a] = pool->atlasDim[a];
+        geom.slotDim[a] = pool->slotDim[a];
+        geom.slots[a] = pool->slots[a];
     }
+    return geom;
+}
 
+/* node table + brick grid (vrc_tables.h), re-derived and re-uploaded only when the node list changed
+ * (the reference re-uploads synchronously every pass, Renderer.cu:259-267) */
+static int render_nodes( vrc_ctx* c, render_pass& p )
+{
+    p.sameNodes = c->cachedPoolUid == p.pool->uid && c->cachedNodes.size() == p.nNodes && c->cachedRayLod == c->rayLod &&
+                  std::memcmp( c->cachedNodes.data(), p.nodes, p.nNodes * sizeof( vrc_node_data ) ) == 0;
+    if( p.sameNodes )
+        return VRC_OK;
+    c->walk.state = vrc_walk_cache::IDLE; /* the walk cache's lists index the node table that is replaced here */
+    vrc_host_tables t;
+    const vrc_atlas_geom geom = pool_geom( p.pool );
+    vrc_build_tables( geom, p.nodes, p.nNodes, t );
+    if( c->rayLod )
+        vrc_build_lod_tables( geom, p.nodes, p.nNodes, t );
+    const size_t nb = t.nodes.size() * sizeof( vrc_dev_node );
+    const size_t gb = t.grid.size() * sizeof( int32_t );
+    VRC_TRY( ctx_grow( c, c->dNodesCap, t.nodes.size(), std::max< size_t >( t.nodes.size(), 1024 ), { c->dNodes } ) );
+    VRC_TRY( ctx_grow( c, c->dGridCap, t.grid.size(), std::max< size_t >( t.grid.size(), 4096 ), { c->dGrid } ) );
+    /* pinned staging: kNodeStages areas of hStageCap bytes */
+    bool grew = false;
+    VRC_TRY( ctx_grow( c, c->hStageCap, nb + gb, ( std::max< size_t >( nb + gb, 1 << 18 ) + 255 ) / 256 * 256,
+                       { { c->hStage, kNodeStages, 0, vrc_grown::PINNED } }, &grew ) );
+    for( int i = 0; grew && i < kNodeStages; ++i )
+        c->stageUsed[i] = false;
+    const uint32_t stage = c->stageNext++ % kNodeStages;
+    if( c->stageUsed[stage] ) /* the copies issued from this area four node lists ago */
+        VRC_HIP_CHECK( hipEventSynchronize( c->stageEvent[stage] ) );
+    if( !c->stageEvent[stage] )
+        VRC_HIP_CHECK( hipEventCreateWithFlags( &c->stageEvent[stage], hipEventDisableTiming ) );
+    uint8_t* h = (uint8_t*)c->hStage + (size_t)stage * c->hStageCap;
+    std::memcpy( h, t.nodes.data(), nb );
+    VRC_HIP_CHECK( hipMemcpyAsync( c->dNodes, h, nb, hipMemcpyHostToDevice, c->stream ) );
+    if( gb )
+    {
+        std::memcpy( h + nb, t.grid.data(), gb );
+        VRC_HIP_CHECK( hipMemcpyAsync( c->dGrid, h + nb, gb, hipMemcpyHostToDevice, c->stream ) );
+    }
+    VRC_HIP_CHECK( hipEventRecord( c->stageEvent[stage], c->stream ) );
+    c->stageUsed[stage] = true;
+    c->cachedNodes.assign( p.nodes, p.nodes + p.nNodes );
+    c->cachedPoolUid = p.pool->uid;
+    c->cachedGridOk = t.gridOk && !c->rayLod; /* the grid buffer holds the per-level tables */
+    c->cachedOneCell = t.oneCellPerBrick;
+    c->cachedRayLod = c->rayLod;
+    c->cachedLodOk = t.lodOk;
+    c->cachedLodLevels = t.lodLevels;
+    c->cachedFinestVoxel = t.finestVoxelWorld;
+    c->cachedClamp = t.clamp;
+    c->cachedGridFrame = t.g;
+    return VRC_OK;
+}
+
+/* which kernel form marches the frame (vrc_plan_form), or why none does; the pool's packed atlas where the form wants
+ * it.  Refuses with the tables up to date, as it always has; VRC_ENOMEM is the last refusal of all */
+static int render_form( vrc_ctx* c, render_pass& p )
+{
+    const vrc_pool* const pool = p.pool;
+    const vrc_form_facts k = { c->rayLod, c->cachedGridOk, c->cachedOneCell, c->cachedLodOk, c->cachedClamp, p.nNodes,
+                               p.render->samplesPerPixel, { pool->slotDim[0], pool->slotDim[1], pool->slotDim[2] },
+                               pool->elemBytes, pool->bigAtlas, pool_packed_possible( pool ) };
+    const vrc_refusal r = vrc_plan_form( c->opt, p.mode, k, p.form );
+    if( r.code != VRC_OK )
+        return fail( r.code, r.msg );
+    p.form.usePacked = p.form.packed != VRC_PACKED_NONE && pool_enable_packed( p.pool );
+    if( p.form.packed == VRC_PACKED_REQUIRED && !p.form.usePacked )
+        return fail( vrc_plan_no_packed_memory.code, vrc_plan_no_packed_memory.msg );
+    p.form.useLds = vrc_plan_use_lds( c->opt, p.mode, k, p.form, p.form.usePacked );
+    p.tableWalk = vrc_plan_table_walk( c->opt, p.mode, k, p.form );
+    return VRC_OK;
+}
+
+/* the frame constants, as far as every cached copy of them compares them */
+static void render_frame( vrc_ctx* c, render_pass& p )
+{
+    std::memset( &p.a, 0, sizeof( p.a ) );
+    p.a.shade = p.mode.shade;
+    p.a.cdepth = p.mode.cdepth;
+    p.a.preint = p.mode.preint;
+    vrc_frame& f = p.a.frame;
+    /* the GLSL twin casts through the pixel centre (gl_FragCoord, fragRaycast.glsl:127), the
+     * CUDA kernel through the pixel corner (Renderer.cu:106-112) */
+    const float centre = c->opt.variant == VRC_VARIANT_GLRAYCASTER ? 0.5f : 0.0f;
+    vrc_fill_frame( f, *p.view, *p.render, pool_geom( p.pool ), c->cachedGridFrame, c->planes, c->nPlanes, p.nNodes,
+                    c->fbW, c->fbH, centre, centre );
+    f.rowMap = c->rowMap.empty() ? nullptr : c->dRowMap;
+    f.variant = c->opt.variant == VRC_VARIANT_GLRAYCASTER ? VRC_VARIANT_GL : VRC_VARIANT_CUDA;
+    f.samplesPerPixel = ( f.variant == VRC_VARIANT_GL && p.render->samplesPerPixel > 1u ) ? p.render->samplesPerPixel : 1u;
     if( c->rayLod )
     {
-        if( !c->cachedLodOk )
-            return fail( VRC_EHIERARCHY, "vrc_render: per-ray LOD needs a brick hierarchy (every level a regular grid of bricks, one brick per cell)" );
-        if( c->optVariant != VRC_VARIANT_CUDARAYCASTER )
-            return fail( VRC_EINVAL, "vrc_render: per-ray LOD is defined for the cudaRaycaster variant only" );
-        /* AUTO: the LDS-staged form for the trilinear filter where it applies, else the gather form; GRID_DDA asks for
-         * the gather form, LDS for the staged one */
-        if( c->optKernel == VRC_KERNEL_REFERENCE_ORDER )
-            return fail( VRC_EINVAL, "vrc_render: per-ray LOD walks the hierarchy; VRC_OPT_KERNEL = AUTO, GRID_DDA (gathers), LDS or PACKED" );
+        f.lodLevels = c->cachedLodLevels;
+        f.lodBase = (float)( c->cachedFinestVoxel /
+                             ( (double)c->rayLodSse * (double)c->rayLodWorldPerPixel ) );
     }
-    bool useDda = c->cachedGridOk;
-    /* AUTO keeps the reference's frame: bricks of one size are met by the grid walk in the reference's
-     * order; a list that mixes brick sizes (an LOD cut) is composited in the host's centre-distance order,
-     * which is not a visibility order for every ray (quirk Q6) -- the literal loop reproduces that as long
-     * as testing every brick per ray is affordable.  GRID_DDA can always be asked for (true visibility
-     * order); the trilinear filter (extension, no reference frame to keep) stays on the grid. */
-    if( c->optKernel == VRC_KERNEL_AUTO && useDda && !c->cachedOneCell && !linear &&
-        nNodes <= VRC_REFERENCE_ORDER_MAX_NODES )
-        useDda = false;
-    /* glRaycaster with more than one sample per pixel (fragRaycast.glsl:121-129): the pixel is averaged brick by
-     * brick in the host's order -- the reference-order loop is the only form that has a "brick by brick" */
-    const bool glSuper = c->optVariant == VRC_VARIANT_GLRAYCASTER && render->samplesPerPixel > 1u;
-    if( glSuper )
-    {
-        if( c->optKernel == VRC_KERNEL_GRID_DDA || c->optKernel == VRC_KERNEL_LDS )
-            return fail( VRC_EINVAL, "vrc_render: the glRaycaster variant with samplesPerPixel > 1 is rendered by the "
-                                     "reference-order kernel (VRC_OPT_KERNEL = AUTO or REFERENCE_ORDER)" );
-        useDda = false;
-    }
-    if( c->optKernel == VRC_KERNEL_REFERENCE_ORDER )
-        useDda = false;
-    else if( c->optKernel == VRC_KERNEL_GRID_DDA && !c->cachedGridOk && !c->rayLod )
-        return fail( VRC_EINVAL, "vrc_render: node set is not grid-aligned; GRID_DDA unavailable" );
-    /* LDS-staged kernel: brick-grid DDA + unclamped sampler (overlap >= 1).  AUTO takes it for
-     * the trilinear filter (eight taps per sample), the gather kernel for point sampling. */
-    /* its trilinear form takes the transfer-function texel and CUDA's 1.8 fixed-point lerp weight out of one
-     * float -> integer conversion (vrc_kernels_lds.hip: lds_classify): other weight widths use the gather form */
-    /* slot-local positions in 8.24 fixed point (fixed-point stepping, the per-axis address tables, the LDS kernel's boxes)
-     * need every slot dimension to fit eight bits; pool creation bounds a slot's VOLUME only (2^24 voxels), so a flat
-     * or long brick can exceed it: such pools march with float positions */
-    const bool slotsFit8Bits = pool->slotDim[0] <= 248u && pool->slotDim[1] <= 248u && pool->slotDim[2] <= 248u;
-    /* 16-bit voxels: its trilinear form only (a 16-bit density does not index the classified table of the point form) */
-    const bool ldsVoxels = slotsFit8Bits && ( pool->elemBytes == 1 || ( pool->elemBytes == 2 && linear ) );
-    /* atlases of more than 2^32 voxels (64-bit slot bases): its trilinear form only */
-    const bool ldsEligible = c->cachedGridOk && !c->cachedClamp && ldsVoxels && ( !pool->bigAtlas || linear ) &&
-                             ( !linear || c->optTfFracBits == 8 );
-    if( !c->rayLod && c->optKernel == VRC_KERNEL_LDS && !ldsEligible )
-        return fail( VRC_EINVAL, "vrc_render: the LDS kernel needs a grid-aligned node set of 8-bit bricks in an atlas of at most 2^32 voxels (trilinear: 8- or 16-bit, any atlas, VRC_OPT_TF_FRAC_BITS = 8) with overlap >= 1" );
-    /* per-ray LOD: the staged kernel's trilinear form only (samples classified one by one: no table per level) */
-    const bool ldsLodEligible = c->rayLod && linear && !c->cachedClamp && ldsVoxels && !pool->bigAtlas &&
-                                c->optTfFracBits == 8;
-    if( c->rayLod && c->optKernel == VRC_KERNEL_LDS && !ldsLodEligible )
-        return fail( VRC_EINVAL, "vrc_render: under per-ray LOD the LDS kernel needs the trilinear filter, 8- or 16-bit bricks with overlap >= 1 and VRC_OPT_TF_FRAC_BITS = 8" );
-    /* tap-packed atlas (VRC_KERNEL_PACKED; vrc_core.h): the trilinear filter as two gathers per sample.  Needs what its
-     * positions and its classifier need -- 8- or 16-bit bricks with overlap >= 1 in slots of at most 248 voxels a side,
-     * VRC_OPT_TF_FRAC_BITS = 8, fixed-point stepping -- and 2.25 times the atlas in device memory; either brick
-     * enumeration (grid walk where the node set is grid-aligned, else the reference-order loop) */
-    const bool packedEligible = linear && !glSuper && !mip && !shade && !cdepth && !preint && !c->cachedClamp && slotsFit8Bits &&
-                                pool_packed_possible( pool ) && c->optTfFracBits == 8 && c->optStepping != 0;
-    bool usePacked = false;
-    if( c->optKernel == VRC_KERNEL_PACKED )
-    {
-        if( !packedEligible )
-            return fail( VRC_EINVAL, "vrc_render: the packed kernel needs the trilinear filter on 8- or 16-bit bricks with overlap >= 1 (slots of at most 248 voxels a side), VRC_OPT_TF_FRAC_BITS = 8, fixed-point stepping" );
-        if( !pool_enable_packed( pool ) )
-            return fail( VRC_ENOMEM, "vrc_render: no device memory for the tap-packed atlas (2.25 times the brick atlas)" );
-        usePacked = true;
-    }
-    else if( c->optKernel == VRC_KERNEL_AUTO && packedEligible && c->optPackedAtlas )
-        /* measured on C2: 1.2 against 1.7 ms along the axis, 1.5 against 2.4 at 30/20 degrees;
-         * under per-ray LOD 1.4-2.1 x the staged form (profiles/r4_c5_trilinear_three_forms.txt); without the memory for
-         * it the frame takes the staged form below */
-        usePacked = pool_enable_packed( pool );
-    const bool useLds = c->rayLod ? ( ldsLodEligible && c->optKernel != VRC_KERNEL_GRID_DDA && !usePacked )
-                                  : !glSuper && !usePacked && !mip && !shade && !cdepth && !preint && ( c->optKernel == VRC_KERNEL_LDS ||
-                                                  ( c->optKernel == VRC_KERNEL_AUTO && linear && ldsEligible ) );
+    p.pixels = (size_t)c->fbW * c->fbH;
+    p.plane = (size_t)( ( c->fbW + VRC_TILE_W - 1 ) / VRC_TILE_W ) * ( ( c->fbH + VRC_TILE_H - 1 ) / VRC_TILE_H ) * 64u;
+}
 
-    vrc_raycast_args a;
-    std::memset( &a, 0, sizeof( a ) );
-    a.shade = shade;
-    a.cdepth = cdepth;
-    a.preint = preint;
-    vrc_frame& f = a.frame;
+/* tile schedule, recomputed only when the frame constants changed */
+static int render_tile_schedule( vrc_ctx* c, render_pass& p )
+{
+    const vrc_frame& f = p.a.frame;
+    p.a.tileOrder = nullptr;
+    if( !c->opt.tileOrder )
+        return VRC_OK;
+    /* one entry per schedule slot: four per 2x2 block of tiles (vrc_internal.h) */
+    const size_t nTiles = vrc_schedule_slots( ( c->fbW + VRC_TILE_W - 1 ) / VRC_TILE_W,
+                                              ( c->fbH + VRC_TILE_H - 1 ) / VRC_TILE_H );
+    /* order[nTiles] | scratch[VRC_TILE_SCRATCH_WORDS] | bucket[nTiles] (bytes) */
+    bool grew = false;
+    VRC_TRY( ctx_grow( c, c->dTileOrderCap, nTiles, nTiles,
+                       { { c->dTileOrder, sizeof( uint32_t ) + 1, VRC_TILE_SCRATCH_WORDS * sizeof( uint32_t ) } }, &grew ) );
+    if( grew )
+        c->tileOrderValid = false;
+    /* The schedule is a heuristic (any permutation of the tiles renders the same frame): a camera
+     * that moved a little keeps the last one -- same pixel buffer and volume box, eye and ray
+     * matrices within 2 % -- for at most 15 frames in a row; two small kernels and a memset
+     * less per frame of an orbit. */
+    bool reuse = c->tileOrderValid;
+    if( reuse && std::memcmp( &c->tileOrderFrame, &f, sizeof( f ) ) != 0 )
     {
-        vrc_atlas_geom geom;
-        for( int i = 0; i < 3; ++i )
-        {
-            geom.atlasDim[i] = pool->atlasDim[i];
-            geom.slotDim[i] = pool->slotDim[i];
-        }
-        for( int a = 0; a < 3; ++a )
-            geom.slots[a] = pool->slots[a];
-        /* the GLSL twin casts through the pixel centre (gl_FragCoord, fragRaycast.glsl:127), the
-         * CUDA kernel through the pixel corner (Renderer.cu:106-112) */
-        const float centre = c->optVariant == VRC_VARIANT_GLRAYCASTER ? 0.5f : 0.0f;
-        vrc_fill_frame( f, *view, *render, geom, c->cachedGridFrame, c->planes, c->nPlanes, nNodes,
-                        c->fbW, c->fbH, centre, centre );
-        f.rowMap = c->rowMap.empty() ? nullptr : c->dRowMap;
-        f.variant = c->optVariant == VRC_VARIANT_GLRAYCASTER ? VRC_VARIANT_GL : VRC_VARIANT_CUDA;
-        f.samplesPerPixel = ( f.variant == VRC_VARIANT_GL && render->samplesPerPixel > 1u ) ? render->samplesPerPixel : 1u;
-        if( c->rayLod )
-        {
-            f.lodLevels = c->cachedLodLevels;
-            f.lodBase = (float)( c->cachedFinestVoxel /
-                                 ( (double)c->rayLodSse * (double)c->rayLodWorldPerPixel ) );
-        }
+        const vrc_frame& o = c->tileOrderFrame;
+        reuse = c->tileOrderReused < 15u && o.width == f.width && o.height == f.height && o.vpW == f.vpW &&
+                o.vpH == f.vpH && o.vpX == f.vpX && o.vpY == f.vpY && o.pixelOffX == f.pixelOffX &&
+                o.pixelOffY == f.pixelOffY && o.rowMap == f.rowMap && o.nPlanes == f.nPlanes &&
+                std::memcmp( o.planes, f.planes, sizeof( f.planes ) ) == 0 &&
+                std::memcmp( o.aabbMin, f.aabbMin, sizeof( f.aabbMin ) ) == 0 &&
+                std::memcmp( o.aabbMax, f.aabbMax, sizeof( f.aabbMax ) ) == 0 &&
+                std::memcmp( o.invProj, f.invProj, sizeof( f.invProj ) ) == 0;
+        for( int i = 0; reuse && i < 3; ++i )
+            reuse = std::fabs( o.eye[i] - f.eye[i] ) <= 0.02f;
+        for( int i = 0; reuse && i < 16; ++i )
+            reuse = std::fabs( o.invView[i] - f.invView[i] ) <= 0.02f;
+        if( reuse )
+            ++c->tileOrderReused;
     }
-
-    /* tile schedule, recomputed only when the frame constants changed */
-    a.tileOrder = nullptr;
-    if( c->optTileOrder )
+    if( !reuse )
     {
-        /* one entry per schedule slot: four per 2x2 block of tiles (vrc_internal.h) */
-        const size_t nTiles = vrc_schedule_slots( ( c->fbW + VRC_TILE_W - 1 ) / VRC_TILE_W,
-                                                  ( c->fbH + VRC_TILE_H - 1 ) / VRC_TILE_H );
-        if( nTiles > c->dTileOrderCap )
-        {
-            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-            if( c->dTileOrder ) VRC_HIP_CHECK( hipFree( c->dTileOrder ) );
-            c->dTileOrder = nullptr;
-            c->dTileOrderCap = 0;
-            /* order[nTiles] | scratch[VRC_TILE_SCRATCH_WORDS] | bucket[nTiles] (bytes) */
-            VRC_HIP_CHECK( hipMalloc( &c->dTileOrder, ( nTiles + VRC_TILE_SCRATCH_WORDS ) * sizeof( uint32_t ) + nTiles ) );
-            c->dTileOrderCap = nTiles;
-            c->tileOrderValid = false;
-        }
-        /* The schedule is a heuristic (any permutation of the tiles renders the same frame): a camera
-         * that moved a little keeps the last one -- same pixel buffer and volume box, eye and ray
-         * matrices within 2 % -- for at most 15 frames in a row; two small kernels and a memset
-         * less per frame of an orbit. */
-        bool reuse = c->tileOrderValid;
-        if( reuse && std::memcmp( &c->tileOrderFrame, &f, sizeof( f ) ) != 0 )
-        {
-            const vrc_frame& o = c->tileOrderFrame;
-            reuse = c->tileOrderReused < 15u && o.width == f.width && o.height == f.height && o.vpW == f.vpW &&
-                    o.vpH == f.vpH && o.vpX == f.vpX && o.vpY == f.vpY && o.pixelOffX == f.pixelOffX &&
-                    o.pixelOffY == f.pixelOffY && o.rowMap == f.rowMap && o.nPlanes == f.nPlanes &&
-                    std::memcmp( o.planes, f.planes, sizeof( f.planes ) ) == 0 &&
-                    std::memcmp( o.aabbMin, f.aabbMin, sizeof( f.aabbMin ) ) == 0 &&
-                    std::memcmp( o.aabbMax, f.aabbMax, sizeof( f.aabbMax ) ) == 0 &&
-                    std::memcmp( o.invProj, f.invProj, sizeof( f.invProj ) ) == 0;
-            for( int i = 0; reuse && i < 3; ++i )
-                reuse = std::fabs( o.eye[i] - f.eye[i] ) <= 0.02f;
-            for( int i = 0; reuse && i < 16; ++i )
-                reuse = std::fabs( o.invView[i] - f.invView[i] ) <= 0.02f;
-            if( reuse )
-                ++c->tileOrderReused;
-        }
-        if( !reuse )
-        {
-            c->tileOrderReused = 0;
-            VRC_HIP_CHECK( vrc_launch_tile_order( f, c->dTileOrder, c->dTileOrder + c->dTileOrderCap,
-                                                  (uint8_t*)( c->dTileOrder + c->dTileOrderCap + VRC_TILE_SCRATCH_WORDS ),
-                                                  c->stream ) );
-            std::memcpy( &c->tileOrderFrame, &f, sizeof( f ) );
-            c->tileOrderValid = true;
-        }
-        a.tileOrder = c->dTileOrder;
+        c->tileOrderReused = 0;
+        VRC_HIP_CHECK( vrc_launch_tile_order( f, c->dTileOrder, c->dTileOrder + c->dTileOrderCap,
+                                              (uint8_t*)( c->dTileOrder + c->dTileOrderCap + VRC_TILE_SCRATCH_WORDS ),
+                                              c->stream ) );
+        std::memcpy( &c->tileOrderFrame, &f, sizeof( f ) );
+        c->tileOrderValid = true;
     }
+    p.a.tileOrder = c->dTileOrder;
+    return VRC_OK;
+}
 
-    /* fold the frame's clear into this march (after the tile-schedule cache compared frames) */
-    f.clearFirst = c->clearPending ? 1u : 0u;
+/* fold the frame's clear into this march (after the tile-schedule cache compared frames), and hand it the pool's
+ * uniformity words (VRC_OPT_UNIFORM_BRICKS): NULL = every brick takes the general march */
+static void render_clear_and_slot_words( vrc_ctx* c, render_pass& p )
+{
+    p.a.frame.clearFirst = c->clearPending ? 1u : 0u;
     c->clearPending = false;
-    /* the pool's uniformity words (VRC_OPT_UNIFORM_BRICKS): NULL = every brick takes the general march */
-    f.slotInfo = c->optUniformBricks ? pool->dSlotInfo : nullptr;
-    if( mip )
+    p.a.frame.slotInfo = c->opt.uniformBricks ? p.pool->dSlotInfo : nullptr;
+}
+
+/* The running state per pixel of the pixel buffer in use, grown with it: dMipMax (a MIP frame's M, a composite-depth
+ * frame's V) and dMipDepth (the D of both).  A later pass of a frame whose pixel buffer grew (vrc_set_framebuffer), or
+ * whose buffer before was large enough from an earlier frame and keeps the passes so far, fills the new one with
+ * "nothing known as far as this buffer knows": all bits set for the value, +infinity for the depth (no sample equals M,
+ * no pixel has crossed).  The first pass of a frame reads neither (mipFirst) */
+static int grow_pixel_values( vrc_ctx* c, size_t pixels )
+{
+    bool grew = false;
+    VRC_TRY( ctx_grow( c, c->dMipMaxPixels, pixels, pixels, { c->dMipMax }, &grew ) );
+    if( grew && !c->mipFirst )
+        VRC_HIP_CHECK( hipMemsetAsync( c->dMipMax, 0xFF, pixels * sizeof( uint32_t ), c->stream ) );
+    return VRC_OK;
+}
+static int grow_pixel_depths( vrc_ctx* c, size_t pixels )
+{
+    bool grew = false;
+    VRC_TRY( ctx_grow( c, c->dMipDepthPixels, pixels, pixels, { c->dMipDepth }, &grew ) );
+    if( grew && !c->mipFirst )
+        VRC_HIP_CHECK( hipMemsetD32Async( reinterpret_cast< hipDeviceptr_t >( c->dMipDepth ), 0x7F800000, pixels, c->stream ) );
+    return VRC_OK;
+}
+
+/* what a pass leaves for vrc_get_projection_values and vrc_get_projection_depths */
+static void leave_projection( vrc_ctx* c, render_pass& p, uint32_t fold, bool sums )
+{
+    c->depthValid = p.mode.mipDepth || p.mode.cdepth;
+    if( c->depthValid )
     {
-        /* the running maxima: one word per pixel of the pixel buffer in use */
-        const size_t pixels = (size_t)c->fbW * c->fbH;
-        if( pixels > c->dMipMaxPixels )
+        c->depthFrame = p.a.frame;
+        c->depthRows = c->rowMap;
+    }
+    c->mipFirst = false;
+    c->projState.mipMax = c->dMipMax;
+    c->projState.meanSum = sums ? c->dMeanSum : nullptr;
+    c->projState.meanCount = sums ? c->dMeanCount : nullptr;
+    c->projState.pixels = (uint32_t)p.pixels;
+    c->projState.fold = fold;
+    c->projState.floatState = ( p.mode.linear || p.pool->elemBytes == 4 ) ? 1u : 0u;
+    c->projState.shift = p.pool->rangeShift;
+}
+
+/* projection state: the per-pixel buffers of a MIP, isosurface or composite-depth frame, what the pass leaves for the
+ * read-backs, and the latches -- written here and nowhere else, each by the pass that read its option */
+static int render_projection( vrc_ctx* c, render_pass& p )
+{
+    vrc_pool* const pool = p.pool;
+    const vrc_mode& m = p.mode;
+    vrc_frame& f = p.a.frame;
+    const size_t pixels = p.pixels;
+    if( m.mip )
+    {
+        bool grew = false;
+        VRC_TRY( grow_pixel_values( c, pixels ) );
+        if( m.mean )
         {
-            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-            if( c->dMipMax ) VRC_HIP_CHECK( hipFree( c->dMipMax ) );
-            c->dMipMax = nullptr;
-            c->dMipMaxPixels = 0;
-            VRC_HIP_CHECK( hipMalloc( &c->dMipMax, pixels * sizeof( uint32_t ) ) );
-            c->dMipMaxPixels = pixels;
-            if( !c->mipFirst ) /* a later pass of a frame whose pixel buffer grew (vrc_set_framebuffer): nothing known */
-                VRC_HIP_CHECK( hipMemsetAsync( c->dMipMax, 0xFF, pixels * sizeof( uint32_t ), c->stream ) );
-        }
-        const bool mean = !iso && c->optMipFold == VRC_MIP_FOLD_MEAN;
-        if( mean && pixels > c->dMeanPixels )
-        {
-            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-            if( c->dMeanSum ) VRC_HIP_CHECK( hipFree( c->dMeanSum ) );
-            if( c->dMeanCount ) VRC_HIP_CHECK( hipFree( c->dMeanCount ) );
-            c->dMeanSum = nullptr;
-            c->dMeanCount = nullptr;
-            c->dMeanPixels = 0;
-            VRC_HIP_CHECK( hipMalloc( &c->dMeanSum, pixels * sizeof( unsigned long long ) ) );
-            VRC_HIP_CHECK( hipMalloc( &c->dMeanCount, pixels * sizeof( uint32_t ) ) );
-            c->dMeanPixels = pixels;
-            if( !c->mipFirst ) /* as above: no sample yet, which is a sum of 0 (integer and double alike) and a count of 0 */
+            VRC_TRY( ctx_grow( c, c->dMeanPixels, pixels, pixels, { c->dMeanSum, c->dMeanCount }, &grew ) );
+            if( grew && !c->mipFirst ) /* no sample yet, which is a sum of 0 (integer and double alike) and a count of 0 */
             {
                 VRC_HIP_CHECK( hipMemsetAsync( c->dMeanSum, 0, pixels * sizeof( unsigned long long ), c->stream ) );
                 VRC_HIP_CHECK( hipMemsetAsync( c->dMeanCount, 0, pixels * sizeof( uint32_t ), c->stream ) );
@@ -2146,154 +1948,99 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         }
         f.mipMax = c->dMipMax;
         f.mipFirst = c->mipFirst ? 1u : 0u;
-        f.slotMax = c->optMipSkip ? pool->dSlotMax : nullptr;
-        f.slotMin = c->optMipSkip ? pool->dSlotMin : nullptr;
-        f.meanSum = mean ? c->dMeanSum : nullptr;
-        f.meanCount = mean ? c->dMeanCount : nullptr;
-        if( mipDepth && pixels > c->dMipDepthPixels )
+        f.slotMax = c->opt.mipSkip ? pool->dSlotMax : nullptr;
+        f.slotMin = c->opt.mipSkip ? pool->dSlotMin : nullptr;
+        f.meanSum = m.mean ? c->dMeanSum : nullptr;
+        f.meanCount = m.mean ? c->dMeanCount : nullptr;
+        if( m.mipDepth )
+            VRC_TRY( grow_pixel_depths( c, pixels ) );
+        f.mipDepth = m.mipDepth ? c->dMipDepth : nullptr;
+        f.mipCue = ( m.mipDepth && !m.iso ) ? (float)c->opt.mipDepthCue / 1000.0f : 0.0f;
+        if( m.iso )
         {
-            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-            if( c->dMipDepth ) VRC_HIP_CHECK( hipFree( c->dMipDepth ) );
-            c->dMipDepth = nullptr;
-            c->dMipDepthPixels = 0;
-            VRC_HIP_CHECK( hipMalloc( &c->dMipDepth, pixels * sizeof( float ) ) );
-            c->dMipDepthPixels = pixels;
-            if( !c->mipFirst ) /* a later pass (the pixel buffer grew, or dMipMax was large enough from an earlier frame
-                                * and keeps the passes so far): no sample equals M yet as far as this buffer knows */
-                VRC_HIP_CHECK( hipMemsetD32Async( reinterpret_cast< hipDeviceptr_t >( c->dMipDepth ), 0x7F800000, pixels, c->stream ) );
-        }
-        f.mipDepth = mipDepth ? c->dMipDepth : nullptr;
-        f.mipCue = ( mipDepth && !iso ) ? (float)c->optMipDepthCue / 1000.0f : 0.0f;
-        if( iso )
-        {
-            if( pixels > c->dIsoGradPixels )
-            {
-                VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-                if( c->dIsoGrad ) VRC_HIP_CHECK( hipFree( c->dIsoGrad ) );
-                c->dIsoGrad = nullptr;
-                c->dIsoGradPixels = 0;
-                VRC_HIP_CHECK( hipMalloc( &c->dIsoGrad, pixels * 3u * sizeof( float ) ) );
-                c->dIsoGradPixels = pixels;
-                if( !c->mipFirst ) /* (as dMipDepth above: no hit yet as far as this buffer knows) */
-                    VRC_HIP_CHECK( hipMemsetAsync( c->dIsoGrad, 0, pixels * 3u * sizeof( float ), c->stream ) );
-            }
+            VRC_TRY( ctx_grow( c, c->dIsoGradPixels, pixels, pixels, { { c->dIsoGrad, 3u * sizeof( float ) } }, &grew ) );
+            if( grew && !c->mipFirst ) /* (as dMipDepth: no hit yet as far as this buffer knows) */
+                VRC_HIP_CHECK( hipMemsetAsync( c->dIsoGrad, 0, pixels * 3u * sizeof( float ), c->stream ) );
             f.isoGrad = c->dIsoGrad;
             f.isoThreshold = vrc_iso_int_threshold( c->isoValue, pool->rangeShift, pool->elemBytes == 1 ? 255u : 65535u );
             f.isoStored = vrc_iso_float_threshold( c->isoValue, pool->rangeShift );
             f.isoClassify = c->isoValue + pool->rangeShift;
             f.isoAmbient = c->isoAmbient;
-            c->frameIso = true;
-            c->frameIsoValue = c->isoValue;
-            c->frameIsoAmbient = c->isoAmbient;
+            c->latch.iso = true;
+            c->latch.isoValue = c->isoValue;
+            c->latch.isoAmbient = c->isoAmbient;
         }
-        c->gradValid = iso;
-        if( !mean && !iso )
+        c->gradValid = m.iso;
+        if( !m.mean && !m.iso )
         {
-            c->frameDepth = c->optMipDepth;
-            c->frameCue = c->optMipDepthCue;
+            c->latch.depth = c->opt.mipDepth;
+            c->latch.cue = c->opt.mipDepthCue;
         }
-        c->depthValid = mipDepth;
-        if( mipDepth )
-        {
-            c->depthFrame = f;
-            c->depthRows = c->rowMap;
-        }
-        c->mipFirst = false;
-        if( !iso )
-            c->frameFold = c->optMipFold;
-        /* what this pass leaves for vrc_get_projection_values */
-        c->projState.mipMax = c->dMipMax;
-        c->projState.meanSum = c->dMeanSum;
-        c->projState.meanCount = c->dMeanCount;
-        c->projState.pixels = (uint32_t)pixels;
-        c->projState.fold = iso ? (uint32_t)VRC_FOLD_FIRST : (uint32_t)c->optMipFold;
-        c->projState.floatState = ( linear || pool->elemBytes == 4 ) ? 1u : 0u;
-        c->projState.shift = pool->rangeShift;
+        if( !m.iso )
+            c->latch.fold = c->opt.mipFold;
+        leave_projection( c, p, m.iso ? (uint32_t)VRC_FOLD_FIRST : (uint32_t)c->opt.mipFold, true );
     }
-    if( cdepth )
+    if( m.cdepth )
     {
-        /* the pair per pixel of the pixel buffer in use, where a MIP frame's running maximum and depth are: grown,
-         * invalidated by vrc_pre_render (mipFirst) and not read by the frame's first pass as those are */
-        const size_t pixels = (size_t)c->fbW * c->fbH;
-        if( pixels > c->dMipMaxPixels )
-        {
-            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-            if( c->dMipMax ) VRC_HIP_CHECK( hipFree( c->dMipMax ) );
-            c->dMipMax = nullptr;
-            c->dMipMaxPixels = 0;
-            VRC_HIP_CHECK( hipMalloc( &c->dMipMax, pixels * sizeof( uint32_t ) ) );
-            c->dMipMaxPixels = pixels;
-            if( !c->mipFirst ) /* a later pass of a frame whose pixel buffer grew: no pixel has crossed as far as this knows */
-                VRC_HIP_CHECK( hipMemsetAsync( c->dMipMax, 0xFF, pixels * sizeof( uint32_t ), c->stream ) );
-        }
-        if( pixels > c->dMipDepthPixels )
-        {
-            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-            if( c->dMipDepth ) VRC_HIP_CHECK( hipFree( c->dMipDepth ) );
-            c->dMipDepth = nullptr;
-            c->dMipDepthPixels = 0;
-            VRC_HIP_CHECK( hipMalloc( &c->dMipDepth, pixels * sizeof( float ) ) );
-            c->dMipDepthPixels = pixels;
-            if( !c->mipFirst )
-                VRC_HIP_CHECK( hipMemsetD32Async( reinterpret_cast< hipDeviceptr_t >( c->dMipDepth ), 0x7F800000, pixels, c->stream ) );
-        }
+        /* the pair per pixel where a MIP frame's running maximum and depth are: grown, invalidated by vrc_pre_render
+         * (mipFirst) and not read by the frame's first pass as those are */
+        VRC_TRY( grow_pixel_values( c, pixels ) );
+        VRC_TRY( grow_pixel_depths( c, pixels ) );
         f.mipMax = c->dMipMax;
         f.mipDepth = c->dMipDepth;
         f.mipFirst = c->mipFirst ? 1u : 0u;
-        c->mipFirst = false;
         c->gradValid = false;
-        c->depthValid = true;
-        c->depthFrame = f;
-        c->depthRows = c->rowMap;
-        /* what this pass leaves for vrc_get_projection_values: V as a first-crossing frame leaves it */
-        c->projState.mipMax = c->dMipMax;
-        c->projState.meanSum = nullptr;
-        c->projState.meanCount = nullptr;
-        c->projState.pixels = (uint32_t)pixels;
-        c->projState.fold = (uint32_t)VRC_FOLD_FIRST;
-        c->projState.floatState = ( linear || pool->elemBytes == 4 ) ? 1u : 0u;
-        c->projState.shift = pool->rangeShift;
+        leave_projection( c, p, (uint32_t)VRC_FOLD_FIRST, false ); /* V as a first-crossing frame leaves it */
     }
-    f.cdepthTau = cdepth ? (float)c->optCompositeDepth / 1000.0f : 0.0f;
-    f.preintTable = preint ? c->dPreint : nullptr;
-    if( !mip )
-        c->framePreint = c->optPreint;
-    c->frameProjection = c->optProjection;
-    if( !mip )
-        c->frameCompositeDepth = c->optCompositeDepth;
-    if( !mip )
+    f.cdepthTau = m.cdepth ? (float)c->opt.compositeDepth / 1000.0f : 0.0f;
+    f.preintTable = m.preint ? c->dPreint : nullptr;
+    f.shadeAmbient = m.shade ? (float)c->opt.shadingAmbient / 1000.0f : 0.0f;
+    c->latch.projection = c->opt.projection;
+    if( !m.mip )
     {
-        c->frameShading = c->optShading;
-        c->frameShadingAmbient = c->optShadingAmbient;
+        c->latch.preint = c->opt.preint;
+        c->latch.compositeDepth = c->opt.compositeDepth;
+        c->latch.shading = c->opt.shading;
+        c->latch.shadingAmbient = c->opt.shadingAmbient;
     }
-    f.shadeAmbient = shade ? (float)c->optShadingAmbient / 1000.0f : 0.0f;
+    return VRC_OK;
+}
 
+/* the launcher's arguments; the depth split and ray compaction of the table walk kernel */
+static int render_split_and_compact( vrc_ctx* c, render_pass& p )
+{
+    vrc_pool* const pool = p.pool;
+    vrc_raycast_args& a = p.a;
+    const vrc_frame& f = a.frame;
+    const bool gridWalk = p.form.useDda || c->rayLod;
     a.nodes = c->dNodes;
-    a.gridTable = ( useDda || c->rayLod ) ? c->dGrid : nullptr;
-    a.atlas = usePacked ? pool->dPacked : pool->dAtlas;
-    a.packed = usePacked;
+    a.gridTable = gridWalk ? c->dGrid : nullptr;
+    a.atlas = p.form.usePacked ? pool->dPacked : pool->dAtlas;
+    a.packed = p.form.usePacked;
     /* a packed atlas of more than 4 GiB, or of a pool of more than 2^32 voxels: 64-bit lane pointers (the BIG instances of
      * the packed modes) */
-    a.packedWide = usePacked && ( pool->bigAtlas || pool_packed_bytes( pool ) > 0xFFFFFFFFull );
+    a.packedWide = p.form.usePacked && ( pool->bigAtlas || pool_packed_bytes( pool ) > 0xFFFFFFFFull );
     a.lut = c->dLut;
     a.pixelBuffer = ctx_fb( c );
-    a.sampleCounter = c->optCount ? c->dCounter : nullptr;
+    a.sampleCounter = c->opt.count ? c->dCounter : nullptr;
     a.clamp = c->cachedClamp;
-    a.gridDda = useDda;
-    a.fixedStepping = c->optStepping != 0 && slotsFit8Bits;
-    a.linear = linear;
+    a.gridDda = p.form.useDda;
+    a.fixedStepping = c->opt.stepping != 0 && p.form.slotsFit8Bits;
+    a.linear = p.mode.linear;
     a.elemBytes = pool->elemBytes;
     a.bigAtlas = pool->bigAtlas;
+    a.classifier = vrc_make_classifier( p.lp );
+    /* grey transfer function, frame starting from zero: two-float table entries, the same bits (VRC_MODE_GREY) */
+    a.greyTable = c->opt.greyTable && c->tfGrey && f.clearFirst && !p.form.glSuper; /* (a sub-ray starts from the pixel so far) */
     /* depth split: only where it is exact.  (i) The far half cannot know the near half's opacity, so early ray
      * termination must be impossible: (1 - largest classified alpha)^(most samples a ray can take) stays above
      * 1 - 0.999 (a ray crosses at most sqrt(3) world units -- the volume's longest edge is 1 -- plus one
      * restart sample per brick).  (ii) The frame starts from zero (first pass: the clear is folded in).
      * (iii) the table-driven point-sampling walk kernel. */
     a.depthSplit = false;
-    if( c->optDepthSplit && !mip && !shade && !cdepth && !preint && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 && !pool->bigAtlas &&
-        !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && f.clearFirst )
+    if( c->opt.depthSplit && p.tableWalk && f.clearFirst )
     {
-        const double nMax = 1.7320508 * (double)render->samplesPerRay +
+        const double nMax = 1.7320508 * (double)p.render->samplesPerRay +
                             3.0 * ( f.gridDim[0] + f.gridDim[1] + f.gridDim[2] ) + 8.0;
         /* with a margin: the kernel accumulates the opacity in float with contracted multiply-adds and regroups the
          * far half's additions, ~1e-6 absolute after 2000 samples = 1e-3 of the 0.001 of transmittance left at
@@ -2302,226 +2049,205 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         a.depthSplit = VRC_TILE_W == 8u && c->lutMaxAlpha < 1.0f &&
                        nMax * std::log1p( -(double)c->lutMaxAlpha ) > std::log( 1.0 - 0.999 ) + 0.01;
     }
-    /* ray compaction: the table-driven point-sampling walk kernel; packed 16-bit pixel coordinates */
+    /* ray compaction: the table walk kernel; packed 16-bit pixel coordinates */
     a.ertParts = 0;
     a.rayList = nullptr;
     /* (the same predicate as the launcher's, vrc_launch_raycast: what vrc_get_ray_counts reports is what ran) */
-    if( c->optErtParts > 1 && !mip && !shade && !cdepth && !preint && !a.depthSplit && useDda && !useLds && !c->rayLod && !linear && pool->elemBytes == 1 &&
-        !pool->bigAtlas && !c->cachedClamp && c->optStepping != 0 && slotsFit8Bits && c->fbW < 65536u && c->fbH < 65536u &&
-        VRC_TILE_W == 8u )
+    if( c->opt.ertParts > 1 && p.tableWalk && !a.depthSplit && c->fbW < 65536u && c->fbH < 65536u && VRC_TILE_W == 8u )
     {
-        const size_t pixels = (size_t)c->fbW * c->fbH;
-        if( pixels > c->dRayListCap )
-        {
-            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-            if( c->dRayList ) VRC_HIP_CHECK( hipFree( c->dRayList ) );
-            c->dRayList = nullptr;
-            c->dRayListCap = 0;
-            VRC_HIP_CHECK( hipMalloc( &c->dRayList, ( VRC_MAX_ERT_PARTS + 2 * pixels ) * sizeof( uint32_t ) ) );
-            c->dRayListCap = pixels;
-        }
-        a.ertParts = (int)c->optErtParts;
+        /* counts | two ray lists (vrc_internal.h) */
+        VRC_TRY( ctx_grow( c, c->dRayListCap, p.pixels, p.pixels,
+                           { { c->dRayList, 2 * sizeof( uint32_t ), VRC_MAX_ERT_PARTS * sizeof( uint32_t ) } } ) );
+        a.ertParts = (int)c->opt.ertParts;
         a.rayList = c->dRayList;
     }
     c->lastErtParts = a.ertParts;
-    /* ray cache (VRC_OPT_RAY_CACHE): the tile-scheduled grid walk of vrc_k_raycast only (vrc_pixel_grid_dda; the
-     * supersampled GL variant, whose rays are jittered, is not a grid walk).  A frame whose ray constants differ from
-     * those of the vrc_render before computes its rays (a moving camera pays nothing); the first that repeats them
-     * also stores them, and the ones after that load them.  The kernel-visible fields are set here, after the tile
-     * schedule compared frames */
+    return VRC_OK;
+}
+
+/* ray cache (VRC_OPT_RAY_CACHE): the tile-scheduled grid walk of vrc_k_raycast only (vrc_pixel_grid_dda; the
+ * supersampled GL variant, whose rays are jittered, is not a grid walk).  A frame whose ray constants differ from
+ * those of the vrc_render before computes its rays (a moving camera pays nothing); the first that repeats them
+ * also stores them, and the ones after that load them.  The kernel-visible fields are set here, after the tile
+ * schedule compared frames */
+static int render_ray_cache( vrc_ctx* c, render_pass& p )
+{
+    vrc_frame& f = p.a.frame;
+    const size_t plane = p.plane;
     c->rayCacheUsed = 0;
+    const bool eligible = c->opt.rayCache && p.form.useDda && !p.form.useLds && !c->rayLod && !p.mode.mip && !p.form.glSuper &&
+                          !p.a.depthSplit && p.a.ertParts <= 1 && VRC_TILE_W * VRC_TILE_H == 64u &&
+                          plane * VRC_RAY_CACHE_PLANES <= 0xFFFFFFFFull; /* (32-bit word offsets in the kernel) */
+    if( !eligible )
+        c->rayCacheValid = c->rayPrevSet = false;
+    else
     {
-        const size_t tiles = (size_t)( ( c->fbW + VRC_TILE_W - 1 ) / VRC_TILE_W ) * ( ( c->fbH + VRC_TILE_H - 1 ) / VRC_TILE_H );
-        const size_t plane = tiles * 64u; /* whole tiles */
-        const bool eligible = c->optRayCache && useDda && !useLds && !c->rayLod && !mip && !glSuper && !a.depthSplit &&
-                              a.ertParts <= 1 && VRC_TILE_W * VRC_TILE_H == 64u &&
-                              plane * VRC_RAY_CACHE_PLANES <= 0xFFFFFFFFull; /* (32-bit word offsets in the kernel) */
-        if( !eligible )
-            c->rayCacheValid = c->rayPrevSet = false;
-        else
+        const bool same = c->rayPrevSet && ray_constants_equal( c->rayPrevFrame, f );
+        if( !same )
+            c->rayCacheValid = false;
+        else if( !c->rayCacheValid )
         {
-            const bool same = c->rayPrevSet && ray_constants_equal( c->rayPrevFrame, f );
-            if( !same )
-                c->rayCacheValid = false;
-            else if( !c->rayCacheValid )
-            {
-                if( plane > c->dRayCacheCap )
-                {
-                    VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-                    if( c->dRayCache ) VRC_HIP_CHECK( hipFree( c->dRayCache ) );
-                    c->dRayCache = nullptr;
-                    c->dRayCacheCap = 0;
-                    VRC_HIP_CHECK( hipMalloc( &c->dRayCache, plane * VRC_RAY_CACHE_PLANES * sizeof( float ) ) );
-                    c->dRayCacheCap = plane;
-                }
-                c->rayCacheUsed = VRC_RAY_STORE; /* (valid once the march is on the stream, below) */
-            }
-            else
-                c->rayCacheUsed = VRC_RAY_LOAD;
-            std::memcpy( &c->rayPrevFrame, &f, sizeof( f ) );
-            c->rayPrevSet = true;
+            VRC_TRY( ctx_grow( c, c->dRayCacheCap, plane, plane, { { c->dRayCache, VRC_RAY_CACHE_PLANES * sizeof( float ) } } ) );
+            c->rayCacheUsed = VRC_RAY_STORE; /* (valid once the march is on the stream: render_march) */
         }
-        f.rayMode = (uint32_t)c->rayCacheUsed;
-        f.rayCache = c->rayCacheUsed ? c->dRayCache : nullptr;
-        f.rayCachePlane = c->rayCacheUsed ? (uint32_t)plane : 0u;
+        else
+            c->rayCacheUsed = VRC_RAY_LOAD;
+        std::memcpy( &c->rayPrevFrame, &f, sizeof( f ) );
+        c->rayPrevSet = true;
     }
-    /* grey transfer function, frame starting from zero: two-float table entries, the same bits (VRC_MODE_GREY) */
-    a.greyTable = c->optGreyTable && c->tfGrey && f.clearFirst && !glSuper; /* (a sub-ray starts from the pixel so far) */
-    /* walk cache (VRC_OPT_WALK_CACHE): a frame that loads its rays, of the instances the replay march exists for
-     * (vrc_internal.h: vrc_walk_replay_eligible).  The first such frame also runs the count pass; the first one after
-     * its result has arrived (polled, never waited for) sizes the planes and runs the record pass; the ones after that
-     * replay.  Both passes go on the stream in front of the march's timing pair and are no marches: not timed, not
-     * counted as launches.  Whatever the lists depend on starts over when it changes: walk_constants_equal here,
-     * the node list above, the stream, the row map and the options where they are set; the transfer function, the
-     * uniformity words and the pixel buffer's contents are not among them.  What the lists do not depend on may still
-     * decide whether they are worth using: where every visit gathers the replay is no faster than the walk, and by 1 to
-     * 3 % slower (profiles/r10_walk_cache.txt), so with the option at 1 a view more than half of whose visits gather, by
-     * the count pass and the uniformity words it read, is not recorded and stays on the walk until the pool's uploads or
-     * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold */
-    c->walkCacheUsed = 0;
-    c->walkLeanUsed = 0;
-    c->walkUniformUsed = 0;
+    f.rayMode = (uint32_t)c->rayCacheUsed;
+    f.rayCache = c->rayCacheUsed ? c->dRayCache : nullptr;
+    f.rayCachePlane = c->rayCacheUsed ? (uint32_t)plane : 0u;
+    return VRC_OK;
+}
+
+/* walk cache (VRC_OPT_WALK_CACHE): a frame that loads its rays, of the instances the replay march exists for
+ * (vrc_internal.h: vrc_walk_replay_eligible).  The first such frame also runs the count pass; the first one after
+ * its result has arrived (polled, never waited for) sizes the planes and runs the record pass; the ones after that
+ * replay.  Both passes go on the stream in front of the march's timing pair and are no marches: not timed, not
+ * counted as launches.  Whatever the lists depend on starts over when it changes: walk_constants_equal here,
+ * the node list in render_nodes, the stream, the row map and the options where they are set; the transfer function, the
+ * uniformity words and the pixel buffer's contents are not among them.  What the lists do not depend on may still
+ * decide whether they are worth using: where every visit gathers the replay is no faster than the walk, and by 1 to
+ * 3 % slower (profiles/r10_walk_cache.txt), so with the option at 1 a view more than half of whose visits gather, by
+ * the count pass and the uniformity words it read, is not recorded and stays on the walk until the pool's uploads or
+ * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold.
+ * Decides: walkCount / walkRecord (the passes render_march launches), walk.used (VRC_OPT_WALK_CACHE_USED: 0 walk,
+ * 1 count, 2 waiting for the count, 3 record, 4 replay), walk.leanUsed, walk.uniformUsed, and the frame's walk fields */
+static int render_walk_cache( vrc_ctx* c, render_pass& p )
+{
+    vrc_walk_cache& w = c->walk;
+    vrc_frame& f = p.a.frame;
+    const size_t plane = p.plane;
+    w.used = 0;
+    w.leanUsed = 0;
+    w.uniformUsed = 0;
     f.walkCache = nullptr;
     f.walkPlane = f.walkK = 0u;
     f.walkLean = f.walkSlots = 0u;
-    bool walkCount = false, walkRecord = false;
+    p.walkCount = p.walkRecord = false;
+    /* the form of the lists.  A lean list (vrc_core.h: vrc_frame::walkLean) holds every visit's step count and slot
+     * index in one word of 12 + 20 bits.  What the host can see of that: the step is one vrc_exact_step_count counts
+     * (its own test, asked here with a travel that passes it), and the pool's slot indices fit.  The rest -- no
+     * visit whose count is inexact or takes more than 12 bits -- the count pass reports with the count */
+    uint32_t one = 0u;
+    const size_t nSlots = p.pool->resident.size();
+    const bool leanAsked = vrc_exact_step_count( f.stepSize, f.stepSize, &one ) && nSlots >= 1u &&
+                           nSlots < ( (size_t)1u << VRC_WALK_LEAN_INDEX_BITS );
+    const auto fits = [&]( uint32_t k ) { /* the planes of k visits: 32-bit word offsets in the kernels, and the budget */
+        const unsigned long long words = ( 1ull + 4ull * k ) * plane;
+        return words <= 0xFFFFFFFFull && words * sizeof( uint32_t ) <= (unsigned long long)c->opt.walkBudget;
+    };
+    const bool eligible = c->opt.walkCache && c->rayCacheUsed == VRC_RAY_LOAD && vrc_walk_replay_eligible( p.a ) &&
+                          f.nodeCount > 0u && plane > 0u && fits( 1u );
+    const bool byContent = c->opt.walkCache != VRC_WALK_CACHE_ALWAYS;
+    const uint64_t gen = p.pool->uploadGen; /* (compared only where the choice goes by the bricks' content) */
+    if( !eligible || ( w.state != vrc_walk_cache::IDLE &&
+                       ( !walk_constants_equal( w.frame, f ) || leanAsked != w.leanAsked ||
+                         ( byContent && ( w.gen != gen || w.slotInfo != f.slotInfo ) ) ) ) )
+        w.state = vrc_walk_cache::IDLE;
+    const bool repeats = p.sameNodes && w.prevSet && ( !byContent || w.prevGen == gen ) && walk_constants_equal( w.prevFrame, f );
+    std::memcpy( &w.prevFrame, &f, sizeof( f ) );
+    w.prevSet = true;
+    w.prevGen = gen;
+    if( eligible && w.state == vrc_walk_cache::IDLE && repeats )
     {
-        /* the form of the lists.  A lean list (vrc_core.h: vrc_frame::walkLean) holds every visit's step count and slot
-         * index in one word of 12 + 20 bits.  What the host can see of that: the step is one vrc_exact_step_count counts
-         * (its own test, asked here with a travel that passes it), and the pool's slot indices fit.  The rest -- no
-         * visit whose count is inexact or takes more than 12 bits -- the count pass reports with the count */
-        uint32_t one = 0u;
-        const size_t nSlots = pool->resident.size();
-        const bool leanAsked = vrc_exact_step_count( f.stepSize, f.stepSize, &one ) && nSlots >= 1u &&
-                               nSlots < ( (size_t)1u << VRC_WALK_LEAN_INDEX_BITS );
-        const size_t tiles = (size_t)( ( c->fbW + VRC_TILE_W - 1 ) / VRC_TILE_W ) * ( ( c->fbH + VRC_TILE_H - 1 ) / VRC_TILE_H );
-        const size_t plane = tiles * 64u;
-        const auto fits = [&]( uint32_t k ) { /* the planes of k visits: 32-bit word offsets in the kernels, and the budget */
-            const unsigned long long words = ( 1ull + 4ull * k ) * plane;
-            return words <= 0xFFFFFFFFull && words * sizeof( uint32_t ) <= (unsigned long long)c->optWalkBudget;
-        };
-        const bool eligible = c->optWalkCache && c->rayCacheUsed == VRC_RAY_LOAD && vrc_walk_replay_eligible( a ) &&
-                              f.nodeCount > 0u && plane > 0u && fits( 1u );
-        const bool byContent = c->optWalkCache != VRC_WALK_CACHE_ALWAYS;
-        const uint64_t gen = pool->uploadGen; /* (compared only where the choice goes by the bricks' content) */
-        if( !eligible || ( c->walkState != vrc_ctx::WALK_IDLE &&
-                           ( !walk_constants_equal( c->walkFrame, f ) ||
-                             leanAsked != c->walkLeanAsked ||
-                             ( byContent && ( c->walkGen != gen || c->walkSlotInfo != f.slotInfo ) ) ) ) )
-            c->walkState = vrc_ctx::WALK_IDLE;
-        const bool repeats = sameNodes && c->walkPrevSet && ( !byContent || c->walkPrevGen == gen ) &&
-                             walk_constants_equal( c->walkPrevFrame, f );
-        std::memcpy( &c->walkPrevFrame, &f, sizeof( f ) );
-        c->walkPrevSet = true;
-        c->walkPrevGen = gen;
-        if( eligible )
+        if( !w.dMax )
         {
-            if( c->walkState == vrc_ctx::WALK_IDLE && !repeats )
-                ; /* mode 0: the next call counts if it is this one again */
-            else if( c->walkState == vrc_ctx::WALK_IDLE )
-            {
-                if( !c->dWalkMax )
-                {
-                    VRC_HIP_CHECK( hipMalloc( &c->dWalkMax, sizeof( vrc_walk_count ) ) );
-                    VRC_HIP_CHECK( hipHostMalloc( &c->hWalkMax, sizeof( vrc_walk_count ) ) );
-                    VRC_HIP_CHECK( hipEventCreateWithFlags( &c->evWalk, hipEventDisableTiming ) );
-                }
-                walkCount = true;
-                c->walkLeanAsked = leanAsked;
-                c->walkGen = gen;
-                c->walkSlotInfo = f.slotInfo;
-                c->walkCacheUsed = 1;
-            }
-            else if( c->walkState == vrc_ctx::WALK_COUNTING )
-            {
-                c->walkCacheUsed = 2;
-                const hipError_t q = hipEventQuery( c->evWalk );
-                if( q == hipErrorNotReady )
-                    (void)hipGetLastError(); /* (not an error: nothing later may find it there) */
-                else if( q != hipSuccess )
-                    VRC_HIP_CHECK( q );
-                if( q == hipSuccess )
-                {
-                    const uint32_t k = c->hWalkMax->longest > 0u ? c->hWalkMax->longest : 1u;
-                    if( !fits( k ) )
-                        c->walkCacheUsed = 0; /* over the budget or the offset limit: this view stays on the walk */
-                    else if( byContent && 2u * c->hWalkMax->gathers > c->hWalkMax->visits )
-                        c->walkCacheUsed = 0; /* most visits gather: so does this one */
-                    else
-                    {
-                        const size_t words = ( 1u + 4u * (size_t)k ) * plane;
-                        if( words > c->dWalkWords )
-                        {
-                            VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-                            if( c->dWalk ) VRC_HIP_CHECK( hipFree( c->dWalk ) );
-                            c->dWalk = nullptr;
-                            c->dWalkWords = 0;
-                            VRC_HIP_CHECK( hipMalloc( &c->dWalk, words * sizeof( uint32_t ) ) );
-                            c->dWalkWords = words;
-                        }
-                        c->walkK = k;
-                        c->walkLean = c->walkLeanAsked && c->hWalkMax->notLean == 0u;
-                        c->walkGathers = c->hWalkMax->gathers;
-                        walkRecord = true;
-                        c->walkCacheUsed = 3;
-                    }
-                }
-            }
+            VRC_HIP_CHECK( hipMalloc( &w.dMax, sizeof( vrc_walk_count ) ) );
+            VRC_HIP_CHECK( hipHostMalloc( &w.hMax, sizeof( vrc_walk_count ) ) );
+            VRC_HIP_CHECK( hipEventCreateWithFlags( &w.ev, hipEventDisableTiming ) );
+        }
+        p.walkCount = true;
+        w.leanAsked = leanAsked;
+        w.gen = gen;
+        w.slotInfo = f.slotInfo;
+        w.used = 1;
+    }
+    else if( eligible && w.state == vrc_walk_cache::COUNTING )
+    {
+        w.used = 2;
+        const hipError_t q = hipEventQuery( w.ev );
+        if( q == hipErrorNotReady )
+            (void)hipGetLastError(); /* (not an error: nothing later may find it there) */
+        else if( q != hipSuccess )
+            VRC_HIP_CHECK( q );
+        if( q == hipSuccess )
+        {
+            const uint32_t k = w.hMax->longest > 0u ? w.hMax->longest : 1u;
+            if( !fits( k ) )
+                w.used = 0; /* over the budget or the offset limit: this view stays on the walk */
+            else if( byContent && 2u * w.hMax->gathers > w.hMax->visits )
+                w.used = 0; /* most visits gather: so does this one */
             else
-                c->walkCacheUsed = 4;
-        }
-        if( walkRecord || c->walkCacheUsed == 4 )
-        {
-            f.walkCache = c->dWalk;
-            f.walkPlane = (uint32_t)plane;
-            f.walkK = c->walkK;
-            f.walkLean = c->walkLean ? 1u : 0u;
-            f.walkSlots = (uint32_t)nSlots;
-            c->walkLeanUsed = ( c->walkLean && c->walkCacheUsed == 4 ) ? 1 : 0;
-            /* the uniform-only instance (vrc_kernels_walk.hip): a replayed lean frame none of whose visits gathers --
-             * by the count pass of these lists, which is still the answer while the pool has taken no upload and the
-             * words are the ones it read.  Where the lists outlive that (VRC_WALK_CACHE_ALWAYS) the frame goes back to
-             * the lean instance and keeps them */
-            if( c->walkLeanUsed && c->optWalkUniformOnly && c->walkGathers == 0ull && c->walkGen == gen &&
-                c->walkSlotInfo == f.slotInfo )
             {
-                f.walkLean = VRC_WALK_LEAN_UNIFORM;
-                c->walkUniformUsed = 1;
+                const size_t words = ( 1u + 4u * (size_t)k ) * plane;
+                VRC_TRY( ctx_grow( c, w.words, words, words, { w.dLists } ) );
+                w.k = k;
+                w.lean = w.leanAsked && w.hMax->notLean == 0u;
+                w.gathers = w.hMax->gathers;
+                p.walkRecord = true;
+                w.used = 3;
             }
         }
-        else if( walkCount )
-            f.walkLean = leanAsked ? 1u : 0u; /* (the count pass: check every visit) */
     }
-    a.classifier = vrc_make_classifier( lp );
+    else if( eligible && w.state == vrc_walk_cache::VALID )
+        w.used = 4;
+    /* (eligible, IDLE and not a repeat: mode 0 -- the next call counts if it is this one again) */
+    if( p.walkRecord || w.used == 4 )
+    {
+        f.walkCache = w.dLists;
+        f.walkPlane = (uint32_t)plane;
+        f.walkK = w.k;
+        f.walkLean = w.lean ? 1u : 0u;
+        f.walkSlots = (uint32_t)nSlots;
+        w.leanUsed = ( w.lean && w.used == 4 ) ? 1 : 0;
+        /* the uniform-only instance (vrc_kernels_walk.hip): a replayed lean frame none of whose visits gathers --
+         * by the count pass of these lists, which is still the answer while the pool has taken no upload and the
+         * words are the ones it read.  Where the lists outlive that (VRC_WALK_CACHE_ALWAYS) the frame goes back to
+         * the lean instance and keeps them */
+        if( w.leanUsed && c->opt.walkUniformOnly && w.gathers == 0ull && w.gen == gen && w.slotInfo == f.slotInfo )
+        {
+            f.walkLean = VRC_WALK_LEAN_UNIFORM;
+            w.uniformUsed = 1;
+        }
+    }
+    else if( p.walkCount )
+        f.walkLean = leanAsked ? 1u : 0u; /* (the count pass: check every visit) */
+    return VRC_OK;
+}
 
+/* the march: behind the pool's uploads, the walk cache's passes in front of it, the timing pair around it, the pool's
+ * fence and the counter's read-back behind it */
+static int render_march( vrc_ctx* c, render_pass& p )
+{
+    vrc_raycast_args& a = p.a;
+    vrc_frame& f = a.frame;
+    const vrc_mode& m = p.mode;
     /* order the march after every brick upload issued so far (fixes quirk Q9) */
+    VRC_TRY( ctx_wait_uploads( c, p.pool ) );
+    if( p.walkCount )
     {
-        const int rc = ctx_wait_uploads( c, pool );
-        if( rc != VRC_OK )
-            return rc;
-    }
-    if( walkCount )
-    {
-        VRC_HIP_CHECK( hipMemsetAsync( c->dWalkMax, 0, sizeof( vrc_walk_count ), c->stream ) );
-        VRC_HIP_CHECK( vrc_launch_walk_record( a, c->dWalkMax, c->stream ) );
-        VRC_HIP_CHECK( hipMemcpyAsync( c->hWalkMax, c->dWalkMax, sizeof( vrc_walk_count ), hipMemcpyDeviceToHost, c->stream ) );
-        VRC_HIP_CHECK( hipEventRecord( c->evWalk, c->stream ) );
-        std::memcpy( &c->walkFrame, &f, sizeof( f ) );
-        c->walkState = vrc_ctx::WALK_COUNTING;
+        VRC_HIP_CHECK( hipMemsetAsync( c->walk.dMax, 0, sizeof( vrc_walk_count ), c->stream ) );
+        VRC_HIP_CHECK( vrc_launch_walk_record( a, c->walk.dMax, c->stream ) );
+        VRC_HIP_CHECK( hipMemcpyAsync( c->walk.hMax, c->walk.dMax, sizeof( vrc_walk_count ), hipMemcpyDeviceToHost, c->stream ) );
+        VRC_HIP_CHECK( hipEventRecord( c->walk.ev, c->stream ) );
+        std::memcpy( &c->walk.frame, &f, sizeof( f ) );
+        c->walk.state = vrc_walk_cache::COUNTING;
         f.walkLean = 0u; /* (asked of the count pass alone) */
     }
-    if( walkRecord )
+    if( p.walkRecord )
     {
         VRC_HIP_CHECK( vrc_launch_walk_record( a, nullptr, c->stream ) );
-        c->walkState = vrc_ctx::WALK_VALID;
+        c->walk.state = vrc_walk_cache::VALID;
         /* this frame still walks: the march below reads none of the planes */
         f.walkCache = nullptr;
         f.walkPlane = f.walkK = 0u;
         f.walkLean = f.walkSlots = 0u;
     }
-    if( c->optCount )
+    if( c->opt.count )
         VRC_HIP_CHECK( hipMemsetAsync( c->dCounter, 0, sizeof( unsigned long long ), c->stream ) );
-    if( c->optTiming && c->evUsed == c->evRing->pairs.size() )
+    if( c->opt.timing && c->evUsed == c->evRing->pairs.size() )
     {
         if( c->evRing->pairs.size() >= 4096 )
         {
@@ -2546,7 +2272,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
         }
     }
     const std::pair< hipEvent_t, hipEvent_t > evp =
-        c->optTiming ? c->evRing->pairs[c->evUsed++] : std::pair< hipEvent_t, hipEvent_t >( nullptr, nullptr );
+        c->opt.timing ? c->evRing->pairs[c->evUsed++] : std::pair< hipEvent_t, hipEvent_t >( nullptr, nullptr );
     vrc_internal_note_kernel_fn( nullptr, 0, 0 ); /* set again by the launchers that report their occupancy */
     /* VRC_OPT_STREAM_MARKERS = 0: the dispatch of a timed march that is one launch carries the pair's second event as its
      * stop event, and that event is also what an upload that recycles a slot waits for.  The pair's first event is
@@ -2555,45 +2281,75 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
      * launcher says whether it attached the event; the marches of several launches (depth split, ray compaction) do
      * not, and theirs is recorded behind the sequence.  VRC_OPT_STREAM_MARKERS = 1, and a march that is not timed,
      * record the pool's own fence behind the march */
-    const bool pairFences = c->optTiming && !c->optStreamMarkers;
+    const bool pairFences = c->opt.timing && !c->opt.streamMarkers;
     bool attached = false;
     a.stopEvent = pairFences ? evp.second : nullptr;
     a.attached = &attached;
-    if( c->optTiming )
+    if( c->opt.timing )
         VRC_HIP_CHECK( hipEventRecord( evp.first, c->stream ) );
-    VRC_HIP_CHECK( iso         ? vrc_launch_raycast_iso( a, c->stream )
-                   : mipDepth  ? vrc_launch_raycast_mip_depth( a, (int)c->optMipFold, c->stream )
-                   : mip       ? ( c->optMipFold == VRC_MIP_FOLD_MIN    ? vrc_launch_raycast_minip( a, c->stream )
-                                   : c->optMipFold == VRC_MIP_FOLD_MEAN ? vrc_launch_raycast_meanip( a, c->stream )
-                                                                        : vrc_launch_raycast_mip( a, c->stream ) )
-                   : cdepth    ? vrc_launch_raycast_cdepth( a, c->stream )
-                   : preint    ? vrc_launch_raycast_preint( a, c->stream )
-                   : shade     ? vrc_launch_raycast_shade( a, c->stream )
-                   : useLds    ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
-                   : c->rayLod ? vrc_launch_raycast_raylod( a, c->stream )
-                   : c->walkCacheUsed == 4 ? vrc_launch_raycast_replay( a, c->stream )
-                               : vrc_launch_raycast( a, c->stream ) );
+    VRC_HIP_CHECK( m.iso        ? vrc_launch_raycast_iso( a, c->stream )
+                   : m.mipDepth ? vrc_launch_raycast_mip_depth( a, (int)c->opt.mipFold, c->stream )
+                   : m.mip      ? ( c->opt.mipFold == VRC_MIP_FOLD_MIN    ? vrc_launch_raycast_minip( a, c->stream )
+                                    : c->opt.mipFold == VRC_MIP_FOLD_MEAN ? vrc_launch_raycast_meanip( a, c->stream )
+                                                                          : vrc_launch_raycast_mip( a, c->stream ) )
+                   : m.cdepth   ? vrc_launch_raycast_cdepth( a, c->stream )
+                   : m.preint   ? vrc_launch_raycast_preint( a, c->stream )
+                   : m.shade    ? vrc_launch_raycast_shade( a, c->stream )
+                   : p.form.useLds ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
+                   : c->rayLod  ? vrc_launch_raycast_raylod( a, c->stream )
+                   : c->walk.used == 4 ? vrc_launch_raycast_replay( a, c->stream )
+                                : vrc_launch_raycast( a, c->stream ) );
     if( c->rayCacheUsed == VRC_RAY_STORE )
         c->rayCacheValid = true;
-    if( c->optTiming && !attached ) /* (also a frame without tiles, which launches nothing) */
+    if( c->opt.timing && !attached ) /* (also a frame without tiles, which launches nothing) */
         VRC_HIP_CHECK( hipEventRecord( evp.second, c->stream ) );
-    {
-        const int rc = pool_fence_behind( pool, c, pairFences ? evp.second : nullptr );
-        if( rc != VRC_OK )
-            return rc;
-    }
-    if( c->optCount )
+    VRC_TRY( pool_fence_behind( p.pool, c, pairFences ? evp.second : nullptr ) );
+    if( c->opt.count )
         VRC_HIP_CHECK( hipMemcpyAsync( c->hCounter, c->dCounter, sizeof( unsigned long long ),
                                        hipMemcpyDeviceToHost, c->stream ) );
+    return VRC_OK;
+}
+
+static void render_stats( vrc_ctx* c, const render_pass& p )
+{
+    const bool gridWalk = p.form.useDda || c->rayLod;
     c->timed = true; /* a render has happened: vrc_get_stats has something to report */
-    c->stats.kernel_variant =
-        c->rayLod ? VRC_KERNEL_RAY_LOD
-        : useLds  ? VRC_KERNEL_LDS
-        : usePacked ? VRC_KERNEL_PACKED
-                  : ( useDda ? VRC_KERNEL_GRID_DDA : VRC_KERNEL_REFERENCE_ORDER );
+    c->stats.kernel_variant = c->rayLod          ? VRC_KERNEL_RAY_LOD
+                              : p.form.useLds    ? VRC_KERNEL_LDS
+                              : p.form.usePacked ? VRC_KERNEL_PACKED
+                              : p.form.useDda    ? VRC_KERNEL_GRID_DDA
+                                                 : VRC_KERNEL_REFERENCE_ORDER;
     for( int i = 0; i < 3; ++i )
-        c->stats.grid_dims[i] = ( useDda || c->rayLod ) ? (uint32_t)f.gridDim[i] : 0u;
-    c->gridWalkUsed = ( useDda || c->rayLod ) ? 1 : 0;
+        c->stats.grid_dims[i] = gridWalk ? (uint32_t)p.a.frame.gridDim[i] : 0u;
+    c->gridWalkUsed = gridWalk ? 1 : 0;
+}
+
+int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* nodes, uint32_t nNodes,
+                const vrc_render_data* render, vrc_pool* pool )
+{
+    VRC_TRY( render_check_args( c, view, nodes, nNodes, render, pool ) );
+    if( nNodes == 0 ) /* CudaRaycastRenderer.cpp:157-158 */
+        return VRC_OK;
+    VRC_HIP_CHECK( hipSetDevice( c->device ) );
+    render_pass p;
+    p.view = view;
+    p.nodes = nodes;
+    p.nNodes = nNodes;
+    p.render = render;
+    p.pool = pool;
+    VRC_TRY( render_mode( c, p ) );
+    VRC_TRY( render_tables( c, p ) );
+    VRC_TRY( render_nodes( c, p ) );
+    VRC_TRY( render_form( c, p ) );
+    render_frame( c, p );
+    VRC_TRY( render_tile_schedule( c, p ) );
+    render_clear_and_slot_words( c, p );
+    VRC_TRY( render_projection( c, p ) );
+    VRC_TRY( render_split_and_compact( c, p ) );
+    VRC_TRY( render_ray_cache( c, p ) );
+    VRC_TRY( render_walk_cache( c, p ) );
+    VRC_TRY( render_march( c, p ) );
+    render_stats( c, p );
     return VRC_OK;
 }
 
@@ -2602,11 +2358,7 @@ int vrc_post_render( vrc_ctx* c, float* hostRgba )
     if( !c )
         return fail( VRC_EINVAL, "vrc_post_render: ctx is NULL" );
     VRC_HIP_CHECK( hipSetDevice( c->device ) );
-    {
-        const int rc = resolve_clear( c ); /* a frame without a march still ends cleared */
-        if( rc != VRC_OK )
-            return rc;
-    }
+    VRC_TRY( resolve_clear( c ) ); /* a frame without a march still ends cleared */
     if( hostRgba )
     {
         if( !ctx_fb( c ) || c->fbW == 0 )
@@ -2631,15 +2383,7 @@ int vrc_get_projection_values( vrc_ctx* c, float* hostValues, uint32_t* hostCoun
                                  "vrc_pre_render; the values exist from a frame's first MIP pass until the next frame" );
     VRC_HIP_CHECK( hipSetDevice( c->device ) );
     const size_t pixels = c->projState.pixels;
-    if( pixels > c->dProjOutPixels )
-    {
-        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-        if( c->dProjOut ) VRC_HIP_CHECK( hipFree( c->dProjOut ) );
-        c->dProjOut = nullptr;
-        c->dProjOutPixels = 0;
-        VRC_HIP_CHECK( hipMalloc( &c->dProjOut, pixels * ( sizeof( float ) + sizeof( uint32_t ) ) ) );
-        c->dProjOutPixels = pixels;
-    }
+    VRC_TRY( ctx_grow( c, c->dProjOutPixels, pixels, pixels, { { c->dProjOut, sizeof( float ) + sizeof( uint32_t ) } } ) );
     uint32_t* const dCounts = reinterpret_cast< uint32_t* >( c->dProjOut + pixels );
     VRC_HIP_CHECK( vrc_launch_projection_values( c->projState, c->dProjOut, dCounts, c->stream ) );
     VRC_HIP_CHECK( hipMemcpyAsync( hostValues, c->dProjOut, pixels * sizeof( float ), hipMemcpyDeviceToHost, c->stream ) );
@@ -2668,15 +2412,7 @@ int vrc_get_projection_depths( vrc_ctx* c, float* hostT, float* hostXyz )
     if( pixels != (size_t)f.width * f.height || ( !c->depthRows.empty() && c->depthRows.size() != f.height ) )
         return fail( VRC_EINVAL, "vrc_get_projection_depths: the frame's geometry does not match its state" );
     const size_t words = pixels * 4u + f.height;
-    if( words > c->dDepthOutWords )
-    {
-        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-        if( c->dDepthOut ) VRC_HIP_CHECK( hipFree( c->dDepthOut ) );
-        c->dDepthOut = nullptr;
-        c->dDepthOutWords = 0;
-        VRC_HIP_CHECK( hipMalloc( &c->dDepthOut, words * sizeof( float ) ) );
-        c->dDepthOutWords = words;
-    }
+    VRC_TRY( ctx_grow( c, c->dDepthOutWords, words, words, { c->dDepthOut } ) );
     float* const dXyz = c->dDepthOut + pixels;
     uint32_t* const dRows = reinterpret_cast< uint32_t* >( c->dDepthOut + pixels * 4u );
     f.rowMap = nullptr;
@@ -2745,11 +2481,7 @@ int vrc_synchronize( vrc_ctx* c )
     if( !c )
         return fail( VRC_EINVAL, "vrc_synchronize: ctx is NULL" );
     VRC_HIP_CHECK( hipSetDevice( c->device ) );
-    {
-        const int rc = resolve_clear( c );
-        if( rc != VRC_OK )
-            return rc;
-    }
+    VRC_TRY( resolve_clear( c ) );
     VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
     return VRC_OK;
 }
@@ -2795,12 +2527,12 @@ int vrc_get_stats( vrc_ctx* c, vrc_stats* out )
         c->evFoldedMs = 0.0;
         c->evFoldedLaunches = 0;
     }
-    else if( !c->optTiming )
+    else if( !c->opt.timing )
         c->stats.kernel_ms = 0.f;
     if( c->timed )
     {
         /* the sample counter of the last vrc_render (VRC_OPT_COUNT_SAMPLES) */
-        if( c->optCount )
+        if( c->opt.count )
         {
             VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
             c->stats.samples = *c->hCounter;
@@ -2848,40 +2580,15 @@ int vrc_frame_histogram( vrc_ctx* c, vrc_pool* pool, const float* slots, const u
     }
     if( accumulate && c->frameHistBins != bins )
         return fail( VRC_EINVAL, "vrc_frame_histogram: the bin count changed inside a frame" );
-    if( c->frameHistCap < bins )
-    {
-        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-        if( c->dFrameHist ) VRC_HIP_CHECK( hipFree( c->dFrameHist ) );
-        if( c->hFrameHist ) VRC_HIP_CHECK( hipHostFree( c->hFrameHist ) );
-        c->dFrameHist = nullptr;
-        c->hFrameHist = nullptr;
-        c->frameHistCap = 0;
-        VRC_HIP_CHECK( hipMalloc( &c->dFrameHist, bins * sizeof( unsigned long long ) ) );
-        VRC_HIP_CHECK( hipHostMalloc( &c->hFrameHist, bins * sizeof( unsigned long long ) ) );
-        c->frameHistCap = bins;
-    }
-    if( n > c->histRefsCap )
-    {
-        /* grow the pinned ring and the device list: wait for every copy that reads the old ones */
-        VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
-        if( c->hHistRefs ) VRC_HIP_CHECK( hipHostFree( c->hHistRefs ) );
-        if( c->dHistRefs ) VRC_HIP_CHECK( hipFree( c->dHistRefs ) );
-        c->hHistRefs = nullptr;
-        c->dHistRefs = nullptr;
-        c->histRefsCap = 0;
-        const size_t cap = std::max< size_t >( 1024, n );
-        VRC_HIP_CHECK( hipHostMalloc( &c->hHistRefs, kNodeStages * cap * sizeof( vrc_hist_ref ) ) );
-        VRC_HIP_CHECK( hipMalloc( &c->dHistRefs, cap * sizeof( vrc_hist_ref ) ) );
-        c->histRefsCap = cap;
-        for( int s = 0; s < kNodeStages; ++s )
-            c->histRefsUsed[s] = false;
-    }
+    VRC_TRY( ctx_grow( c, c->frameHistCap, bins, bins, { c->dFrameHist, { c->hFrameHist, sizeof( unsigned long long ), 0, vrc_grown::PINNED } } ) );
+    /* the pinned ring and the device list: grown behind every copy that reads the old ones */
+    bool grew = false;
+    VRC_TRY( ctx_grow( c, c->histRefsCap, n, std::max< size_t >( 1024, n ),
+                       { { c->hHistRefs, kNodeStages * sizeof( vrc_hist_ref ), 0, vrc_grown::PINNED }, c->dHistRefs }, &grew ) );
+    for( int s = 0; grew && s < kNodeStages; ++s )
+        c->histRefsUsed[s] = false;
     /* the rows are written on the pool's upload stream */
-    {
-        const int rc = ctx_wait_uploads( c, pool );
-        if( rc != VRC_OK )
-            return rc;
-    }
+    VRC_TRY( ctx_wait_uploads( c, pool ) );
     if( n )
     {
         const uint32_t s = c->histRefsNext++ % kNodeStages;
@@ -2897,14 +2604,9 @@ int vrc_frame_histogram( vrc_ctx* c, vrc_pool* pool, const float* slots, const u
     }
     VRC_HIP_CHECK( vrc_launch_frame_histogram( dRows, bins, c->dHistRefs, n, c->dFrameHist, accumulate != 0, c->stream ) );
     c->frameHistBins = bins;
-    {
-        /* the context's render fence on the pool (pool_upload) now stands behind this reduction too: an upload that
-         * recycles one of these slots does not overwrite its row while the reduction reads it */
-        const int rc = pool_fence_behind( pool, c, nullptr );
-        if( rc != VRC_OK )
-            return rc;
-    }
-    return VRC_OK;
+    /* the context's render fence on the pool (pool_upload) now stands behind this reduction too: an upload that
+     * recycles one of these slots does not overwrite its row while the reduction reads it */
+    return pool_fence_behind( pool, c, nullptr );
 }
 
 int vrc_get_frame_histogram( vrc_ctx* c, uint64_t* hostBins, uint32_t binCount )
