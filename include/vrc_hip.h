@@ -288,6 +288,15 @@ typedef struct
                                     * other value: VRC_EINVAL */
 #define VRC_OPT_WALK_UNIFORM_ONLY_USED 35 /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render
                                     * replayed its lists with that instance, 0 if it did anything else */
+#define VRC_OPT_STORE_THROUGH 36    /* 1 (default) | 0.  A replayed frame (VRC_OPT_WALK_CACHE_USED = 4) of less than 4 GiB
+                                    * writes its pixels with 16-byte write-through stores: the frame streams out of
+                                    * the L2 while the march runs, and the kernel ends without a frame of dirty lines
+                                    * to write back.  The same frame and sample count, bit for bit; whoever reads the
+                                    * pixel buffer behind the frame on the stream sees the same bytes.  Every other
+                                    * frame, and every frame at 0, stores as before; changing the option starts
+                                    * nothing over.  Any other value: VRC_EINVAL */
+#define VRC_OPT_STORE_THROUGH_USED 37 /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render stored
+                                    * its pixels that way, 0 if it did anything else */
 /* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
  * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
  * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots

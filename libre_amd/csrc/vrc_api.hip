@@ -173,6 +173,7 @@ struct vrc_walk_cache
      * VRC_OPT_WALK_UNIFORM_ONLY_USED */
     unsigned long long gathers = 0;
     int64_t uniformUsed = 0;
+    int64_t throughUsed = 0; /* VRC_OPT_STORE_THROUGH_USED */
 };
 
 struct vrc_ctx
@@ -562,6 +563,13 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
         return VRC_OK;
     case VRC_OPT_WALK_UNIFORM_ONLY_USED:
         return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_UNIFORM_ONLY_USED is read-only" );
+    case VRC_OPT_STORE_THROUGH:
+        if( value != 0 && value != 1 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_STORE_THROUGH is 0 (plain stores) or 1 (write-through)" );
+        c->opt.storeThrough = value; /* (how the replay stores its pixels: nothing starts over) */
+        return VRC_OK;
+    case VRC_OPT_STORE_THROUGH_USED:
+        return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_STORE_THROUGH_USED is read-only" );
     case VRC_OPT_PROJECTION:
         if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP && value != VRC_PROJECTION_ISO )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite), 1 (maximum intensity) or 2 (isosurface)" );
@@ -652,6 +660,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_WALK_LEAN_USED: *value = c->walk.leanUsed; return VRC_OK;
     case VRC_OPT_WALK_UNIFORM_ONLY: *value = c->opt.walkUniformOnly; return VRC_OK;
     case VRC_OPT_WALK_UNIFORM_ONLY_USED: *value = c->walk.uniformUsed; return VRC_OK;
+    case VRC_OPT_STORE_THROUGH: *value = c->opt.storeThrough; return VRC_OK;
+    case VRC_OPT_STORE_THROUGH_USED: *value = c->walk.throughUsed; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->opt.projection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->opt.mipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->opt.mipFold; return VRC_OK;
@@ -2113,7 +2123,8 @@ static int render_ray_cache( vrc_ctx* c, render_pass& p )
  * the count pass and the uniformity words it read, is not recorded and stays on the walk until the pool's uploads or
  * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold.
  * Decides: walkCount / walkRecord (the passes render_march launches), walk.used (VRC_OPT_WALK_CACHE_USED: 0 walk,
- * 1 count, 2 waiting for the count, 3 record, 4 replay), walk.leanUsed, walk.uniformUsed, and the frame's walk fields */
+ * 1 count, 2 waiting for the count, 3 record, 4 replay), walk.leanUsed, walk.uniformUsed, walk.throughUsed, and the
+ * frame's walk fields and storeThrough */
 static int render_walk_cache( vrc_ctx* c, render_pass& p )
 {
     vrc_walk_cache& w = c->walk;
@@ -2122,6 +2133,7 @@ static int render_walk_cache( vrc_ctx* c, render_pass& p )
     w.used = 0;
     w.leanUsed = 0;
     w.uniformUsed = 0;
+    w.throughUsed = 0;
     f.walkCache = nullptr;
     f.walkPlane = f.walkK = 0u;
     f.walkLean = f.walkSlots = 0u;
@@ -2214,6 +2226,10 @@ static int render_walk_cache( vrc_ctx* c, render_pass& p )
     }
     else if( p.walkCount )
         f.walkLean = leanAsked ? 1u : 0u; /* (the count pass: check every visit) */
+    /* how the replay stores its pixels (vrc_core.h: vrc_store_pixel): set behind prevFrame's copy, and not among what
+     * walk_constants_equal compares -- the lists do not depend on it */
+    w.throughUsed = vrc_plan_store_through( c->opt, w.used, f.width, f.height ) ? 1 : 0;
+    f.storeThrough = (uint32_t)w.throughUsed;
     return VRC_OK;
 }
 

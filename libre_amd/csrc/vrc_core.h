@@ -264,6 +264,11 @@ struct vrc_frame
      * above moves): the 256 x 256 table of the frame, value-indexed (point samples of 8-bit voxels) or texel-indexed
      * (vrc_preint_entry).  No other kernel reads it */
     const vrc_f4* preintTable;
+    /* how a replayed frame's pixels leave the march (VRC_OPT_STORE_THROUGH, vrc_store_pixel; at the end: no field above
+     * moves).  1: every pixel store of the replay is a 16-byte write-through store through a buffer resource of
+     * width * height * 16 bytes, which the host has checked fits 32 bits (vrc_plan_store_through); 0: the plain store.
+     * The same bytes either way.  Set behind everything that compares frames; no other kernel reads it */
+    uint32_t storeThrough;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -5002,6 +5007,42 @@ struct vrc_segment_from_walk
     }
 };
 
+/* The pixel a replayed march leaves (both replay functions: the final store and the clear of a ray without visits).
+ * A frame's worth of plain stores stays in the L2s as dirty lines -- 16 bytes per pixel, about as much per XCD as half
+ * its L2 holds at 1024 x 1024 -- and the release at the end of the kernel writes them back before the next packet of
+ * the stream may start.  vrc_frame::storeThrough = 1 sends the four floats through the L2 instead: one 16-byte store
+ * marked sc1 (write-through, the line is not kept), so the frame streams out while the march runs and the kernel ends
+ * on an L2 that holds nothing of it.  The eight lanes of a tile row write one whole 128-byte line.  The store goes
+ * through a buffer resource over the pixel buffer -- base and size are kernel arguments, so the descriptor is scalar --
+ * of width * height * 16 bytes: an offset outside the frame is dropped by the range check, not written.  The choice is
+ * the frame's, the same in every lane: a scalar branch.  On the host (the CPU harnesses) it is the assignment.
+ * The pixel comes by value: taken by reference, `zero` of the callers becomes an object with an address and the
+ * replay of the other form picks its first colour through a pointer into scratch (20 bytes per lane, as compiled).
+ * The plain store's index passes through a lane move that moves nothing (quad_perm 0, 1, 2, 3: every lane reads itself),
+ * so that its 64-bit address is formed at the store.  Without it the compiler keeps the address it formed for the
+ * pixel's load (clearFirst = 0) alive across the visit loop beside the 32-bit offset the other store needs -- three
+ * registers where the loop held two, one more in every instance, and the counted grey instance of the other form in
+ * groups of 24 goes from 90 to 99 and loses its fifth wave.  With it the loop holds the pixel's number alone: every
+ * instance needs as many registers as before or up to two fewer (one needs one more, within its waves) */
+VRC_HD void vrc_store_pixel( const vrc_frame& f, vrc_f4* __restrict__ pixelBuffer, uint32_t pixelPos, const vrc_f4 c )
+{
+#if defined( __HIP_DEVICE_COMPILE__ )
+    if( f.storeThrough != 0u )
+    {
+        typedef uint32_t vrc_u4 __attribute__( ( ext_vector_type( 4 ) ) );
+        const vrc_u4 bits = { vrc_float_bits( c.x ), vrc_float_bits( c.y ), vrc_float_bits( c.z ), vrc_float_bits( c.w ) };
+        __builtin_amdgcn_raw_buffer_store_b128(
+            bits, __builtin_amdgcn_make_buffer_rsrc( pixelBuffer, 0, (int)( f.width * f.height * 16u ), 0x00020000 ),
+            (int)( pixelPos * 16u ), 0, 16 /* sc1 */ );
+        return;
+    }
+    pixelBuffer[(uint32_t)__builtin_amdgcn_update_dpp( 0, (int)pixelPos, 0xE4, 0xF, 0xF, false )] = c;
+#else
+    (void)f;
+    pixelBuffer[pixelPos] = c;
+#endif
+}
+
 /* Replay form of vrc_pixel_grid_dda for the instances of the uniform-brick march (8-bit atlas, fixed-point stepping, no
  * clamp, 32-bit slot bases): the pixel's clear, early exit and store are the walk's, and every recorded visit goes to
  * the one visit body vrc_march_brick_from -- the slot word, its ballot, both uniform marches, the gather march and the
@@ -5027,7 +5068,7 @@ VRC_HD void vrc_pixel_walk_replay( const vrc_frame& f, const vrc_dev_node* __res
     if( count == 0u )
     {
         if( f.clearFirst )
-            pixelBuffer[pixelPos] = zero;
+            vrc_store_pixel( f, pixelBuffer, pixelPos, zero );
         return;
     }
     vrc_f4 color = f.clearFirst ? zero : pixelBuffer[pixelPos];
@@ -5061,7 +5102,7 @@ VRC_HD void vrc_pixel_walk_replay( const vrc_frame& f, const vrc_dev_node* __res
         node = nodeNext;
         dist = distNext;
     }
-    pixelBuffer[pixelPos] = color;
+    vrc_store_pixel( f, pixelBuffer, pixelPos, color );
 }
 
 /* The replay of a lean list (vrc_frame::walkLean): the pixel's clear, early exit and store, the order of the visits,
@@ -5140,7 +5181,7 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
     if( count == 0u )
     {
         if( f.clearFirst )
-            pixelBuffer[pixelPos] = zero;
+            vrc_store_pixel( f, pixelBuffer, pixelPos, zero );
         return;
     }
     const vrc_f4 start = f.clearFirst ? zero : pixelBuffer[pixelPos];
@@ -5196,7 +5237,7 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
         packedNext = packedAfter;
         loaded = loadedNext;
     }
-    pixelBuffer[pixelPos] = vrc_lean_widen( color );
+    vrc_store_pixel( f, pixelBuffer, pixelPos, vrc_lean_widen( color ) );
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -1,10 +1,11 @@
 /*
  * vrc_plan.h -- what vrc_render decides from options and facts alone (host only: no HIP, no vrc_ctx, no vrc_pool).
  *
- * The options and per-frame latches of a context as two plain structs, and three decisions over them: which frame a
- * pass renders (vrc_plan_mode), which kernel form marches it (vrc_plan_form, vrc_plan_use_lds) and whether that is the
- * table walk kernel (vrc_plan_table_walk).  A refusal is a code and a message; the ORDER of the refusals is part of the
- * contract (tests/test_render_plan_cpu.py holds both functions to the text they replaced, message for message).
+ * The options and per-frame latches of a context as two plain structs, and four decisions over them: which frame a
+ * pass renders (vrc_plan_mode), which kernel form marches it (vrc_plan_form, vrc_plan_use_lds), whether that is the
+ * table walk kernel (vrc_plan_table_walk) and how a replayed frame stores its pixels (vrc_plan_store_through).  A
+ * refusal is a code and a message; the ORDER of the refusals is part of the contract (tests/test_render_plan_cpu.py
+ * holds both functions to the text they replaced, message for message).
  */
 #ifndef VRC_PLAN_H
 #define VRC_PLAN_H
@@ -24,6 +25,7 @@ struct vrc_options
     int64_t mipDepth = 0, mipDepthCue = 0;     /* VRC_OPT_MIP_DEPTH; _MIP_DEPTH_CUE, thousandths */
     int64_t shading = 0, shadingAmbient = 250; /* VRC_OPT_SHADING; _SHADING_AMBIENT, thousandths */
     int64_t compositeDepth = 0, preint = 0;    /* VRC_OPT_COMPOSITE_DEPTH, thousandths; _PREINTEGRATION */
+    int64_t storeThrough = 1;                  /* VRC_OPT_STORE_THROUGH */
 };
 
 /* what the frame's first vrc_render read of the options its later passes must not change (-1 / false: none yet; written
@@ -288,6 +290,14 @@ inline bool vrc_plan_table_walk( const vrc_options& o, const vrc_mode& m, const 
 {
     return m.plain() && fm.useDda && !fm.useLds && !k.rayLod && !m.linear && k.elemBytes == 1 && !k.bigAtlas && !k.clamp &&
            o.stepping != 0 && fm.slotsFit8Bits;
+}
+
+/* write-through pixel stores (VRC_OPT_STORE_THROUGH; vrc_core.h: vrc_store_pixel): a replayed frame (walkUsed:
+ * VRC_OPT_WALK_CACHE_USED of this pass, 4 = replay) whose pixel buffer, width * height * 16 bytes, a 32-bit buffer offset
+ * spans -- 4 GiB and more keeps the plain stores */
+inline bool vrc_plan_store_through( const vrc_options& o, int64_t walkUsed, uint32_t width, uint32_t height )
+{
+    return o.storeThrough != 0 && walkUsed == 4 && (uint64_t)width * height < ( 1ull << 28 ); /* (pixels of 16 bytes) */
 }
 
 #endif /* VRC_PLAN_H */

@@ -19,6 +19,10 @@ VRC_OPT_WALK_CACHE (the brick grid walked every frame against the march replayed
        python tools/uniform_ab.py --walk-cache [--steps 2000] [--rounds 3]
 Frames and sample counts at 0 and 1 are compared bit for bit, and the option at 1 must have reached the replay
 (VRC_OPT_WALK_CACHE_USED = 4), before anything is timed; the kernel instance of either side is reported.
+VRC_OPT_STORE_THROUGH (the replayed frame's pixels stored plainly against written through the L2) the same way:
+       python tools/uniform_ab.py --store-through [--steps 2000] [--rounds 3]
+One context, one set of lists: frames and sample counts at 0 and 1 are compared bit for bit on replayed frames, with
+VRC_OPT_STORE_THROUGH_USED reading what was asked, before the clock runs; the wall time per frame is the figure to compare.
 With --steps of 200 or more, --libs reports the wall time per frame and the mean kernel time of such a loop as well.
 VRC_OPT_WALK_UNIFORM_ONLY (the lean replay against its uniform-only instance) beside builds, in one process:
        python tools/uniform_ab.py --uniform-only --libs parent=variants/libvrc_hip_parent.so new=libre_amd/lib/libvrc_hip.so
@@ -145,9 +149,12 @@ def markers(a, option=None, names=("lean", "markers")):
     g = GpuScene(s, lib=L)
     frames = {}
     walk = option == vrc.OPT_WALK_CACHE
+    store = option == vrc.OPT_STORE_THROUGH  # (both sides are replayed frames: the option starts nothing over)
     on = vrc.WALK_CACHE_ALWAYS if walk else 1  # (the replay on any volume: at 1 a view that gathers keeps the walk)
-    settle = 6 if walk else 3  # synchronised frames until the steady state (the ray cache: computed, stored, loaded;
-    #                            the walk cache: counted, recorded and replayed behind that)
+    settle = 6 if walk or store else 3  # synchronised frames until the steady state (the ray cache: computed, stored,
+    #                                     loaded; the walk cache: counted, recorded and replayed behind that)
+    if store and a.volume != "mem":
+        vrc.check(L, L.vrc_set_option(g.ctx, vrc.OPT_WALK_CACHE, vrc.WALK_CACHE_ALWAYS))
 
     def walk_mode():
         used = C.c_int64(-1)
@@ -163,6 +170,9 @@ def markers(a, option=None, names=("lean", "markers")):
         if option == vrc.OPT_RAY_CACHE:
             vrc.check(L, L.vrc_get_option(g.ctx, vrc.OPT_RAY_CACHE_USED, C.byref(used)))
             assert used.value == (2 if v else 0), "the third frame did not load its rays"
+        if store:
+            vrc.check(L, L.vrc_get_option(g.ctx, vrc.OPT_STORE_THROUGH_USED, C.byref(used)))
+            assert walk_mode() == 4 and used.value == v, "mode %d, VRC_OPT_STORE_THROUGH_USED reads %d" % (walk_mode(), used.value)
     assert (frames[0][0] == frames[1][0]).all() and frames[0][1] == frames[1][1], "frames differ"
     g.render(count=False)
     run = frame_loop(g, s)
@@ -179,11 +189,13 @@ def markers(a, option=None, names=("lean", "markers")):
             w, k = timed_loop(g, run, a.steps)
             if walk:
                 assert walk_mode() == (4 if v else 0)
+            if store:
+                assert walk_mode() == 4
             wall[v].append(w)
             kernel[v].append(k)
             ran[names[v]] = L.vrc_last_kernel().decode()
     print(json.dumps({"volume": a.volume, "spin": list(a.spin), "samples": frames[0][1],
-                      "kernel": ran if walk else L.vrc_last_kernel().decode(), "steps": a.steps,
+                      "kernel": ran if walk or store else L.vrc_last_kernel().decode(), "steps": a.steps,
                       "wall_ms_per_frame": {names[1]: wall[1], names[0]: wall[0]},
                       "kernel_ms_mean": {names[1]: kernel[1], names[0]: kernel[0]}, "frames_bit_identical": True}))
     g.close()
@@ -208,6 +220,7 @@ def main():
     ap.add_argument("--markers", action="store_true", help="A/B of VRC_OPT_STREAM_MARKERS instead (see above)")
     ap.add_argument("--ray-cache", action="store_true", help="A/B of VRC_OPT_RAY_CACHE instead (see above)")
     ap.add_argument("--walk-cache", action="store_true", help="A/B of VRC_OPT_WALK_CACHE instead (see above)")
+    ap.add_argument("--store-through", action="store_true", help="A/B of VRC_OPT_STORE_THROUGH instead (see above)")
     a = ap.parse_args()
     if a.markers:
         return markers(a)
@@ -215,6 +228,8 @@ def main():
         return markers(a, vrc.OPT_RAY_CACHE, ("computed", "cached"))
     if a.walk_cache:
         return markers(a, vrc.OPT_WALK_CACHE, ("walked", "replayed"))
+    if a.store_through:
+        return markers(a, vrc.OPT_STORE_THROUGH, ("plain", "through"))
     if a.libs:
         return several(a)
     s = orc.build_scene(voxels=(a.voxels,) * 3, block=a.block, viewport=(a.viewport,) * 2, volume=a.volume,
