@@ -297,6 +297,18 @@ typedef struct
                                     * nothing over.  Any other value: VRC_EINVAL */
 #define VRC_OPT_STORE_THROUGH_USED 37 /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render stored
                                     * its pixels that way, 0 if it did anything else */
+#define VRC_OPT_FIRST_VISIT_TABLE 38 /* 1 (default) | 0.  A replayed lean frame (VRC_OPT_WALK_LEAN_USED = 1) that starts
+                                    * from cleared pixels, without VRC_OPT_COUNT_SAMPLES, takes the result of a ray's
+                                    * first visit, where that is a uniform brick of fewer than 256 steps, from a table
+                                    * of the classified table's 256 entries by step count instead of compositing it:
+                                    * the march's own composites from zero, run once per transfer function (512 KiB or
+                                    * 1 MiB of device memory per context).  The table is built by the second frame in
+                                    * a row that renders with one transfer function, so an edit a frame pays no
+                                    * build.  The same frame, bit for bit.  Every other frame, and every frame at 0,
+                                    * marches every visit; changing the option starts nothing over.  Any other value:
+                                    * VRC_EINVAL */
+#define VRC_OPT_FIRST_VISIT_TABLE_USED 39 /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render
+                                    * handed its march the table, 0 if it did anything else */
 /* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
  * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
  * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots

@@ -176,6 +176,19 @@ struct vrc_walk_cache
     int64_t throughUsed = 0; /* VRC_OPT_STORE_THROUGH_USED */
 };
 
+/* the first-visit table of the lean replay (VRC_OPT_FIRST_VISIT_TABLE; vrc_core.h: vrc_first_visit_row).  It depends on
+ * the classified table alone -- transfer function, opacity correction -- and on the form the frame marches, not on the
+ * view, the volume or the lists.  dTable: allocated by the first build, for the four-float form.  gen, grey: the
+ * generation (vrc_ctx::lutGen) and form it was built for (gen 0: never).  prevGen: the generation the vrc_render before
+ * rendered with (0: none).  used: VRC_OPT_FIRST_VISIT_TABLE_USED */
+struct vrc_first_visit
+{
+    void* dTable = nullptr;
+    uint64_t gen = 0, prevGen = 0;
+    bool grey = false;
+    int64_t used = 0;
+};
+
 struct vrc_ctx
 {
     int device = 0;
@@ -200,6 +213,8 @@ struct vrc_ctx
     bool tfGrey = false;      /* red == green == blue in every entry of the transfer function (bitwise) */
     bool lutLinear = false;
     uint32_t lutLevels = 1;
+    uint64_t lutGen = 0; /* bumped wherever render_tables rebuilds the classified table (0: never built) */
+    vrc_first_visit first;
 
     /* pixel buffer (cuda::PixelBufferObject) */
     vrc_f4* fbOwn = nullptr;
@@ -478,7 +493,7 @@ void vrc_ctx_destroy( vrc_ctx* c )
     const std::initializer_list< void* > device = {
         c->dTf,      c->dLut,     c->dPreint,  c->fbOwn,     c->dNodes,    c->dGrid,    c->dTileOrder, c->dRayCache,
         c->walk.dLists, c->walk.dMax, c->dRayList, c->dMipMax, c->dMeanSum, c->dMeanCount, c->dProjOut, c->dMipDepth,
-        c->dIsoGrad, c->dDepthOut, c->dRowMap, c->dCounter,  c->dFrameHist, c->dHistRefs };
+        c->dIsoGrad, c->dDepthOut, c->dRowMap, c->dCounter,  c->dFrameHist, c->dHistRefs, c->first.dTable };
     const std::initializer_list< void* > pinned = { c->hTf, c->hStage, c->walk.hMax, c->hCounter, c->hFrameHist, c->hHistRefs };
     for( void* d : device )
         if( d ) (void)hipFree( d );
@@ -570,6 +585,13 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
         return VRC_OK;
     case VRC_OPT_STORE_THROUGH_USED:
         return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_STORE_THROUGH_USED is read-only" );
+    case VRC_OPT_FIRST_VISIT_TABLE:
+        if( value != 0 && value != 1 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_FIRST_VISIT_TABLE is 0 (march every visit) or 1 (first visits from the table)" );
+        c->opt.firstVisitTable = value; /* (how the replay takes a first visit: nothing starts over) */
+        return VRC_OK;
+    case VRC_OPT_FIRST_VISIT_TABLE_USED:
+        return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_FIRST_VISIT_TABLE_USED is read-only" );
     case VRC_OPT_PROJECTION:
         if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP && value != VRC_PROJECTION_ISO )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite), 1 (maximum intensity) or 2 (isosurface)" );
@@ -662,6 +684,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_WALK_UNIFORM_ONLY_USED: *value = c->walk.uniformUsed; return VRC_OK;
     case VRC_OPT_STORE_THROUGH: *value = c->opt.storeThrough; return VRC_OK;
     case VRC_OPT_STORE_THROUGH_USED: *value = c->walk.throughUsed; return VRC_OK;
+    case VRC_OPT_FIRST_VISIT_TABLE: *value = c->opt.firstVisitTable; return VRC_OK;
+    case VRC_OPT_FIRST_VISIT_TABLE_USED: *value = c->first.used; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->opt.projection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->opt.mipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->opt.mipFold; return VRC_OK;
@@ -1694,6 +1718,7 @@ static int render_tables( vrc_ctx* c, render_pass& p )
         c->lutLevels = lutLevels;
         c->lutTfVersion = c->tfVersion;
         c->lutValid = true;
+        ++c->lutGen; /* (what was built from the table before -- vrc_first_visit -- is no longer current) */
         /* the largest classified opacity of a sample (same function as the device table, evaluated on the
          * pinned copy of the transfer function): decides whether early ray termination can occur at all */
         c->lutMaxAlpha = 1.0f;
@@ -2230,6 +2255,25 @@ static int render_walk_cache( vrc_ctx* c, render_pass& p )
      * walk_constants_equal compares -- the lists do not depend on it */
     w.throughUsed = vrc_plan_store_through( c->opt, w.used, f.width, f.height ) ? 1 : 0;
     f.storeThrough = (uint32_t)w.throughUsed;
+    /* ... and whether it takes first visits from the table (vrc_core.h: vrc_first_visit_row), set behind the same
+     * copies for the same reason.  The table is built here, on the stream behind the classified table it reads and in
+     * front of the march's timing pair: no march, not timed, not counted as a launch */
+    vrc_first_visit& fv = c->first;
+    const bool grey = p.a.greyTable;
+    vrc_first_visit_facts k = { w.used, f.walkLean, f.clearFirst != 0u, p.mode.classify,
+                                fv.gen != 0u && fv.gen == c->lutGen && fv.grey == grey };
+    if( vrc_plan_first_visit_build( c->opt, k, fv.prevGen == c->lutGen ) )
+    {
+        if( !fv.dTable )
+            VRC_HIP_CHECK( hipMalloc( &fv.dTable, (size_t)VRC_FIRST_VISIT_ENTRIES * VRC_FIRST_VISIT_ROWS * sizeof( vrc_f4 ) ) );
+        VRC_HIP_CHECK( vrc_launch_build_first_visit( c->dLut, fv.dTable, grey, c->stream ) );
+        fv.gen = c->lutGen;
+        fv.grey = grey;
+        k.current = true;
+    }
+    fv.prevGen = c->lutGen;
+    fv.used = vrc_plan_first_visit( c->opt, k ) ? 1 : 0;
+    f.firstVisit = fv.used ? fv.dTable : nullptr;
     return VRC_OK;
 }
 

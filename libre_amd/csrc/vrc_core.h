@@ -269,6 +269,12 @@ struct vrc_frame
      * width * height * 16 bytes, which the host has checked fits 32 bits (vrc_plan_store_through); 0: the plain store.
      * The same bytes either way.  Set behind everything that compares frames; no other kernel reads it */
     uint32_t storeThrough;
+    /* the first-visit table of a replayed lean frame (VRC_OPT_FIRST_VISIT_TABLE, vrc_first_visit_row; at the end: no
+     * field above moves).  VRC_FIRST_VISIT_ENTRIES rows of VRC_FIRST_VISIT_ROWS colours in the form the frame marches
+     * (vrc_lean_colour: two floats under a grey table, else four), built from the classified table the frame stages;
+     * NULL: every first visit is marched (vrc_plan_first_visit).  Set behind everything that compares frames; read by
+     * the uncounted lean instances of vrc_k_raycast_replay alone */
+    const void* firstVisit;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -1140,6 +1146,37 @@ VRC_HD bool vrc_march_uniform_lean( E& color, const E ue, uint32_t nLeft, uint32
             return true;
     }
     return false;
+}
+
+/* The first-visit table of the lean replay (VRC_OPT_FIRST_VISIT_TABLE, vrc_frame::firstVisit).  A ray's first visit
+ * starts from the cleared colour, so where it is a uniform brick its result depends on the brick's classified entry e
+ * and the step count n of the list word alone, not on the ray: T[e][j], e in 0 .. 255, j in 0 .. ROWS - 1, is the
+ * colour after min( j, cross_e ) composites of entry e from `start`, cross_e the first sample after which
+ * w > VRC_EARLY_EXIT.  A row is the single-sample loop -- vrc_composite, then the exit test -- frozen after the
+ * crossing: the sequence vrc_march_uniform_lean reproduces by construction (its groups and bodies go back to a saved
+ * colour and replay sample by sample where the threshold was crossed), so T[e][n] is that march's colour from `start`
+ * bit for bit, and its return value is T[e][n].w > VRC_EARLY_EXIT (alpha never decreases, and the row is frozen).
+ * The colour is in the march's own form E (vrc_lean_colour).  Layout [e][j]: the lanes of a wave share e and differ a
+ * little in j.  ROWS = 256: C2's first visits take at most 151 steps, a view rotated by 30 and 20 degrees stays below
+ * 128 sqrt(3) = 222; 512 KiB in the grey form, 1 MiB in the four-float form.  `start` is an argument, not a literal: a
+ * compiler that knows it is zero may fold the first composite, and fma( -0, 1, +0 ) is +0 where the product alone is -0 */
+#ifndef VRC_FIRST_VISIT_ROWS
+#define VRC_FIRST_VISIT_ROWS 256u
+#endif
+#define VRC_FIRST_VISIT_ENTRIES 256u
+template < typename E >
+VRC_HD void vrc_first_visit_row( E* row, const E ue, E color )
+{
+    bool frozen = false;
+    for( uint32_t j = 0u; j < VRC_FIRST_VISIT_ROWS; ++j )
+    {
+        row[j] = color;
+        if( !frozen )
+        {
+            vrc_composite( color, ue );
+            frozen = color.w > VRC_EARLY_EXIT;
+        }
+    }
 }
 
 /* The second plane of a lean list's visit (vrc_frame::walkLean): n << 20 | slotInfoIndex, n = the samples of the
@@ -5164,7 +5201,22 @@ VRC_HD uint32_t vrc_lean_list_word( const vrc_frame& f, uint32_t rayIndex, uint3
  * wave then never asks whether one of its lanes gathers -- no ballot -- and the gather march is not in the function:
  * what is left is the loads, the rule and vrc_march_uniform_lean, in 20 registers where the other form holds the gather
  * march's 79 across the loop.  A word that does not hold one value after all (the host's rule is what keeps it from
- * happening) is clamped like any other and ends the ray's list at that visit: nothing is read through it */
+ * happening) is clamped like any other and ends the ray's list at that visit: nothing is read through it.
+ * The first visit from the table (vrc_frame::firstVisit, vrc_first_visit_row): peeled in front of the visit loop, in the
+ * uncounted instances -- a counted frame marches every visit, its sample count being the oracle's yardstick.  The list
+ * words of visits 0 and 1 and the slot word of visit 0 are loaded as ever; in a frame that starts from zero and has a
+ * table, a lane whose slot word holds one value and whose n is below the rows takes color = T[word & 0xFF][n],
+ * done = color.w > VRC_EARLY_EXIT -- what vrc_march_uniform_lean leaves from zero, bit for bit.  Uniform-only: any other
+ * lane (n >= ROWS, a word that does not hold one value) runs the visit's body in the peel.  The form that can gather
+ * peels per wave instead: where every lane of the wave can take its colour from the table the wave does, and where one
+ * cannot the whole wave starts the loop at visit 0 as it always did -- the visit's body with its gather march stands in
+ * the function once, and the instances keep their registers and waves (with the body in the peel as well the
+ * grey instance in groups of 24 went from 89 to 98 registers and lost its fifth wave).  Behind the peel the loop starts
+ * at visit 1 with its prefetch state as if visit 0 had been an iteration; the visit number stays the wave's (a ray that
+ * ended in the peel is masked out of the loop, not given a count of its own: a per-lane number turns the clamp of the
+ * list word's plane into vector work and moves the loop's wait to its latch).  The table's load stands in front of the
+ * loop, never in it under a condition: a load that a path may skip leaves the compiler one safe wait, vmcnt(0), behind
+ * the loop's own loads (profiles/r13_lean_prefetch.txt) */
 template < bool COUNT, int MODE, int GROUP, bool UNIFORM_ONLY = false >
 VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* __restrict__ nodes,
                                         const uint8_t* __restrict__ atlas, const vrc_f4* lut, const vrc_classifier& cls,
@@ -5193,7 +5245,49 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
     uint32_t packed = vrc_lean_list_word( f, rayIndex, 0u );
     uint32_t packedNext = vrc_lean_list_word( f, rayIndex, 1u );
     uint32_t loaded = vrc_lean_slot_load( f, packed );
-    for( uint32_t k = 0u; k < count; ++k )
+    uint32_t k = 0u;
+    bool ended = false; /* the ray ends at its first visit: it runs no visit of the loop */
+    if constexpr( !COUNT )
+    {
+        const E* const first = static_cast< const E* >( f.firstVisit );
+        if( first != nullptr && f.clearFirst ) /* (the frame's: the same in every lane) */
+        {
+            const uint32_t word = vrc_lean_slot_word( f, packed, loaded );
+            const uint32_t n = packed >> VRC_WALK_LEAN_INDEX_BITS;
+            const bool one = vrc_slot_holds_one_value( word );
+            const bool row = n < VRC_FIRST_VISIT_ROWS;
+            bool peel = true;
+            if constexpr( !UNIFORM_ONLY )
+            {
+                peel = one && row;
+#if defined( __HIP_DEVICE_COMPILE__ )
+                peel = __builtin_amdgcn_ballot_w64( !peel ) == 0ull;
+#endif
+            }
+            if( peel )
+            {
+                const uint32_t loadedNext = vrc_lean_slot_load( f, packedNext );
+                const uint32_t packedAfter = vrc_lean_list_word( f, rayIndex, 2u );
+                bool done = true; /* (uniform-only: a word that does not hold one value ends the list, as in the loop) */
+                if( one && row )
+                {
+                    color = first[( word & 0xFFu ) * VRC_FIRST_VISIT_ROWS + n];
+                    done = color.w > VRC_EARLY_EXIT;
+                }
+                else if constexpr( UNIFORM_ONLY )
+                {
+                    if( one )
+                        done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], n, nSamples );
+                }
+                packed = packedNext;
+                packedNext = packedAfter;
+                loaded = loadedNext;
+                k = 1u; /* (the same in every lane of the wave, as in the loop) */
+                ended = done;
+            }
+        }
+    }
+    for( const uint32_t visits = ended ? 0u : count; k < visits; ++k )
     {
         /* the two prefetches, neither under a branch (the slot word first: its address is a list word that arrived a
          * visit ago) */

@@ -67,6 +67,12 @@ __device__ inline uint32_t vrc_slot_tile( const uint32_t* __restrict__ tileOrder
 hipError_t vrc_launch_build_lut( const float* tf, vrc_f4* lut, vrc_lut_params p, bool linear,
                                  hipStream_t stream );
 
+/* the first-visit table of the lean replay (vrc_core.h: vrc_first_visit_row) from the classified table `lut` (device,
+ * not the padded transfer function): VRC_FIRST_VISIT_ENTRIES x VRC_FIRST_VISIT_ROWS colours at `table` (device), of two
+ * floats (grey: what the grey instances stage of an entry, x and w) or four.  One lane per entry, behind the table's own
+ * build on `stream` */
+hipError_t vrc_launch_build_first_visit( const vrc_f4* lut, void* table, bool grey, hipStream_t stream );
+
 /* row-major brick (size voxels, elemBytes per voxel) -> micro-blocked slot (slot = device
  * pointer to the slot's first element; slotDim = padded slot size in voxels).  A brick smaller
  * than the slot gets its border voxels replicated into the padding.

@@ -92,6 +92,31 @@ hipError_t vrc_launch_walk_record( const vrc_raycast_args& a, vrc_walk_count* re
     return hipGetLastError();
 }
 
+/* The first-visit table (vrc_core.h: vrc_first_visit_row): one lane per entry of the classified table, each filling its
+ * row from `start` -- zero, handed in as an argument so that the compiler composites the first sample as the march
+ * does.  The entry is narrowed as vrc_k_raycast_replay narrows what it stages */
+template < typename E >
+__global__ __launch_bounds__( 64 ) void vrc_k_build_first_visit( const vrc_f4* __restrict__ lut, E* __restrict__ table, const E start )
+{
+    const uint32_t e = blockIdx.x * 64u + threadIdx.x;
+    if( e < VRC_FIRST_VISIT_ENTRIES )
+        vrc_first_visit_row< E >( table + (size_t)e * VRC_FIRST_VISIT_ROWS, vrc_lean_narrow( lut[e], (const E*)nullptr ), start );
+}
+
+hipError_t vrc_launch_build_first_visit( const vrc_f4* lut, void* table, bool grey, hipStream_t stream )
+{
+    if( !lut || !table )
+        return hipErrorInvalidValue;
+    const dim3 grid( ( VRC_FIRST_VISIT_ENTRIES + 63u ) / 64u ), block( 64 );
+    if( grey )
+        hipLaunchKernelGGL( vrc_k_build_first_visit< vrc_f2 >, grid, block, 0, stream, lut, static_cast< vrc_f2* >( table ),
+                            vrc_f2{ 0.f, 0.f } );
+    else
+        hipLaunchKernelGGL( vrc_k_build_first_visit< vrc_f4 >, grid, block, 0, stream, lut, static_cast< vrc_f4* >( table ),
+                            vrc_f4{ 0.f, 0.f, 0.f, 0.f } );
+    return hipGetLastError();
+}
+
 /* waves per SIMD, as vrc_k_raycast says them for the walking instances of the same march (vrc_kernels.hip) -- except that
  * the grey form in groups of 14, the judged instance, is allowed a sixth wave.  The walking instance is held at five
  * because six thrash the L1 under its gathers; the replay needs 76 registers (79 with the sample counter), and

@@ -1,9 +1,10 @@
 /*
  * vrc_plan.h -- what vrc_render decides from options and facts alone (host only: no HIP, no vrc_ctx, no vrc_pool).
  *
- * The options and per-frame latches of a context as two plain structs, and four decisions over them: which frame a
+ * The options and per-frame latches of a context as two plain structs, and five decisions over them: which frame a
  * pass renders (vrc_plan_mode), which kernel form marches it (vrc_plan_form, vrc_plan_use_lds), whether that is the
- * table walk kernel (vrc_plan_table_walk) and how a replayed frame stores its pixels (vrc_plan_store_through).  A
+ * table walk kernel (vrc_plan_table_walk), how a replayed frame stores its pixels (vrc_plan_store_through) and whether
+ * it takes its rays' first visits from a table (vrc_plan_first_visit, vrc_plan_first_visit_build).  A
  * refusal is a code and a message; the ORDER of the refusals is part of the contract (tests/test_render_plan_cpu.py
  * holds both functions to the text they replaced, message for message).
  */
@@ -26,6 +27,7 @@ struct vrc_options
     int64_t shading = 0, shadingAmbient = 250; /* VRC_OPT_SHADING; _SHADING_AMBIENT, thousandths */
     int64_t compositeDepth = 0, preint = 0;    /* VRC_OPT_COMPOSITE_DEPTH, thousandths; _PREINTEGRATION */
     int64_t storeThrough = 1;                  /* VRC_OPT_STORE_THROUGH */
+    int64_t firstVisitTable = 1;               /* VRC_OPT_FIRST_VISIT_TABLE */
 };
 
 /* what the frame's first vrc_render read of the options its later passes must not change (-1 / false: none yet; written
@@ -298,6 +300,36 @@ inline bool vrc_plan_table_walk( const vrc_options& o, const vrc_mode& m, const 
 inline bool vrc_plan_store_through( const vrc_options& o, int64_t walkUsed, uint32_t width, uint32_t height )
 {
     return o.storeThrough != 0 && walkUsed == 4 && (uint64_t)width * height < ( 1ull << 28 ); /* (pixels of 16 bytes) */
+}
+
+/* the first-visit table (VRC_OPT_FIRST_VISIT_TABLE; vrc_core.h: vrc_first_visit_row, vrc_frame::firstVisit): a pass
+ * takes the first uniform visit of its rays from the table where the option is on, the pass is a replayed lean frame
+ * (walkUsed 4, walkLean != 0) that starts from zero (a later pass of a frame starts from the pixels so far, and takes
+ * the four-float form at that: it neither reads nor rebuilds a grey frame's table), is not classified per sample, does
+ * not count its samples -- the counted instances march every visit -- and the table is current: built for the
+ * classified table's present generation, in the form (two floats or four) the pass marches */
+struct vrc_first_visit_facts
+{
+    int64_t walkUsed; /* VRC_OPT_WALK_CACHE_USED of this pass */
+    uint32_t walkLean;
+    bool clearFirst;
+    bool classify; /* vrc_mode::classify */
+    bool current;
+};
+inline bool vrc_plan_first_visit_wanted( const vrc_options& o, const vrc_first_visit_facts& k )
+{
+    return o.firstVisitTable != 0 && k.walkUsed == 4 && k.walkLean != 0u && k.clearFirst && !k.classify && o.count == 0;
+}
+inline bool vrc_plan_first_visit( const vrc_options& o, const vrc_first_visit_facts& k )
+{
+    return vrc_plan_first_visit_wanted( o, k ) && k.current;
+}
+/* ... and a table that is not current is built by such a pass only if the vrc_render before it, in the same context,
+ * rendered with the same generation of the classified table: someone dragging a transfer-function point over a still
+ * view pays no build per edit -- one frame marches as ever, the next builds the table and uses it */
+inline bool vrc_plan_first_visit_build( const vrc_options& o, const vrc_first_visit_facts& k, bool prevSameGeneration )
+{
+    return vrc_plan_first_visit_wanted( o, k ) && !k.current && prevSameGeneration;
 }
 
 #endif /* VRC_PLAN_H */

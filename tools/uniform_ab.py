@@ -23,6 +23,10 @@ VRC_OPT_STORE_THROUGH (the replayed frame's pixels stored plainly against writte
        python tools/uniform_ab.py --store-through [--steps 2000] [--rounds 3]
 One context, one set of lists: frames and sample counts at 0 and 1 are compared bit for bit on replayed frames, with
 VRC_OPT_STORE_THROUGH_USED reading what was asked, before the clock runs; the wall time per frame is the figure to compare.
+VRC_OPT_FIRST_VISIT_TABLE (a ray's first uniform visit marched against taken from the context's table) the same way:
+       python tools/uniform_ab.py --first-visit [--steps 2000] [--rounds 3]
+The frames compared are uncounted replayed ones (a counted frame marches every visit), with
+VRC_OPT_FIRST_VISIT_TABLE_USED reading what was asked before the clock runs and behind every timed loop.
 With --steps of 200 or more, --libs reports the wall time per frame and the mean kernel time of such a loop as well.
 VRC_OPT_WALK_UNIFORM_ONLY (the lean replay against its uniform-only instance) beside builds, in one process:
        python tools/uniform_ab.py --uniform-only --libs parent=variants/libvrc_hip_parent.so new=libre_amd/lib/libvrc_hip.so
@@ -149,7 +153,9 @@ def markers(a, option=None, names=("lean", "markers")):
     g = GpuScene(s, lib=L)
     frames = {}
     walk = option == vrc.OPT_WALK_CACHE
-    store = option == vrc.OPT_STORE_THROUGH  # (both sides are replayed frames: the option starts nothing over)
+    first = option == vrc.OPT_FIRST_VISIT_TABLE
+    store = option == vrc.OPT_STORE_THROUGH or first  # (both sides are replayed frames: the option starts nothing over)
+    read_back = vrc.OPT_FIRST_VISIT_TABLE_USED if first else vrc.OPT_STORE_THROUGH_USED
     on = vrc.WALK_CACHE_ALWAYS if walk else 1  # (the replay on any volume: at 1 a view that gathers keeps the walk)
     settle = 6 if walk or store else 3  # synchronised frames until the steady state (the ray cache: computed, stored,
     #                                     loaded; the walk cache: counted, recorded and replayed behind that)
@@ -163,7 +169,7 @@ def markers(a, option=None, names=("lean", "markers")):
     for v in (1, 0):
         vrc.check(L, L.vrc_set_option(g.ctx, option, on if v else 0))
         for _ in range(settle):
-            frames[v] = g.render(count=True)[:2]
+            frames[v] = g.render(count=not first)[:2]  # (the table serves uncounted frames alone)
         used = C.c_int64(0)
         if walk:
             assert walk_mode() == (4 if v else 0), "the frame compared was not replayed"
@@ -171,8 +177,8 @@ def markers(a, option=None, names=("lean", "markers")):
             vrc.check(L, L.vrc_get_option(g.ctx, vrc.OPT_RAY_CACHE_USED, C.byref(used)))
             assert used.value == (2 if v else 0), "the third frame did not load its rays"
         if store:
-            vrc.check(L, L.vrc_get_option(g.ctx, vrc.OPT_STORE_THROUGH_USED, C.byref(used)))
-            assert walk_mode() == 4 and used.value == v, "mode %d, VRC_OPT_STORE_THROUGH_USED reads %d" % (walk_mode(), used.value)
+            vrc.check(L, L.vrc_get_option(g.ctx, read_back, C.byref(used)))
+            assert walk_mode() == 4 and used.value == v, "mode %d, the option's read-back reads %d" % (walk_mode(), used.value)
     assert (frames[0][0] == frames[1][0]).all() and frames[0][1] == frames[1][1], "frames differ"
     g.render(count=False)
     run = frame_loop(g, s)
@@ -190,7 +196,8 @@ def markers(a, option=None, names=("lean", "markers")):
             if walk:
                 assert walk_mode() == (4 if v else 0)
             if store:
-                assert walk_mode() == 4
+                vrc.check(L, L.vrc_get_option(g.ctx, read_back, C.byref(used)))
+                assert walk_mode() == 4 and used.value == v
             wall[v].append(w)
             kernel[v].append(k)
             ran[names[v]] = L.vrc_last_kernel().decode()
@@ -221,7 +228,10 @@ def main():
     ap.add_argument("--ray-cache", action="store_true", help="A/B of VRC_OPT_RAY_CACHE instead (see above)")
     ap.add_argument("--walk-cache", action="store_true", help="A/B of VRC_OPT_WALK_CACHE instead (see above)")
     ap.add_argument("--store-through", action="store_true", help="A/B of VRC_OPT_STORE_THROUGH instead (see above)")
+    ap.add_argument("--first-visit", action="store_true", help="A/B of VRC_OPT_FIRST_VISIT_TABLE instead (see above)")
     a = ap.parse_args()
+    if a.first_visit:
+        return markers(a, vrc.OPT_FIRST_VISIT_TABLE, ("marched", "table"))
     if a.markers:
         return markers(a)
     if a.ray_cache:
