@@ -309,6 +309,15 @@ typedef struct
                                     * VRC_EINVAL */
 #define VRC_OPT_FIRST_VISIT_TABLE_USED 39 /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render
                                     * handed its march the table, 0 if it did anything else */
+#define VRC_OPT_LEAN_FREE_MARCH 40  /* 1 (default) | 0.  A replayed lean frame (VRC_OPT_WALK_LEAN_USED = 1) without
+                                    * VRC_OPT_COUNT_SAMPLES marches a uniform visit without the early-exit test where
+                                    * the visit cannot reach the exit threshold: its start opacity w, its entry's
+                                    * opacity e and its step count n are non-negative with w + n e <= 0.99, decided
+                                    * per ray and visit.  Every other visit keeps the tested march.  The same frame,
+                                    * bit for bit.  Every other frame, and every frame at 0, marches as before;
+                                    * changing the option starts nothing over.  Any other value: VRC_EINVAL */
+#define VRC_OPT_LEAN_FREE_MARCH_USED 41 /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render
+                                    * allowed its march that form, 0 if it did anything else */
 /* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
  * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
  * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots

@@ -174,6 +174,7 @@ struct vrc_walk_cache
     unsigned long long gathers = 0;
     int64_t uniformUsed = 0;
     int64_t throughUsed = 0; /* VRC_OPT_STORE_THROUGH_USED */
+    int64_t freeUsed = 0;    /* VRC_OPT_LEAN_FREE_MARCH_USED */
 };
 
 /* the first-visit table of the lean replay (VRC_OPT_FIRST_VISIT_TABLE; vrc_core.h: vrc_first_visit_row).  It depends on
@@ -592,6 +593,13 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
         return VRC_OK;
     case VRC_OPT_FIRST_VISIT_TABLE_USED:
         return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_FIRST_VISIT_TABLE_USED is read-only" );
+    case VRC_OPT_LEAN_FREE_MARCH:
+        if( value != 0 && value != 1 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_LEAN_FREE_MARCH is 0 (every visit tests for the exit) or 1 (not where it is out of reach)" );
+        c->opt.leanFreeMarch = value; /* (how the replay marches a visit: nothing starts over) */
+        return VRC_OK;
+    case VRC_OPT_LEAN_FREE_MARCH_USED:
+        return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_LEAN_FREE_MARCH_USED is read-only" );
     case VRC_OPT_PROJECTION:
         if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP && value != VRC_PROJECTION_ISO )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite), 1 (maximum intensity) or 2 (isosurface)" );
@@ -686,6 +694,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_STORE_THROUGH_USED: *value = c->walk.throughUsed; return VRC_OK;
     case VRC_OPT_FIRST_VISIT_TABLE: *value = c->opt.firstVisitTable; return VRC_OK;
     case VRC_OPT_FIRST_VISIT_TABLE_USED: *value = c->first.used; return VRC_OK;
+    case VRC_OPT_LEAN_FREE_MARCH: *value = c->opt.leanFreeMarch; return VRC_OK;
+    case VRC_OPT_LEAN_FREE_MARCH_USED: *value = c->walk.freeUsed; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->opt.projection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->opt.mipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->opt.mipFold; return VRC_OK;
@@ -2148,8 +2158,8 @@ static int render_ray_cache( vrc_ctx* c, render_pass& p )
  * the count pass and the uniformity words it read, is not recorded and stays on the walk until the pool's uploads or
  * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold.
  * Decides: walkCount / walkRecord (the passes render_march launches), walk.used (VRC_OPT_WALK_CACHE_USED: 0 walk,
- * 1 count, 2 waiting for the count, 3 record, 4 replay), walk.leanUsed, walk.uniformUsed, walk.throughUsed, and the
- * frame's walk fields and storeThrough */
+ * 1 count, 2 waiting for the count, 3 record, 4 replay), walk.leanUsed, walk.uniformUsed, walk.throughUsed,
+ * walk.freeUsed, and the frame's walk fields, storeThrough, firstVisit and leanFree */
 static int render_walk_cache( vrc_ctx* c, render_pass& p )
 {
     vrc_walk_cache& w = c->walk;
@@ -2159,6 +2169,7 @@ static int render_walk_cache( vrc_ctx* c, render_pass& p )
     w.leanUsed = 0;
     w.uniformUsed = 0;
     w.throughUsed = 0;
+    w.freeUsed = 0;
     f.walkCache = nullptr;
     f.walkPlane = f.walkK = 0u;
     f.walkLean = f.walkSlots = 0u;
@@ -2274,6 +2285,10 @@ static int render_walk_cache( vrc_ctx* c, render_pass& p )
     fv.prevGen = c->lutGen;
     fv.used = vrc_plan_first_visit( c->opt, k ) ? 1 : 0;
     f.firstVisit = fv.used ? fv.dTable : nullptr;
+    /* ... and whether a visit that cannot reach the exit threshold marches without the test (vrc_core.h:
+     * vrc_march_uniform_free): behind the same copies, for the same reason */
+    w.freeUsed = vrc_plan_lean_free_march( c->opt, w.used, f.walkLean, p.mode.classify ) ? 1 : 0;
+    f.leanFree = (uint32_t)w.freeUsed;
     return VRC_OK;
 }
 

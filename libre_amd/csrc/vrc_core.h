@@ -23,7 +23,7 @@
     defined( VRC_ABLATE_NO_FETCH ) || \
     defined( VRC_WG_TIMELINE ) || \
     defined( VRC_UNIFORM_GROUP ) || \
-    defined( VRC_LEAN_GROUP ) || \
+    defined( VRC_LEAN_GROUP ) || defined( VRC_LEAN_FREE_GROUP ) || \
     defined( VRC_TEST_BIAS_ENTRY ) || \
     defined( VRC_LDS_STATS ) || defined( VRC_LDS_STATS2 ) || \
     defined( VRC_LDS_TIMING ) || \
@@ -275,6 +275,12 @@ struct vrc_frame
      * NULL: every first visit is marched (vrc_plan_first_visit).  Set behind everything that compares frames; read by
      * the uncounted lean instances of vrc_k_raycast_replay alone */
     const void* firstVisit;
+    /* the free body of the lean march (VRC_OPT_LEAN_FREE_MARCH, vrc_march_uniform_free; at the end: no field above
+     * moves).  1: a uniform visit of a replayed lean frame that cannot reach VRC_EARLY_EXIT -- by a per-lane test of its
+     * start alpha, entry and count -- runs its composites without the exit test; 0: every lane takes the tested march.
+     * The same bytes either way (vrc_plan_lean_free_march).  Set behind everything that compares frames; read by the
+     * uncounted lean instances of vrc_k_raycast_replay alone */
+    uint32_t leanFree;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -1112,11 +1118,85 @@ VRC_HD bool vrc_march_uniform_counted( E& color, const E ue, uint32_t nLeft, uin
 #ifndef VRC_LEAN_GROUP
 #define VRC_LEAN_GROUP 32 /* samples per whole group of the lean march: a power of two */
 #endif
+/* The free body of the lean march (VRC_OPT_LEAN_FREE_MARCH, vrc_frame::leanFree): a visit that cannot reach the
+ * threshold needs neither the exit test nor what serves it -- the saved colour, the count's reset -- and a trip of its
+ * group loop is the composites and one subtract whose borrow is the loop's condition.
+ * The bound.  A composite adds e.w * t to alpha, t = 1 - w_k rounded.  With 0 <= w_k <= 1 and 0 <= e.w that is at
+ * least 0 and at most e.w, so alpha never falls and, in real arithmetic, w_n <= w_0 + n * e.w.  Every composite rounds
+ * twice at values of at most 1, the test below twice more: under n * 2^-24, below 2.5e-4 for n < 4096 (the list
+ * word's 12 bits).  So a visit with 0 <= w_0, 0 <= e.w and w_0 + n * e.w <= 0.99 stays below 0.99 + 2.5e-4, and
+ * 0.99 leaves VRC_EARLY_EXIT (0.999) a margin of 0.009, 36 times that rounding: every w_k of it is in [0, 0.9903],
+ * the tested march never sees its test fire and never goes back, and n plain composites are its sequence bit for
+ * bit.  (e.w <= 1 need not be asked: with n >= 1 the sum says so, with n = 0 nothing is composited.)  The comparisons
+ * are written so that a NaN on either side fails them; a negative entry or start fails the first two.
+ * Whole groups of VRC_LEAN_FREE_GROUP on a count of groups, then bodies by the bits of n down to four, then the last
+ * zero to three samples one by one.  Groups of 8: the tested march takes 32 because its trip costs eight instructions
+ * beside the composites, and pays for that with lanes that march up to 31 samples in bodies while their neighbours run
+ * a group; at one instruction a trip the small group wins (tools/replay_cost_model.py).  Measured on C2
+ * (profiles/r19_lean_free_march.txt; the tested march: 0.0360 ms): groups of 4 / 8 / 16 / 32 with this remainder
+ * 0.0348 / 0.0331 / 0.0332 / 0.0342 ms.  The remainder decides as much as the group: with bodies of 2 and 1 the
+ * compiler forms selects that always compute three samples, and groups of 8 / 16 / 32 over them take 0.0369 / 0.0374 /
+ * 0.0351 ms -- two of them slower than the tested march; a body of 2 and a branch for the last sample, 0.0360 */
+#ifndef VRC_LEAN_FREE_GROUP
+#define VRC_LEAN_FREE_GROUP 8 /* samples per whole group of the free body: a power of two */
+#endif
+#if defined( VRC_LEAN_FREE_HOOK ) && !defined( __HIPCC__ )
+/* host test builds only (tests/cpu_harness/lean_free_harness.cpp): how many marches took [0] the tested, [1] the free body */
+extern uint64_t vrc_lean_free_taken[2];
+#endif
+template < typename E >
+VRC_HD bool vrc_lean_free_visit( const E& color, const E& ue, uint32_t n )
+{
+    return 0.0f <= color.w && 0.0f <= ue.w && color.w + (float)n * ue.w <= 0.99f;
+}
+template < typename E >
+VRC_HD void vrc_march_uniform_free( E& color, const E ue, const uint32_t n )
+{
+    static_assert( VRC_LEAN_FREE_GROUP >= 4 && ( VRC_LEAN_FREE_GROUP & ( VRC_LEAN_FREE_GROUP - 1 ) ) == 0,
+                   "the bodies below are the bits of a count below the group, the loop behind them its last two" );
+    uint32_t groups = n / (uint32_t)VRC_LEAN_FREE_GROUP;
+    /* (the decrement and the loop's condition in one: the subtract's borrow) */
+    while( !__builtin_sub_overflow( groups, 1u, &groups ) )
+    {
+#pragma unroll
+        for( int k = 0; k < VRC_LEAN_FREE_GROUP; ++k )
+            vrc_composite( color, ue );
+    }
+#pragma unroll
+    for( int body = VRC_LEAN_FREE_GROUP / 2; body > 2; body >>= 1 )
+        if( n & (uint32_t)body )
+        {
+#pragma unroll
+            for( int k = 0; k < body; ++k )
+                vrc_composite( color, ue );
+        }
+    /* what is left below four, sample by sample on the same kind of trip (kept a loop: unrolled it becomes selects) */
+    uint32_t left = n & 3u;
+#pragma unroll 1
+    while( !__builtin_sub_overflow( left, 1u, &left ) )
+        vrc_composite( color, ue );
+}
+
+/* freeMarch: the frame's word (vrc_frame::leanFree != 0, the same in every lane); read by the uncounted instances */
 template < bool COUNT, typename E >
-VRC_HD bool vrc_march_uniform_lean( E& color, const E ue, uint32_t nLeft, uint32_t& nSamples )
+VRC_HD bool vrc_march_uniform_lean( E& color, const E ue, uint32_t nLeft, uint32_t& nSamples, const bool freeMarch = false )
 {
     static_assert( VRC_LEAN_GROUP >= 2 && ( VRC_LEAN_GROUP & ( VRC_LEAN_GROUP - 1 ) ) == 0,
                    "the bodies below are the bits of a count below the group" );
+    if constexpr( !COUNT )
+    {
+        if( freeMarch && vrc_lean_free_visit( color, ue, nLeft ) )
+        {
+#if defined( VRC_LEAN_FREE_HOOK ) && !defined( __HIPCC__ )
+            ++vrc_lean_free_taken[1];
+#endif
+            vrc_march_uniform_free< E >( color, ue, nLeft );
+            return false;
+        }
+#if defined( VRC_LEAN_FREE_HOOK ) && !defined( __HIPCC__ )
+        ++vrc_lean_free_taken[0];
+#endif
+    }
     const bool crossed = vrc_uniform_groups< COUNT, VRC_LEAN_GROUP, E >( color, ue, nLeft, nSamples );
     if( !crossed )
     {
@@ -5241,6 +5321,7 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
         return;
     E color = vrc_lean_narrow( start, (const E*)nullptr );
     const uint32_t lastNode = f.nodeCount - 1u;
+    const bool freeMarch = f.leanFree != 0u; /* (the frame's: a scalar branch in front of the per-lane test) */
     /* the words of the first two visits: unconditional like the loop's (a list of one visit reads its word twice) */
     uint32_t packed = vrc_lean_list_word( f, rayIndex, 0u );
     uint32_t packedNext = vrc_lean_list_word( f, rayIndex, 1u );
@@ -5277,7 +5358,7 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
                 else if constexpr( UNIFORM_ONLY )
                 {
                     if( one )
-                        done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], n, nSamples );
+                        done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], n, nSamples, freeMarch );
                 }
                 packed = packedNext;
                 packedNext = packedAfter;
@@ -5302,7 +5383,7 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
             /* no ballot, and no gather march in the function: such a word ends the list */
             if( general )
                 break;
-            done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], n, nSamples );
+            done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], n, nSamples, freeMarch );
         }
         else
         {
@@ -5310,7 +5391,7 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
             general = __builtin_amdgcn_ballot_w64( general ) != 0ull;
 #endif
             if( !general )
-                done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], n, nSamples );
+                done = vrc_march_uniform_lean< COUNT, E >( color, tab[word & 0xFFu], n, nSamples, freeMarch );
             else
             {
                 /* the gather visit's own loads, all inside its branch: the interval and the ray's direction are asked

@@ -4,7 +4,8 @@
  * The options and per-frame latches of a context as two plain structs, and five decisions over them: which frame a
  * pass renders (vrc_plan_mode), which kernel form marches it (vrc_plan_form, vrc_plan_use_lds), whether that is the
  * table walk kernel (vrc_plan_table_walk), how a replayed frame stores its pixels (vrc_plan_store_through) and whether
- * it takes its rays' first visits from a table (vrc_plan_first_visit, vrc_plan_first_visit_build).  A
+ * it takes its rays' first visits from a table (vrc_plan_first_visit, vrc_plan_first_visit_build) or may march a visit
+ * without the exit test (vrc_plan_lean_free_march).  A
  * refusal is a code and a message; the ORDER of the refusals is part of the contract (tests/test_render_plan_cpu.py
  * holds both functions to the text they replaced, message for message).
  */
@@ -28,6 +29,7 @@ struct vrc_options
     int64_t compositeDepth = 0, preint = 0;    /* VRC_OPT_COMPOSITE_DEPTH, thousandths; _PREINTEGRATION */
     int64_t storeThrough = 1;                  /* VRC_OPT_STORE_THROUGH */
     int64_t firstVisitTable = 1;               /* VRC_OPT_FIRST_VISIT_TABLE */
+    int64_t leanFreeMarch = 1;                 /* VRC_OPT_LEAN_FREE_MARCH */
 };
 
 /* what the frame's first vrc_render read of the options its later passes must not change (-1 / false: none yet; written
@@ -330,6 +332,15 @@ inline bool vrc_plan_first_visit( const vrc_options& o, const vrc_first_visit_fa
 inline bool vrc_plan_first_visit_build( const vrc_options& o, const vrc_first_visit_facts& k, bool prevSameGeneration )
 {
     return vrc_plan_first_visit_wanted( o, k ) && !k.current && prevSameGeneration;
+}
+
+/* the free body of the lean march (VRC_OPT_LEAN_FREE_MARCH; vrc_core.h: vrc_march_uniform_free, vrc_frame::leanFree):
+ * where the option is on and the pass is a replayed lean frame (walkUsed 4, walkLean != 0) that is not classified per
+ * sample and does not count its samples -- the counted instances hold no such body.  Whether the pass clears does not
+ * matter: the per-lane test reads the alpha the visit starts from */
+inline bool vrc_plan_lean_free_march( const vrc_options& o, int64_t walkUsed, uint32_t walkLean, bool classify )
+{
+    return o.leanFreeMarch != 0 && walkUsed == 4 && walkLean != 0u && !classify && o.count == 0;
 }
 
 #endif /* VRC_PLAN_H */

@@ -27,6 +27,9 @@ VRC_OPT_FIRST_VISIT_TABLE (a ray's first uniform visit marched against taken fro
        python tools/uniform_ab.py --first-visit [--steps 2000] [--rounds 3]
 The frames compared are uncounted replayed ones (a counted frame marches every visit), with
 VRC_OPT_FIRST_VISIT_TABLE_USED reading what was asked before the clock runs and behind every timed loop.
+VRC_OPT_LEAN_FREE_MARCH (a visit that cannot reach the exit threshold marched with the exit test against without) the same way:
+       python tools/uniform_ab.py --free-march [--steps 2000] [--rounds 3]
+Uncounted replayed frames again (the counted instances hold no such body), VRC_OPT_LEAN_FREE_MARCH_USED read as above.
 With --steps of 200 or more, --libs reports the wall time per frame and the mean kernel time of such a loop as well.
 VRC_OPT_WALK_UNIFORM_ONLY (the lean replay against its uniform-only instance) beside builds, in one process:
        python tools/uniform_ab.py --uniform-only --libs parent=variants/libvrc_hip_parent.so new=libre_amd/lib/libvrc_hip.so
@@ -153,9 +156,10 @@ def markers(a, option=None, names=("lean", "markers")):
     g = GpuScene(s, lib=L)
     frames = {}
     walk = option == vrc.OPT_WALK_CACHE
-    first = option == vrc.OPT_FIRST_VISIT_TABLE
+    first = option in (vrc.OPT_FIRST_VISIT_TABLE, vrc.OPT_LEAN_FREE_MARCH)  # (what serves uncounted frames alone)
     store = option == vrc.OPT_STORE_THROUGH or first  # (both sides are replayed frames: the option starts nothing over)
-    read_back = vrc.OPT_FIRST_VISIT_TABLE_USED if first else vrc.OPT_STORE_THROUGH_USED
+    read_back = {vrc.OPT_FIRST_VISIT_TABLE: vrc.OPT_FIRST_VISIT_TABLE_USED,
+                 vrc.OPT_LEAN_FREE_MARCH: vrc.OPT_LEAN_FREE_MARCH_USED}.get(option, vrc.OPT_STORE_THROUGH_USED)
     on = vrc.WALK_CACHE_ALWAYS if walk else 1  # (the replay on any volume: at 1 a view that gathers keeps the walk)
     settle = 6 if walk or store else 3  # synchronised frames until the steady state (the ray cache: computed, stored,
     #                                     loaded; the walk cache: counted, recorded and replayed behind that)
@@ -229,9 +233,12 @@ def main():
     ap.add_argument("--walk-cache", action="store_true", help="A/B of VRC_OPT_WALK_CACHE instead (see above)")
     ap.add_argument("--store-through", action="store_true", help="A/B of VRC_OPT_STORE_THROUGH instead (see above)")
     ap.add_argument("--first-visit", action="store_true", help="A/B of VRC_OPT_FIRST_VISIT_TABLE instead (see above)")
+    ap.add_argument("--free-march", action="store_true", help="A/B of VRC_OPT_LEAN_FREE_MARCH instead (see above)")
     a = ap.parse_args()
     if a.first_visit:
         return markers(a, vrc.OPT_FIRST_VISIT_TABLE, ("marched", "table"))
+    if a.free_march:
+        return markers(a, vrc.OPT_LEAN_FREE_MARCH, ("tested", "free"))
     if a.markers:
         return markers(a)
     if a.ray_cache:
