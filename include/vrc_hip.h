@@ -318,6 +318,18 @@ typedef struct
                                     * changing the option starts nothing over.  Any other value: VRC_EINVAL */
 #define VRC_OPT_LEAN_FREE_MARCH_USED 41 /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render
                                     * allowed its march that form, 0 if it did anything else */
+#define VRC_OPT_WALK_RESOLVED 42    /* 1 (default) | 0.  A frame replayed by the uniform-only instance
+                                    * (VRC_OPT_WALK_UNIFORM_ONLY_USED = 1) without VRC_OPT_COUNT_SAMPLES reads one word
+                                    * per visit -- step count, brick value, marched or not -- resolved once from the
+                                    * lists and the bricks' uniformity words, instead of a list word and a uniformity
+                                    * word per visit.  The words take a fifth more of VRC_OPT_WALK_CACHE_BUDGET beside
+                                    * the lists (a view whose lists fit and whose words do not replays as at 0), are
+                                    * built by the first such frame and dropped when the lists, the pool's uploads or
+                                    * its uniformity words change.  The same frame, bit for bit.  Every other frame,
+                                    * and every frame at 0, replays as before; changing the option starts nothing
+                                    * over.  Any other value: VRC_EINVAL */
+#define VRC_OPT_WALK_RESOLVED_USED 43 /* read-only (vrc_get_option), no synchronisation: 1 if the last vrc_render
+                                    * handed its march those words, 0 if it did anything else */
 /* 512 MiB per context: a 1024 x 1024 frame of a 1024^3 volume in 128^3 bricks has lists of at most 12 visits in the
  * default view, (1 + 4 x 12) x 4 MiB = 196 MiB (19 visits, 308 MiB, rotated by 30 and 20 degrees), and 31 visits fit;
  * every renderer slot of a pipeline with frames in flight is a context of its own with a budget of its own (six slots

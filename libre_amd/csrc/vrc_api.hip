@@ -175,6 +175,17 @@ struct vrc_walk_cache
     int64_t uniformUsed = 0;
     int64_t throughUsed = 0; /* VRC_OPT_STORE_THROUGH_USED */
     int64_t freeUsed = 0;    /* VRC_OPT_LEAN_FREE_MARCH_USED */
+    /* the resolved visit words of the uniform-only replay (VRC_OPT_WALK_RESOLVED; vrc_core.h: vrc_walk_resolved_word): k
+     * planes beside the lists, built from them and from the slot words by the first frame that is handed the
+     * uniform-only instance without them.  resolvedValid: the planes hold the words of the lists in dLists as recorded
+     * (a record pass ends it) under the uploads resolvedGen and the array resolvedSlotInfo; a frame that finds another
+     * of the three takes the list words and drops the planes.  resolvedUsed: VRC_OPT_WALK_RESOLVED_USED */
+    uint32_t* dResolved = nullptr;
+    size_t resolvedWords = 0; /* allocated */
+    bool resolvedValid = false;
+    uint64_t resolvedGen = 0;
+    const uint32_t* resolvedSlotInfo = nullptr;
+    int64_t resolvedUsed = 0;
 };
 
 /* the first-visit table of the lean replay (VRC_OPT_FIRST_VISIT_TABLE; vrc_core.h: vrc_first_visit_row).  It depends on
@@ -494,7 +505,8 @@ void vrc_ctx_destroy( vrc_ctx* c )
     const std::initializer_list< void* > device = {
         c->dTf,      c->dLut,     c->dPreint,  c->fbOwn,     c->dNodes,    c->dGrid,    c->dTileOrder, c->dRayCache,
         c->walk.dLists, c->walk.dMax, c->dRayList, c->dMipMax, c->dMeanSum, c->dMeanCount, c->dProjOut, c->dMipDepth,
-        c->dIsoGrad, c->dDepthOut, c->dRowMap, c->dCounter,  c->dFrameHist, c->dHistRefs, c->first.dTable };
+        c->dIsoGrad, c->dDepthOut, c->dRowMap, c->dCounter,  c->dFrameHist, c->dHistRefs, c->first.dTable,
+        c->walk.dResolved };
     const std::initializer_list< void* > pinned = { c->hTf, c->hStage, c->walk.hMax, c->hCounter, c->hFrameHist, c->hHistRefs };
     for( void* d : device )
         if( d ) (void)hipFree( d );
@@ -600,6 +612,13 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
         return VRC_OK;
     case VRC_OPT_LEAN_FREE_MARCH_USED:
         return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_LEAN_FREE_MARCH_USED is read-only" );
+    case VRC_OPT_WALK_RESOLVED:
+        if( value != 0 && value != 1 )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_RESOLVED is 0 (list and slot words) or 1 (resolved visit words)" );
+        c->opt.walkResolved = value; /* (what the uniform-only replay reads of a visit: nothing starts over) */
+        return VRC_OK;
+    case VRC_OPT_WALK_RESOLVED_USED:
+        return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_RESOLVED_USED is read-only" );
     case VRC_OPT_PROJECTION:
         if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP && value != VRC_PROJECTION_ISO )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite), 1 (maximum intensity) or 2 (isosurface)" );
@@ -696,6 +715,8 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_FIRST_VISIT_TABLE_USED: *value = c->first.used; return VRC_OK;
     case VRC_OPT_LEAN_FREE_MARCH: *value = c->opt.leanFreeMarch; return VRC_OK;
     case VRC_OPT_LEAN_FREE_MARCH_USED: *value = c->walk.freeUsed; return VRC_OK;
+    case VRC_OPT_WALK_RESOLVED: *value = c->opt.walkResolved; return VRC_OK;
+    case VRC_OPT_WALK_RESOLVED_USED: *value = c->walk.resolvedUsed; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->opt.projection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->opt.mipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->opt.mipFold; return VRC_OK;
@@ -1668,6 +1689,7 @@ struct render_pass
     bool sameNodes, tableWalk; /* the node list of the vrc_render before, on the same pool; vrc_plan_table_walk */
     size_t pixels, plane; /* of the pixel buffer in use; of a plane of the ray and walk caches: its whole tiles */
     bool walkCount, walkRecord; /* render_walk_cache: run the count / the record pass in front of this march */
+    bool walkResolve;           /* ... or build the resolved visit words the march reads (vrc_walk_cache::dResolved) */
     vrc_raycast_args a;
 };
 
@@ -2159,7 +2181,8 @@ static int render_ray_cache( vrc_ctx* c, render_pass& p )
  * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold.
  * Decides: walkCount / walkRecord (the passes render_march launches), walk.used (VRC_OPT_WALK_CACHE_USED: 0 walk,
  * 1 count, 2 waiting for the count, 3 record, 4 replay), walk.leanUsed, walk.uniformUsed, walk.throughUsed,
- * walk.freeUsed, and the frame's walk fields, storeThrough, firstVisit and leanFree */
+ * walk.freeUsed, walk.resolvedUsed, walkResolve (the build of the resolved visit words render_march launches), and the
+ * frame's walk fields, storeThrough, firstVisit, leanFree and walkResolved */
 static int render_walk_cache( vrc_ctx* c, render_pass& p )
 {
     vrc_walk_cache& w = c->walk;
@@ -2289,6 +2312,27 @@ static int render_walk_cache( vrc_ctx* c, render_pass& p )
      * vrc_march_uniform_free): behind the same copies, for the same reason */
     w.freeUsed = vrc_plan_lean_free_march( c->opt, w.used, f.walkLean, p.mode.classify ) ? 1 : 0;
     f.leanFree = (uint32_t)w.freeUsed;
+    /* ... and whether the uniform-only instance reads resolved visit words (vrc_core.h: vrc_walk_resolved_word): behind
+     * the same copies, for the same reason.  The planes are the lists' as recorded, under the uploads and the slotInfo
+     * the frame renders with -- what a frame must find unchanged to be handed VRC_WALK_LEAN_UNIFORM at all -- and count
+     * against the budget beside the lists.  The first such frame without them builds them (render_march, behind the
+     * pool's uploads and in front of the timing pair: no march); planes of anything else are dropped, and so are they
+     * where the frame is not handed that instance because the triple moved */
+    p.walkResolve = false;
+    const bool uniformOnly = f.walkLean == VRC_WALK_LEAN_UNIFORM;
+    if( w.resolvedValid && ( p.walkRecord || ( w.used == 4 && ( w.resolvedGen != gen || w.resolvedSlotInfo != f.slotInfo ) ) ) )
+        w.resolvedValid = false;
+    const unsigned long long resolvedBytes = ( 1ull + 5ull * w.k ) * plane * sizeof( uint32_t );
+    w.resolvedUsed = vrc_plan_walk_resolved( c->opt, uniformOnly, resolvedBytes <= (unsigned long long)c->opt.walkBudget ) ? 1 : 0;
+    if( w.resolvedUsed && !w.resolvedValid )
+    {
+        const size_t words = (size_t)w.k * plane;
+        VRC_TRY( ctx_grow( c, w.resolvedWords, words, words, { w.dResolved } ) );
+        p.walkResolve = true; /* (valid once render_march has launched the build) */
+        w.resolvedGen = gen;
+        w.resolvedSlotInfo = f.slotInfo;
+    }
+    f.walkResolved = w.resolvedUsed ? w.dResolved : nullptr;
     return VRC_OK;
 }
 
@@ -2319,6 +2363,11 @@ static int render_march( vrc_ctx* c, render_pass& p )
         f.walkCache = nullptr;
         f.walkPlane = f.walkK = 0u;
         f.walkLean = f.walkSlots = 0u;
+    }
+    if( p.walkResolve )
+    {
+        VRC_HIP_CHECK( vrc_launch_walk_resolve( f, c->walk.dResolved, c->stream ) );
+        c->walk.resolvedValid = true;
     }
     if( c->opt.count )
         VRC_HIP_CHECK( hipMemsetAsync( c->dCounter, 0, sizeof( unsigned long long ), c->stream ) );

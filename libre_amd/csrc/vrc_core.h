@@ -281,6 +281,14 @@ struct vrc_frame
      * The same bytes either way (vrc_plan_lean_free_march).  Set behind everything that compares frames; read by the
      * uncounted lean instances of vrc_k_raycast_replay alone */
     uint32_t leanFree;
+    /* the resolved visit words of a uniform-only replay (VRC_OPT_WALK_RESOLVED, vrc_walk_resolved_word; at the end: no
+     * field above moves).  walkK planes of walkPlane words, visit v of ray i at [v * walkPlane + i]: the list word's
+     * step count, the value of the brick's slot word and whether the visit is marched at all -- what the slot words
+     * say of these lists for as long as the pool takes no upload and slotInfo is the same array (vrc_render keeps the
+     * planes to that).  NULL: the replay reads the list word and the slot word of every visit (vrc_plan_walk_resolved).
+     * The same bytes either way.  Set behind everything that compares frames; read by the uncounted uniform-only
+     * instances of vrc_k_raycast_replay alone */
+    const uint32_t* walkResolved;
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -5276,6 +5284,112 @@ VRC_HD uint32_t vrc_lean_list_word( const vrc_frame& f, uint32_t rayIndex, uint3
     return f.walkCache[(size_t)rayIndex + plane * f.walkPlane];
 }
 
+/* The pixel of lane `lane` of tile `tile` in the replay (Morton lane order, tiles of 8 x 8 row-major over tilesX), in two
+ * parts: the tile's origin is the wave's -- the kernel hands it a tile number that is the same in every lane, so the
+ * division stays off the vector unit -- and the lane adds its 3 + 3 bits */
+VRC_HD void vrc_replay_tile_origin( uint32_t tile, uint32_t tilesX, uint32_t& x0, uint32_t& y0 )
+{
+    const uint32_t ty = tile / tilesX;
+    x0 = ( tile - ty * tilesX ) * 8u;
+    y0 = ty * 8u;
+}
+VRC_HD void vrc_replay_lane_pixel( uint32_t x0, uint32_t y0, uint32_t lane, uint32_t& px, uint32_t& py )
+{
+    px = x0 + ( ( lane & 1u ) | ( ( lane >> 1 ) & 2u ) | ( ( lane >> 2 ) & 4u ) );
+    py = y0 + ( ( ( lane >> 1 ) & 1u ) | ( ( lane >> 2 ) & 2u ) | ( ( lane >> 3 ) & 4u ) );
+}
+
+/* The resolved word of visit v of a ray (vrc_frame::walkResolved, VRC_OPT_WALK_RESOLVED): what the uniform-only replay
+ * makes of the visit's list word and slot word in every frame, made once.  The step count n stays in the 12 bits the
+ * list word has it in; the low byte is the slot word's value (vrc_lean_slot_word of the word vrc_lean_slot_load reads:
+ * the same clamp, the same rule); VRC_WALK_RESOLVED_ONE is set iff the visit is below the ray's count and the slot word
+ * holds one value -- iff the uniform-only replay marches it.  A clear bit ends the ray's list there, as the count or a
+ * word that does not hold one value does.  Visits stay one to one: v < walkK, any ray index below walkPlane (the
+ * invariant of vrc_lean_list_word) */
+#define VRC_WALK_RESOLVED_ONE 0x100u
+VRC_HD uint32_t vrc_walk_resolved_word( const vrc_frame& f, uint32_t rayIndex, uint32_t v )
+{
+    const uint32_t listed = f.walkCache[rayIndex];
+    const uint32_t packed = vrc_lean_list_word( f, rayIndex, v );
+    const uint32_t word = vrc_lean_slot_word( f, packed, vrc_lean_slot_load( f, packed ) );
+    const uint32_t one = ( v < listed && vrc_slot_holds_one_value( word ) ) ? VRC_WALK_RESOLVED_ONE : 0u;
+    return ( packed & ~( ( 1u << VRC_WALK_LEAN_INDEX_BITS ) - 1u ) ) | one | ( word & 0xFFu );
+}
+/* ... and its load, v clamped to the last plane as vrc_lean_list_word clamps it: unconditional for the same reason */
+VRC_HD uint32_t vrc_walk_resolved_load( const vrc_frame& f, uint32_t rayIndex, uint32_t v )
+{
+    const uint32_t lastVisit = f.walkK - 1u;
+    return f.walkResolved[(size_t)rayIndex + (size_t)( v < lastVisit ? v : lastVisit ) * f.walkPlane];
+}
+
+/* The uniform-only replay from resolved words (vrc_frame::walkResolved != NULL; the uncounted instances).  The pixel's
+ * clear, early exit and store, the first visit from the table and the march of every visit are those of
+ * vrc_pixel_walk_replay_lean< false, ..., true > below; a visit is one word -- no slot word to load, no rule, no clamp of
+ * an index -- and the loop ends at the first word whose bit is clear, which is where that function's count or its test
+ * of the slot word ends it (a ray that ended in the peel is given such a word).  The count and the words of visits 0
+ * and 1 are asked for together; across the march of visit k the word of visit k + 2 is in flight, its load under no
+ * branch (profiles/r13_lean_prefetch.txt) */
+template < int MODE >
+VRC_HD void vrc_pixel_walk_replay_resolved( const vrc_frame& f, const vrc_f4* lut, vrc_f4* __restrict__ pixelBuffer,
+                                            uint32_t px, uint32_t py, uint32_t rayIndex )
+{
+    typedef typename vrc_lean_colour< MODE >::type E;
+    const E* const tab = reinterpret_cast< const E* >( lut );
+    const uint32_t pixelPos = py * f.width + px;
+    const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
+    uint32_t listed = f.walkCache[rayIndex];
+    uint32_t res = vrc_walk_resolved_load( f, rayIndex, 0u );
+    uint32_t resNext = vrc_walk_resolved_load( f, rayIndex, 1u );
+#if defined( __HIP_DEVICE_COMPILE__ )
+    /* (the three loads in front of the count's branch, one wait for all of them: left alone the compiler sinks the
+     * words' loads behind that branch and the ray waits twice) */
+    asm volatile( "" : "+v"( listed ), "+v"( res ), "+v"( resNext ) );
+#endif
+    if( listed == 0u ) /* (walkK >= 1: the count clamped by it is zero iff this is) */
+    {
+        if( f.clearFirst )
+            vrc_store_pixel( f, pixelBuffer, pixelPos, zero );
+        return;
+    }
+    const vrc_f4 start = f.clearFirst ? zero : pixelBuffer[pixelPos];
+    if( start.w > VRC_EARLY_EXIT )
+        return;
+    E color = vrc_lean_narrow( start, (const E*)nullptr );
+    const bool freeMarch = f.leanFree != 0u;
+    const uint32_t K = f.walkK;
+    uint32_t nSamples = 0u; /* (uncounted) */
+    uint32_t k = 0u;
+    const E* const first = static_cast< const E* >( f.firstVisit );
+    if( first != nullptr && f.clearFirst ) /* (the frame's: the same in every lane) */
+    {
+        const uint32_t resAfter = vrc_walk_resolved_load( f, rayIndex, 2u );
+        const uint32_t n = res >> VRC_WALK_LEAN_INDEX_BITS;
+        const bool one = ( res & VRC_WALK_RESOLVED_ONE ) != 0u;
+        bool done = true;
+        if( one && n < VRC_FIRST_VISIT_ROWS )
+        {
+            color = first[( res & 0xFFu ) * VRC_FIRST_VISIT_ROWS + n];
+            done = color.w > VRC_EARLY_EXIT;
+        }
+        else if( one )
+            done = vrc_march_uniform_lean< false, E >( color, tab[res & 0xFFu], n, nSamples, freeMarch );
+        res = done ? 0u : resNext;
+        resNext = resAfter;
+        k = 1u; /* (the same in every lane of the wave) */
+    }
+    for( ; k < K; ++k )
+    {
+        const uint32_t resAfter = vrc_walk_resolved_load( f, rayIndex, k + 2u );
+        if( ( res & VRC_WALK_RESOLVED_ONE ) == 0u )
+            break;
+        if( vrc_march_uniform_lean< false, E >( color, tab[res & 0xFFu], res >> VRC_WALK_LEAN_INDEX_BITS, nSamples, freeMarch ) )
+            break;
+        res = resNext;
+        resNext = resAfter;
+    }
+    vrc_store_pixel( f, pixelBuffer, pixelPos, vrc_lean_widen( color ) );
+}
+
 /* UNIFORM_ONLY: the same replay for a frame none of whose visits gathers (vrc_frame::walkLean = VRC_WALK_LEAN_UNIFORM:
  * the count pass of these lists found no such visit, and the host has seen no upload and no other slotInfo since).  The
  * wave then never asks whether one of its lanes gathers -- no ballot -- and the gather march is not in the function:
@@ -5305,6 +5419,14 @@ VRC_HD void vrc_pixel_walk_replay_lean( const vrc_frame& f, const vrc_dev_node* 
 {
     typedef typename vrc_lean_colour< MODE >::type E;
     (void)cls;
+    if constexpr( UNIFORM_ONLY && !COUNT )
+    {
+        if( f.walkResolved != nullptr ) /* (the frame's: a scalar branch) */
+        {
+            vrc_pixel_walk_replay_resolved< MODE >( f, lut, pixelBuffer, px, py, rayIndex );
+            return;
+        }
+    }
     const E* const tab = reinterpret_cast< const E* >( lut );
     const uint32_t pixelPos = py * f.width + px;
     const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };

@@ -234,6 +234,10 @@ struct vrc_walk_count
  * into *result (device memory the caller zeroed on `stream`), nothing else is written; walkK > 0: the record pass fills
  * a.frame.walkCache and result is not used.  Not a march: no kernel note, no stop event */
 hipError_t vrc_launch_walk_record( const vrc_raycast_args& a, vrc_walk_count* result, hipStream_t stream );
+/* the resolved visit words of a lean frame's lists (vrc_core.h: vrc_walk_resolved_word): f.walkK planes of f.walkPlane
+ * words at `resolved` (device), from f.walkCache and f.slotInfo as they are on `stream`.  Not a march: no kernel note, no
+ * stop event */
+hipError_t vrc_launch_walk_resolve( const vrc_frame& f, uint32_t* resolved, hipStream_t stream );
 /* the march of a frame whose lists are valid (a.frame.walkCache, walkPlane, walkK; rayMode = VRC_RAY_LOAD); a.gridTable
  * is not read.  hipErrorInvalidValue for a frame outside the instance set */
 hipError_t vrc_launch_raycast_replay( const vrc_raycast_args& a, hipStream_t stream );

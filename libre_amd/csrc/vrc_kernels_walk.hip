@@ -16,6 +16,9 @@
  *                       dist) through vrc_pixel_walk_replay_lean, which neither fetches the node of a uniform visit nor
  *                       counts its steps again; the host picks the form per view (vrc_render), the count pass
  *                       reports whether every visit packs.
+ *   vrc_k_walk_resolve  the resolved visit words of lean lists (vrc_frame::walkResolved): one word per visit from the
+ *                       list word and the slot word, for the uncounted uniform-only instances of the replay.  Run once
+ *                       per set of lists, uploads and slot words.  Not a march either.
  * Instances: the ones the uniform-brick march exists for -- the table-driven point-sampling march of 8-bit voxels with
  * fixed-point stepping (VRC_MODE_TABLE, VRC_MODE_GREY), counted and uncounted, in the group sizes vrc_launch_raycast
  * picks for them.  Every other frame keeps the walk.
@@ -117,6 +120,26 @@ hipError_t vrc_launch_build_first_visit( const vrc_f4* lut, void* table, bool gr
     return hipGetLastError();
 }
 
+/* The resolved visit words (vrc_core.h: vrc_walk_resolved_word, vrc_frame::walkResolved): one lane per ray index below
+ * walkPlane, each writing the walkK words of its ray; visit by visit the lanes of a wave read and write neighbouring
+ * words of one plane.  Reads the lists and the slot words as they are on the stream */
+__global__ __launch_bounds__( 256 ) void vrc_k_walk_resolve( const vrc_frame f, uint32_t* __restrict__ resolved )
+{
+    const uint32_t rayIndex = blockIdx.x * 256u + threadIdx.x;
+    if( rayIndex >= f.walkPlane )
+        return;
+    for( uint32_t v = 0u; v < f.walkK; ++v )
+        resolved[(size_t)rayIndex + (size_t)v * f.walkPlane] = vrc_walk_resolved_word( f, rayIndex, v );
+}
+
+hipError_t vrc_launch_walk_resolve( const vrc_frame& f, uint32_t* resolved, hipStream_t stream )
+{
+    if( !resolved || !f.walkCache || f.walkK == 0u || f.walkPlane == 0u || f.walkLean == 0u || f.walkSlots == 0u )
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL( vrc_k_walk_resolve, dim3( ( f.walkPlane + 255u ) / 256u ), dim3( 256 ), 0, stream, f, resolved );
+    return hipGetLastError();
+}
+
 /* waves per SIMD, as vrc_k_raycast says them for the walking instances of the same march (vrc_kernels.hip) -- except that
  * the grey form in groups of 14, the judged instance, is allowed a sixth wave.  The walking instance is held at five
  * because six thrash the L1 under its gathers; the replay needs 76 registers (79 with the sample counter), and
@@ -183,15 +206,18 @@ __global__ __launch_bounds__( 64u * VRC_REPLAY_K_WAVES ) __attribute__( ( amdgpu
     }
     __syncthreads();
     /* from here on the waves of the workgroup are independent */
-    const uint32_t slotIndex = blockIdx.x * WAVES + ( tid >> 6 );
+    /* the slot and its tile are the wave's: said so, the schedule's read and the tile's division by tilesX are scalar
+     * work, and a lane adds its own 3 + 3 bits (vrc_core.h: vrc_replay_tile_origin) */
+    const uint32_t slotIndex = __builtin_amdgcn_readfirstlane( blockIdx.x * WAVES + ( tid >> 6 ) );
     const uint32_t tilesY = nTiles / tilesX;
     if( slotIndex >= vrc_schedule_slots( tilesX, tilesY ) )
         return;
-    const uint32_t tile = vrc_slot_tile( tileOrder, slotIndex, tilesX, tilesY );
+    const uint32_t tile = __builtin_amdgcn_readfirstlane( vrc_slot_tile( tileOrder, slotIndex, tilesX, tilesY ) );
     if( tile == VRC_NO_TILE )
         return;
-    uint32_t px, py;
-    vrc_walk_lane_pixel( tile, tilesX, lane, px, py );
+    uint32_t x0, y0, px, py;
+    vrc_replay_tile_origin( tile, tilesX, x0, y0 );
+    vrc_replay_lane_pixel( x0, y0, lane, px, py );
 
     uint32_t nSamples = 0;
     if( px < f.width && py < f.height )

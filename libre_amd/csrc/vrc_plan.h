@@ -5,7 +5,7 @@
  * pass renders (vrc_plan_mode), which kernel form marches it (vrc_plan_form, vrc_plan_use_lds), whether that is the
  * table walk kernel (vrc_plan_table_walk), how a replayed frame stores its pixels (vrc_plan_store_through) and whether
  * it takes its rays' first visits from a table (vrc_plan_first_visit, vrc_plan_first_visit_build) or may march a visit
- * without the exit test (vrc_plan_lean_free_march).  A
+ * without the exit test (vrc_plan_lean_free_march), or reads resolved visit words (vrc_plan_walk_resolved).  A
  * refusal is a code and a message; the ORDER of the refusals is part of the contract (tests/test_render_plan_cpu.py
  * holds both functions to the text they replaced, message for message).
  */
@@ -30,6 +30,7 @@ struct vrc_options
     int64_t storeThrough = 1;                  /* VRC_OPT_STORE_THROUGH */
     int64_t firstVisitTable = 1;               /* VRC_OPT_FIRST_VISIT_TABLE */
     int64_t leanFreeMarch = 1;                 /* VRC_OPT_LEAN_FREE_MARCH */
+    int64_t walkResolved = 1;                  /* VRC_OPT_WALK_RESOLVED */
 };
 
 /* what the frame's first vrc_render read of the options its later passes must not change (-1 / false: none yet; written
@@ -341,6 +342,16 @@ inline bool vrc_plan_first_visit_build( const vrc_options& o, const vrc_first_vi
 inline bool vrc_plan_lean_free_march( const vrc_options& o, int64_t walkUsed, uint32_t walkLean, bool classify )
 {
     return o.leanFreeMarch != 0 && walkUsed == 4 && walkLean != 0u && !classify && o.count == 0;
+}
+
+/* the resolved visit words (VRC_OPT_WALK_RESOLVED; vrc_core.h: vrc_walk_resolved_word, vrc_frame::walkResolved): where
+ * the option is on, the pass is handed the uniform-only instance (uniformOnly: vrc_frame::walkLean is
+ * VRC_WALK_LEAN_UNIFORM -- a replayed lean frame, its lists, the pool's uploads and slotInfo those the count pass read),
+ * does not count its samples -- the counted instances read the lists -- and the planes fit VRC_OPT_WALK_CACHE_BUDGET
+ * beside the lists (fits).  Such a pass builds the planes if it has none for its lists, uploads and slotInfo */
+inline bool vrc_plan_walk_resolved( const vrc_options& o, bool uniformOnly, bool fits )
+{
+    return o.walkResolved != 0 && uniformOnly && fits && o.count == 0;
 }
 
 #endif /* VRC_PLAN_H */

@@ -26,6 +26,7 @@ OPT_WALK_UNIFORM_ONLY, OPT_WALK_UNIFORM_ONLY_USED = 34, 35  # replay a view with
 OPT_STORE_THROUGH, OPT_STORE_THROUGH_USED = 36, 37  # write-through pixel stores in a replayed frame: 0 / 1 (default); read-only: 1 = the last render stored that way
 OPT_FIRST_VISIT_TABLE, OPT_FIRST_VISIT_TABLE_USED = 38, 39  # a replayed lean frame takes a ray's first uniform visit from a table: 0 / 1 (default); read-only: 1 = the last render did
 OPT_LEAN_FREE_MARCH, OPT_LEAN_FREE_MARCH_USED = 40, 41  # a replayed lean frame marches a uniform visit that cannot reach the exit threshold without the exit test: 0 / 1 (default); read-only: 1 = the last render allowed it
+OPT_WALK_RESOLVED, OPT_WALK_RESOLVED_USED = 42, 43  # the uniform-only replay reads one resolved word per visit: 0 / 1 (default); read-only: 1 = the last render did
 PREINT_VALUE, PREINT_TEXEL = 0, 1  # kinds of table vrc_get_preintegrated_table reports
 PROJECTION_COMPOSITE, PROJECTION_MIP, PROJECTION_ISO = 0, 1, 2
 MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2

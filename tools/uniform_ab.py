@@ -30,6 +30,10 @@ VRC_OPT_FIRST_VISIT_TABLE_USED reading what was asked before the clock runs and 
 VRC_OPT_LEAN_FREE_MARCH (a visit that cannot reach the exit threshold marched with the exit test against without) the same way:
        python tools/uniform_ab.py --free-march [--steps 2000] [--rounds 3]
 Uncounted replayed frames again (the counted instances hold no such body), VRC_OPT_LEAN_FREE_MARCH_USED read as above.
+VRC_OPT_WALK_RESOLVED (the uniform-only replay reading list and slot words against resolved visit words) the same way:
+       python tools/uniform_ab.py --resolved [--steps 2000] [--rounds 3]
+Uncounted replayed frames again (the counted instances read the lists), VRC_OPT_WALK_RESOLVED_USED read as above.
+With --libs it times every library that knows the option at 0 and at 1 beside those that do not, as --uniform-only does.
 With --steps of 200 or more, --libs reports the wall time per frame and the mean kernel time of such a loop as well.
 VRC_OPT_WALK_UNIFORM_ONLY (the lean replay against its uniform-only instance) beside builds, in one process:
        python tools/uniform_ab.py --uniform-only --libs parent=variants/libvrc_hip_parent.so new=libre_amd/lib/libvrc_hip.so
@@ -92,10 +96,13 @@ def several(a):
             vrc.check(L, L.vrc_set_option(scenes[name].ctx, vrc.OPT_WALK_CACHE, vrc.WALK_CACHE_ALWAYS))
     # --uniform-only: a library that knows VRC_OPT_WALK_UNIFORM_ONLY is timed at 0 and at 1 (NAME@0, NAME@1: one context,
     # the same lists, the option set in front of every timed loop); one that does not is timed once, as NAME
+    # --resolved with --libs: the same with VRC_OPT_WALK_RESOLVED (NAME@0 is the build without its resolved words)
+    sided = a.uniform_only or a.resolved
+    option = vrc.OPT_WALK_RESOLVED if a.resolved else vrc.OPT_WALK_UNIFORM_ONLY
     sides = []  # (label, library's name, value of the option or None)
     for name in names:
         g = scenes[name]
-        if a.uniform_only and g.L.vrc_set_option(g.ctx, vrc.OPT_WALK_UNIFORM_ONLY, 1) == 0:
+        if sided and g.L.vrc_set_option(g.ctx, option, 1) == 0:
             sides += [(name + "@0", name, 0), (name + "@1", name, 1)]
         else:
             sides.append((name, name, None))
@@ -103,17 +110,22 @@ def several(a):
     def select(side):
         g = scenes[side[1]]
         if side[2] is not None:
-            vrc.check(g.L, g.L.vrc_set_option(g.ctx, vrc.OPT_WALK_UNIFORM_ONLY, side[2]))
+            vrc.check(g.L, g.L.vrc_set_option(g.ctx, option, side[2]))
         return g
     first = None
     for side in sides:
         g = select(side)
-        for _ in range(7 if a.uniform_only else 1):  # (--uniform-only: the frame compared is a replayed one)
+        for _ in range(7 if sided else 1):  # (--uniform-only, --resolved: the frame compared is a replayed one)
             fb, n = g.render(count=True)[:2]
         if first is None:
             first = (fb, n)
         assert (fb == first[0]).all() and n == first[1], "%s: frame or count differs from %s" % (side[0], sides[0][0])
-        if side[2] is not None:
+        if side[2] is not None and a.resolved:  # (the words serve uncounted frames: read back behind one)
+            g.render(count=False)
+            used = C.c_int64(-1)
+            vrc.check(g.L, g.L.vrc_get_option(g.ctx, vrc.OPT_WALK_RESOLVED_USED, C.byref(used)))
+            assert used.value == side[2] or a.volume != "mem", "%s: VRC_OPT_WALK_RESOLVED_USED reads %d" % (side[0], used.value)
+        elif side[2] is not None:
             used = C.c_int64(-1)
             vrc.check(g.L, g.L.vrc_get_option(g.ctx, vrc.OPT_WALK_UNIFORM_ONLY_USED, C.byref(used)))
             assert used.value == side[2] or a.volume != "mem", "%s: VRC_OPT_WALK_UNIFORM_ONLY_USED reads %d" % (side[0], used.value)
@@ -156,10 +168,11 @@ def markers(a, option=None, names=("lean", "markers")):
     g = GpuScene(s, lib=L)
     frames = {}
     walk = option == vrc.OPT_WALK_CACHE
-    first = option in (vrc.OPT_FIRST_VISIT_TABLE, vrc.OPT_LEAN_FREE_MARCH)  # (what serves uncounted frames alone)
+    first = option in (vrc.OPT_FIRST_VISIT_TABLE, vrc.OPT_LEAN_FREE_MARCH, vrc.OPT_WALK_RESOLVED)  # (what serves uncounted frames alone)
     store = option == vrc.OPT_STORE_THROUGH or first  # (both sides are replayed frames: the option starts nothing over)
     read_back = {vrc.OPT_FIRST_VISIT_TABLE: vrc.OPT_FIRST_VISIT_TABLE_USED,
-                 vrc.OPT_LEAN_FREE_MARCH: vrc.OPT_LEAN_FREE_MARCH_USED}.get(option, vrc.OPT_STORE_THROUGH_USED)
+                 vrc.OPT_LEAN_FREE_MARCH: vrc.OPT_LEAN_FREE_MARCH_USED,
+                 vrc.OPT_WALK_RESOLVED: vrc.OPT_WALK_RESOLVED_USED}.get(option, vrc.OPT_STORE_THROUGH_USED)
     on = vrc.WALK_CACHE_ALWAYS if walk else 1  # (the replay on any volume: at 1 a view that gathers keeps the walk)
     settle = 6 if walk or store else 3  # synchronised frames until the steady state (the ray cache: computed, stored,
     #                                     loaded; the walk cache: counted, recorded and replayed behind that)
@@ -234,7 +247,10 @@ def main():
     ap.add_argument("--store-through", action="store_true", help="A/B of VRC_OPT_STORE_THROUGH instead (see above)")
     ap.add_argument("--first-visit", action="store_true", help="A/B of VRC_OPT_FIRST_VISIT_TABLE instead (see above)")
     ap.add_argument("--free-march", action="store_true", help="A/B of VRC_OPT_LEAN_FREE_MARCH instead (see above)")
+    ap.add_argument("--resolved", action="store_true", help="A/B of VRC_OPT_WALK_RESOLVED instead (see above)")
     a = ap.parse_args()
+    if a.resolved and not a.libs:
+        return markers(a, vrc.OPT_WALK_RESOLVED, ("lists", "resolved"))
     if a.first_visit:
         return markers(a, vrc.OPT_FIRST_VISIT_TABLE, ("marched", "table"))
     if a.free_march:
