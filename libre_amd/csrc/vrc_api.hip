@@ -139,66 +139,22 @@ struct vrc_pool
     std::vector< std::array< uint32_t, 3 > > slotSize;
 };
 
-/* walk cache (VRC_OPT_WALK_CACHE; vrc_core.h: vrc_frame::walkCache).  state: IDLE nothing known; COUNTING the count pass
- * is on the stream, its result on the way to hMax behind ev; VALID the planes hold the lists of frame's constants over
- * the node table as it is.  Nothing here exists before the first count pass: a camera that moves every frame allocates
- * nothing.  The count pass runs only for a frame whose constants, node list and (option at 1) pool uploads are those of
- * the vrc_render before, prev*: what changes every call -- passes over different node subsets, bricks streaming in --
- * launches nothing extra.  gen, slotInfo: the uploads and uniformity words the count pass read (render_walk_cache) */
+/* walk cache (VRC_OPT_WALK_CACHE; vrc_core.h: vrc_frame::walkCache): the device memory, the event and the frames.  What it
+ * remembers and decides is vrc_plan.h's (s: vrc_walk_state); nothing here exists before the first count pass */
 struct vrc_walk_cache
 {
-    enum { IDLE = 0, COUNTING = 1, VALID = 2 };
-    int state = IDLE;
+    vrc_walk_state s;
     uint32_t* dLists = nullptr;
     size_t words = 0;               /* allocated */
-    uint32_t k = 0;                 /* visits per ray the planes hold */
     vrc_walk_count* dMax = nullptr; /* the count pass's result, and its pinned copy */
     vrc_walk_count* hMax = nullptr;
     hipEvent_t ev = nullptr;
-    vrc_frame frame;
-    vrc_frame prevFrame;
-    bool prevSet = false;
-    uint64_t prevGen = 0, gen = 0;
-    const uint32_t* slotInfo = nullptr;
-    int64_t used = 0; /* VRC_OPT_WALK_CACHE_USED */
-    /* the form of the lists (vrc_core.h: vrc_frame::walkLean).  leanAsked: what the host saw when the count pass went
-     * out -- a step that vrc_exact_step_count counts, a pool whose slot indices fit the word -- and so what that pass was
-     * asked to check; part of what the lists are valid for.  lean: the form the record pass wrote.  leanUsed:
-     * VRC_OPT_WALK_LEAN_USED */
-    bool leanAsked = false, lean = false;
-    int64_t leanUsed = 0;
-    /* the uniform-only replay (VRC_OPT_WALK_UNIFORM_ONLY).  gathers: what the count pass of the lists in the planes
-     * said of the slot words it read, those of gen and slotInfo -- compared for this whatever VRC_OPT_WALK_CACHE
-     * says, because at VRC_WALK_CACHE_ALWAYS the lists outlive an upload and that answer does not.  uniformUsed:
-     * VRC_OPT_WALK_UNIFORM_ONLY_USED */
-    unsigned long long gathers = 0;
-    int64_t uniformUsed = 0;
-    int64_t throughUsed = 0; /* VRC_OPT_STORE_THROUGH_USED */
-    int64_t freeUsed = 0;    /* VRC_OPT_LEAN_FREE_MARCH_USED */
-    /* the resolved visit words of the uniform-only replay (VRC_OPT_WALK_RESOLVED; vrc_core.h: vrc_walk_resolved_word): k
-     * planes beside the lists, built from them and from the slot words by the first frame that is handed the
-     * uniform-only instance without them.  resolvedValid: the planes hold the words of the lists in dLists as recorded
-     * (a record pass ends it) under the uploads resolvedGen and the array resolvedSlotInfo; a frame that finds another
-     * of the three takes the list words and drops the planes.  resolvedUsed: VRC_OPT_WALK_RESOLVED_USED */
-    uint32_t* dResolved = nullptr;
-    size_t resolvedWords = 0; /* allocated */
-    bool resolvedValid = false;
-    uint64_t resolvedGen = 0;
-    const uint32_t* resolvedSlotInfo = nullptr;
-    int64_t resolvedUsed = 0;
-};
-
-/* the first-visit table of the lean replay (VRC_OPT_FIRST_VISIT_TABLE; vrc_core.h: vrc_first_visit_row).  It depends on
- * the classified table alone -- transfer function, opacity correction -- and on the form the frame marches, not on the
- * view, the volume or the lists.  dTable: allocated by the first build, for the four-float form.  gen, grey: the
- * generation (vrc_ctx::lutGen) and form it was built for (gen 0: never).  prevGen: the generation the vrc_render before
- * rendered with (0: none).  used: VRC_OPT_FIRST_VISIT_TABLE_USED */
-struct vrc_first_visit
-{
-    void* dTable = nullptr;
-    uint64_t gen = 0, prevGen = 0;
-    bool grey = false;
-    int64_t used = 0;
+    vrc_frame frame;     /* the frame the lists were counted for */
+    vrc_frame prevFrame; /* the frame of the vrc_render before */
+    uint32_t* dResolved = nullptr; /* the resolved visit words (VRC_OPT_WALK_RESOLVED) */
+    size_t resolvedWords = 0;      /* allocated */
+    void* dFirstVisit = nullptr;   /* the first-visit table (VRC_OPT_FIRST_VISIT_TABLE): allocated by the first build, for
+                                    * the four-float form */
 };
 
 struct vrc_ctx
@@ -226,7 +182,6 @@ struct vrc_ctx
     bool lutLinear = false;
     uint32_t lutLevels = 1;
     uint64_t lutGen = 0; /* bumped wherever render_tables rebuilds the classified table (0: never built) */
-    vrc_first_visit first;
 
     /* pixel buffer (cuda::PixelBufferObject) */
     vrc_f4* fbOwn = nullptr;
@@ -270,16 +225,16 @@ struct vrc_ctx
     bool tileOrderValid = false;
     uint32_t tileOrderReused = 0; /* frames in a row that kept the schedule of a nearby view */
     vrc_frame tileOrderFrame;
-    /* ray cache (VRC_OPT_RAY_CACHE; vrc_core.h: vrc_frame::rayCache): the planes, regrown like dTileOrder; the frame
-     * constants of the vrc_render before (rayPrevSet: there was one that could have used the cache) and whether the
-     * planes hold the rays of exactly those constants; the mode the last vrc_render used (VRC_OPT_RAY_CACHE_USED) */
+    /* ray cache (VRC_OPT_RAY_CACHE; vrc_core.h: vrc_frame::rayCache): the planes, regrown like dTileOrder; what it
+     * remembers (vrc_plan.h) and the frame constants of the vrc_render before; the mode the last vrc_render used
+     * (VRC_OPT_RAY_CACHE_USED) */
     float* dRayCache = nullptr;
     size_t dRayCacheCap = 0; /* words per plane */
-    bool rayCacheValid = false;
-    bool rayPrevSet = false;
+    vrc_ray_state ray;
     vrc_frame rayPrevFrame;
     int64_t rayCacheUsed = 0;
     vrc_walk_cache walk;
+    vrc_walk_plan walkPlan; /* what the last vrc_render did about the walk cache (vrc_plan.h; VRC_OPT_*_USED) */
     bool rayLod = false; /* vrc_set_ray_lod */
     float rayLodSse = 1.0f, rayLodWorldPerPixel = 0.0f;
 
@@ -505,7 +460,7 @@ void vrc_ctx_destroy( vrc_ctx* c )
     const std::initializer_list< void* > device = {
         c->dTf,      c->dLut,     c->dPreint,  c->fbOwn,     c->dNodes,    c->dGrid,    c->dTileOrder, c->dRayCache,
         c->walk.dLists, c->walk.dMax, c->dRayList, c->dMipMax, c->dMeanSum, c->dMeanCount, c->dProjOut, c->dMipDepth,
-        c->dIsoGrad, c->dDepthOut, c->dRowMap, c->dCounter,  c->dFrameHist, c->dHistRefs, c->first.dTable,
+        c->dIsoGrad, c->dDepthOut, c->dRowMap, c->dCounter,  c->dFrameHist, c->dHistRefs, c->walk.dFirstVisit,
         c->walk.dResolved };
     const std::initializer_list< void* > pinned = { c->hTf, c->hStage, c->walk.hMax, c->hCounter, c->hFrameHist, c->hHistRefs };
     for( void* d : device )
@@ -530,8 +485,8 @@ int vrc_ctx_set_stream( vrc_ctx* c, void* s )
     VRC_HIP_CHECK( hipStreamSynchronize( c->stream ) );
     c->stream = s ? (hipStream_t)s : c->ownStream;
     c->waitedPoolUid = c->waitedGen = 0; /* the new stream has waited for no upload */
-    c->rayCacheValid = c->rayPrevSet = false; /* (the planes were written on the stream before) */
-    c->walk.state = vrc_walk_cache::IDLE;        /* (and so were the lists; a count pass in flight has ended above) */
+    vrc_ray_forget( c->ray );         /* (the planes were written on the stream before) */
+    vrc_walk_forget( c->walk.s ); /* (and so were the lists; a count pass in flight has ended above) */
     return VRC_OK;
 }
 
@@ -567,21 +522,21 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
     case VRC_OPT_STREAM_MARKERS: c->opt.streamMarkers = value ? 1 : 0; return VRC_OK;
     case VRC_OPT_RAY_CACHE:
         if( c->opt.rayCache != ( value ? 1 : 0 ) )
-            c->rayCacheValid = c->rayPrevSet = false;
+            vrc_ray_forget( c->ray );
         c->opt.rayCache = value ? 1 : 0;
         return VRC_OK;
     case VRC_OPT_WALK_CACHE:
         if( value < 0 || value > VRC_WALK_CACHE_ALWAYS )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_CACHE is 0 (off), 1 (on) or 2 (on for every view)" );
         if( c->opt.walkCache != value )
-            c->walk.state = vrc_walk_cache::IDLE;
+            vrc_walk_forget( c->walk.s );
         c->opt.walkCache = value;
         return VRC_OK;
     case VRC_OPT_WALK_CACHE_BUDGET:
         if( value < 0 )
             return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_CACHE_BUDGET is a number of bytes" );
         if( c->opt.walkBudget != value )
-            c->walk.state = vrc_walk_cache::IDLE;
+            vrc_walk_forget( c->walk.s );
         c->opt.walkBudget = value;
         return VRC_OK;
     case VRC_OPT_WALK_UNIFORM_ONLY:
@@ -703,20 +658,20 @@ int vrc_get_option( vrc_ctx* c, int option, int64_t* value )
     case VRC_OPT_RAY_CACHE: *value = c->opt.rayCache; return VRC_OK;
     case VRC_OPT_RAY_CACHE_USED: *value = c->rayCacheUsed; return VRC_OK;
     case VRC_OPT_WALK_CACHE: *value = c->opt.walkCache; return VRC_OK;
-    case VRC_OPT_WALK_CACHE_USED: *value = c->walk.used; return VRC_OK;
+    case VRC_OPT_WALK_CACHE_USED: *value = c->walkPlan.used; return VRC_OK;
     case VRC_OPT_WALK_CACHE_BUDGET: *value = c->opt.walkBudget; return VRC_OK;
     case VRC_OPT_WALK_CACHE_BYTES: *value = (int64_t)( c->walk.words * sizeof( uint32_t ) ); return VRC_OK;
-    case VRC_OPT_WALK_LEAN_USED: *value = c->walk.leanUsed; return VRC_OK;
+    case VRC_OPT_WALK_LEAN_USED: *value = c->walkPlan.leanUsed; return VRC_OK;
     case VRC_OPT_WALK_UNIFORM_ONLY: *value = c->opt.walkUniformOnly; return VRC_OK;
-    case VRC_OPT_WALK_UNIFORM_ONLY_USED: *value = c->walk.uniformUsed; return VRC_OK;
+    case VRC_OPT_WALK_UNIFORM_ONLY_USED: *value = c->walkPlan.uniformUsed; return VRC_OK;
     case VRC_OPT_STORE_THROUGH: *value = c->opt.storeThrough; return VRC_OK;
-    case VRC_OPT_STORE_THROUGH_USED: *value = c->walk.throughUsed; return VRC_OK;
+    case VRC_OPT_STORE_THROUGH_USED: *value = c->walkPlan.storeThrough; return VRC_OK;
     case VRC_OPT_FIRST_VISIT_TABLE: *value = c->opt.firstVisitTable; return VRC_OK;
-    case VRC_OPT_FIRST_VISIT_TABLE_USED: *value = c->first.used; return VRC_OK;
+    case VRC_OPT_FIRST_VISIT_TABLE_USED: *value = c->walkPlan.firstVisit; return VRC_OK;
     case VRC_OPT_LEAN_FREE_MARCH: *value = c->opt.leanFreeMarch; return VRC_OK;
-    case VRC_OPT_LEAN_FREE_MARCH_USED: *value = c->walk.freeUsed; return VRC_OK;
+    case VRC_OPT_LEAN_FREE_MARCH_USED: *value = c->walkPlan.leanFree; return VRC_OK;
     case VRC_OPT_WALK_RESOLVED: *value = c->opt.walkResolved; return VRC_OK;
-    case VRC_OPT_WALK_RESOLVED_USED: *value = c->walk.resolvedUsed; return VRC_OK;
+    case VRC_OPT_WALK_RESOLVED_USED: *value = c->walkPlan.resolved; return VRC_OK;
     case VRC_OPT_PROJECTION: *value = c->opt.projection; return VRC_OK;
     case VRC_OPT_MIP_SKIP: *value = c->opt.mipSkip; return VRC_OK;
     case VRC_OPT_MIP_FOLD: *value = c->opt.mipFold; return VRC_OK;
@@ -1572,8 +1527,8 @@ int vrc_set_row_map( vrc_ctx* c, const uint32_t* rows, uint32_t n )
         VRC_HIP_CHECK( hipMemcpy( c->dRowMap, rows, n * sizeof( uint32_t ), hipMemcpyHostToDevice ) );
     c->rowMap.assign( rows, rows + n );
     c->tileOrderValid = false;
-    c->rayCacheValid = c->rayPrevSet = false;
-    c->walk.state = vrc_walk_cache::IDLE; /* (the stream was synchronised above) */
+    vrc_ray_forget( c->ray );
+    vrc_walk_forget( c->walk.s ); /* (the stream was synchronised above) */
     return VRC_OK;
 }
 
@@ -1688,8 +1643,6 @@ struct render_pass
     vrc_form form;
     bool sameNodes, tableWalk; /* the node list of the vrc_render before, on the same pool; vrc_plan_table_walk */
     size_t pixels, plane; /* of the pixel buffer in use; of a plane of the ray and walk caches: its whole tiles */
-    bool walkCount, walkRecord; /* render_walk_cache: run the count / the record pass in front of this march */
-    bool walkResolve;           /* ... or build the resolved visit words the march reads (vrc_walk_cache::dResolved) */
     vrc_raycast_args a;
 };
 
@@ -1750,7 +1703,7 @@ static int render_tables( vrc_ctx* c, render_pass& p )
         c->lutLevels = lutLevels;
         c->lutTfVersion = c->tfVersion;
         c->lutValid = true;
-        ++c->lutGen; /* (what was built from the table before -- vrc_first_visit -- is no longer current) */
+        ++c->lutGen; /* (what was built from the table before -- the first-visit table -- is no longer current) */
         /* the largest classified opacity of a sample (same function as the device table, evaluated on the
          * pinned copy of the transfer function): decides whether early ray termination can occur at all */
         c->lutMaxAlpha = 1.0f;
@@ -1802,7 +1755,7 @@ static int render_nodes( vrc_ctx* c, render_pass& p )
                   std::memcmp( c->cachedNodes.data(), p.nodes, p.nNodes * sizeof( vrc_node_data ) ) == 0;
     if( p.sameNodes )
         return VRC_OK;
-    c->walk.state = vrc_walk_cache::IDLE; /* the walk cache's lists index the node table that is replaced here */
+    vrc_walk_forget( c->walk.s ); /* the walk cache's lists index the node table that is replaced here */
     vrc_host_tables t;
     const vrc_atlas_geom geom = pool_geom( p.pool );
     vrc_build_tables( geom, p.nodes, p.nNodes, t );
@@ -2133,10 +2086,8 @@ static int render_split_and_compact( vrc_ctx* c, render_pass& p )
 }
 
 /* ray cache (VRC_OPT_RAY_CACHE): the tile-scheduled grid walk of vrc_k_raycast only (vrc_pixel_grid_dda; the
- * supersampled GL variant, whose rays are jittered, is not a grid walk).  A frame whose ray constants differ from
- * those of the vrc_render before computes its rays (a moving camera pays nothing); the first that repeats them
- * also stores them, and the ones after that load them.  The kernel-visible fields are set here, after the tile
- * schedule compared frames */
+ * supersampled GL variant, whose rays are jittered, is not a grid walk).  Compute, store or load: vrc_plan_ray_cache.
+ * The kernel-visible fields are set here, after the tile schedule compared frames */
 static int render_ray_cache( vrc_ctx* c, render_pass& p )
 {
     vrc_frame& f = p.a.frame;
@@ -2145,194 +2096,108 @@ static int render_ray_cache( vrc_ctx* c, render_pass& p )
     const bool eligible = c->opt.rayCache && p.form.useDda && !p.form.useLds && !c->rayLod && !p.mode.mip && !p.form.glSuper &&
                           !p.a.depthSplit && p.a.ertParts <= 1 && VRC_TILE_W * VRC_TILE_H == 64u &&
                           plane * VRC_RAY_CACHE_PLANES <= 0xFFFFFFFFull; /* (32-bit word offsets in the kernel) */
-    if( !eligible )
-        c->rayCacheValid = c->rayPrevSet = false;
-    else
-    {
-        const bool same = c->rayPrevSet && ray_constants_equal( c->rayPrevFrame, f );
-        if( !same )
-            c->rayCacheValid = false;
-        else if( !c->rayCacheValid )
-        {
-            VRC_TRY( ctx_grow( c, c->dRayCacheCap, plane, plane, { { c->dRayCache, VRC_RAY_CACHE_PLANES * sizeof( float ) } } ) );
-            c->rayCacheUsed = VRC_RAY_STORE; /* (valid once the march is on the stream: render_march) */
-        }
-        else
-            c->rayCacheUsed = VRC_RAY_LOAD;
+    const bool same = eligible && c->ray.prevSet && ray_constants_equal( c->rayPrevFrame, f );
+    const uint32_t mode = vrc_plan_ray_cache( c->ray, eligible, same );
+    if( mode == VRC_RAY_STORE ) /* (valid once the march is on the stream: render_march) */
+        VRC_TRY( ctx_grow( c, c->dRayCacheCap, plane, plane, { { c->dRayCache, VRC_RAY_CACHE_PLANES * sizeof( float ) } } ) );
+    c->rayCacheUsed = mode;
+    if( eligible )
         std::memcpy( &c->rayPrevFrame, &f, sizeof( f ) );
-        c->rayPrevSet = true;
-    }
-    f.rayMode = (uint32_t)c->rayCacheUsed;
-    f.rayCache = c->rayCacheUsed ? c->dRayCache : nullptr;
-    f.rayCachePlane = c->rayCacheUsed ? (uint32_t)plane : 0u;
+    f.rayMode = mode;
+    f.rayCache = mode ? c->dRayCache : nullptr;
+    f.rayCachePlane = mode ? (uint32_t)plane : 0u;
     return VRC_OK;
 }
 
-/* walk cache (VRC_OPT_WALK_CACHE): a frame that loads its rays, of the instances the replay march exists for
- * (vrc_internal.h: vrc_walk_replay_eligible).  The first such frame also runs the count pass; the first one after
- * its result has arrived (polled, never waited for) sizes the planes and runs the record pass; the ones after that
- * replay.  Both passes go on the stream in front of the march's timing pair and are no marches: not timed, not
- * counted as launches.  Whatever the lists depend on starts over when it changes: walk_constants_equal here,
- * the node list in render_nodes, the stream, the row map and the options where they are set; the transfer function, the
- * uniformity words and the pixel buffer's contents are not among them.  What the lists do not depend on may still
- * decide whether they are worth using: where every visit gathers the replay is no faster than the walk, and by 1 to
- * 3 % slower (profiles/r10_walk_cache.txt), so with the option at 1 a view more than half of whose visits gather, by
- * the count pass and the uniformity words it read, is not recorded and stays on the walk until the pool's uploads or
- * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold.
- * Decides: walkCount / walkRecord (the passes render_march launches), walk.used (VRC_OPT_WALK_CACHE_USED: 0 walk,
- * 1 count, 2 waiting for the count, 3 record, 4 replay), walk.leanUsed, walk.uniformUsed, walk.throughUsed,
- * walk.freeUsed, walk.resolvedUsed, walkResolve (the build of the resolved visit words render_march launches), and the
- * frame's walk fields, storeThrough, firstVisit, leanFree and walkResolved */
+/* has the count pass's answer arrived?  Polled, never waited for */
+static int walk_poll( vrc_walk_cache& w, vrc_walk_counted& n )
+{
+    const hipError_t q = hipEventQuery( w.ev );
+    if( q == hipErrorNotReady )
+        (void)hipGetLastError(); /* (not an error: nothing later may find it there) */
+    else if( q != hipSuccess )
+        VRC_HIP_CHECK( q );
+    if( q == hipSuccess )
+        n = { true, w.hMax->longest, w.hMax->notLean, w.hMax->visits, w.hMax->gathers };
+    return VRC_OK;
+}
+
+/* what the plan asks for, in the order vrc_walk_reached names: the count pass's three objects or the lists; the
+ * first-visit table, built here; the resolved planes */
+static int walk_allocate( vrc_ctx* c, const vrc_walk_plan& pl, bool grey, vrc_walk_reached& reached )
+{
+    vrc_walk_cache& w = c->walk;
+    reached = VRC_WALK_REACHED_NOTHING;
+    if( pl.count && !w.dMax )
+    {
+        VRC_HIP_CHECK( hipMalloc( &w.dMax, sizeof( vrc_walk_count ) ) );
+        VRC_HIP_CHECK( hipHostMalloc( &w.hMax, sizeof( vrc_walk_count ) ) );
+        VRC_HIP_CHECK( hipEventCreateWithFlags( &w.ev, hipEventDisableTiming ) );
+    }
+    if( pl.record )
+        VRC_TRY( ctx_grow( c, w.words, pl.listWords, pl.listWords, { w.dLists } ) );
+    reached = VRC_WALK_REACHED_LISTS;
+    if( pl.firstVisitBuild )
+    {
+        if( !w.dFirstVisit )
+            VRC_HIP_CHECK( hipMalloc( &w.dFirstVisit, (size_t)VRC_FIRST_VISIT_ENTRIES * VRC_FIRST_VISIT_ROWS * sizeof( vrc_f4 ) ) );
+        VRC_HIP_CHECK( vrc_launch_build_first_visit( c->dLut, w.dFirstVisit, grey, c->stream ) );
+    }
+    reached = VRC_WALK_REACHED_TABLE;
+    if( pl.resolveBuild )
+        VRC_TRY( ctx_grow( c, w.resolvedWords, pl.resolvedWords, pl.resolvedWords, { w.dResolved } ) );
+    reached = VRC_WALK_REACHED_ALL;
+    return VRC_OK;
+}
+
+/* walk cache (VRC_OPT_WALK_CACHE) and the riders of its replay: the rules are vrc_plan.h's.  Here: the facts, the poll,
+ * the memory, and the frame's fields from the plan (c->walkPlan; render_march launches what it asks for) */
 static int render_walk_cache( vrc_ctx* c, render_pass& p )
 {
     vrc_walk_cache& w = c->walk;
     vrc_frame& f = p.a.frame;
-    const size_t plane = p.plane;
-    w.used = 0;
-    w.leanUsed = 0;
-    w.uniformUsed = 0;
-    w.throughUsed = 0;
-    w.freeUsed = 0;
-    f.walkCache = nullptr;
-    f.walkPlane = f.walkK = 0u;
-    f.walkLean = f.walkSlots = 0u;
-    p.walkCount = p.walkRecord = false;
-    /* the form of the lists.  A lean list (vrc_core.h: vrc_frame::walkLean) holds every visit's step count and slot
-     * index in one word of 12 + 20 bits.  What the host can see of that: the step is one vrc_exact_step_count counts
-     * (its own test, asked here with a travel that passes it), and the pool's slot indices fit.  The rest -- no
-     * visit whose count is inexact or takes more than 12 bits -- the count pass reports with the count */
     uint32_t one = 0u;
     const size_t nSlots = p.pool->resident.size();
-    const bool leanAsked = vrc_exact_step_count( f.stepSize, f.stepSize, &one ) && nSlots >= 1u &&
-                           nSlots < ( (size_t)1u << VRC_WALK_LEAN_INDEX_BITS );
-    const auto fits = [&]( uint32_t k ) { /* the planes of k visits: 32-bit word offsets in the kernels, and the budget */
-        const unsigned long long words = ( 1ull + 4ull * k ) * plane;
-        return words <= 0xFFFFFFFFull && words * sizeof( uint32_t ) <= (unsigned long long)c->opt.walkBudget;
-    };
-    const bool eligible = c->opt.walkCache && c->rayCacheUsed == VRC_RAY_LOAD && vrc_walk_replay_eligible( p.a ) &&
-                          f.nodeCount > 0u && plane > 0u && fits( 1u );
-    const bool byContent = c->opt.walkCache != VRC_WALK_CACHE_ALWAYS;
-    const uint64_t gen = p.pool->uploadGen; /* (compared only where the choice goes by the bricks' content) */
-    if( !eligible || ( w.state != vrc_walk_cache::IDLE &&
-                       ( !walk_constants_equal( w.frame, f ) || leanAsked != w.leanAsked ||
-                         ( byContent && ( w.gen != gen || w.slotInfo != f.slotInfo ) ) ) ) )
-        w.state = vrc_walk_cache::IDLE;
-    const bool repeats = p.sameNodes && w.prevSet && ( !byContent || w.prevGen == gen ) && walk_constants_equal( w.prevFrame, f );
+    vrc_walk_facts k;
+    k.eligibleSoFar = c->opt.walkCache && c->rayCacheUsed == VRC_RAY_LOAD && vrc_walk_replay_eligible( p.a ) &&
+                      f.nodeCount > 0u && p.plane > 0u;
+    k.leanAsked = vrc_exact_step_count( f.stepSize, f.stepSize, &one ) && nSlots >= 1u &&
+                  nSlots < ( (size_t)1u << VRC_WALK_LEAN_INDEX_BITS );
+    k.sameAsListed = w.s.state != VRC_WALK_IDLE && walk_constants_equal( w.frame, f );
+    k.sameAsPrev = w.s.prevSet && walk_constants_equal( w.prevFrame, f );
+    k.sameNodes = p.sameNodes;
+    k.uploadGen = p.pool->uploadGen;
+    k.slotInfo = f.slotInfo;
+    k.plane = p.plane;
+    k.nSlots = nSlots;
+    k.width = f.width;
+    k.height = f.height;
+    k.clearFirst = f.clearFirst != 0u;
+    k.classify = p.mode.classify;
+    k.greyTable = p.a.greyTable;
+    k.lutGen = c->lutGen;
+    vrc_walk_plan pl;
+    vrc_walk_counted n;
+    int rc = VRC_OK;
+    if( vrc_walk_open( c->opt, w.s, k, pl ) )
+        rc = walk_poll( w, n );
     std::memcpy( &w.prevFrame, &f, sizeof( f ) );
-    w.prevSet = true;
-    w.prevGen = gen;
-    if( eligible && w.state == vrc_walk_cache::IDLE && repeats )
-    {
-        if( !w.dMax )
-        {
-            VRC_HIP_CHECK( hipMalloc( &w.dMax, sizeof( vrc_walk_count ) ) );
-            VRC_HIP_CHECK( hipHostMalloc( &w.hMax, sizeof( vrc_walk_count ) ) );
-            VRC_HIP_CHECK( hipEventCreateWithFlags( &w.ev, hipEventDisableTiming ) );
-        }
-        p.walkCount = true;
-        w.leanAsked = leanAsked;
-        w.gen = gen;
-        w.slotInfo = f.slotInfo;
-        w.used = 1;
-    }
-    else if( eligible && w.state == vrc_walk_cache::COUNTING )
-    {
-        w.used = 2;
-        const hipError_t q = hipEventQuery( w.ev );
-        if( q == hipErrorNotReady )
-            (void)hipGetLastError(); /* (not an error: nothing later may find it there) */
-        else if( q != hipSuccess )
-            VRC_HIP_CHECK( q );
-        if( q == hipSuccess )
-        {
-            const uint32_t k = w.hMax->longest > 0u ? w.hMax->longest : 1u;
-            if( !fits( k ) )
-                w.used = 0; /* over the budget or the offset limit: this view stays on the walk */
-            else if( byContent && 2u * w.hMax->gathers > w.hMax->visits )
-                w.used = 0; /* most visits gather: so does this one */
-            else
-            {
-                const size_t words = ( 1u + 4u * (size_t)k ) * plane;
-                VRC_TRY( ctx_grow( c, w.words, words, words, { w.dLists } ) );
-                w.k = k;
-                w.lean = w.leanAsked && w.hMax->notLean == 0u;
-                w.gathers = w.hMax->gathers;
-                p.walkRecord = true;
-                w.used = 3;
-            }
-        }
-    }
-    else if( eligible && w.state == vrc_walk_cache::VALID )
-        w.used = 4;
-    /* (eligible, IDLE and not a repeat: mode 0 -- the next call counts if it is this one again) */
-    if( p.walkRecord || w.used == 4 )
-    {
-        f.walkCache = w.dLists;
-        f.walkPlane = (uint32_t)plane;
-        f.walkK = w.k;
-        f.walkLean = w.lean ? 1u : 0u;
-        f.walkSlots = (uint32_t)nSlots;
-        w.leanUsed = ( w.lean && w.used == 4 ) ? 1 : 0;
-        /* the uniform-only instance (vrc_kernels_walk.hip): a replayed lean frame none of whose visits gathers --
-         * by the count pass of these lists, which is still the answer while the pool has taken no upload and the
-         * words are the ones it read.  Where the lists outlive that (VRC_WALK_CACHE_ALWAYS) the frame goes back to
-         * the lean instance and keeps them */
-        if( w.leanUsed && c->opt.walkUniformOnly && w.gathers == 0ull && w.gen == gen && w.slotInfo == f.slotInfo )
-        {
-            f.walkLean = VRC_WALK_LEAN_UNIFORM;
-            w.uniformUsed = 1;
-        }
-    }
-    else if( p.walkCount )
-        f.walkLean = leanAsked ? 1u : 0u; /* (the count pass: check every visit) */
-    /* how the replay stores its pixels (vrc_core.h: vrc_store_pixel): set behind prevFrame's copy, and not among what
-     * walk_constants_equal compares -- the lists do not depend on it */
-    w.throughUsed = vrc_plan_store_through( c->opt, w.used, f.width, f.height ) ? 1 : 0;
-    f.storeThrough = (uint32_t)w.throughUsed;
-    /* ... and whether it takes first visits from the table (vrc_core.h: vrc_first_visit_row), set behind the same
-     * copies for the same reason.  The table is built here, on the stream behind the classified table it reads and in
-     * front of the march's timing pair: no march, not timed, not counted as a launch */
-    vrc_first_visit& fv = c->first;
-    const bool grey = p.a.greyTable;
-    vrc_first_visit_facts k = { w.used, f.walkLean, f.clearFirst != 0u, p.mode.classify,
-                                fv.gen != 0u && fv.gen == c->lutGen && fv.grey == grey };
-    if( vrc_plan_first_visit_build( c->opt, k, fv.prevGen == c->lutGen ) )
-    {
-        if( !fv.dTable )
-            VRC_HIP_CHECK( hipMalloc( &fv.dTable, (size_t)VRC_FIRST_VISIT_ENTRIES * VRC_FIRST_VISIT_ROWS * sizeof( vrc_f4 ) ) );
-        VRC_HIP_CHECK( vrc_launch_build_first_visit( c->dLut, fv.dTable, grey, c->stream ) );
-        fv.gen = c->lutGen;
-        fv.grey = grey;
-        k.current = true;
-    }
-    fv.prevGen = c->lutGen;
-    fv.used = vrc_plan_first_visit( c->opt, k ) ? 1 : 0;
-    f.firstVisit = fv.used ? fv.dTable : nullptr;
-    /* ... and whether a visit that cannot reach the exit threshold marches without the test (vrc_core.h:
-     * vrc_march_uniform_free): behind the same copies, for the same reason */
-    w.freeUsed = vrc_plan_lean_free_march( c->opt, w.used, f.walkLean, p.mode.classify ) ? 1 : 0;
-    f.leanFree = (uint32_t)w.freeUsed;
-    /* ... and whether the uniform-only instance reads resolved visit words (vrc_core.h: vrc_walk_resolved_word): behind
-     * the same copies, for the same reason.  The planes are the lists' as recorded, under the uploads and the slotInfo
-     * the frame renders with -- what a frame must find unchanged to be handed VRC_WALK_LEAN_UNIFORM at all -- and count
-     * against the budget beside the lists.  The first such frame without them builds them (render_march, behind the
-     * pool's uploads and in front of the timing pair: no march); planes of anything else are dropped, and so are they
-     * where the frame is not handed that instance because the triple moved */
-    p.walkResolve = false;
-    const bool uniformOnly = f.walkLean == VRC_WALK_LEAN_UNIFORM;
-    if( w.resolvedValid && ( p.walkRecord || ( w.used == 4 && ( w.resolvedGen != gen || w.resolvedSlotInfo != f.slotInfo ) ) ) )
-        w.resolvedValid = false;
-    const unsigned long long resolvedBytes = ( 1ull + 5ull * w.k ) * plane * sizeof( uint32_t );
-    w.resolvedUsed = vrc_plan_walk_resolved( c->opt, uniformOnly, resolvedBytes <= (unsigned long long)c->opt.walkBudget ) ? 1 : 0;
-    if( w.resolvedUsed && !w.resolvedValid )
-    {
-        const size_t words = (size_t)w.k * plane;
-        VRC_TRY( ctx_grow( c, w.resolvedWords, words, words, { w.dResolved } ) );
-        p.walkResolve = true; /* (valid once render_march has launched the build) */
-        w.resolvedGen = gen;
-        w.resolvedSlotInfo = f.slotInfo;
-    }
-    f.walkResolved = w.resolvedUsed ? w.dResolved : nullptr;
+    vrc_walk_decide( c->opt, w.s, k, n, pl );
+    vrc_walk_reached reached = VRC_WALK_REACHED_NOTHING;
+    if( rc == VRC_OK )
+        rc = walk_allocate( c, pl, k.greyTable, reached );
+    vrc_walk_commit( w.s, k, pl, reached, c->walkPlan );
+    VRC_TRY( rc );
+    f.walkCache = pl.lists() ? w.dLists : nullptr;
+    f.walkPlane = pl.lists() ? (uint32_t)p.plane : 0u;
+    f.walkK = pl.walkK;
+    f.walkLean = pl.walkLean;
+    f.walkSlots = pl.walkSlots;
+    /* (the riders' fields: behind prevFrame's copy, and not among what walk_constants_equal compares) */
+    f.storeThrough = (uint32_t)pl.storeThrough;
+    f.firstVisit = pl.firstVisit ? w.dFirstVisit : nullptr;
+    f.leanFree = (uint32_t)pl.leanFree;
+    f.walkResolved = pl.resolved ? w.dResolved : nullptr;
     return VRC_OK;
 }
 
@@ -2345,29 +2210,30 @@ static int render_march( vrc_ctx* c, render_pass& p )
     const vrc_mode& m = p.mode;
     /* order the march after every brick upload issued so far (fixes quirk Q9) */
     VRC_TRY( ctx_wait_uploads( c, p.pool ) );
-    if( p.walkCount )
+    const vrc_walk_plan& pl = c->walkPlan;
+    if( pl.count )
     {
         VRC_HIP_CHECK( hipMemsetAsync( c->walk.dMax, 0, sizeof( vrc_walk_count ), c->stream ) );
         VRC_HIP_CHECK( vrc_launch_walk_record( a, c->walk.dMax, c->stream ) );
         VRC_HIP_CHECK( hipMemcpyAsync( c->walk.hMax, c->walk.dMax, sizeof( vrc_walk_count ), hipMemcpyDeviceToHost, c->stream ) );
         VRC_HIP_CHECK( hipEventRecord( c->walk.ev, c->stream ) );
         std::memcpy( &c->walk.frame, &f, sizeof( f ) );
-        c->walk.state = vrc_walk_cache::COUNTING;
+        vrc_walk_launched( c->walk.s, VRC_WALK_LAUNCHED_COUNT );
         f.walkLean = 0u; /* (asked of the count pass alone) */
     }
-    if( p.walkRecord )
+    if( pl.record )
     {
         VRC_HIP_CHECK( vrc_launch_walk_record( a, nullptr, c->stream ) );
-        c->walk.state = vrc_walk_cache::VALID;
+        vrc_walk_launched( c->walk.s, VRC_WALK_LAUNCHED_RECORD );
         /* this frame still walks: the march below reads none of the planes */
         f.walkCache = nullptr;
         f.walkPlane = f.walkK = 0u;
         f.walkLean = f.walkSlots = 0u;
     }
-    if( p.walkResolve )
+    if( pl.resolveBuild )
     {
         VRC_HIP_CHECK( vrc_launch_walk_resolve( f, c->walk.dResolved, c->stream ) );
-        c->walk.resolvedValid = true;
+        vrc_walk_launched( c->walk.s, VRC_WALK_LAUNCHED_RESOLVE );
     }
     if( c->opt.count )
         VRC_HIP_CHECK( hipMemsetAsync( c->dCounter, 0, sizeof( unsigned long long ), c->stream ) );
@@ -2421,10 +2287,10 @@ static int render_march( vrc_ctx* c, render_pass& p )
                    : m.shade    ? vrc_launch_raycast_shade( a, c->stream )
                    : p.form.useLds ? vrc_launch_raycast_lds( a, c->stream ) /* (also its per-ray LOD form) */
                    : c->rayLod  ? vrc_launch_raycast_raylod( a, c->stream )
-                   : c->walk.used == 4 ? vrc_launch_raycast_replay( a, c->stream )
+                   : pl.used == 4      ? vrc_launch_raycast_replay( a, c->stream )
                                 : vrc_launch_raycast( a, c->stream ) );
     if( c->rayCacheUsed == VRC_RAY_STORE )
-        c->rayCacheValid = true;
+        vrc_ray_stored( c->ray );
     if( c->opt.timing && !attached ) /* (also a frame without tiles, which launches nothing) */
         VRC_HIP_CHECK( hipEventRecord( evp.second, c->stream ) );
     VRC_TRY( pool_fence_behind( p.pool, c, pairFences ? evp.second : nullptr ) );

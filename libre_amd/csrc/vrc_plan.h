@@ -8,6 +8,15 @@
  * without the exit test (vrc_plan_lean_free_march), or reads resolved visit words (vrc_plan_walk_resolved).  A
  * refusal is a code and a message; the ORDER of the refusals is part of the contract (tests/test_render_plan_cpu.py
  * holds both functions to the text they replaced, message for message).
+ *
+ * And the two caches of a still view, each as what it remembers between calls plus the functions that read and write
+ * that memory -- the context keeps the device memory, the event and the frames, and assigns none of this itself:
+ *   ray cache   vrc_ray_state; vrc_plan_ray_cache (compute, store or load), vrc_ray_stored, vrc_ray_forget;
+ *   walk cache  vrc_walk_state, vrc_walk_facts, vrc_walk_counted, vrc_walk_plan; vrc_walk_open (what the frame ends, is
+ *               it a repeat, is the count's answer wanted), vrc_walk_decide (count, record, replay or walk; the replay
+ *               instance; the four riders; what to allocate and build), vrc_walk_commit (what is remembered, by how far
+ *               the caller got), vrc_walk_launched (the transitions behind the launches), vrc_walk_forget.
+ * tests/test_walk_plan_cpu.py drives both through generated sequences of renders beside the text they replaced.
  */
 #ifndef VRC_PLAN_H
 #define VRC_PLAN_H
@@ -353,5 +362,328 @@ inline bool vrc_plan_walk_resolved( const vrc_options& o, bool uniformOnly, bool
 {
     return o.walkResolved != 0 && uniformOnly && fits && o.count == 0;
 }
+
+/* ---------------------------------------------------------------------------------------- */
+/* The values of vrc_core.h this header speaks of and does not include (a source that includes both checks them here) */
+#ifndef VRC_RAY_COMPUTE
+#define VRC_RAY_COMPUTE 0u
+#define VRC_RAY_STORE 1u
+#define VRC_RAY_LOAD 2u
+#endif
+#ifndef VRC_WALK_LEAN_UNIFORM
+#define VRC_WALK_LEAN_UNIFORM 2u
+#endif
+static_assert( VRC_RAY_COMPUTE == 0u && VRC_RAY_STORE == 1u && VRC_RAY_LOAD == 2u && VRC_WALK_LEAN_UNIFORM == 2u,
+               "vrc_plan.h and vrc_core.h name the same modes" );
+
+/* ray cache (VRC_OPT_RAY_CACHE; vrc_core.h: vrc_frame::rayCache).  prevSet: there was a vrc_render before that could have
+ * used the cache; valid: the planes hold the rays of exactly its frame constants */
+struct vrc_ray_state
+{
+    bool valid = false, prevSet = false;
+};
+
+/* A frame whose ray constants differ from those of the vrc_render before (sameAsPrev: prevSet, and ray_constants_equal)
+ * computes its rays -- a moving camera pays nothing; the first that repeats them also stores them, and the ones after
+ * that load them.  A frame that cannot use the cache (eligible: vrc_api.hip) forgets the one before.  The planes a
+ * storing frame writes are valid once its march is on the stream (vrc_ray_stored) */
+inline uint32_t vrc_plan_ray_cache( vrc_ray_state& s, bool eligible, bool sameAsPrev )
+{
+    if( !eligible )
+        s.valid = s.prevSet = false;
+    else if( !sameAsPrev )
+        s.valid = false;
+    const uint32_t mode = !( eligible && sameAsPrev ) ? VRC_RAY_COMPUTE : s.valid ? VRC_RAY_LOAD : VRC_RAY_STORE;
+    s.prevSet = eligible;
+    return mode;
+}
+inline void vrc_ray_stored( vrc_ray_state& s ) { s.valid = true; }
+/* whatever the planes were written under is gone: the stream, the row map's contents, the option */
+inline void vrc_ray_forget( vrc_ray_state& s ) { s.valid = s.prevSet = false; }
+
+/* walk cache (VRC_OPT_WALK_CACHE; vrc_core.h: vrc_frame::walkCache): a frame that loads its rays, of the instances the
+ * replay march exists for (vrc_internal.h: vrc_walk_replay_eligible).  The first such frame that repeats the one before
+ * also runs the count pass; the first one after its result has arrived (polled, never waited for) sizes the planes and
+ * runs the record pass; the ones after that replay.  Both passes go on the stream in front of the march's timing pair
+ * and are no marches: not timed, not counted as launches.
+ * state: IDLE nothing known; COUNTING the count pass is on the stream, its result on the way behind the event; VALID the
+ * planes hold the lists of the listed frame's constants over the node table as it is.  Nothing exists before the first
+ * count pass: a camera that moves every frame allocates nothing.  The count pass runs only for a frame whose constants,
+ * node list and (option at 1) pool uploads are those of the vrc_render before, prev*: what changes every call -- passes
+ * over different node subsets, bricks streaming in -- launches nothing extra.
+ * Whatever the lists depend on starts them over when it changes: the frame constants (vrc_walk_open), the node list,
+ * the stream, the row map and the two options, where they are set (vrc_walk_forget); the transfer function, the
+ * uniformity words and the pixel buffer's contents are not among them.  What the lists do not depend on may still decide
+ * whether they are worth using: where every visit gathers the replay is no faster than the walk, and by 1 to 3 % slower
+ * (profiles/r10_walk_cache.txt), so with the option at 1 a view more than half of whose visits gather, by the count pass
+ * and the uniformity words it read, is not recorded and stays on the walk until the pool's uploads or
+ * VRC_OPT_UNIFORM_BRICKS change; VRC_WALK_CACHE_ALWAYS replays whatever the bricks hold. */
+enum
+{
+    VRC_WALK_IDLE = 0,
+    VRC_WALK_COUNTING = 1,
+    VRC_WALK_VALID = 2
+};
+
+/* what the walk cache remembers between calls, the first-visit table's part included */
+struct vrc_walk_state
+{
+    int state = VRC_WALK_IDLE;
+    uint32_t k = 0; /* visits per ray the planes hold */
+    /* the form of the lists (vrc_core.h: vrc_frame::walkLean).  leanAsked: what the host saw when the count pass went
+     * out -- a step that vrc_exact_step_count counts, a pool whose slot indices fit the word -- and so what that pass was
+     * asked to check; part of what the lists are valid for.  lean: the form the record pass wrote */
+    bool leanAsked = false, lean = false;
+    /* what the count pass of the lists in the planes said of the slot words it read, those of gen and slotInfo --
+     * compared for the uniform-only instance whatever VRC_OPT_WALK_CACHE says, because at VRC_WALK_CACHE_ALWAYS the
+     * lists outlive an upload and that answer does not */
+    unsigned long long gathers = 0;
+    uint64_t gen = 0; /* gen, slotInfo: the uploads and the uniformity words the count pass read */
+    const void* slotInfo = nullptr;
+    bool prevSet = false; /* the vrc_render before: there was one, and its uploads (its frame: the context's) */
+    uint64_t prevGen = 0;
+    /* the resolved visit words (VRC_OPT_WALK_RESOLVED): k planes beside the lists, built from them and from the slot
+     * words by the first frame that is handed the uniform-only instance without them.  resolvedValid: the planes hold the
+     * words of the lists as recorded (a record pass ends it) under the uploads resolvedGen and the array
+     * resolvedSlotInfo; a frame that finds another of the three takes the list words and drops the planes */
+    bool resolvedValid = false;
+    uint64_t resolvedGen = 0;
+    const void* resolvedSlotInfo = nullptr;
+    /* the first-visit table (VRC_OPT_FIRST_VISIT_TABLE).  It depends on the classified table alone -- transfer function,
+     * opacity correction -- and on the form the frame marches, not on the view, the volume or the lists.  tableGen,
+     * tableGrey: the generation (lutGen) and form it was built for (0: never).  tablePrevGen: the generation the
+     * vrc_render before rendered with (0: none) */
+    uint64_t tableGen = 0, tablePrevGen = 0;
+    bool tableGrey = false;
+};
+
+/* what a call finds, and the plan may not work out itself */
+struct vrc_walk_facts
+{
+    /* VRC_OPT_WALK_CACHE on, the ray cache in LOAD, vrc_walk_replay_eligible, nodes and a plane at all (the plan adds
+     * that the planes of one visit fit: vrc_walk_fits) */
+    bool eligibleSoFar;
+    /* the form of the lists.  A lean list holds every visit's step count and slot index in one word of 12 + 20 bits.
+     * What the host can see of that: the step is one vrc_exact_step_count counts (its own test, asked with a travel that
+     * passes it), and the pool's slot indices fit.  The rest -- no visit whose count is inexact or takes more than 12
+     * bits -- the count pass reports with the count */
+    bool leanAsked;
+    bool sameAsListed; /* walk_constants_equal: the frame the lists were counted for (read unless IDLE) and this one */
+    bool sameAsPrev;   /* ... the frame of the vrc_render before (prevSet, and equal) and this one */
+    bool sameNodes;    /* the node list of the vrc_render before, on the same pool */
+    uint64_t uploadGen; /* the pool's (compared only where the choice goes by the bricks' content) */
+    const void* slotInfo;
+    size_t plane, nSlots; /* words of a plane of the lists; the pool's slots */
+    uint32_t width, height;
+    bool clearFirst, classify, greyTable; /* vrc_frame::clearFirst, vrc_mode::classify, vrc_raycast_args::greyTable */
+    uint64_t lutGen;
+};
+
+/* the count pass's answer, once vrc_walk_open asked for it: has it arrived, and vrc_walk_count */
+struct vrc_walk_counted
+{
+    bool ready = false;
+    uint32_t longest = 0, notLean = 0;
+    unsigned long long visits = 0, gathers = 0;
+};
+
+/* what a vrc_render does about the walk cache; the context keeps the last one, and VRC_OPT_*_USED read it */
+struct vrc_walk_plan
+{
+    int64_t used = 0; /* VRC_OPT_WALK_CACHE_USED: 0 walk, 1 count, 2 waiting for the count, 3 record, 4 replay */
+    bool count = false, record = false;   /* the passes to launch in front of the march */
+    bool firstVisitBuild = false;         /* build the first-visit table, here and now */
+    bool resolveBuild = false;            /* build the resolved visit words in front of the march */
+    bool resolvedDrop = false;            /* the resolved planes the state holds are of something else */
+    uint32_t walkK = 0, walkLean = 0, walkSlots = 0; /* vrc_frame's (count: walkLean alone, "check every visit") */
+    unsigned long long gathers = 0;       /* of the lists the frame records or replays */
+    int64_t leanUsed = 0, uniformUsed = 0; /* VRC_OPT_WALK_LEAN_USED, _WALK_UNIFORM_ONLY_USED */
+    int64_t storeThrough = 0, firstVisit = 0, leanFree = 0, resolved = 0; /* the four riders' _USED */
+    size_t listWords = 0, resolvedWords = 0; /* to allocate (0: nothing): the lists to record, the planes to build */
+    bool lists() const { return record || used == 4; } /* the frame carries the lists' fields */
+};
+
+/* the planes of k visits: 32-bit word offsets in the kernels, and VRC_OPT_WALK_CACHE_BUDGET */
+inline unsigned long long vrc_walk_list_words( size_t plane, uint32_t k ) { return ( 1ull + 4ull * k ) * plane; }
+inline bool vrc_walk_fits( const vrc_options& o, size_t plane, uint32_t k )
+{
+    const unsigned long long words = vrc_walk_list_words( plane, k );
+    return words <= 0xFFFFFFFFull && words * sizeof( uint32_t ) <= (unsigned long long)o.walkBudget;
+}
+
+/* The opening step.  Ends what this frame ends: lists of another frame, another form, or (byContent) other uploads or
+ * uniformity words, and any lists where the frame is not eligible.  Notes whether the frame repeats the vrc_render
+ * before, and becomes "the one before" itself.  Starts the plan: used is 4 over VALID lists, 2 over a count in flight,
+ * 1 where an eligible repeat finds nothing, else 0 (eligible, IDLE and not a repeat: the next call counts if it is this
+ * one again).  Returns whether the count's answer is wanted: the caller polls then, and only then */
+inline bool vrc_walk_open( const vrc_options& o, vrc_walk_state& s, const vrc_walk_facts& k, vrc_walk_plan& pl )
+{
+    pl = vrc_walk_plan();
+    const bool eligible = k.eligibleSoFar && vrc_walk_fits( o, k.plane, 1u );
+    const bool byContent = o.walkCache != VRC_WALK_CACHE_ALWAYS;
+    if( !eligible || ( s.state != VRC_WALK_IDLE &&
+                       ( !k.sameAsListed || k.leanAsked != s.leanAsked ||
+                         ( byContent && ( s.gen != k.uploadGen || s.slotInfo != k.slotInfo ) ) ) ) )
+        s.state = VRC_WALK_IDLE;
+    const bool repeats = k.sameNodes && s.prevSet && ( !byContent || s.prevGen == k.uploadGen ) && k.sameAsPrev;
+    s.prevSet = true;
+    s.prevGen = k.uploadGen;
+    pl.used = !eligible ? 0 : s.state == VRC_WALK_VALID ? 4 : s.state == VRC_WALK_COUNTING ? 2 : repeats ? 1 : 0;
+    pl.count = pl.used == 1;
+    return pl.used == 2;
+}
+
+/* The deciding step: everything the frame does, written into the plan alone.  The caller allocates and builds what the
+ * plan asks for (listWords; firstVisitBuild; resolvedWords), says how far it got (vrc_walk_commit) and fills the
+ * frame's fields from the plan */
+inline void vrc_walk_decide( const vrc_options& o, const vrc_walk_state& s, const vrc_walk_facts& k, const vrc_walk_counted& n,
+                             vrc_walk_plan& pl )
+{
+    const bool byContent = o.walkCache != VRC_WALK_CACHE_ALWAYS;
+    pl.walkK = s.k;
+    pl.gathers = s.gathers;
+    bool lean = s.lean;
+    if( pl.used == 2 && n.ready )
+    {
+        const uint32_t longest = n.longest > 0u ? n.longest : 1u;
+        if( !vrc_walk_fits( o, k.plane, longest ) )
+            pl.used = 0; /* over the budget or the offset limit: this view stays on the walk */
+        else if( byContent && 2u * n.gathers > n.visits )
+            pl.used = 0; /* most visits gather: so does this one */
+        else
+        {
+            pl.used = 3;
+            pl.record = true;
+            pl.listWords = (size_t)vrc_walk_list_words( k.plane, longest );
+            pl.walkK = longest;
+            pl.gathers = n.gathers;
+            lean = s.leanAsked && n.notLean == 0u;
+        }
+    }
+    if( pl.lists() )
+    {
+        pl.walkLean = lean ? 1u : 0u;
+        pl.walkSlots = (uint32_t)k.nSlots;
+        pl.leanUsed = ( lean && pl.used == 4 ) ? 1 : 0;
+        /* the uniform-only instance (vrc_kernels_walk.hip): a replayed lean frame none of whose visits gathers -- by
+         * the count pass of these lists, which is still the answer while the pool has taken no upload and the words are
+         * the ones it read.  Where the lists outlive that (VRC_WALK_CACHE_ALWAYS) the frame goes back to the lean
+         * instance and keeps them */
+        if( pl.leanUsed && o.walkUniformOnly && pl.gathers == 0ull && s.gen == k.uploadGen && s.slotInfo == k.slotInfo )
+        {
+            pl.walkLean = VRC_WALK_LEAN_UNIFORM;
+            pl.uniformUsed = 1;
+        }
+    }
+    else
+    {
+        pl.walkK = 0u;
+        pl.walkLean = ( pl.count && k.leanAsked ) ? 1u : 0u; /* (the count pass: check every visit) */
+    }
+    /* The riders: how the replay stores its pixels, takes a first visit, marches a visit, reads a visit.  None is among
+     * what walk_constants_equal compares -- the lists do not depend on them -- so the frame's fields for them are set
+     * behind the copies of the frame the context keeps */
+    pl.storeThrough = vrc_plan_store_through( o, pl.used, k.width, k.height ) ? 1 : 0;
+    /* the first-visit table is built on the stream behind the classified table it reads and in front of the march's
+     * timing pair: no march, not timed, not counted as a launch */
+    vrc_first_visit_facts fv = { pl.used, pl.walkLean, k.clearFirst, k.classify,
+                                 s.tableGen != 0u && s.tableGen == k.lutGen && s.tableGrey == k.greyTable };
+    pl.firstVisitBuild = vrc_plan_first_visit_build( o, fv, s.tablePrevGen == k.lutGen );
+    fv.current = fv.current || pl.firstVisitBuild;
+    pl.firstVisit = vrc_plan_first_visit( o, fv ) ? 1 : 0;
+    pl.leanFree = vrc_plan_lean_free_march( o, pl.used, pl.walkLean, k.classify ) ? 1 : 0;
+    /* the resolved planes are the lists' as recorded, under the uploads and the slotInfo the frame renders with -- what
+     * a frame must find unchanged to be handed VRC_WALK_LEAN_UNIFORM at all -- and count against the budget beside the
+     * lists.  The first such frame without them builds them (behind the pool's uploads and in front of the timing
+     * pair: no march); planes of anything else are dropped, and so are they where the frame is not handed that
+     * instance because the triple moved */
+    pl.resolvedDrop = s.resolvedValid && ( pl.record || ( pl.used == 4 && ( s.resolvedGen != k.uploadGen || s.resolvedSlotInfo != k.slotInfo ) ) );
+    const unsigned long long resolvedBytes = ( 1ull + 5ull * pl.walkK ) * k.plane * sizeof( uint32_t );
+    pl.resolved = vrc_plan_walk_resolved( o, pl.walkLean == VRC_WALK_LEAN_UNIFORM, resolvedBytes <= (unsigned long long)o.walkBudget ) ? 1 : 0;
+    pl.resolveBuild = pl.resolved && ( !s.resolvedValid || pl.resolvedDrop );
+    pl.resolvedWords = pl.resolveBuild ? (size_t)pl.walkK * k.plane : 0u;
+}
+
+/* how far the caller got with what the plan asked for, in the order it goes about it */
+enum vrc_walk_reached
+{
+    VRC_WALK_REACHED_NOTHING = 0, /* the poll, the count pass's three objects or the lists failed */
+    VRC_WALK_REACHED_LISTS,       /* ... the build of the first-visit table failed */
+    VRC_WALK_REACHED_TABLE,       /* ... the resolved planes could not grow */
+    VRC_WALK_REACHED_ALL
+};
+
+/* The commit: what the state remembers of the plan, and `last`, the context's record of the call.  A vrc_render that
+ * fails on the way remembers what it got to and nothing behind it: lists that could not grow leave the count in flight
+ * with k, lean and gathers as they were, and the call reads back as one still waiting for it; planes that could not grow
+ * leave resolvedGen and resolvedSlotInfo alone.  The read-backs of the riders such a call did not get to stay the call
+ * before's */
+inline void vrc_walk_commit( vrc_walk_state& s, const vrc_walk_facts& k, const vrc_walk_plan& pl, vrc_walk_reached reached,
+                             vrc_walk_plan& last )
+{
+    const vrc_walk_plan before = last;
+    last = pl;
+    if( reached < VRC_WALK_REACHED_TABLE )
+    {
+        last.firstVisit = before.firstVisit;
+        last.resolved = before.resolved;
+        last.leanFree = 0;
+    }
+    if( reached == VRC_WALK_REACHED_NOTHING )
+    {
+        last.used = pl.record ? 2 : pl.count ? 0 : pl.used;
+        last.leanUsed = last.uniformUsed = last.storeThrough = 0;
+        return;
+    }
+    if( pl.count )
+    {
+        s.leanAsked = k.leanAsked;
+        s.gen = k.uploadGen;
+        s.slotInfo = k.slotInfo;
+    }
+    if( pl.record )
+    {
+        s.k = pl.walkK;
+        s.lean = pl.walkLean != 0u;
+        s.gathers = pl.gathers;
+    }
+    if( reached == VRC_WALK_REACHED_LISTS )
+        return;
+    if( pl.firstVisitBuild )
+    {
+        s.tableGen = k.lutGen;
+        s.tableGrey = k.greyTable;
+    }
+    s.tablePrevGen = k.lutGen;
+    if( pl.resolvedDrop )
+        s.resolvedValid = false;
+    if( pl.resolveBuild && reached == VRC_WALK_REACHED_ALL )
+    {
+        s.resolvedGen = k.uploadGen;
+        s.resolvedSlotInfo = k.slotInfo;
+    }
+}
+
+/* the three transitions behind the launches in front of the march, each once its launch succeeded: the count pass is on
+ * the stream; the record pass is; the resolved planes' build is */
+enum vrc_walk_launch
+{
+    VRC_WALK_LAUNCHED_COUNT,
+    VRC_WALK_LAUNCHED_RECORD,
+    VRC_WALK_LAUNCHED_RESOLVE
+};
+inline void vrc_walk_launched( vrc_walk_state& s, vrc_walk_launch what )
+{
+    if( what == VRC_WALK_LAUNCHED_COUNT )
+        s.state = VRC_WALK_COUNTING;
+    else if( what == VRC_WALK_LAUNCHED_RECORD )
+        s.state = VRC_WALK_VALID;
+    else
+        s.resolvedValid = true;
+}
+
+/* start over: what the lists index or were written on is gone -- the node table, the stream, the row map, the option or
+ * the budget they were made under.  (The resolved planes go with the next record pass; the repeat bookkeeping stays) */
+inline void vrc_walk_forget( vrc_walk_state& s ) { s.state = VRC_WALK_IDLE; }
 
 #endif /* VRC_PLAN_H */
