@@ -2109,10 +2109,13 @@ VRC_HD bool vrc_march_segment_packed( const vrc_frame& f, const vrc_dev_node& n,
  * EXTENSION: maximum-intensity projection (VRC_OPT_PROJECTION = VRC_PROJECTION_MIP; include/vrc_hip.h has the
  * definition of a MIP frame).  The sample set of a ray is the composite march's with an all-transparent transfer
  * function -- same ray, same bricks in the same order, same segments, positions and counts, no early termination -- and
- * the pixel is ONE classification of the largest sampled density, after the march.  The march bodies below keep the
- * control structure of vrc_march_segment_as / vrc_march_segment_linear (whole groups under the same guard, the
- * sequential travel chain, the same tails), so positions and counts are theirs by construction; the per-sample work
- * is a maximum folded into one register (integer voxels: two samples per instruction, v_max3_u32).
+ * the pixel is ONE classification of the largest sampled density, after the march.  A brick segment is walked by
+ * vrc_projection_walk_point or vrc_projection_walk_trilinear, once for every projection (maximum, minimum, mean, first
+ * crossing, with and without depth): they keep the control structure of vrc_march_segment_as /
+ * vrc_march_segment_linear (whole groups under the same guard, the sequential travel chain, the same tails), so
+ * positions and counts are theirs by construction.  What a projection makes of a group of samples is its fold; the
+ * maximum's is folded into one register (integer voxels: two samples per instruction, v_max3_u32).  A brick visit
+ * is the projection's own skip / uniform-brick preamble (lane-wise) and then vrc_projection_march.
  *
  * M is held as uint32_t for point samples of the integer atlases (the stored, offset-binary value: the shift is
  * monotone) and as float for the float atlas and every trilinear sample; a float M starts at -infinity and is folded
@@ -2368,11 +2371,24 @@ VRC_HD uint32_t vrc_step_count( float travel, float stepSize )
     return n;
 }
 
-/* point samples of one brick segment (travel > 0 or nothing is taken): vrc_march_segment_as without table, blend and exit */
-template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename D, int FOLD = VRC_FOLD_MAX, bool DEPTH = false >
-VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
-                                   const ATLAS_T* __restrict__ atlas, D& m, uint32_t& nSamples, vrc_mip_depth* z = nullptr )
+/* ---- the two walks of a brick segment: every projection takes its samples from these --------------------------------------
+ * vrc_projection_walk_point is vrc_march_segment_as without table, blend and exit; vrc_projection_walk_trilinear is
+ * vrc_march_segment_linear without classification, blend and exit.  What is made of the samples is the walk's FOLD
+ * (vrc_extremum_fold, vrc_mean_fold, vrc_first_crossing_fold).  Per group of N samples a walk adds the samples the
+ * reference takes to nSamples and calls
+ *   fold.template group< N >( d, taken, elem )
+ *     d[k]      the value of sample k: the stored voxel of a point sample (vrc_density< ATLAS_T >::type), the interpolated
+ *               float of a trilinear one;
+ *     taken[k]  the reference takes step k.  All true in a whole group; a step of a tail that the reference does not
+ *               take reads element 0, and the fold leaves its d[k] out;
+ *     elem( k ) the atlas element sample k is read from, for the fold that keeps where it hit;
+ *   which returns true to leave the segment in front of the next group (the first-crossing fold of a ray that skips;
+ *   every other fold returns false). */
+template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename FOLD >
+VRC_HD void vrc_projection_walk_point( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
+                                       const ATLAS_T* __restrict__ atlas, FOLD& fold, uint32_t& nSamples )
 {
+    typedef typename vrc_density< ATLAS_T >::type D;
     const float stepSize = f.stepSize;
     const vrc_sampler sm = vrc_make_sampler( n, f );
     vrc_f3 pos = s.pos;
@@ -2393,32 +2409,23 @@ VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, co
         for( int k = 0; k < GROUP; ++k )
             travel -= stepSize; /* same sequential subtraction as the reference */
         D d[GROUP];
+        bool taken[GROUP];
 #pragma unroll
         for( int k = 0; k < GROUP; ++k )
-            d[k] = (D)vrc_gather( atlas, idx[k] );
-        const D m0 = m;
-#pragma unroll
-        for( int k = 0; k + 1 < GROUP; k += 2 )
-            m = vrc_mip_fold3< FOLD >( m, d[k], d[k + 1] );
-        if( GROUP & 1 )
-            m = vrc_mip_fold< FOLD >( m, d[GROUP - 1] );
-        nSamples += GROUP;
-        if constexpr( DEPTH )
         {
-            bool taken[GROUP];
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-                taken[k] = true;
-            vrc_mip_depth_group< GROUP >( *z, m0, m, d, taken, stepSize );
+            d[k] = (D)vrc_gather( atlas, idx[k] );
+            taken[k] = true;
         }
+        nSamples += GROUP;
+        if( fold.template group< GROUP >( d, taken, [&]( int k ) { return idx[k]; } ) )
+            travel = 0.0f;
     }
     constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
-    D none;
-    vrc_mip_fold_identity< FOLD >( none );
     while( travel > 0.0f )
     {
         uint32_t idx[TAILG], cnt = 0;
         D d[TAILG];
+        bool taken[TAILG];
         if( FIXED )
             vrc_group_indices_fixed< TAILG >( sm, fp, idx );
         else
@@ -2426,34 +2433,26 @@ VRC_HD void vrc_mip_segment_point( const vrc_frame& f, const vrc_dev_node& n, co
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
         {
-            const bool v = travel > 0.0f;
-            cnt += v ? 1u : 0u;
-            idx[k] = v ? idx[k] : 0u; /* a step the reference does not take reads element 0 and contributes nothing */
+            taken[k] = travel > 0.0f;
+            cnt += taken[k] ? 1u : 0u;
+            idx[k] = taken[k] ? idx[k] : 0u; /* a step the reference does not take reads element 0 and contributes nothing */
             travel -= stepSize;
         }
 #pragma unroll
         for( int k = 0; k < TAILG; ++k )
             d[k] = (D)vrc_gather( atlas, idx[k] );
-        const D m0 = m;
-#pragma unroll
-        for( int k = 0; k < TAILG; ++k )
-            m = vrc_mip_fold< FOLD >( m, (uint32_t)k < cnt ? d[k] : none );
         nSamples += cnt;
-        if constexpr( DEPTH )
-        {
-            bool taken[TAILG];
-#pragma unroll
-            for( int k = 0; k < TAILG; ++k )
-                taken[k] = (uint32_t)k < cnt;
-            vrc_mip_depth_group< TAILG >( *z, m0, m, d, taken, stepSize );
-        }
+        if( fold.template group< TAILG >( d, taken, [&]( int k ) { return idx[k]; } ) )
+            travel = 0.0f;
     }
 }
 
-/* vrc_trilerp with its fused multiply-adds written out, for the depth-tracking instances: a frame has to come out with the
- * same M, bit for bit, with depth tracking on and off, and under contract(fast) the compiler is free to fuse either
- * product of a (1 - w) + b w -- which one it takes depends on the code around the expression (it keeps as a product the
- * one with more uses).  Read off the gfx950 code of the instances without depth tracking, all of them:
+/* vrc_trilerp with its fused multiply-adds written out, for the maximum and the minimum, with and without depth tracking
+ * (the SPELT walk): a frame has to come out with the same M, bit for bit, with depth tracking on and off, and under
+ * contract(fast) the compiler is free to fuse either product of a (1 - w) + b w -- which one it takes depends on the
+ * code around the expression (it keeps as a product the one with more uses; moving the fold behind the walk changed it
+ * for the 8- and 16-bit atlases, profiles/r21_projection_walk.txt).  Read off the gfx950 code of the instances without
+ * depth tracking as they were while they left the choice to the compiler, all of them:
  *   8- and 16-bit atlases  the first product is fused, fma( a, 1 - w, b * w ), at all three levels of every sample;
  *   the float atlas        the same, but for the first interpolation along x (c00) of the first sample of a group,
  *                          which comes out as fma( b, w, a * (1 - w) ) -- firstOfFloatGroup.
@@ -2478,17 +2477,14 @@ VRC_HD float vrc_trilerp_fused_as_plain( const float v[8], float wx, float wy, f
 #endif
 }
 
-/* trilinear samples of one brick segment: vrc_march_segment_linear without classification, blend and exit */
-template < bool CLAMP, typename ATLAS_T, int FOLD = VRC_FOLD_MAX, bool DEPTH = false >
-VRC_HD void vrc_mip_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
-                                       const ATLAS_T* __restrict__ atlas, float& m, uint32_t& nSamples,
-                                       vrc_mip_depth* z = nullptr )
+/* the trilinear walk: masked groups of VRC_LGROUP.  SPELT: interpolate by vrc_trilerp_fused_as_plain */
+template < bool CLAMP, bool SPELT, typename ATLAS_T, typename FOLD >
+VRC_HD void vrc_projection_walk_trilinear( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
+                                           const ATLAS_T* __restrict__ atlas, FOLD& fold, uint32_t& nSamples )
 {
     const float stepSize = f.stepSize;
     const vrc_sampler sm = vrc_make_sampler( n, f );
     vrc_f3 pos = s.pos;
-    float none;
-    vrc_mip_fold_identity< FOLD >( none );
     while( travel > 0.0f )
     {
         bool valid[VRC_LGROUP];
@@ -2520,27 +2516,82 @@ VRC_HD void vrc_mip_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n
 #pragma unroll
         for( int k = 0; k < VRC_LGROUP; ++k )
         {
-            if constexpr( DEPTH )
+            if constexpr( SPELT )
                 d[k] = vrc_trilerp_fused_as_plain( v[k], t[k].wx, t[k].wy, t[k].wz, k == 0 && sizeof( ATLAS_T ) == 4 );
             else
-            d[k] = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
-            d[k] = valid[k] ? d[k] : none;
+                d[k] = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
             nSamples += valid[k] ? 1u : 0u;
         }
-        const float m0 = m;
-#pragma unroll
-        for( int k = 0; k + 1 < VRC_LGROUP; k += 2 )
-            m = vrc_mip_fold3< FOLD >( m, d[k], d[k + 1] );
-        if( VRC_LGROUP & 1 )
-            m = vrc_mip_fold< FOLD >( m, d[VRC_LGROUP - 1] );
-        if constexpr( DEPTH )
-            vrc_mip_depth_group< VRC_LGROUP >( *z, m0, m, d, valid, stepSize );
+        /* The element a sample stands for (a hit's gradient is centred on it) is the voxel the point sampler addresses at
+         * its position, the floor of the slot-local coordinate l: of the two taps of an axis (floor( l - 0.5 ) and the next,
+         * clamped as the sampler clamps) it is the second exactly when the weight is >= 0.5 (l - 0.5 and the weight are
+         * exact for l >= 0.5; below, both taps are 0). */
+        if( fold.template group< VRC_LGROUP >( d, valid, [&]( int k ) {
+                return t[k].ax[t[k].wx >= 0.5f ? 1 : 0] + t[k].ay[t[k].wy >= 0.5f ? 1 : 0] + t[k].az[t[k].wz >= 0.5f ? 1 : 0];
+            } ) )
+            travel = 0.0f;
     }
 }
 
+/* The end of a brick visit, whatever the fold: the lanes with `march` set walk segment s, the others stand by without
+ * travel, and a wave none of whose lanes is left to march does not set the walk up.  BIG: the atlas holds more than 2^32
+ * voxels; offsets inside a slot stay 32-bit and the slot's 64-bit base moves into the lane's atlas pointer
+ * (vrc_march_brick), so the elements a fold is handed are slot-local */
+template < bool CLAMP, bool FIXED, bool TRILINEAR, bool SPELT, typename ATLAS_T, int GROUP, bool BIG, typename FOLD >
+VRC_HD void vrc_projection_march( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, bool march,
+                                  const ATLAS_T* __restrict__ atlas, FOLD& fold, uint32_t& nSamples )
+{
+    bool any = march;
+#if defined( __HIP_DEVICE_COMPILE__ )
+    any = __builtin_amdgcn_ballot_w64( march ) != 0ull;
+#endif
+    if( !any )
+        return;
+    const float travel = march ? s.dist : 0.0f;
+    vrc_dev_node local = n;
+    const ATLAS_T* slot = atlas;
+    if( BIG )
+    {
+        local.slotBase = 0u;
+        slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
+    }
+    if constexpr( TRILINEAR )
+        vrc_projection_walk_trilinear< CLAMP, SPELT, ATLAS_T >( f, local, s, travel, slot, fold, nSamples );
+    else
+        vrc_projection_walk_point< CLAMP, FIXED, ATLAS_T, GROUP >( f, local, s, travel, slot, fold, nSamples );
+}
+
+/* the maximum or the minimum of a ray, m, with its depth z where DEPTH (vrc_mip_depth_group).  Integer voxels: two
+ * samples per instruction, v_max3_u32 / v_min3_u32.  A step that is not taken contributes the fold's identity */
+template < int FOLD, bool DEPTH, typename D >
+struct vrc_extremum_fold
+{
+    D& m;
+    vrc_mip_depth& z;
+    const float stepSize;
+
+    template < int N, typename ELEM >
+    VRC_HD bool group( const D* d, const bool* taken, const ELEM& ) const
+    {
+        D none, e[N];
+        vrc_mip_fold_identity< FOLD >( none );
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+            e[k] = taken[k] ? d[k] : none;
+        const D m0 = m;
+#pragma unroll
+        for( int k = 0; k + 1 < N; k += 2 )
+            m = vrc_mip_fold3< FOLD >( m, e[k], e[k + 1] );
+        if( N & 1 )
+            m = vrc_mip_fold< FOLD >( m, e[N - 1] );
+        if constexpr( DEPTH )
+            vrc_mip_depth_group< N >( z, m0, m, e, taken, stepSize );
+        return false;
+    }
+};
+
 /* ---- the mean fold (VRC_FOLD_MEAN) ------------------------------------------------------------------------------------
- * The two marches above once more, control structure and all -- groups, guard, travel chain, tails: positions and
- * counts stay the composite's -- with an accumulate where the maximum was.  The sum of a ray is
+ * The two walks above with an accumulate where the maximum was (vrc_mean_fold).  The sum of a ray is
  *   an unsigned 64-bit integer  for point samples of the 8- and 16-bit atlases: the stored values add exactly.  A group
  *     is summed in 32 bits, two samples per three-operand add (v_add3_u32; a group of 16-bit voxels stays far below
  *     2^32), and carried into the 64 once;
@@ -2570,141 +2621,37 @@ VRC_HD ACC vrc_mean_from_bits( uint32_t lo, uint32_t hi )
     return sum;
 }
 
-template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename ACC >
-VRC_HD void vrc_mean_segment_point( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
-                                    const ATLAS_T* __restrict__ atlas, ACC& sum, uint32_t& nSamples )
+template < typename ACC >
+struct vrc_mean_fold
 {
-    constexpr bool INTEGER = sizeof( ATLAS_T ) <= 2;
-    const float stepSize = f.stepSize;
-    const vrc_sampler sm = vrc_make_sampler( n, f );
-    vrc_f3 pos = s.pos;
-    if( !( travel > 0.0f ) )
-        return;
-    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
-    if( FIXED )
-        fp = vrc_fixpos_init( sm, pos, s.step );
-    const float guard = stepSize * (float)( GROUP + 1 );
-    while( travel > guard )
+    ACC& sum;
+
+    template < int N, typename D, typename ELEM >
+    VRC_HD bool group( const D* d, const bool* taken, const ELEM& ) const
     {
-        uint32_t idx[GROUP];
-        if( FIXED )
-            vrc_group_indices_fixed< GROUP >( sm, fp, idx );
-        else
-            vrc_group_indices< CLAMP, GROUP >( sm, pos, s.step, idx );
-#pragma unroll
-        for( int k = 0; k < GROUP; ++k )
-            travel -= stepSize; /* same sequential subtraction as the reference */
-        if constexpr( INTEGER )
+        if constexpr( std::is_integral< ACC >::value )
         {
-            uint32_t d[GROUP], g = 0u;
+            uint32_t e[N], g = 0u;
 #pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-                d[k] = (uint32_t)vrc_gather( atlas, idx[k] );
+            for( int k = 0; k < N; ++k )
+                e[k] = taken[k] ? d[k] : 0u;
 #pragma unroll
-            for( int k = 0; k + 1 < GROUP; k += 2 )
-                g = g + d[k] + d[k + 1];
-            if( GROUP & 1 )
-                g += d[GROUP - 1];
+            for( int k = 0; k + 1 < N; k += 2 )
+                g = g + e[k] + e[k + 1];
+            if( N & 1 )
+                g += e[N - 1];
             sum += (ACC)g;
         }
         else
         {
-            float d[GROUP];
 #pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-                d[k] = (float)vrc_gather( atlas, idx[k] );
-#pragma unroll
-            for( int k = 0; k < GROUP; ++k )
-                sum += (ACC)d[k];
-        }
-        nSamples += GROUP;
-    }
-    constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
-    while( travel > 0.0f )
-    {
-        uint32_t idx[TAILG], cnt = 0;
-        if( FIXED )
-            vrc_group_indices_fixed< TAILG >( sm, fp, idx );
-        else
-            vrc_group_indices< CLAMP, TAILG >( sm, pos, s.step, idx );
-#pragma unroll
-        for( int k = 0; k < TAILG; ++k )
-        {
-            const bool v = travel > 0.0f;
-            cnt += v ? 1u : 0u;
-            idx[k] = v ? idx[k] : 0u; /* a step the reference does not take reads element 0 and contributes nothing */
-            travel -= stepSize;
-        }
-        if constexpr( INTEGER )
-        {
-            uint32_t d[TAILG], g = 0u;
-#pragma unroll
-            for( int k = 0; k < TAILG; ++k )
-                d[k] = (uint32_t)vrc_gather( atlas, idx[k] );
-#pragma unroll
-            for( int k = 0; k < TAILG; ++k )
-                g += (uint32_t)k < cnt ? d[k] : 0u;
-            sum += (ACC)g;
-        }
-        else
-        {
-            float d[TAILG];
-#pragma unroll
-            for( int k = 0; k < TAILG; ++k )
-                d[k] = (float)vrc_gather( atlas, idx[k] );
-#pragma unroll
-            for( int k = 0; k < TAILG; ++k )
-                if( (uint32_t)k < cnt )
+            for( int k = 0; k < N; ++k )
+                if( taken[k] )
                     sum += (ACC)d[k];
         }
-        nSamples += cnt;
+        return false;
     }
-}
-
-template < bool CLAMP, typename ATLAS_T >
-VRC_HD void vrc_mean_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
-                                        const ATLAS_T* __restrict__ atlas, double& sum, uint32_t& nSamples )
-{
-    const float stepSize = f.stepSize;
-    const vrc_sampler sm = vrc_make_sampler( n, f );
-    vrc_f3 pos = s.pos;
-    while( travel > 0.0f )
-    {
-        bool valid[VRC_LGROUP];
-        vrc_taps t[VRC_LGROUP];
-#pragma unroll
-        for( int k = 0; k < VRC_LGROUP; ++k )
-        {
-            VRC_FAST_FP
-            valid[k] = travel > 0.0f;
-            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
-            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
-            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
-            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
-            pos.x += s.step.x;
-            pos.y += s.step.y;
-            pos.z += s.step.z;
-            travel -= stepSize;
-        }
-        float v[VRC_LGROUP][8];
-#pragma unroll
-        for( int k = 0; k < VRC_LGROUP; ++k )
-#pragma unroll
-            for( int c = 0; c < 8; ++c )
-            {
-                const uint32_t e = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
-                v[k][c] = (float)vrc_gather( atlas, valid[k] ? e : 0u );
-            }
-#pragma unroll
-        for( int k = 0; k < VRC_LGROUP; ++k )
-        {
-            const float d = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
-            if( valid[k] )
-                sum += (double)d;
-            nSamples += valid[k] ? 1u : 0u;
-        }
-    }
-}
+};
 
 /* the mean of a pixel's state, less the shift of an offset-binary atlas: the quotient in double, rounded to float once */
 template < bool INTEGER >
@@ -2766,32 +2713,16 @@ VRC_HD void vrc_mean_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc
             }
         }
     }
-    bool any = march;
-#if defined( __HIP_DEVICE_COMPILE__ )
-    any = __builtin_amdgcn_ballot_w64( march ) != 0ull;
-#endif
-    if( any )
-    {
-        const float travel = march ? s.dist : 0.0f;
-        vrc_dev_node local = n;
-        const ATLAS_T* slot = atlas;
-        if( BIG )
-        {
-            local.slotBase = 0u;
-            slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
-        }
-        if constexpr( TRILINEAR )
-            vrc_mean_segment_trilinear< CLAMP, ATLAS_T >( f, local, s, travel, slot, sum, nSamples );
-        else
-            vrc_mean_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, ACC >( f, local, s, travel, slot, sum, nSamples );
-    }
+    /* (false: the interpolation is vrc_trilerp, fused as the compiler chooses, as it always was for this fold) */
+    vrc_mean_fold< ACC > fold = { sum };
+    vrc_projection_march< CLAMP, FIXED, TRILINEAR, false, ATLAS_T, GROUP, BIG >( f, n, s, march, atlas, fold, nSamples );
     state.x = vrc_bits_float( vrc_mean_bits_lo( sum ) );
     state.y = vrc_bits_float( vrc_mean_bits_hi( sum ) );
 }
 
 /* ---- the first-crossing fold (VRC_FOLD_FIRST): an isosurface frame ------------------------------------------------------
- * include/vrc_hip.h has the definition ("An isosurface frame").  The sample set is the MIP frame's; the marches below are
- * the two above once more -- groups, guard, travel chain, tails -- and what is kept per ray is the hitting sample of the
+ * include/vrc_hip.h has the definition ("An isosurface frame").  The sample set is the MIP frame's, taken by the same
+ * two walks (vrc_first_crossing_fold), and what is kept per ray is the hitting sample of the
  * smallest t_j (vrc_mip_sample_t): its value V, its depth D, and where it was read, for the gradient that is gathered once
  * after the march.  A sample hits when it is >= the frame's threshold: an integer comparison of the stored voxel for point
  * samples of the 8- and 16-bit atlases, a float comparison (false for a NaN) for everything else.
@@ -2878,85 +2809,34 @@ VRC_HD bool vrc_iso_group( vrc_iso_march< D >& z, D thr, D gmax, const D* d, con
     return z.tGroup > z.d;
 }
 
-/* point samples of one brick segment: vrc_mip_segment_point with the search in place of the fold */
-template < bool CLAMP, bool FIXED, typename ATLAS_T, int GROUP, typename D >
-VRC_HD void vrc_iso_segment_point( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
-                                   const ATLAS_T* __restrict__ atlas, D thr, bool skip, vrc_iso_march< D >& z,
-                                   uint32_t& nSamples )
+/* the first crossing of a ray, z, with the search in place of the maximum: per group the largest sample, NaN left out,
+ * then vrc_iso_group.  skip: leave the segment once nothing behind the group can change the ray */
+template < typename D >
+struct vrc_first_crossing_fold
 {
-    const float stepSize = f.stepSize;
-    const vrc_sampler sm = vrc_make_sampler( n, f );
-    vrc_f3 pos = s.pos;
-    if( !( travel > 0.0f ) )
-        return;
-    vrc_fixpos fp = { 0, 0, 0, 0, 0, 0 };
-    if( FIXED )
-        fp = vrc_fixpos_init( sm, pos, s.step );
-    const float guard = stepSize * (float)( GROUP + 1 );
-    while( travel > guard )
-    {
-        uint32_t idx[GROUP];
-        if( FIXED )
-            vrc_group_indices_fixed< GROUP >( sm, fp, idx );
-        else
-            vrc_group_indices< CLAMP, GROUP >( sm, pos, s.step, idx );
-#pragma unroll
-        for( int k = 0; k < GROUP; ++k )
-            travel -= stepSize; /* same sequential subtraction as the reference */
-        D d[GROUP];
-#pragma unroll
-        for( int k = 0; k < GROUP; ++k )
-            d[k] = (D)vrc_gather( atlas, idx[k] );
-        D gmax;
-        vrc_mip_identity( gmax );
-#pragma unroll
-        for( int k = 0; k + 1 < GROUP; k += 2 )
-            gmax = vrc_mip_max3( gmax, d[k], d[k + 1] );
-        if( GROUP & 1 )
-            gmax = vrc_mip_max( gmax, d[GROUP - 1] );
-        nSamples += GROUP;
-        bool taken[GROUP];
-#pragma unroll
-        for( int k = 0; k < GROUP; ++k )
-            taken[k] = true;
-        if( vrc_iso_group< GROUP >( z, thr, gmax, d, taken, stepSize, [&]( int k ) { return idx[k]; } ) && skip )
-            travel = 0.0f;
-    }
-    constexpr int TAILG = GROUP >= 8 ? ( GROUP + 2 ) / 4 : ( GROUP >= 2 ? GROUP / 2 : 1 );
-    while( travel > 0.0f )
-    {
-        uint32_t idx[TAILG], cnt = 0;
-        D d[TAILG];
-        bool taken[TAILG];
-        if( FIXED )
-            vrc_group_indices_fixed< TAILG >( sm, fp, idx );
-        else
-            vrc_group_indices< CLAMP, TAILG >( sm, pos, s.step, idx );
-#pragma unroll
-        for( int k = 0; k < TAILG; ++k )
-        {
-            taken[k] = travel > 0.0f;
-            cnt += taken[k] ? 1u : 0u;
-            idx[k] = taken[k] ? idx[k] : 0u; /* a step the reference does not take reads element 0 and is not looked at */
-            travel -= stepSize;
-        }
-#pragma unroll
-        for( int k = 0; k < TAILG; ++k )
-            d[k] = (D)vrc_gather( atlas, idx[k] );
-        D gmax;
-        vrc_mip_identity( gmax );
-#pragma unroll
-        for( int k = 0; k < TAILG; ++k )
-            gmax = vrc_mip_max( gmax, taken[k] ? d[k] : gmax );
-        nSamples += cnt;
-        if( vrc_iso_group< TAILG >( z, thr, gmax, d, taken, stepSize, [&]( int k ) { return idx[k]; } ) && skip )
-            travel = 0.0f;
-    }
-}
+    vrc_iso_march< D >& z;
+    const D thr;
+    const bool skip;
+    const float stepSize;
 
-/* What the uniform-brick shortcut counts for a segment it does not march: the samples vrc_iso_segment_point would have
- * taken -- all of them without skipping, and with it the groups up to the one in front of which the ray leaves, by the
- * same travel chain.  d: the ray's D after the segment's first sample (a uniform segment changes it there or nowhere). */
+    template < int N, typename ELEM >
+    VRC_HD bool group( const D* d, const bool* taken, const ELEM& elem ) const
+    {
+        D gmax;
+        vrc_mip_identity( gmax );
+#pragma unroll
+        for( int k = 0; k < N; ++k )
+            gmax = vrc_mip_max( gmax, taken[k] ? d[k] : gmax );
+        return vrc_iso_group< N >( z, thr, gmax, d, taken, stepSize, elem ) && skip;
+    }
+};
+
+/* What the uniform-brick shortcut counts for a segment it does not march: the samples vrc_projection_walk_point would
+ * have taken under vrc_first_crossing_fold -- all of them without skipping, and with it the groups up to the one in front
+ * of which the ray leaves.  It MIRRORS that walk's travel chain (guard, whole groups, TAILG, masked tail) and
+ * vrc_iso_group's leave test by hand: a change to either is a change here.  Kept apart because the walk cannot run
+ * without its addresses and gathers, and the host and the device have to count the same.  d: the ray's D after the
+ * segment's first sample (a uniform segment changes it there or nowhere). */
 template < int GROUP >
 VRC_HD uint32_t vrc_iso_uniform_count( float travel, float stepSize, float tNear, float d, bool skip )
 {
@@ -2986,61 +2866,6 @@ VRC_HD uint32_t vrc_iso_uniform_count( float travel, float stepSize, float tNear
             return n;
     }
     return n;
-}
-
-/* trilinear samples of one brick segment: vrc_mip_segment_trilinear with the search in place of the fold.  The element
- * a hit's gradient is centred on is the voxel the point sampler addresses at the sample's position, the floor of the
- * slot-local coordinate l: of the two taps of an axis (floor( l - 0.5 ) and the next, clamped as the sampler clamps) it is
- * the second exactly when the weight is >= 0.5 (l - 0.5 and the weight are exact for l >= 0.5; below, both taps are 0). */
-template < bool CLAMP, typename ATLAS_T >
-VRC_HD void vrc_iso_segment_trilinear( const vrc_frame& f, const vrc_dev_node& n, const vrc_segment& s, float travel,
-                                       const ATLAS_T* __restrict__ atlas, float thr, bool skip, vrc_iso_march< float >& z,
-                                       uint32_t& nSamples )
-{
-    const float stepSize = f.stepSize;
-    const vrc_sampler sm = vrc_make_sampler( n, f );
-    vrc_f3 pos = s.pos;
-    while( travel > 0.0f )
-    {
-        bool valid[VRC_LGROUP];
-        vrc_taps t[VRC_LGROUP];
-#pragma unroll
-        for( int k = 0; k < VRC_LGROUP; ++k )
-        {
-            VRC_FAST_FP
-            valid[k] = travel > 0.0f;
-            const float lx = ( pos.x - sm.minx ) * sm.kx + sm.ox;
-            const float ly = ( pos.y - sm.miny ) * sm.ky + sm.oy;
-            const float lz = ( pos.z - sm.minz ) * sm.kz + sm.oz;
-            t[k] = vrc_trilinear_taps< CLAMP >( sm, lx, ly, lz );
-            pos.x += s.step.x;
-            pos.y += s.step.y;
-            pos.z += s.step.z;
-            travel -= stepSize;
-        }
-        float v[VRC_LGROUP][8];
-#pragma unroll
-        for( int k = 0; k < VRC_LGROUP; ++k )
-#pragma unroll
-            for( int c = 0; c < 8; ++c )
-            {
-                const uint32_t e = t[k].ax[c & 1] + t[k].ay[( c >> 1 ) & 1] + t[k].az[c >> 2];
-                v[k][c] = (float)vrc_gather( atlas, valid[k] ? e : 0u );
-            }
-        float d[VRC_LGROUP];
-        float gmax = vrc_bits_float( 0xFF800000u );
-#pragma unroll
-        for( int k = 0; k < VRC_LGROUP; ++k )
-        {
-            d[k] = vrc_trilerp( v[k], t[k].wx, t[k].wy, t[k].wz );
-            gmax = vrc_mip_max( gmax, valid[k] ? d[k] : gmax );
-            nSamples += valid[k] ? 1u : 0u;
-        }
-        if( vrc_iso_group< VRC_LGROUP >( z, thr, gmax, d, valid, stepSize, [&]( int k ) {
-                return t[k].ax[t[k].wx >= 0.5f ? 1 : 0] + t[k].ay[t[k].wy >= 0.5f ? 1 : 0] + t[k].az[t[k].wz >= 0.5f ? 1 : 0];
-            } ) && skip )
-            travel = 0.0f;
-    }
 }
 
 /* vrc_pixel_mip's state word of a hit in a uniform brick: there is nothing to gather, the gradient is 0 */
@@ -3112,29 +2937,13 @@ VRC_HD bool vrc_iso_brick( const vrc_frame& f, const vrc_dev_node& n, uint32_t n
             }
         }
     }
-    bool any = march;
-#if defined( __HIP_DEVICE_COMPILE__ )
-    any = __builtin_amdgcn_ballot_w64( march ) != 0ull;
-#endif
-    uint32_t base = n.slotBase;
-    if( any )
-    {
-        const float travel = march ? s.dist : 0.0f;
-        vrc_dev_node local = n;
-        const ATLAS_T* slot = atlas;
-        if( BIG )
-        {
-            local.slotBase = 0u;
-            base = 0u;
-            slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
-        }
-        if constexpr( TRILINEAR )
-            vrc_iso_segment_trilinear< CLAMP, ATLAS_T >( f, local, s, travel, slot, thr, skip, z, nSamples );
-        else
-            vrc_iso_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, D >( f, local, s, travel, slot, thr, skip, z, nSamples );
-    }
+    /* (false: vrc_trilerp, as vrc_mean_brick) */
+    vrc_first_crossing_fold< D > fold = { z, thr, skip, f.stepSize };
+    vrc_projection_march< CLAMP, FIXED, TRILINEAR, false, ATLAS_T, GROUP, BIG >( f, n, s, march, atlas, fold, nSamples );
     if( z.lowered )
     {
+        /* (z.where of a marched hit: slot-local already where BIG) */
+        const uint32_t base = BIG ? 0u : n.slotBase;
         state.x = vrc_bits_float( vrc_mip_bits( z.v ) );
         state.y = vrc_bits_float( uniformHit ? VRC_ISO_WHERE_UNIFORM : z.where - base + 1u );
         state.z = z.d;
@@ -3313,35 +3122,10 @@ VRC_HD bool vrc_mip_brick( const vrc_frame& f, const vrc_dev_node& n, const vrc_
             }
         }
     }
-    bool any = march;
-#if defined( __HIP_DEVICE_COMPILE__ )
-    any = __builtin_amdgcn_ballot_w64( march ) != 0ull;
-#endif
-    if( any )
-    {
-        const float travel = march ? s.dist : 0.0f;
-        vrc_dev_node local = n;
-        const ATLAS_T* slot = atlas;
-        if( BIG )
-        {
-            /* the slot's 64-bit base moves into the lane's atlas pointer (vrc_march_brick) */
-            local.slotBase = 0u;
-            slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
-        }
-        if constexpr( DEPTH )
-        {
-            if constexpr( TRILINEAR )
-                vrc_mip_segment_trilinear< CLAMP, ATLAS_T, FOLD, true >( f, local, s, travel, slot, m, nSamples, &z );
-            else
-                vrc_mip_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, D, FOLD, true >( f, local, s, travel, slot, m, nSamples, &z );
-        }
-        else
-        if constexpr( TRILINEAR )
-            vrc_mip_segment_trilinear< CLAMP, ATLAS_T, FOLD >( f, local, s, travel, slot, m, nSamples );
-        else
-            vrc_mip_segment_point< CLAMP, FIXED, ATLAS_T, GROUP, D, FOLD >( f, local, s, travel, slot, m, nSamples );
-        has = has || march;
-    }
+    /* (every maximum and minimum spells the interpolation out, with depth and without: vrc_trilerp_fused_as_plain) */
+    vrc_extremum_fold< FOLD, DEPTH, D > fold = { m, z, f.stepSize };
+    vrc_projection_march< CLAMP, FIXED, TRILINEAR, true, ATLAS_T, GROUP, BIG >( f, n, s, march, atlas, fold, nSamples );
+    has = has || march;
     state.x = vrc_bits_float( vrc_mip_bits( m ) );
     state.y = has ? 1.0f : 0.0f;
     if constexpr( DEPTH )

@@ -2,8 +2,9 @@
  * vrc_kernel_frame.h -- the frame every tile kernel puts around its march, in pieces: one wave64 = one 8x8 pixel tile in
  * Morton lane order, four tiles of a schedule unit per workgroup, the tile schedule, the tile culling of the
  * reference-order loop, a table and the per-axis address tables of the fixed-point stepping in LDS, the sample count's
- * reduction; and what the launchers of such kernels share.  Included by vrc_kernels_mip.h,
- * vrc_kernels_shade.hip and vrc_kernels_cdepth.hip; the __shared__ arrays stay where the kernels declare them.
+ * reduction; and what the launchers of such kernels share: one launch and one ladder from the frame's
+ * options to the instance.  Included by vrc_kernels_mip.h, vrc_kernels_shade.hip, vrc_kernels_cdepth.hip and (the
+ * launchers' side alone) vrc_kernels_preint.hip; the __shared__ arrays stay where the kernels declare them.
  * vrc_k_raycast (vrc_kernels.hip), whose frame this is, keeps its own text: its code object is held to the last byte,
  * and with the pieces called from here its registers are numbered differently.  vrc_k_raycast_preint keeps its own as
  * well: its 8-bit fixed-point grid-walk instance is 6-7 % slower over these pieces (profiles/r14_shared_march.txt).
@@ -150,16 +151,16 @@ static hipError_t vrc_frame_launch( const char* name, void ( *kernel )( KArgs...
     return hipGetLastError();
 }
 
-/* The instances of a shaded or a depth-tracking composite (K::POINT, K::TRILINEAR: its two modes; K::launch< DDA, CLAMP, FIXED, MODE,
- * ATLAS_T, BIG >: one launch) by the sampler of the plain composite forms (vrc_launch_raycast): fixed-point stepping where
- * the caller asked for it and the slot has an overlap (point samples), the float chain with or without clamped
- * addressing otherwise; the trilinear gather form always steps in float.  8-bit point samples of an atlas of more than
- * 2^32 voxels step in float, as vrc_launch_raycast's BIG instances do: the extension takes the plain frame's sample
- * positions */
+/* The instances of a kernel family K (K::POINT, K::TRILINEAR: its two modes; K::launch< DDA, CLAMP, FIXED, MODE, ATLAS_T,
+ * BIG >: one launch) by the sampler of the plain composite forms (vrc_launch_raycast): fixed-point stepping where the
+ * caller asked for it and the slot has an overlap (point samples), the float chain with or without clamped addressing
+ * otherwise; the trilinear gather form always steps in float.  K::FIXED_BIG8: do 8-bit point samples of an atlas of more
+ * than 2^32 voxels step in fixed point too?  The projections': yes.  The composite extensions': no, in float, as
+ * vrc_launch_raycast's BIG instances do -- they take the plain frame's sample positions */
 template < typename K, int MODE, typename ATLAS_T, bool BIG >
 static hipError_t vrc_frame_launch_sampler( const vrc_raycast_args& a, hipStream_t stream )
 {
-    if constexpr( MODE == K::POINT && ( !BIG || sizeof( ATLAS_T ) >= 2 ) )
+    if constexpr( MODE == K::POINT && ( K::FIXED_BIG8 || !BIG || sizeof( ATLAS_T ) >= 2 ) )
         if( a.fixedStepping && !a.clamp )
             return a.gridDda ? K::template launch< true, false, true, MODE, ATLAS_T, BIG >( a, stream )
                              : K::template launch< false, false, true, MODE, ATLAS_T, BIG >( a, stream );
@@ -181,10 +182,8 @@ static hipError_t vrc_frame_launch_atlas( const vrc_raycast_args& a, hipStream_t
 }
 
 template < typename K >
-static hipError_t vrc_frame_launch_extension( const vrc_raycast_args& a, hipStream_t stream )
+static hipError_t vrc_frame_launch_family( const vrc_raycast_args& a, hipStream_t stream )
 {
-    if( a.gridDda && a.gridTable == nullptr )
-        return hipErrorInvalidValue;
     switch( a.elemBytes )
     {
     case 1: return vrc_frame_launch_atlas< K, uint8_t >( a, stream );
@@ -192,6 +191,14 @@ static hipError_t vrc_frame_launch_extension( const vrc_raycast_args& a, hipStre
     case 4: return vrc_frame_launch_atlas< K, float >( a, stream );
     default: return hipErrorInvalidValue;
     }
+}
+
+template < typename K >
+static hipError_t vrc_frame_launch_extension( const vrc_raycast_args& a, hipStream_t stream )
+{
+    if( a.gridDda && a.gridTable == nullptr )
+        return hipErrorInvalidValue;
+    return vrc_frame_launch_family< K >( a, stream );
 }
 
 #endif

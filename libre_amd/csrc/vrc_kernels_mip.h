@@ -66,40 +66,20 @@ __global__ __launch_bounds__( VRC_FRAME_WG_THREADS ) __attribute__( ( amdgpu_wav
         vrc_frame_add_samples( sampleCounter, nSamples, lane );
 }
 
-template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
-static hipError_t launch_mip( const vrc_raycast_args& a, hipStream_t stream )
+/* the kernel family of one fold for the launch ladder of vrc_kernel_frame.h.  Point samples step in fixed point wherever
+ * the caller asked for it, 8-bit voxels of an atlas of more than 2^32 voxels included */
+template < int FOLD >
+struct vrc_mip_kernels
 {
-    return vrc_frame_launch< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >(
-        "vrc_k_raycast_mip", &vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >, a, stream );
-}
-
-/* the sampler of the composite forms: fixed-point stepping where the slot has an overlap and fits eight bits a side
- * (point samples), the float chain with or without clamped addressing otherwise; the trilinear gather form always
- * steps in float, as vrc_march_segment_linear does */
-template < int MODE, typename ATLAS_T, bool BIG >
-static hipError_t launch_mip_sampler( const vrc_raycast_args& a, hipStream_t stream )
-{
-    if constexpr( vrc_mode_base( MODE ) == VRC_MODE_MIP )
-        if( a.fixedStepping && !a.clamp )
-            return a.gridDda ? launch_mip< true, false, true, MODE, ATLAS_T, BIG >( a, stream )
-                             : launch_mip< false, false, true, MODE, ATLAS_T, BIG >( a, stream );
-    if( a.clamp )
-        return a.gridDda ? launch_mip< true, true, false, MODE, ATLAS_T, BIG >( a, stream )
-                         : launch_mip< false, true, false, MODE, ATLAS_T, BIG >( a, stream );
-    return a.gridDda ? launch_mip< true, false, false, MODE, ATLAS_T, BIG >( a, stream )
-                     : launch_mip< false, false, false, MODE, ATLAS_T, BIG >( a, stream );
-}
-
-template < int FOLD, typename ATLAS_T >
-static hipError_t launch_mip_atlas( const vrc_raycast_args& a, hipStream_t stream )
-{
-    constexpr int POINT = VRC_MODE_WITH_FOLD( VRC_MODE_MIP, FOLD ), TRILINEAR = VRC_MODE_WITH_FOLD( VRC_MODE_MIP_TRILINEAR, FOLD );
-    if( a.linear )
-        return a.bigAtlas ? launch_mip_sampler< TRILINEAR, ATLAS_T, true >( a, stream )
-                          : launch_mip_sampler< TRILINEAR, ATLAS_T, false >( a, stream );
-    return a.bigAtlas ? launch_mip_sampler< POINT, ATLAS_T, true >( a, stream )
-                      : launch_mip_sampler< POINT, ATLAS_T, false >( a, stream );
-}
+    static constexpr int POINT = VRC_MODE_WITH_FOLD( VRC_MODE_MIP, FOLD ), TRILINEAR = VRC_MODE_WITH_FOLD( VRC_MODE_MIP_TRILINEAR, FOLD );
+    static constexpr bool FIXED_BIG8 = true;
+    template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
+    static hipError_t launch( const vrc_raycast_args& a, hipStream_t stream )
+    {
+        return vrc_frame_launch< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >(
+            "vrc_k_raycast_mip", &vrc_k_raycast_mip< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >, a, stream );
+    }
+};
 
 /* the instances of one fold: what a translation unit's entry point is */
 template < int FOLD >
@@ -111,13 +91,7 @@ static hipError_t launch_mip_fold( const vrc_raycast_args& a, hipStream_t stream
         return hipErrorInvalidValue;
     if( FOLD == VRC_FOLD_FIRST && ( a.frame.mipDepth == nullptr || a.frame.isoGrad == nullptr ) )
         return hipErrorInvalidValue;
-    switch( a.elemBytes )
-    {
-    case 1: return launch_mip_atlas< FOLD, uint8_t >( a, stream );
-    case 2: return launch_mip_atlas< FOLD, uint16_t >( a, stream );
-    case 4: return launch_mip_atlas< FOLD, float >( a, stream );
-    default: return hipErrorInvalidValue;
-    }
+    return vrc_frame_launch_family< vrc_mip_kernels< FOLD > >( a, stream );
 }
 
 #endif

@@ -11,9 +11,7 @@
  * lives in the L2, and the reads of a march cluster at its diagonal).  Samples are always counted in a register; the
  * counter is only added to where the caller asked for it (vrc_kernels_mip.h does the same: half the instances).
  */
-#include "vrc_internal.h"
-
-#include <type_traits>
+#include "vrc_kernel_frame.h" /* (the launchers' side: the kernel below keeps its own text) */
 
 #define VRC_PREINT_WG_THREADS ( 64u * VRC_WAVES_PER_GROUP )
 
@@ -168,67 +166,22 @@ __global__ __launch_bounds__( VRC_PREINT_WG_THREADS ) __attribute__( ( amdgpu_wa
     }
 }
 
-template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
-static hipError_t launch_preint( const vrc_raycast_args& a, hipStream_t stream )
+/* the kernel family for the launch ladder of vrc_kernel_frame.h: the sampler of the plain composite forms */
+struct vrc_preint_kernels
 {
-    const uint32_t tilesX = ( a.frame.width + VRC_TILE_W - 1 ) / VRC_TILE_W;
-    const uint32_t tilesY = ( a.frame.height + VRC_TILE_H - 1 ) / VRC_TILE_H;
-    const uint32_t nTiles = tilesX * tilesY;
-    if( nTiles == 0 )
-        return hipSuccess;
-    vrc_internal_note_kernel( "vrc_k_raycast_preint<%s,%s,%s,%d,%s,%s>", DDA ? "true" : "false", CLAMP ? "true" : "false",
-                              FIXED ? "true" : "false", (int)MODE,
-                              std::is_same< ATLAS_T, float >::value ? "float" : sizeof( ATLAS_T ) == 1 ? "unsigned char" : "unsigned short",
-                              BIG ? "true" : "false" );
-    vrc_internal_note_kernel_fn( (const void*)&vrc_k_raycast_preint< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >,
-                                 (int)VRC_PREINT_WG_THREADS, 0 );
-    vrc_launch_march( a, &vrc_k_raycast_preint< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >,
-                      dim3( ( vrc_schedule_slots( tilesX, tilesY ) + VRC_WAVES_PER_GROUP - 1u ) / VRC_WAVES_PER_GROUP ),
-                      dim3( VRC_PREINT_WG_THREADS ), 0, stream, a.frame, a.nodes, a.gridTable, (const ATLAS_T*)a.atlas,
-                      a.lut, a.classifier, a.pixelBuffer, a.sampleCounter, a.tileOrder, tilesX, nTiles );
-    return hipGetLastError();
-}
-
-/* the sampler of the plain composite forms (vrc_launch_raycast): fixed-point stepping where the caller asked for it
- * and the slot has an overlap (point samples), the float chain with or without clamped addressing otherwise; the
- * trilinear gather form always steps in float */
-template < int MODE, typename ATLAS_T, bool BIG >
-static hipError_t launch_preint_sampler( const vrc_raycast_args& a, hipStream_t stream )
-{
-    /* (8-bit point samples of an atlas of more than 2^32 voxels step in float, as vrc_launch_raycast's BIG instances do:
-     * the pre-integrated frame takes the plain frame's sample positions) */
-    if constexpr( MODE == VRC_MODE_PREINT && ( !BIG || sizeof( ATLAS_T ) >= 2 ) )
-        if( a.fixedStepping && !a.clamp )
-            return a.gridDda ? launch_preint< true, false, true, MODE, ATLAS_T, BIG >( a, stream )
-                             : launch_preint< false, false, true, MODE, ATLAS_T, BIG >( a, stream );
-    if( a.clamp )
-        return a.gridDda ? launch_preint< true, true, false, MODE, ATLAS_T, BIG >( a, stream )
-                         : launch_preint< false, true, false, MODE, ATLAS_T, BIG >( a, stream );
-    return a.gridDda ? launch_preint< true, false, false, MODE, ATLAS_T, BIG >( a, stream )
-                     : launch_preint< false, false, false, MODE, ATLAS_T, BIG >( a, stream );
-}
-
-template < typename ATLAS_T >
-static hipError_t launch_preint_atlas( const vrc_raycast_args& a, hipStream_t stream )
-{
-    if( a.linear )
-        return a.bigAtlas ? launch_preint_sampler< VRC_MODE_PREINT_TRILINEAR, ATLAS_T, true >( a, stream )
-                          : launch_preint_sampler< VRC_MODE_PREINT_TRILINEAR, ATLAS_T, false >( a, stream );
-    return a.bigAtlas ? launch_preint_sampler< VRC_MODE_PREINT, ATLAS_T, true >( a, stream )
-                      : launch_preint_sampler< VRC_MODE_PREINT, ATLAS_T, false >( a, stream );
-}
+    static constexpr int POINT = VRC_MODE_PREINT, TRILINEAR = VRC_MODE_PREINT_TRILINEAR;
+    static constexpr bool FIXED_BIG8 = false;
+    template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
+    static hipError_t launch( const vrc_raycast_args& a, hipStream_t stream )
+    {
+        return vrc_frame_launch< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >(
+            "vrc_k_raycast_preint", &vrc_k_raycast_preint< DDA, CLAMP, FIXED, MODE, ATLAS_T, BIG >, a, stream );
+    }
+};
 
 hipError_t vrc_launch_raycast_preint( const vrc_raycast_args& a, hipStream_t stream )
 {
     if( VRC_TILE_W != 8u || a.lut == nullptr || !a.preint || a.frame.preintTable == nullptr || a.packed )
         return hipErrorInvalidValue;
-    if( a.gridDda && a.gridTable == nullptr )
-        return hipErrorInvalidValue;
-    switch( a.elemBytes )
-    {
-    case 1: return launch_preint_atlas< uint8_t >( a, stream );
-    case 2: return launch_preint_atlas< uint16_t >( a, stream );
-    case 4: return launch_preint_atlas< float >( a, stream );
-    default: return hipErrorInvalidValue;
-    }
+    return vrc_frame_launch_extension< vrc_preint_kernels >( a, stream );
 }

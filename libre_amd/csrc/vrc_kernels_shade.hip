@@ -55,6 +55,7 @@ __global__ __launch_bounds__( VRC_FRAME_WG_THREADS ) __attribute__( ( amdgpu_wav
 struct vrc_shade_kernels
 {
     static constexpr int POINT = VRC_MODE_SHADE, TRILINEAR = VRC_MODE_SHADE_TRILINEAR;
+    static constexpr bool FIXED_BIG8 = false;
     template < bool DDA, bool CLAMP, bool FIXED, int MODE, typename ATLAS_T, bool BIG >
     static hipError_t launch( const vrc_raycast_args& a, hipStream_t stream )
     {
