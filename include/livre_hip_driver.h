@@ -77,6 +77,11 @@ int lvh_app_set_option( lvh_app* app, int vrc_option, int64_t value );
  * under VRC_OPT_PROJECTION = VRC_PROJECTION_ISO, which lvh_app_set_option accepts only after this call.  An error, with the device layer's message, for a NaN or an ambient
  * share outside [0, 1]. */
 int lvh_app_set_isosurface( lvh_app* app, float iso_value, float ambient );
+/* vrc_set_slice on every renderer of the app, those of extra slots and those made later included, as the isosurface is
+ * handed on: the plane (nx, ny, nz, d), n.x + d = 0 in world coordinates, of the frames rendered under VRC_OPT_PROJECTION
+ * = VRC_PROJECTION_SLICE, which lvh_app_set_option accepts only after this call.  An error, with the device layer's
+ * message, for NULL, an entry that is not finite or a zero normal. */
+int lvh_app_set_slice( lvh_app* app, const float plane[4] );
 /* vrc_get_option on the renderer of the selected slot (read-only options such as VRC_OPT_RAY_CACHE_USED included) */
 int lvh_app_get_option( lvh_app* app, int vrc_option, int64_t* value );
 /* RenderInputs::dataSourceRange, in the volume's own values, for volumes that are not uint8 (the reference forces
@@ -122,7 +127,9 @@ int lvh_app_frame_histogram( lvh_app* app, uint64_t* bins, uint32_t capacity, ui
  * minimum) or in an isosurface frame (VRC_PROJECTION_ISO, which always tracks depth: *hit = 1 where the ray reached
  * the isovalue, *value = V of the first sample that did, *t = its D, xyz = the surface point) or in a composite frame
  * rendered with VRC_OPT_COMPOSITE_DEPTH above 0 (lvh_app_set_option; *hit = 1 where the ray's opacity reached the
- * threshold, *value = V of the sample at which it did, *t = its D, xyz = that point):
+ * threshold, *value = V of the sample at which it did, *t = its D, xyz = that point) or in a slice frame
+ * (VRC_PROJECTION_SLICE: *hit = 1 where the pixel's ray meets the plane inside a brick of the frame, *value = the voxel or
+ * interpolated value there, *t = the ray parameter of the plane, xyz = the point on it):
  * what lies behind pixel (x, y) of the window in the selected slot's last frame.  *hit = 1 if the pixel's ray
  * took a sample, *value = the projected value M in the volume's own units, *t = the ray parameter D of the nearest sample
  * that equals M, xyz = its position origin + D * dir (vrc_get_projection_values / vrc_get_projection_depths of that

@@ -157,10 +157,14 @@ typedef struct
                                     * VRC_PROJECTION_MIP (maximum-intensity projection, an extension: see below) |
                                     * VRC_PROJECTION_ISO (shaded isosurface, an extension: "An isosurface frame" below;
                                     * VRC_EINVAL, naming vrc_set_isosurface, on a context that has not called it yet: such
-                                    * a context accepts and refuses the values it did before the projection existed) */
+                                    * a context accepts and refuses the values it did before the projection existed) |
+                                    * VRC_PROJECTION_SLICE (the volume on a plane, an extension: "A slice frame" below;
+                                    * VRC_EINVAL, naming vrc_set_slice, on a context that has not called it yet).  The
+                                    * value 3 is no projection and stays refused: the slice is 4 */
 #define VRC_PROJECTION_COMPOSITE 0
 #define VRC_PROJECTION_MIP 1
 #define VRC_PROJECTION_ISO 2
+#define VRC_PROJECTION_SLICE 4
 #define VRC_OPT_MIP_SKIP 17         /* 1 (default) | 0.  MIP only: a ray does not march a brick whose largest voxel cannot
                                     * beat the maximum the ray already holds (every upload notes it per slot).  The
                                     * maximum does not depend on the order or on samples that cannot raise it: the same
@@ -465,6 +469,58 @@ typedef struct
  * the option for an explicit VRC_KERNEL_LDS or _PACKED, vrc_set_ray_lod on and VRC_VARIANT_GLRAYCASTER;
  * VRC_OPT_DEPTH_SPLIT and VRC_OPT_ERT_COMPACTION are silently the plain kernel.  A depth cue, a "<=" surface, smooth
  * (trilinear) gradients and several isovalues are not part of it. */
+
+/* A slice frame (VRC_OPT_PROJECTION = VRC_PROJECTION_SLICE; vrc_set_slice gives the plane).  The pixel shows the volume
+ * where its ray meets one plane -- an axial, coronal, sagittal or oblique cut -- classified by the transfer function, with
+ * the value and the position under every pixel to read back.  One sample per ray, at a given ray parameter and not on the
+ * ray's sample lattice.  VRC_PROJECTION_SLICE is 4: the value 3 is no projection and stays VRC_EINVAL.
+ *   Plane.  (nx, ny, nz, d) in the clip planes' convention: n.x + d = 0; n need not be a unit vector.
+ *   Ray.  The pixel's ray, its interval [tNearGlobal, tFarGlobal] (global box and clip planes) and tNearPlane are the
+ *     composite frame's, unchanged.  rn = dot(dir, n) and t_p = -(dot(n, origin) + d) / rn in float32, formed in the order
+ *     the clip planes form theirs.  The pixel takes its one sample if and only if the ray hits the box, rn != 0 and
+ *     max(tNearGlobal, tNearPlane) <= t_p <= tFarGlobal.  There is no VRC_EPSILON in place of rn == 0: a ray that lies in
+ *     the plane takes no sample.
+ *   Position.  P = origin + dir * t_p, every product and sum rounded, nothing fused.
+ *   Brick.  The sample is read from a node of this pass's list whose box contains P, faces included.  The list-order
+ *     quirk of the reference loop (a brick with tNear > tFarGlobal ends the ray) is NOT applied: every node is a candidate.
+ *     Containment is decided on the ray: t_p lies in the node's interval of the slab test, widened by 2e-6 max(1, |t_p|)
+ *     -- a few units in the last place of t_p -- so that a P inside the union of the list's boxes never goes unsampled
+ *     because rounding opened a gap between two neighbours.  Where P lies on, or within that rounding of, a face shared
+ *     by several nodes, the sample comes from any one of them.  If no node of this pass contains P, the pixel is left to
+ *     a later pass.
+ *   Sample.  l_a = (P_a - aabbMin_a) * voxPerWorld_a + localOrigin_a, product and sum each rounded, always clamped to
+ *     [0, slotDim_a - 1]: one sample per pixel has no un-clamped instance.  VRC_FILTER_NEAREST: the voxel trunc(l).
+ *     VRC_FILTER_TRILINEAR: the eight taps and weights of the trilinear gather march at l (texel centres at i + 0.5, taps
+ *     clamped to the slot), interpolated x, then y, then z.  V is the value as vrc_get_projection_values reports a MIP
+ *     sample: the volume's own units, signed types un-shifted.
+ *   Pixel.  A sampled pixel is classified exactly as a MIP pixel is: TF((V - r0) / (r1 - r0)), no opacity correction,
+ *     stored (t.rgb * t.a, t.a); a NaN classifies as a NaN density does.  An unsampled pixel keeps its cleared value.
+ *   Passes.  The context keeps (V, D = t_p) per pixel of the pixel buffer, in the running words of a MIP frame with depth:
+ *     same ownership, same invalidation by vrc_pre_render, not read by the first pass.  A later pass sets only a pixel
+ *     whose D is still +infinity.  Changing the plane or VRC_OPT_PROJECTION between vrc_pre_render and vrc_post_render:
+ *     the next vrc_render returns VRC_EINVAL (the plane is latched at the frame's first slice pass).  A vrc_render under
+ *     VRC_PROJECTION_SLICE before the first vrc_set_slice: VRC_EINVAL, naming the function -- and so is the vrc_set_option
+ *     that would select the projection on such a context.
+ *   Read-backs, valid from the frame's first slice pass until the next vrc_pre_render.  vrc_get_projection_values: V,
+ *     count 1 where the pixel is sampled, else 0.  vrc_get_projection_depths: D and origin + D * dir; depth is always
+ *     tracked.  vrc_get_projection_gradients: VRC_EINVAL, as after any frame that is no isosurface frame.
+ *   vrc_stats.samples (VRC_OPT_COUNT_SAMPLES): the pixels this pass sampled.
+ *   VRC_OPT_UNIFORM_BRICKS.  A slot known to hold one value yields that value without a gather (point samples of 8- and
+ *     16-bit voxels).  Frame, V, D and counts are bit-identical with the option on or off.
+ * Served: VRC_KERNEL_AUTO, _REFERENCE_ORDER (the nodes its tile culling leaves, the first that contains P) and _GRID_DDA
+ * (the cell of P looked up in the brick grid, no walk; the neighbouring cells where rounding put P across a cell face);
+ * all seven voxel types, both filters; atlases of more than 2^32 voxels; row maps, caller-owned frame buffers, frames of
+ * several passes; VRC_OPT_RAY_CACHE on the grid form (a still view of slice frames loads its rays; to the frames of another
+ * projection a slice frame is what a MIP frame is: the rays kept for them are forgotten, and kept again as ever).  Refused
+ * as a MIP frame is, VRC_EINVAL
+ * naming the option: an explicit VRC_KERNEL_LDS or _PACKED, vrc_set_ray_lod on, VRC_VARIANT_GLRAYCASTER.  Not read:
+ * VRC_OPT_MIP_*, VRC_OPT_SHADING, VRC_OPT_COMPOSITE_DEPTH, VRC_OPT_PREINTEGRATION, samplesPerRay and VRC_OPT_STEPPING.
+ * Silently the plain slice kernel: VRC_OPT_DEPTH_SPLIT, VRC_OPT_ERT_COMPACTION and VRC_OPT_WALK_CACHE (as a MIP frame: not
+ * replayed, VRC_OPT_WALK_CACHE_USED reads 0, nothing is allocated).  With another projection every frame launches the
+ * kernel instances it launched before the projection existed, and no memory is allocated for it.
+ * Not part of it: thick slabs (a MIP or mean frame between two clip planes is one, quantised to the sample lattice),
+ * curved reformats, an opaque or window / level mode that bypasses the transfer function's alpha, a depth cue, gradients
+ * at the slice, several planes per frame, per-ray LOD and the LDS / packed forms. */
 
 /* A shaded composite frame (VRC_OPT_PROJECTION = VRC_PROJECTION_COMPOSITE, VRC_OPT_SHADING = 1).  The composite frame
  * with one change: the colour a sample adds is multiplied by a headlight term; its opacity is not.
@@ -810,6 +866,11 @@ int vrc_set_isosurface( vrc_ctx* ctx, float iso_value, float ambient );
  * projection. */
 int vrc_get_projection_gradients( vrc_ctx* ctx, float* host_g /* W x H x 3 */ );
 
+/* The plane of VRC_PROJECTION_SLICE frames ("A slice frame" above): plane = (nx, ny, nz, d), the points with
+ * n.x + d = 0, in world coordinates as the clip planes of vrc_update are.  VRC_EINVAL, naming the argument, for NULL, an
+ * entry that is not finite or a zero normal; the plane set before stays. */
+int vrc_set_slice( vrc_ctx* ctx, const float plane[4] );
+
 /* The table the last pre-integrated vrc_render of this context used ("A pre-integrated composite frame" above):
  * host_rgba[(row * 256 + col) * 4 + channel]; *kind (may be NULL) = 0 for the value-indexed table, 1 for the
  * texel-indexed one.  Synchronous on the context's stream.  VRC_EINVAL before any such render. */
@@ -865,8 +926,8 @@ int vrc_last_kernel_occupancy( int* workgroups_per_cu, int* threads_per_workgrou
                            * (added since without a new number, as symbols a caller may bind weakly: the frame histogram,
                            * vrc_pool_create_typed / vrc_pool_voxel_type, vrc_get_projection_values,
                            * vrc_get_projection_depths, vrc_set_isosurface, vrc_get_projection_gradients,
-                           * vrc_get_preintegrated_table; as option
-                           * values only: VRC_PROJECTION_ISO, VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP,
+                           * vrc_get_preintegrated_table, vrc_set_slice; as option
+                           * values only: VRC_PROJECTION_ISO, VRC_PROJECTION_SLICE, VRC_OPT_PROJECTION, VRC_OPT_MIP_SKIP,
                            * VRC_OPT_MIP_FOLD, VRC_OPT_MIP_DEPTH, VRC_OPT_MIP_DEPTH_CUE) */
 /* = VRC_ABI_VERSION for the product build; -VRC_ABI_VERSION for a developer build of the library (compiled with
  * -DVRC_DEV_BUILD: experiment switches, statistics, ablations that render wrong pixels on purpose) */

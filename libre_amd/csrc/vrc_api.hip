@@ -232,6 +232,11 @@ struct vrc_ctx
     size_t dRayCacheCap = 0; /* words per plane */
     vrc_ray_state ray;
     vrc_frame rayPrevFrame;
+    /* ... of which kind of frame: slice frames keep their rays in the same planes, and a frame of the other kind
+     * forgets the state first (render_ray_kind).  To the frames of another projection a slice frame is thereby what a
+     * MIP frame is -- behind it they compute, store and load, and count, record and replay their walk, as they would
+     * without it -- and the other way round */
+    bool rayOfSlice = false;
     int64_t rayCacheUsed = 0;
     vrc_walk_cache walk;
     vrc_walk_plan walkPlan; /* what the last vrc_render did about the walk cache (vrc_plan.h; VRC_OPT_*_USED) */
@@ -287,6 +292,11 @@ struct vrc_ctx
     float* dIsoGrad = nullptr;
     size_t dIsoGradPixels = 0;
     bool gradValid = false;
+    /* a slice frame (include/vrc_hip.h, "A slice frame"): vrc_set_slice's plane (sliceSet: called at all).  Its (V, D) per
+     * pixel are dMipMax and dMipDepth; sliceFrame: the read-backs' messages speak of the frame the state is of */
+    bool sliceSet = false;
+    float slicePlane[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    bool sliceFrame = false;
     /* a pre-integrated composite frame (include/vrc_hip.h, "A pre-integrated composite frame"): the one table, allocated
      * by the first frame that needs it, rebuilt when the kind or one of the classified table's inputs changed */
     vrc_f4* dPreint = nullptr;
@@ -575,8 +585,13 @@ int vrc_set_option( vrc_ctx* c, int option, int64_t value )
     case VRC_OPT_WALK_RESOLVED_USED:
         return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_WALK_RESOLVED_USED is read-only" );
     case VRC_OPT_PROJECTION:
-        if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP && value != VRC_PROJECTION_ISO )
-            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite), 1 (maximum intensity) or 2 (isosurface)" );
+        if( value != VRC_PROJECTION_COMPOSITE && value != VRC_PROJECTION_MIP && value != VRC_PROJECTION_ISO &&
+            value != VRC_PROJECTION_SLICE )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION is 0 (composite), 1 (maximum intensity), 2 (isosurface) "
+                                     "or 4 (slice)" );
+        /* ... and one that never called vrc_set_slice what it had before the slice projection existed */
+        if( value == VRC_PROJECTION_SLICE && !c->sliceSet )
+            return fail( VRC_EINVAL, "vrc_set_option: VRC_OPT_PROJECTION = VRC_PROJECTION_SLICE needs vrc_set_slice first" );
         /* a context that never called vrc_set_isosurface keeps what it had before the isosurface projection existed: the
          * value is refused, here and not only by the render it could not serve */
         if( value == VRC_PROJECTION_ISO && !c->isoSet )
@@ -1676,7 +1691,8 @@ static int render_mode( vrc_ctx* c, render_pass& p )
     p.lp.rangeMax = p.render->dataSourceRange[1] + p.pool->rangeShift;
     p.lp.alphaCorrection = (float)p.render->maxSamplesPerRay / (float)p.render->samplesPerRay;
     p.lp.fracBits = (int)c->opt.tfFracBits;
-    const vrc_refusal r = vrc_plan_mode( c->opt, c->latch, c->rayLod, c->isoSet, c->isoValue, c->isoAmbient, p.pool->elemBytes, p.mode );
+    const vrc_refusal r = vrc_plan_mode( c->opt, c->latch, c->rayLod, c->isoSet, c->isoValue, c->isoAmbient, p.pool->elemBytes, p.mode,
+                                         c->sliceSet, c->slicePlane );
     return r.code == VRC_OK ? VRC_OK : fail( r.code, r.msg );
 }
 
@@ -1825,6 +1841,7 @@ static void render_frame( vrc_ctx* c, render_pass& p )
     p.a.shade = p.mode.shade;
     p.a.cdepth = p.mode.cdepth;
     p.a.preint = p.mode.preint;
+    p.a.slice = p.mode.slice;
     vrc_frame& f = p.a.frame;
     /* the GLSL twin casts through the pixel centre (gl_FragCoord, fragRaycast.glsl:127), the
      * CUDA kernel through the pixel corner (Renderer.cu:106-112) */
@@ -1929,7 +1946,8 @@ static int grow_pixel_depths( vrc_ctx* c, size_t pixels )
 /* what a pass leaves for vrc_get_projection_values and vrc_get_projection_depths */
 static void leave_projection( vrc_ctx* c, render_pass& p, uint32_t fold, bool sums )
 {
-    c->depthValid = p.mode.mipDepth || p.mode.cdepth;
+    c->depthValid = p.mode.mipDepth || p.mode.cdepth || p.mode.slice;
+    c->sliceFrame = p.mode.slice;
     if( c->depthValid )
     {
         c->depthFrame = p.a.frame;
@@ -2012,11 +2030,26 @@ static int render_projection( vrc_ctx* c, render_pass& p )
         c->gradValid = false;
         leave_projection( c, p, (uint32_t)VRC_FOLD_FIRST, false ); /* V as a first-crossing frame leaves it */
     }
+    if( m.slice )
+    {
+        /* (V, D) per pixel where a composite-depth frame keeps its pair, read back as that frame's are; the plane goes
+         * into the frame behind the tile schedule's comparison of frames, which does not depend on it */
+        VRC_TRY( grow_pixel_values( c, pixels ) );
+        VRC_TRY( grow_pixel_depths( c, pixels ) );
+        f.mipMax = c->dMipMax;
+        f.mipDepth = c->dMipDepth;
+        f.mipFirst = c->mipFirst ? 1u : 0u;
+        for( int i = 0; i < 4; ++i )
+            f.slicePlane[i] = c->latch.slicePlane[i] = c->slicePlane[i];
+        c->latch.slice = true;
+        c->gradValid = false;
+        leave_projection( c, p, (uint32_t)VRC_FOLD_FIRST, false );
+    }
     f.cdepthTau = m.cdepth ? (float)c->opt.compositeDepth / 1000.0f : 0.0f;
     f.preintTable = m.preint ? c->dPreint : nullptr;
     f.shadeAmbient = m.shade ? (float)c->opt.shadingAmbient / 1000.0f : 0.0f;
     c->latch.projection = c->opt.projection;
-    if( !m.mip )
+    if( !m.mip && !m.slice )
     {
         c->latch.preint = c->opt.preint;
         c->latch.compositeDepth = c->opt.compositeDepth;
@@ -2083,6 +2116,16 @@ static int render_split_and_compact( vrc_ctx* c, render_pass& p )
     }
     c->lastErtParts = a.ertParts;
     return VRC_OK;
+}
+
+/* whose rays the ray cache keeps: a slice frame's or another frame's.  A change of kind forgets them (vrc_ctx::rayOfSlice) */
+static void render_ray_kind( vrc_ctx* c, const render_pass& p )
+{
+    if( c->rayOfSlice != p.mode.slice )
+    {
+        vrc_ray_forget( c->ray );
+        c->rayOfSlice = p.mode.slice;
+    }
 }
 
 /* ray cache (VRC_OPT_RAY_CACHE): the tile-scheduled grid walk of vrc_k_raycast only (vrc_pixel_grid_dda; the
@@ -2282,6 +2325,7 @@ static int render_march( vrc_ctx* c, render_pass& p )
                    : m.mip      ? ( c->opt.mipFold == VRC_MIP_FOLD_MIN    ? vrc_launch_raycast_minip( a, c->stream )
                                     : c->opt.mipFold == VRC_MIP_FOLD_MEAN ? vrc_launch_raycast_meanip( a, c->stream )
                                                                           : vrc_launch_raycast_mip( a, c->stream ) )
+                   : m.slice    ? vrc_launch_raycast_slice( a, c->stream )
                    : m.cdepth   ? vrc_launch_raycast_cdepth( a, c->stream )
                    : m.preint   ? vrc_launch_raycast_preint( a, c->stream )
                    : m.shade    ? vrc_launch_raycast_shade( a, c->stream )
@@ -2336,6 +2380,7 @@ int vrc_render( vrc_ctx* c, const vrc_view_data* view, const vrc_node_data* node
     render_clear_and_slot_words( c, p );
     VRC_TRY( render_projection( c, p ) );
     VRC_TRY( render_split_and_compact( c, p ) );
+    render_ray_kind( c, p );
     VRC_TRY( render_ray_cache( c, p ) );
     VRC_TRY( render_walk_cache( c, p ) );
     VRC_TRY( render_march( c, p ) );
@@ -2369,8 +2414,8 @@ int vrc_get_projection_values( vrc_ctx* c, float* hostValues, uint32_t* hostCoun
     if( !c || !hostValues )
         return fail( VRC_EINVAL, "vrc_get_projection_values: NULL argument" );
     if( c->projState.pixels == 0u )
-        return fail( VRC_EINVAL, "vrc_get_projection_values: no VRC_OPT_PROJECTION = MIP vrc_render since the last "
-                                 "vrc_pre_render; the values exist from a frame's first MIP pass until the next frame" );
+        return fail( VRC_EINVAL, "vrc_get_projection_values: no VRC_OPT_PROJECTION = MIP, ISO or SLICE vrc_render since the last "
+                                 "vrc_pre_render; the values exist from a frame's first such pass until the next frame" );
     VRC_HIP_CHECK( hipSetDevice( c->device ) );
     const size_t pixels = c->projState.pixels;
     VRC_TRY( ctx_grow( c, c->dProjOutPixels, pixels, pixels, { { c->dProjOut, sizeof( float ) + sizeof( uint32_t ) } } ) );
@@ -2388,8 +2433,8 @@ int vrc_get_projection_depths( vrc_ctx* c, float* hostT, float* hostXyz )
     if( !c || !hostT )
         return fail( VRC_EINVAL, "vrc_get_projection_depths: NULL argument" );
     if( c->projState.pixels == 0u )
-        return fail( VRC_EINVAL, "vrc_get_projection_depths: no VRC_OPT_PROJECTION = MIP vrc_render since the last "
-                                 "vrc_pre_render; the depths exist from a frame's first MIP pass until the next frame" );
+        return fail( VRC_EINVAL, "vrc_get_projection_depths: no VRC_OPT_PROJECTION = MIP, ISO or SLICE vrc_render since the last "
+                                 "vrc_pre_render; the depths exist from a frame's first such pass until the next frame" );
     if( c->projState.fold == (uint32_t)VRC_MIP_FOLD_MEAN )
         return fail( VRC_EINVAL, "vrc_get_projection_depths: the frame's fold is VRC_MIP_FOLD_MEAN (VRC_OPT_MIP_FOLD); the mean "
                                  "has no position" );
@@ -2436,10 +2481,30 @@ int vrc_set_isosurface( vrc_ctx* c, float isoValue, float ambient )
     return VRC_OK;
 }
 
+int vrc_set_slice( vrc_ctx* c, const float plane[4] )
+{
+    if( !c )
+        return fail( VRC_EINVAL, "vrc_set_slice: ctx is NULL" );
+    if( !plane )
+        return fail( VRC_EINVAL, "vrc_set_slice: plane is NULL" );
+    for( int i = 0; i < 4; ++i )
+        if( !std::isfinite( plane[i] ) )
+            return fail( VRC_EINVAL, "vrc_set_slice: plane has an entry that is not finite" );
+    if( plane[0] == 0.0f && plane[1] == 0.0f && plane[2] == 0.0f )
+        return fail( VRC_EINVAL, "vrc_set_slice: plane has a zero normal" );
+    c->sliceSet = true;
+    for( int i = 0; i < 4; ++i )
+        c->slicePlane[i] = plane[i];
+    return VRC_OK;
+}
+
 int vrc_get_projection_gradients( vrc_ctx* c, float* hostG )
 {
     if( !c || !hostG )
         return fail( VRC_EINVAL, "vrc_get_projection_gradients: NULL argument" );
+    if( c->projState.pixels != 0u && c->sliceFrame )
+        return fail( VRC_EINVAL, "vrc_get_projection_gradients: the frame is a slice frame (VRC_OPT_PROJECTION = SLICE); "
+                                 "gradients exist after an isosurface frame" );
     if( c->projState.pixels == 0u || !c->gradValid )
         return fail( VRC_EINVAL, "vrc_get_projection_gradients: no VRC_OPT_PROJECTION = ISO vrc_render since the last "
                                  "vrc_pre_render; the gradients exist from a frame's first ISO pass until the next frame" );

@@ -289,6 +289,11 @@ struct vrc_frame
      * The same bytes either way.  Set behind everything that compares frames; read by the uncounted uniform-only
      * instances of vrc_k_raycast_replay alone */
     const uint32_t* walkResolved;
+    /* a slice frame (VRC_OPT_PROJECTION = VRC_PROJECTION_SLICE, the vrc_k_raycast_slice instances; at the end: no field
+     * above moves): vrc_set_slice's plane (nx, ny, nz, d), n.x + d = 0.  The passes of the frame meet in mipMax (the bits
+     * of V, VRC_MIP_EMPTY = not sampled) and mipDepth (D = t_p), owned, invalidated and not read by a first pass (mipFirst)
+     * as a composite-depth frame's are.  All zero in every other frame; no other kernel reads it */
+    float slicePlane[4];
 };
 #define VRC_RAY_COMPUTE 0u
 #define VRC_RAY_STORE 1u
@@ -1500,7 +1505,9 @@ VRC_HD vrc_classifier vrc_make_classifier( vrc_lut_params p )
     return k;
 }
 
-#if defined( __HIP_DEVICE_COMPILE__ )
+/* (VRC_HOST_FUSED_LERP: a host build that is to give the device's bits -- tests/slice_ref.py: harness( fused ) -- takes
+ * the device's form; with a compiler that honours VRC_FAST_FP and a target that has the instruction) */
+#if defined( __HIP_DEVICE_COMPILE__ ) || defined( VRC_HOST_FUSED_LERP )
 #define VRC_LERP2( B, X, A, Y ) __builtin_fmaf( ( A ), ( Y ), ( B ) * ( X ) )
 #else
 #define VRC_LERP2( B, X, A, Y ) ( ( B ) * ( X ) + ( A ) * ( Y ) )
@@ -5736,6 +5743,240 @@ VRC_HD void vrc_pixel_mip( const vrc_frame& f, const vrc_dev_node* __restrict__ 
             if( f.clearFirst )
                 pixelBuffer[pixelPos] = zero;
         }
+    }
+}
+
+/* ------------------------------------------------------------------------------------------
+ * Slice pixel (include/vrc_hip.h, "A slice frame"): one sample per ray, where it meets vrc_frame::slicePlane.  No march,
+ * no step, no lattice: the ray parameter of the plane, the position, the node whose box contains it, one point sample or
+ * eight taps, one classification.  The passes of a frame meet in vrc_frame::mipMax (the bits of V) and mipDepth
+ * (D = t_p): the first pass writes both for every pixel, a later one samples only where D is still +infinity.
+ * ---------------------------------------------------------------------------------------- */
+/* the ray of pixel rayIndex into the ray cache (f.rayMode == VRC_RAY_STORE): what vrc_ray_from_cache reads, plane for
+ * plane what vrc_pixel_grid_dda stores */
+VRC_HD void vrc_ray_to_cache( const vrc_frame& f, uint32_t rayIndex, const vrc_ray& r )
+{
+    float* const rc = f.rayCache + rayIndex;
+    const uint32_t P = f.rayCachePlane;
+    rc[0] = r.dir.x;
+    rc[P] = r.dir.y;
+    rc[2u * P] = r.dir.z;
+    rc[3u * P] = r.invDir.x;
+    rc[4u * P] = r.invDir.y;
+    rc[5u * P] = r.invDir.z;
+    rc[6u * P] = r.tNearGlobal;
+    rc[7u * P] = r.tFarGlobal;
+    rc[8u * P] = r.tNearPlane;
+    rc[9u * P] = vrc_bits_float( r.hit ? 1u : 0u );
+}
+
+/* how far the containment test on the ray is widened: a few units in the last place of t */
+VRC_HD float vrc_slice_tolerance( float t )
+{
+    VRC_STRICT_FP
+    const float a = fabsf( t );
+    return 2e-6f * ( a > 1.0f ? a : 1.0f );
+}
+
+/* the ray parameter at which r meets the plane, where the pixel takes its sample at all: the clip planes' expressions in
+ * their order, without their VRC_EPSILON -- a ray in the plane takes none */
+VRC_HD bool vrc_slice_parameter( const vrc_frame& f, const vrc_ray& r, float& t )
+{
+    VRC_STRICT_FP
+    t = 0.0f;
+    if( !r.hit )
+        return false;
+    const vrc_f3 n = { f.slicePlane[0], f.slicePlane[1], f.slicePlane[2] };
+    const float rn = vrc_dot( r.dir, n );
+    if( rn == 0.0f )
+        return false;
+    t = -( vrc_dot( n, r.origin ) + f.slicePlane[3] ) / rn;
+    const float lo = fmaxf( r.tNearGlobal, r.tNearPlane );
+    return lo <= t && t <= r.tFarGlobal; /* (a NaN takes no sample) */
+}
+
+/* does the box contain the ray's point at t?  Decided on the ray: t in the slab test's interval, widened by tol on both
+ * sides, faces included */
+VRC_HD bool vrc_slice_box_contains( const vrc_ray& r, const float* aabbMin, const float* aabbSize, float t, float tol )
+{
+    VRC_STRICT_FP
+    const vrc_f3 boxMin = { aabbMin[0], aabbMin[1], aabbMin[2] };
+    const vrc_f3 boxMax = { boxMin.x + aabbSize[0], boxMin.y + aabbSize[1], boxMin.z + aabbSize[2] };
+    float tn = 0.0f, tf = 0.0f;
+    (void)vrc_intersect_box( r.origin, r.invDir, boxMin, boxMax, &tn, &tf );
+    return tn - tol <= t && t <= tf + tol;
+}
+
+/* the slot-local coordinate of a world position along one axis, clamped to the slot: every operation rounded */
+VRC_HD float vrc_slice_local( float p, float boxMin, float voxPerWorld, float localOrigin, float hi )
+{
+    VRC_STRICT_FP
+    const float d = p - boxMin;
+    const float s = d * voxPerWorld;
+    const float l = s + localOrigin;
+    return fminf( fmaxf( l, 0.0f ), hi );
+}
+
+/* Grid form: the node of the brick-grid cell that holds P, looked up and not walked to; where that cell is empty or its
+ * brick does not hold the ray's point at t (rounding put P across a cell face), the cells on the nearer side of P along
+ * every axis, all seven combinations.  -1: no node of this pass contains P */
+VRC_HD int32_t vrc_slice_grid_node( const vrc_frame& f, const vrc_ray& r, const vrc_dev_node* __restrict__ nodes,
+                                    const int32_t* __restrict__ gridTable, const vrc_f3& P, float t, float tol )
+{
+    const float p[3] = { P.x, P.y, P.z };
+    int cell[3], other[3];
+#pragma unroll
+    for( int a = 0; a < 3; ++a )
+    {
+        VRC_STRICT_FP
+        const float u = ( p[a] - f.gridMin[a] ) * f.invCellSize[a];
+        const float fl = floorf( u );
+        const int last = f.gridDim[a] - 1;
+        const int c = fl > 0.0f ? ( fl < (float)last ? (int)fl : last ) : 0; /* (a NaN reads cell 0) */
+        int o = ( u - fl ) < 0.5f ? c - 1 : c + 1;
+        o = o < 0 ? 0 : ( o > last ? last : o );
+        cell[a] = c;
+        other[a] = o;
+    }
+    for( uint32_t m = 0; m < 8u; ++m )
+    {
+        if( ( ( m & 1u ) && other[0] == cell[0] ) || ( ( m & 2u ) && other[1] == cell[1] ) || ( ( m & 4u ) && other[2] == cell[2] ) )
+            continue;
+        const int cx = ( m & 1u ) ? other[0] : cell[0], cy = ( m & 2u ) ? other[1] : cell[1], cz = ( m & 4u ) ? other[2] : cell[2];
+        const int32_t node = gridTable[( cz * f.gridDim[1] + cy ) * f.gridDim[0] + cx];
+        if( node >= 0 && vrc_slice_box_contains( r, nodes[node].aabbMin, nodes[node].aabbSize, t, tol ) )
+            return node;
+    }
+    return -1;
+}
+
+/* the sample of node n at P as the bits the running word holds: the stored voxel of a point sample of the 8- and 16-bit
+ * atlases (an integer), the bits of a float otherwise -- all ones, which means "not sampled" there, is a NaN and is held as
+ * another.  BIG: as vrc_projection_march, the slot's 64-bit base moves into the pointer */
+template < bool LINEAR, typename ATLAS_T, bool BIG >
+VRC_HD uint32_t vrc_slice_sample( const vrc_frame& f, const vrc_dev_node& n, const ATLAS_T* __restrict__ atlas, const vrc_f3& P )
+{
+    if constexpr( !LINEAR && sizeof( ATLAS_T ) <= 2 )
+    {
+        if( f.slotInfo != nullptr && n.slotInfoIndex != 0u )
+        {
+            const uint32_t word = f.slotInfo[n.slotInfoIndex - 1u];
+            if( vrc_slot_holds_one_value( word ) )
+                return word & VRC_SLOT_VALUE_MASK;
+        }
+    }
+    vrc_dev_node local = n;
+    const ATLAS_T* slot = atlas;
+    if( BIG )
+    {
+        local.slotBase = 0u;
+        slot = atlas + ( ( (uint64_t)n.slotBaseHi << 32 ) | n.slotBase );
+    }
+    const vrc_sampler sm = vrc_make_sampler( local, f );
+    const float lx = vrc_slice_local( P.x, sm.minx, sm.kx, sm.ox, sm.hix );
+    const float ly = vrc_slice_local( P.y, sm.miny, sm.ky, sm.oy, sm.hiy );
+    const float lz = vrc_slice_local( P.z, sm.minz, sm.kz, sm.oz, sm.hiz );
+    uint32_t bits;
+    if constexpr( LINEAR )
+    {
+        const vrc_taps tp = vrc_trilinear_taps< true >( sm, lx, ly, lz );
+        float v[8];
+#pragma unroll
+        for( int c = 0; c < 8; ++c )
+            v[c] = (float)vrc_gather( slot, tp.ax[c & 1] + tp.ay[( c >> 1 ) & 1] + tp.az[c >> 2] );
+        bits = vrc_float_bits( vrc_trilerp( v, tp.wx, tp.wy, tp.wz ) );
+    }
+    else
+    {
+        const ATLAS_T v = vrc_gather( slot, vrc_voxel_address( sm, (uint32_t)(int)lx, (uint32_t)(int)ly, (uint32_t)(int)lz ) );
+        if constexpr( sizeof( ATLAS_T ) == 4 )
+            bits = vrc_float_bits( v );
+        else
+            return (uint32_t)v;
+    }
+    return bits == VRC_MIP_EMPTY ? 0x7FC00000u : bits;
+}
+
+template < bool GRID, bool LINEAR, typename ATLAS_T, bool BIG >
+VRC_HD void vrc_pixel_slice( const vrc_frame& f, const vrc_dev_node* __restrict__ nodes,
+                             const int32_t* __restrict__ gridTable, const ATLAS_T* __restrict__ atlas,
+                             const vrc_f4* __restrict__ tfp, const vrc_classifier& cls, vrc_f4* __restrict__ pixelBuffer,
+                             uint32_t px, uint32_t py, uint32_t& nSamples, const uint16_t* candidates = nullptr,
+                             uint32_t nCandidates = 0, uint32_t rayIndex = 0u )
+{
+    constexpr bool FLOAT_V = LINEAR || sizeof( ATLAS_T ) == 4;
+    const uint32_t pixelPos = py * f.width + px;
+    const float inf = vrc_bits_float( 0x7F800000u );
+    /* the grid form keeps its rays in the ray cache as vrc_pixel_grid_dda does (the same planes, the same bits) */
+    vrc_ray r;
+    if( GRID && f.rayMode == VRC_RAY_LOAD )
+        r = vrc_ray_from_cache( f, rayIndex );
+    else
+    {
+        r = vrc_setup_ray( f, px, f.rowMap ? f.rowMap[py] : py );
+        if( GRID && f.rayMode == VRC_RAY_STORE )
+            vrc_ray_to_cache( f, rayIndex, r );
+    }
+    uint32_t bits = VRC_MIP_EMPTY;
+    float depth = inf;
+    if( !f.mipFirst )
+    {
+        bits = f.mipMax[pixelPos];
+        depth = f.mipDepth[pixelPos];
+    }
+    bool sampled = false;
+    float t;
+    if( !( depth < inf ) && vrc_slice_parameter( f, r, t ) )
+    {
+        vrc_f3 P;
+        {
+            VRC_STRICT_FP
+            P.x = r.origin.x + r.dir.x * t;
+            P.y = r.origin.y + r.dir.y * t;
+            P.z = r.origin.z + r.dir.z * t;
+        }
+        const float tol = vrc_slice_tolerance( t );
+        int32_t node = -1;
+        if constexpr( GRID )
+            node = vrc_slice_grid_node( f, r, nodes, gridTable, P, t, tol );
+        else
+        {
+            /* every node is a candidate, in list order, the first that contains P: no `break` at a brick beyond the
+             * ray's interval (a brick the tile culling left out is hit by none of the tile's rays) */
+            const uint32_t nLoop = candidates ? nCandidates : f.nodeCount;
+            for( uint32_t c = 0; c < nLoop && node < 0; ++c )
+            {
+                const uint32_t i = candidates ? (uint32_t)candidates[c] : c;
+                if( vrc_slice_box_contains( r, nodes[i].aabbMin, nodes[i].aabbSize, t, tol ) )
+                    node = (int32_t)i;
+            }
+        }
+        if( node >= 0 )
+        {
+            bits = vrc_slice_sample< LINEAR, ATLAS_T, BIG >( f, nodes[node], atlas, P );
+            depth = t;
+            sampled = true;
+            nSamples += 1u;
+        }
+    }
+    if( f.mipFirst || sampled )
+    {
+        f.mipMax[pixelPos] = bits;
+        f.mipDepth[pixelPos] = depth;
+    }
+    if( sampled )
+    {
+        float d;
+        if constexpr( FLOAT_V )
+            d = vrc_bits_float( bits );
+        else
+            d = (float)bits;
+        pixelBuffer[pixelPos] = vrc_classify_mip( tfp, d, cls );
+    }
+    else if( f.clearFirst )
+    {
+        const vrc_f4 zero = { 0.f, 0.f, 0.f, 0.f };
+        pixelBuffer[pixelPos] = zero;
     }
 }
 

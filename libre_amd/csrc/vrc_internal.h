@@ -166,6 +166,8 @@ struct vrc_raycast_args
                   * frame.mipMax and frame.mipDepth set): vrc_launch_raycast_cdepth marches it */
     bool preint; /* a pre-integrated composite frame (VRC_OPT_PREINTEGRATION = 1; frame.preintTable set):
                   * vrc_launch_raycast_preint marches it */
+    bool slice;  /* a slice frame (VRC_OPT_PROJECTION = VRC_PROJECTION_SLICE; frame.slicePlane, frame.mipMax and
+                  * frame.mipDepth set): vrc_launch_raycast_slice renders it */
 };
 
 /* the one dispatch of a single-launch march: with a's stop event if it has one (the dispatch then carries its own
@@ -215,7 +217,8 @@ hipError_t vrc_launch_raycast( const vrc_raycast_args& a, hipStream_t stream );
 static inline bool vrc_walk_replay_eligible( const vrc_raycast_args& a )
 {
     return a.gridDda && a.gridTable && !a.packed && !a.linear && a.elemBytes == 1 && !a.bigAtlas && !a.clamp &&
-           a.fixedStepping && a.ertParts <= 1 && !a.depthSplit && !a.shade && !a.cdepth && !a.preint && VRC_TILE_W == 8u;
+           a.fixedStepping && a.ertParts <= 1 && !a.depthSplit && !a.shade && !a.cdepth && !a.preint && !a.slice &&
+           VRC_TILE_W == 8u;
 }
 static inline int vrc_walk_replay_group( const vrc_raycast_args& a )
 {
@@ -276,6 +279,11 @@ hipError_t vrc_launch_projection_depths( const vrc_frame& f, const float* depth,
 /* an isosurface frame (vrc_kernels_iso.hip; VRC_OPT_PROJECTION = VRC_PROJECTION_ISO): the first-crossing fold of the MIP
  * kernel; frame.mipMax, frame.mipDepth and frame.isoGrad set, frame.slotMax = NULL: every sample is taken */
 hipError_t vrc_launch_raycast_iso( const vrc_raycast_args& a, hipStream_t stream );
+
+/* a slice frame (vrc_kernels_slice.hip; VRC_OPT_PROJECTION = VRC_PROJECTION_SLICE): a.slice, frame.slicePlane, frame.mipMax
+ * and frame.mipDepth set; the culled list of the reference-order form or a look-up in the brick grid (a.gridDda), one
+ * point sample or eight taps (a.linear), every atlas type; lut = the padded transfer function.  One launch */
+hipError_t vrc_launch_raycast_slice( const vrc_raycast_args& a, hipStream_t stream );
 
 /* a shaded composite frame (vrc_kernels_shade.hip; VRC_OPT_SHADING = 1): a.shade and frame.shadeAmbient set; the
  * reference-order loop or the grid walk (a.gridDda), point or trilinear (a.linear) samples by gathers, every atlas type;

@@ -45,13 +45,15 @@ struct vrc_options
 /* what the frame's first vrc_render read of the options its later passes must not change (-1 / false: none yet; written
  * by the pass that reads the option, forgotten by vrc_pre_render).  projection: of the first pass; fold: of the first
  * MIP pass; depth, cue: of the first maximum / minimum pass; iso*: vrc_set_isosurface's two values at the first ISO
- * pass; shading .. preint: of the first composite pass */
+ * pass; shading .. preint: of the first composite pass; slice*: vrc_set_slice's plane at the first slice pass */
 struct vrc_latches
 {
     int64_t projection = -1, fold = -1, depth = -1, cue = -1;
     bool iso = false;
     float isoValue = 0.0f, isoAmbient = 0.0f;
     int64_t shading = -1, shadingAmbient = -1, compositeDepth = -1, preint = -1;
+    bool slice = false;
+    float slicePlane[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
 };
 
 struct vrc_refusal
@@ -66,12 +68,13 @@ struct vrc_mode
     bool iso = false, mip = false;           /* iso: a MIP frame with the first-crossing fold (mip is set too) */
     bool mipDepth = false, mean = false;     /* depth tracking: the maximum and the minimum only; the mean reads neither option */
     bool shade = false, cdepth = false, preint = false; /* the composite extensions: read by composite frames only */
+    bool slice = false; /* a slice frame: one sample per ray where it meets vrc_set_slice's plane; none of the above is set */
     bool linear = false;
     /* samples classified one by one (padded transfer function in the table buffer) whenever the 257-entry classified
      * table cannot be used: continuous or 16-bit densities (MIP: the one classification per ray reads it too) */
     bool classify = false;
     /* the plain composite: none of the frames marched by the gather kernels of the extensions */
-    bool plain() const { return !mip && !shade && !cdepth && !preint; }
+    bool plain() const { return !mip && !shade && !cdepth && !preint && !slice; }
 };
 
 /* A frame marched by the gather kernels of an extension is not defined for the staged and packed forms, per-ray LOD and
@@ -86,6 +89,7 @@ struct vrc_gather_only
 };
 static const vrc_gather_only vrc_plan_iso_only = VRC_PLAN_GATHER_ONLY( "isosurface", "VRC_OPT_PROJECTION = ISO", "renders" );
 static const vrc_gather_only vrc_plan_mip_only = VRC_PLAN_GATHER_ONLY( "maximum-intensity", "VRC_OPT_PROJECTION = MIP", "renders" );
+static const vrc_gather_only vrc_plan_slice_only = VRC_PLAN_GATHER_ONLY( "slice", "VRC_OPT_PROJECTION = SLICE", "renders" );
 static const vrc_gather_only vrc_plan_cdepth_only = VRC_PLAN_GATHER_ONLY( "depth-tracking", "VRC_OPT_COMPOSITE_DEPTH", "tracks" );
 static const vrc_gather_only vrc_plan_preint_only = VRC_PLAN_GATHER_ONLY( "pre-integrated", "VRC_OPT_PREINTEGRATION = 1", "renders" );
 static const vrc_gather_only vrc_plan_shade_only = VRC_PLAN_GATHER_ONLY( "shaded", "VRC_OPT_SHADING = 1", "renders" );
@@ -104,10 +108,12 @@ inline const char* vrc_plan_gather_only( const vrc_options& o, bool rayLod, cons
 inline bool vrc_plan_changed( int64_t latched, int64_t now ) { return latched >= 0 && latched != now; }
 
 /* Which frame is this pass, and may it be?  Reads the options, the latches of the passes before, vrc_set_ray_lod,
- * vrc_set_isosurface (isoSet: called at all, and its two values) and the bytes of an atlas element.  Changes nothing:
- * a refused pass has latched nothing. */
+ * vrc_set_isosurface (isoSet: called at all, and its two values), the bytes of an atlas element and vrc_set_slice
+ * (sliceSet: called at all, and its plane; read by a slice frame only).  Changes nothing: a refused pass has latched
+ * nothing. */
 inline vrc_refusal vrc_plan_mode( const vrc_options& o, const vrc_latches& l, bool rayLod, bool isoSet, float isoValue,
-                                  float isoAmbient, uint32_t elemBytes, vrc_mode& m )
+                                  float isoAmbient, uint32_t elemBytes, vrc_mode& m, bool sliceSet = false,
+                                  const float* slicePlane = nullptr )
 {
 #define VRC_PLAN_BETWEEN " changed between vrc_pre_render and vrc_post_render; "
     m = vrc_mode();
@@ -117,6 +123,9 @@ inline vrc_refusal vrc_plan_mode( const vrc_options& o, const vrc_latches& l, bo
     /* an isosurface frame reads none of the MIP frame's options but VRC_OPT_MIP_SKIP, and is served and refused as one */
     m.iso = o.projection == VRC_PROJECTION_ISO;
     m.mip = o.projection == VRC_PROJECTION_MIP || m.iso;
+    /* a slice frame reads none of the options of the MIP, isosurface and composite frames, and is served and refused as
+     * a MIP frame is */
+    m.slice = o.projection == VRC_PROJECTION_SLICE;
     const bool fold = m.mip && !m.iso; /* a MIP frame that reads VRC_OPT_MIP_FOLD */
     m.mean = fold && o.mipFold == VRC_MIP_FOLD_MEAN;
     if( vrc_plan_changed( l.projection, o.projection ) )
@@ -126,6 +135,13 @@ inline vrc_refusal vrc_plan_mode( const vrc_options& o, const vrc_latches& l, bo
     if( m.iso && l.iso && ( l.isoValue != isoValue || l.isoAmbient != isoAmbient ) )
         VRC_PLAN_REFUSE( "vrc_render: vrc_set_isosurface changed iso_value or ambient between vrc_pre_render and "
                          "vrc_post_render; the passes of one frame take one isosurface" );
+    if( m.slice && ( !sliceSet || slicePlane == nullptr ) )
+        VRC_PLAN_REFUSE( "vrc_render: VRC_OPT_PROJECTION = SLICE needs vrc_set_slice first" );
+    if( m.slice && l.slice &&
+        ( l.slicePlane[0] != slicePlane[0] || l.slicePlane[1] != slicePlane[1] || l.slicePlane[2] != slicePlane[2] ||
+          l.slicePlane[3] != slicePlane[3] ) )
+        VRC_PLAN_REFUSE( "vrc_render: vrc_set_slice changed the plane between vrc_pre_render and vrc_post_render; the "
+                         "passes of one frame take one plane" );
     if( fold && vrc_plan_changed( l.fold, o.mipFold ) )
         VRC_PLAN_REFUSE( "vrc_render: VRC_OPT_MIP_FOLD" VRC_PLAN_BETWEEN "the passes of one frame take one fold" );
     m.mipDepth = m.iso || ( fold && !m.mean && ( o.mipDepth != 0 || o.mipDepthCue > 0 ) );
@@ -140,10 +156,13 @@ inline vrc_refusal vrc_plan_mode( const vrc_options& o, const vrc_latches& l, bo
     /* what the maximum-intensity projection is not defined for (include/vrc_hip.h) */
     if( m.mip && ( no = vrc_plan_gather_only( o, rayLod, m.iso ? vrc_plan_iso_only : vrc_plan_mip_only ) ) )
         VRC_PLAN_REFUSE( no );
-    m.shade = !m.mip && o.shading != 0;
-    m.cdepth = !m.mip && o.compositeDepth != 0;
-    m.preint = !m.mip && o.preint != 0;
-    if( !m.mip )
+    if( m.slice && ( no = vrc_plan_gather_only( o, rayLod, vrc_plan_slice_only ) ) )
+        VRC_PLAN_REFUSE( no );
+    const bool composite = !m.mip && !m.slice; /* a frame that reads the composite extensions' options */
+    m.shade = composite && o.shading != 0;
+    m.cdepth = composite && o.compositeDepth != 0;
+    m.preint = composite && o.preint != 0;
+    if( composite )
     {
         if( vrc_plan_changed( l.shading, o.shading ) )
             VRC_PLAN_REFUSE( "vrc_render: VRC_OPT_SHADING" VRC_PLAN_BETWEEN "the passes of one frame are all shaded or none is" );
@@ -160,7 +179,7 @@ inline vrc_refusal vrc_plan_mode( const vrc_options& o, const vrc_latches& l, bo
         if( ( no = vrc_plan_gather_only( o, rayLod, vrc_plan_cdepth_only ) ) )
             VRC_PLAN_REFUSE( no );
     }
-    if( !m.mip && vrc_plan_changed( l.preint, o.preint ) )
+    if( composite && vrc_plan_changed( l.preint, o.preint ) )
         VRC_PLAN_REFUSE( "vrc_render: VRC_OPT_PREINTEGRATION" VRC_PLAN_BETWEEN "the passes of one frame are all pre-integrated or none is" );
     if( m.preint )
     {
@@ -176,7 +195,7 @@ inline vrc_refusal vrc_plan_mode( const vrc_options& o, const vrc_latches& l, bo
     if( m.shade && ( no = vrc_plan_gather_only( o, rayLod, vrc_plan_shade_only ) ) )
         VRC_PLAN_REFUSE( no );
     m.linear = o.filter == VRC_FILTER_TRILINEAR;
-    m.classify = m.linear || elemBytes != 1 || m.mip;
+    m.classify = m.linear || elemBytes != 1 || m.mip || m.slice;
     return vrc_refusal{ VRC_OK, nullptr };
 #undef VRC_PLAN_BETWEEN
 }

@@ -35,7 +35,7 @@ EXPORTS = [
     "lvh_app_set_modelview", "lvh_app_set_time_step", "lvh_datasource_frame_range", "lvh_app_set_colormap", "lvh_app_set_clip_planes",
     "lvh_app_set_bands", "lvh_app_set_frames_in_flight", "lvh_app_select_slot", "lvh_app_set_option", "lvh_app_get_option", "lvh_app_set_data_range", "lvh_app_set_ray_lod", "lvh_app_set_stream", "lvh_app_set_framebuffer", "lvh_app_render_frame",
     "lvh_app_get_stats", "lvh_app_wait_uploads", "lvh_app_synchronize", "lvh_app_volume_info",
-    "lvh_app_set_histogram", "lvh_app_frame_histogram", "lvh_app_pick", "lvh_app_set_isosurface",
+    "lvh_app_set_histogram", "lvh_app_frame_histogram", "lvh_app_pick", "lvh_app_set_isosurface", "lvh_app_set_slice",
     "lvh_comm_unique_id", "lvh_app_comm_create", "lvh_app_set_layout", "lvh_app_gather_tiles",
     "lvh_app_visible_set", "lvh_app_node_order", "lvh_app_view_matrices", "lvh_app_cache_stats", "lvh_select_visibles",
     "lvh_selftest_cache", "lvh_selftest_plugin_factory", "lvh_selftest_camera",
@@ -68,6 +68,7 @@ def load_library():
     L.lvh_app_set_option.argtypes = [vp, C.c_int, C.c_int64]
     L.lvh_app_get_option.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
     L.lvh_app_set_isosurface.argtypes = [vp, C.c_float, C.c_float]
+    L.lvh_app_set_slice.argtypes = [vp, C.POINTER(C.c_float)]
     L.lvh_app_set_data_range.argtypes = [vp, C.c_float, C.c_float]
     L.lvh_app_set_ray_lod.argtypes = [vp, C.c_int]
     L.lvh_app_set_stream.argtypes = [vp, vp]
@@ -168,6 +169,13 @@ class App:
         units and the ambient share of the shading in [0, 1]; reaches every renderer slot."""
         check(self.L, self.L.lvh_app_set_isosurface(self.h, float(iso_value), float(ambient)))
 
+    def set_slice(self, point, normal):
+        """The plane of frames rendered under VRC_OPT_PROJECTION = PROJECTION_SLICE, through `point` with normal `normal`
+        (world coordinates; the normal need not be a unit vector): (n, d = -n . point); reaches every renderer slot."""
+        n = [float(v) for v in normal]
+        d = -sum(a * float(b) for a, b in zip(n, point))
+        check(self.L, self.L.lvh_app_set_slice(self.h, (C.c_float * 4)(n[0], n[1], n[2], d)))
+
     def set_shading(self, on, ambient=0.25):
         """A shaded composite frame (VRC_OPT_SHADING, VRC_OPT_SHADING_AMBIENT): every sample's colour lit by the volume's
         gradient, with the ambient share in [0, 1] (kept in thousandths); reaches every renderer slot."""
@@ -235,7 +243,9 @@ class App:
         minimum) rendered with VRC_OPT_MIP_DEPTH or a depth cue: (hit, value, t, (x, y, z)); value is the projected
         value in the volume's own units, t the ray parameter of the nearest sample that has it, xyz its position.
         In an isosurface frame (PROJECTION_ISO): hit says whether the ray reached the isovalue, value, t and xyz are
-        those of the first sample that did -- the surface under the pixel."""
+        those of the first sample that did -- the surface under the pixel.  In a slice frame (PROJECTION_SLICE): hit
+        says whether the pixel shows the plane inside a brick of the frame, value is the voxel (or interpolated value)
+        there in the volume's own units, t the ray parameter of the plane and xyz the point on it."""
         hit, value, t, xyz = C.c_int(), C.c_float(), C.c_float(), (C.c_float * 3)()
         check(self.L, self.L.lvh_app_pick(self.h, int(x), int(y), C.byref(hit), C.byref(value), C.byref(t), xyz))
         return bool(hit.value), float(value.value), float(t.value), (float(xyz[0]), float(xyz[1]), float(xyz[2]))

@@ -94,6 +94,8 @@ public:
     int64_t getOption( int option ) const;
     /** vrc_set_isosurface: the isovalue (the volume's own units) and the ambient share of VRC_PROJECTION_ISO frames */
     void setIsosurface( float isoValue, float ambient );
+    /** vrc_set_slice: the plane (nx, ny, nz, d), n.x + d = 0 in world coordinates, of VRC_PROJECTION_SLICE frames */
+    void setSlice( const float plane[4] );
     /** VRC_OPT_PROJECTION = VRC_PROJECTION_MIP or _ISO was set: neither projection has a per-ray LOD form, a frame
      *  that asks for per-ray LOD is then rendered with its per-brick cut (the path taken on VRC_EHIERARCHY) */
     bool projectionIsMip() const { return _mip; }

@@ -43,6 +43,8 @@ struct lvh_app
     std::vector< std::unique_ptr< Renderer > > extraRenderers; /* frames in flight beyond the first */
     bool isoSet = false; /* lvh_app_set_isosurface as called: for renderers made later */
     float isoValue = 0.f, isoAmbient = 0.f;
+    bool sliceSet = false; /* lvh_app_set_slice as called: for renderers made later */
+    float slicePlane[4] = { 0.f, 0.f, 0.f, 0.f };
     std::map< int, int64_t > projectionOptions; /* VRC_OPT_PROJECTION / VRC_OPT_MIP_SKIP / _FOLD / _DEPTH / _DEPTH_CUE as set: for renderers made later */
     struct PickFrame /* per renderer slot: where its last frame's pixel buffer lies in the window (lvh_app_pick) */
     {
@@ -301,6 +303,8 @@ int lvh_app_set_frames_in_flight( lvh_app* app, uint32_t n )
             app->extraRenderers.emplace_back( new Renderer( app->rendererName ) );
             if( app->isoSet ) /* (first: VRC_PROJECTION_ISO is refused on a context without an isosurface) */
                 static_cast< HipRaycastRenderer& >( app->extraRenderers.back()->getPlugin() ).setIsosurface( app->isoValue, app->isoAmbient );
+            if( app->sliceSet ) /* (as the isosurface: VRC_PROJECTION_SLICE is refused on a context without a plane) */
+                static_cast< HipRaycastRenderer& >( app->extraRenderers.back()->getPlugin() ).setSlice( app->slicePlane );
             for( const auto& o : app->projectionOptions )
                 static_cast< HipRaycastRenderer& >( app->extraRenderers.back()->getPlugin() ).setOption( o.first, o.second );
             if( app->histogram )
@@ -366,6 +370,25 @@ int lvh_app_set_isosurface( lvh_app* app, float iso_value, float ambient )
         app->isoSet = true;
         app->isoValue = iso_value;
         app->isoAmbient = ambient;
+        return 0;
+    }
+    catch( const std::exception& e )
+    {
+        return fail( e.what() );
+    }
+}
+int lvh_app_set_slice( lvh_app* app, const float plane[4] )
+{
+    if( !app ) return fail( "NULL argument" );
+    /* as the isosurface: every renderer the app has, and every one it makes later */
+    try
+    {
+        static_cast< HipRaycastRenderer& >( app->pipeline->getRenderer().getPlugin() ).setSlice( plane );
+        for( auto& r : app->extraRenderers )
+            static_cast< HipRaycastRenderer& >( r->getPlugin() ).setSlice( plane );
+        app->sliceSet = true;
+        for( int i = 0; i < 4; ++i )
+            app->slicePlane[i] = plane[i];
         return 0;
     }
     catch( const std::exception& e )

@@ -28,6 +28,8 @@
 #pragma weak vrc_pool_create_typed
 /* ... and the isosurface of VRC_PROJECTION_ISO frames: without it setIsosurface says so */
 #pragma weak vrc_set_isosurface
+/* ... and the plane of VRC_PROJECTION_SLICE frames: without it setSlice says so */
+#pragma weak vrc_set_slice
 
 extern "C" int LunchboxPluginGetVersion() { return 1; } /* LIVRECORE_VERSION_ABI, CudaRaycastPipeline.cpp:50-51 */
 extern "C" bool LunchboxPluginRegister() { return true; } /* CudaRaycastPipeline.cpp:53-54 */
@@ -762,7 +764,14 @@ void HipRaycastRenderer::setOption( int o, int64_t v )
 {
     throwOnVrcError( vrc_set_option( _ctx, o, v ), "vrc_set_option" );
     if( o == VRC_OPT_PROJECTION ) /* (whichever VRC_OPT_MIP_FOLD: every fold of a MIP frame takes the per-brick cut) */
-        _mip = v == VRC_PROJECTION_MIP || v == VRC_PROJECTION_ISO; /* (an isosurface frame is served as a MIP frame is) */
+        /* (an isosurface frame and a slice frame are served as a MIP frame is: the per-brick cut) */
+        _mip = v == VRC_PROJECTION_MIP || v == VRC_PROJECTION_ISO || v == VRC_PROJECTION_SLICE;
+}
+void HipRaycastRenderer::setSlice( const float plane[4] )
+{
+    if( vrc_set_slice == nullptr )
+        throw std::runtime_error( "vrc_set_slice: the device layer has no slice projection" );
+    throwOnVrcError( vrc_set_slice( _ctx, plane ), "vrc_set_slice" );
 }
 void HipRaycastRenderer::setIsosurface( float isoValue, float ambient )
 {

@@ -29,6 +29,7 @@ OPT_LEAN_FREE_MARCH, OPT_LEAN_FREE_MARCH_USED = 40, 41  # a replayed lean frame 
 OPT_WALK_RESOLVED, OPT_WALK_RESOLVED_USED = 42, 43  # the uniform-only replay reads one resolved word per visit: 0 / 1 (default); read-only: 1 = the last render did
 PREINT_VALUE, PREINT_TEXEL = 0, 1  # kinds of table vrc_get_preintegrated_table reports
 PROJECTION_COMPOSITE, PROJECTION_MIP, PROJECTION_ISO = 0, 1, 2
+PROJECTION_SLICE = 4  # the volume on vrc_set_slice's plane (3 is no projection and stays refused)
 MIP_FOLD_MAX, MIP_FOLD_MIN, MIP_FOLD_MEAN = 0, 1, 2
 VARIANT_CUDARAYCASTER, VARIANT_GLRAYCASTER = 0, 1
 FILTER_NEAREST, FILTER_TRILINEAR = 0, 1
@@ -80,7 +81,7 @@ EXPORTS = [
     "vrc_pool_histogram", "vrc_pool_enable_histograms", "vrc_frame_histogram", "vrc_get_frame_histogram",
     "vrc_update", "vrc_pre_render", "vrc_set_row_map", "vrc_set_framebuffer", "vrc_get_framebuffer", "vrc_render",
     "vrc_post_render", "vrc_synchronize", "vrc_get_stats", "vrc_get_ray_counts", "vrc_get_projection_values", "vrc_get_projection_depths",
-    "vrc_set_isosurface", "vrc_get_projection_gradients", "vrc_get_preintegrated_table", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
+    "vrc_set_isosurface", "vrc_get_projection_gradients", "vrc_set_slice", "vrc_get_preintegrated_table", "vrc_last_error", "vrc_last_kernel", "vrc_last_kernel_occupancy", "vrc_abi_version", "vrc_is_dev_build",
     "vrc_comm_unique_id", "vrc_comm_create", "vrc_comm_destroy", "vrc_comm_info", "vrc_gather_tiles",
 ]
 COMM_ID_BYTES = 128
@@ -156,6 +157,8 @@ def load_library(path=None):
     if hasattr(L, "vrc_set_isosurface"):
         L.vrc_set_isosurface.argtypes = [vp, C.c_float, C.c_float]
         L.vrc_get_projection_gradients.argtypes = [vp, vp]
+    if hasattr(L, "vrc_set_slice"):
+        L.vrc_set_slice.argtypes = [vp, C.POINTER(C.c_float)]
     if hasattr(L, "vrc_get_preintegrated_table"):
         L.vrc_get_preintegrated_table.argtypes = [vp, vp, C.POINTER(C.c_int)]
     L.vrc_comm_unique_id.argtypes = [C.c_char_p]
@@ -194,6 +197,15 @@ def set_isosurface(L, ctx, iso_value, ambient=0.2):
     if not hasattr(L, "vrc_set_isosurface"):
         raise VrcError(VRC_EUNSUPPORTED, "this libvrc_hip.so has no vrc_set_isosurface")
     check(L, L.vrc_set_isosurface(ctx, float(iso_value), float(ambient)))
+
+
+def set_slice(L, ctx, plane):
+    """vrc_set_slice: the plane (nx, ny, nz, d), n.x + d = 0 in world coordinates, of the frames rendered under
+    VRC_OPT_PROJECTION = PROJECTION_SLICE.  plane = None passes NULL (an error the library names)."""
+    if not hasattr(L, "vrc_set_slice"):
+        raise VrcError(VRC_EUNSUPPORTED, "this libvrc_hip.so has no vrc_set_slice")
+    arg = None if plane is None else (C.c_float * 4)(*[float(v) for v in plane])
+    check(L, L.vrc_set_slice(ctx, arg))
 
 
 def projection_gradients(L, ctx, width, height):
